@@ -47,8 +47,8 @@ CONFIGS = {
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=8)
+    ap.add_argument('--steps', type=int, default=None, help='cycles in each timed region (default 10; 5 with --iterative)')
+    ap.add_argument('--warmup', type=int, default=None, help='untimed cycles in front of the first timed region (default 8; 3 with --iterative)')
     ap.add_argument('--config', type=str, default='C2', choices=sorted(CONFIGS), help='workload preset (see the module docstring)')
     ap.add_argument('--scaling', type=str, default=None, choices=('weak', 'strong'),
                     help='default: one GPU runs the preset as it stands; at --gpus N > 1 BOTH legs run — `value` is the strong-scaling rate of the '
@@ -72,14 +72,23 @@ def parse_args(argv=None):
                          'overlapped with the next block as the driver does; `value` is then the recorded rate, `record` holds both rates '
                          'and the I/O share')
     ap.add_argument('--record-dir', type=str, default=None, help='where --record writes (default: a temporary directory, removed afterwards)')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help="after the last timed region, write what its last cycle left a caller of the hot path (rank 0's replicas: x, v, box, "
+                         'dxdvdt = Engine.get_state(), thermo = Engine.thermo(), slot = their global slot numbers) as DIR/<name>.npy in float64, '
+                         'at most 64 MB in all (a fixed, seeded sample of the replicas beyond that); the same arguments give the same inputs')
     args = ap.parse_args(argv)
     if args.iterative:
         # The reference's iterative position move never undoes a rejected trial while its step size keeps growing (remcmc:522-545,
         # 733-737): from about cycle 10 on atoms overlap, energies reach 1e12-1e18 per atom and sooner or later leave the floating-point
         # range (NM_ST_NONFINITE; LAMMPS would stop the reference there).  That mode has no equilibrated regime to time: window only.
         args.equil = 0
-        if (args.warmup, args.steps) == (ap.get_default('warmup'), ap.get_default('steps')):
-            args.warmup, args.steps = 3, 5   # cycles 3-7: before the chains leave the floating-point range
+    # iterative: cycles 3-7 by default, before the chains leave the floating-point range
+    if args.warmup is None:
+        args.warmup = 3 if args.iterative else 8
+    if args.steps is None:
+        args.steps = 5 if args.iterative else 10
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     return args
 
 
@@ -117,12 +126,13 @@ def main(argv=None, make_engine=None):
     # Which legs.  One GPU: the preset as it stands (`scaling` "weak" by the contract's definition: per-GPU work fixed).  N > 1 without
     # --scaling: the metric's own grid dealt out over the ranks (strong scaling: BASELINE.json's "8x8 PxT grid, 1/2/4/8 GPUs") is
     # `value`; the grid of N times as many pressure rows (weak scaling) rides along under `weak`.
+    # --dump-outputs: the leg whose rate is `value`
     if args.scaling is not None:
-        out = run_leg(args, env, args.scaling, with_cpu=not args.no_cpu)
+        out = run_leg(args, env, args.scaling, with_cpu=not args.no_cpu, dump=args.dump_outputs)
     elif world == 1:
-        out = run_leg(args, env, 'weak', with_cpu=not args.no_cpu)
+        out = run_leg(args, env, 'weak', with_cpu=not args.no_cpu, dump=args.dump_outputs)
     else:
-        out = run_leg(args, env, 'strong', with_cpu=not args.no_cpu)
+        out = run_leg(args, env, 'strong', with_cpu=not args.no_cpu, dump=args.dump_outputs)
         weak = run_leg(args, env, 'weak', with_cpu=False)
         if rank == 0:
             out['weak'] = {k: weak[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'scaling', 'window', 'sustained')}
@@ -137,8 +147,9 @@ def main(argv=None, make_engine=None):
     return out
 
 
-def run_leg(args, env, scaling, with_cpu):
-    """one workload (grid) on all ranks: warm-up, the timed window, equilibration, the timed sustained region; rank 0 returns the line"""
+def run_leg(args, env, scaling, with_cpu, dump=None):
+    """one workload (grid) on all ranks: warm-up, the timed window, equilibration, the timed sustained region; rank 0 returns the line
+    (and with `dump` writes what the last timed cycle left into that directory)"""
     import torch
     rank, world, local, dist, backend = env['rank'], env['world'], env['local'], env['dist'], env['backend']
     el, sz, rows, np_cfg, tn, mod, desc = CONFIGS[args.config]
@@ -303,6 +314,8 @@ def run_leg(args, env, scaling, with_cpu):
         if args.record_dir is None:
             shutil.rmtree(rdir, ignore_errors=True)
     world_seen = dist.get_world_size() if dist is not None else 1
+    if dump is not None and rank == 0:
+        dump_outputs(eng, dump, k0)
 
     # one more block outside the timed region, read before gen_mc_params zeroes the counters: the per-replica acceptance
     # ratios and U, V the metric's definition asks to see next to the rate
@@ -479,6 +492,26 @@ class Recorder:
     def summary(self, steps):
         return {'write_ms_per_step': self.write_s / steps * 1e3, 'fetch_ms_per_step': self.d2h_s / steps * 1e3,
                 'text_bytes_per_step': self.bytes // max(steps, 1)}
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(eng, ddir, k0):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last cycle (Engine.get_state, Engine.thermo) as ddir/<name>.npy,
+    float64.  Beyond DUMP_BYTES in all, a fixed, seeded sample of the replicas (the same for every run of the same grid); `slot` names them."""
+    x, v, box, d = eng.get_state()
+    arrs = {'x': x, 'v': v, 'box': box, 'dxdvdt': d, 'thermo': eng.thermo()}
+    ns = len(box)
+    slots = np.arange(ns)
+    per_slot = sum(a.nbytes for a in arrs.values()) / ns + 8
+    if per_slot * ns > DUMP_BYTES:
+        slots = np.sort(np.random.default_rng(0).choice(ns, max(int(DUMP_BYTES // per_slot), 1), replace=False))
+        arrs = {k: a[slots] for k, a in arrs.items()}
+    arrs['slot'] = (k0 + slots).astype(np.float64)
+    os.makedirs(ddir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(ddir, k + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def measured_profile(config, ns, mod, cycles_per_launch=1.0):

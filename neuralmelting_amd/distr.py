@@ -1,6 +1,6 @@
 """Structural histograms on the GPU with lammps_distr.py's command line and outputs.
 
-Mirrors /root/reference/scripts/lammps_distr.py ("distr"): loads <PREFIX>.natoms/.box/.pos.npy written by
+Mirrors the reference's scripts/lammps_distr.py ("distr"): loads <PREFIX>.natoms/.box/.pos.npy written by
 lammps_parse.py, computes the per-sample radial distribution over the 27 periodic images (calculate_rdf, distr:123-135)
 and the 3-D histogram of pair displacement vectors (calculate_cdf, distr:161-171) — here one kernel launch over all
 samples (include/nm_distr.h) instead of a Dask/joblib map of numpy calls — and writes the same .dni/.r/.rdf/.dn/.rv/.cdf

@@ -1,6 +1,6 @@
 """Reader of the sampler's text output with lammps_parse.py's command line and outputs.
 
-Mirrors /root/reference/scripts/lammps_parse.py ("parse"): loads <PREFIX>.virial.trgt.npy / .temp.trgt.npy for the grid
+Mirrors the reference's scripts/lammps_parse.py ("parse"): loads <PREFIX>.virial.trgt.npy / .temp.trgt.npy for the grid
 shape, turns the consolidated <PREFIX>.thrm into the 17 float32 arrays of shape (PN, TN, SN) (parse:48-85) and the
 consolidated <PREFIX>.traj into .natoms (uint16, (PN, TN, SN)), .box (float32, flat, parse:92 does not reshape it) and .pos
 (float32, (PN, TN, SN, natoms, 3)) (parse:88-104).  The text is read by the multi-threaded reader of include/nm_parse.h

@@ -1,5 +1,5 @@
 """CPU ORACLE (test infrastructure) for the structural histograms: numpy restatement of calculate_rdf / calculate_cdf of
-/root/reference/scripts/lammps_distr.py ("distr").  Pinned by tests/golden/ref_distr.npz, which holds what the reference's
+the reference's scripts/lammps_distr.py ("distr").  Pinned by tests/golden/ref_distr.npz, which holds what the reference's
 own two functions return (tests/golden/make_golden_distr.py)."""
 import numpy as np
 

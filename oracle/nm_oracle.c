@@ -2,7 +2,7 @@
  * nm_oracle.c — CPU ORACLE (test infrastructure, NOT product code).  See nm_oracle.h.
  *
  * Every function cites the reference lines it restates: "remcmc" =
- * /root/reference/scripts/lammps_remcmc.py.  LAMMPS behaviour is restated from its published
+ * the reference's scripts/lammps_remcmc.py.  LAMMPS behaviour is restated from its published
  * algorithm (pair_lj_cut, fix_nve, velocity, displace_atoms, compute_pe/ke/temp/pressure);
  * liblammps itself is not available in this image ("parity unpinned" for that arithmetic).
  */

@@ -1,6 +1,6 @@
 """Generates the golden fixtures of tests/golden/ by running the REFERENCE's own Python functions
-(/root/reference/scripts/lammps_remcmc.py, "remcmc") in this container.  Run once here; only the numbers it
-writes travel (the reference itself never leaves this container and is never copied).
+(scripts/lammps_remcmc.py of the checkout NM_REFERENCE names, "remcmc").  Run once beside that checkout; only the numbers it
+writes travel (the reference itself is never copied).
 
 The reference cannot be imported as is: `numba` and `lammps` are not installed (ordinary ModuleNotFoundError) and
 `np.unravel_index(k, dims=...)` lost its `dims` keyword in NumPy 2.  So, as SURVEY.md §8c describes:
@@ -34,7 +34,6 @@ sys.dont_write_bytecode = True
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = '/root/reference/scripts/lammps_remcmc.py'
 
 from oracle import oracle as O  # noqa: E402
 from neuralmelting_amd import lattice  # noqa: E402
@@ -168,7 +167,7 @@ def load_reference():
     def unravel(indices, shape=None, order='C', dims=None):
         return orig(indices, shape if shape is not None else dims, order)
     np.unravel_index = unravel
-    spec = importlib.util.spec_from_file_location('lammps_remcmc_ref', REF)
+    spec = importlib.util.spec_from_file_location('lammps_remcmc_ref', os.path.join(os.environ['NM_REFERENCE'], 'scripts', 'lammps_remcmc.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)   # __main__ block does not run
     return mod

@@ -1,5 +1,5 @@
 """Golden fixtures for the structural histograms: runs the REFERENCE's own calculate_rdf / calculate_cdf
-(/root/reference/scripts/lammps_distr.py) in this container — `numba` replaced by an identity `jit` stub, nothing else —
+(scripts/lammps_distr.py of the checkout NM_REFERENCE names) — `numba` replaced by an identity `jit` stub, nothing else —
 on small float32 samples and stores inputs + outputs as numbers in ref_distr.npz."""
 import importlib.util
 import os
@@ -25,7 +25,7 @@ def load_reference():
         return lambda f: f
     nb.jit = nb.njit = jit
     sys.modules['numba'] = nb
-    spec = importlib.util.spec_from_file_location('lammps_distr_ref', '/root/reference/scripts/lammps_distr.py')
+    spec = importlib.util.spec_from_file_location('lammps_distr_ref', os.path.join(os.environ['NM_REFERENCE'], 'scripts', 'lammps_distr.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod

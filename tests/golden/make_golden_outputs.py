@@ -1,5 +1,5 @@
 """Golden fixture for the whole output path (writer half): the REFERENCE's own init_outputs,
-init_headers, write_outputs and consolidate_outputs (/root/reference/scripts/lammps_remcmc.py:153-316; module imported as
+init_headers, write_outputs and consolidate_outputs (scripts/lammps_remcmc.py:153-316; module imported as
 tests/golden/make_golden.py does) run on a synthetic STATE for three recorded cycles of a 2x3 grid; the two consolidated files
 they leave are stored byte for byte in ref_outputs.npz with the numbers that went in.
 tests/test_driver.py::test_output_files_equal_the_references replays it through the driver's writer."""

@@ -1,5 +1,5 @@
 """Golden fixture for the .thrm / .traj reader: runs the REFERENCE's own scripts/lammps_parse.py, unmodified, as a child
-process in a scratch directory of this container (it needs numpy only) on a small synthetic run whose text was produced with
+process in a scratch directory (it needs numpy only) on a small synthetic run whose text was produced with
 the reference's formatting expressions (remcmc:245, 254-256), and stores the input text plus every array the script wrote
 (20 .npy files) in ref_parse.npz.  tests/test_parse.py::test_golden_from_the_reference_script replays it."""
 import os
@@ -9,7 +9,6 @@ import tempfile
 
 import numpy as np
 
-REF = '/root/reference/scripts/lammps_parse.py'
 HERE = os.path.dirname(os.path.abspath(__file__))
 NAMES = ('temp', 'pe', 'ke', 'virial', 'vol', 'dx', 'dv', 'dt', 'ntp', 'nap', 'ntv', 'nav', 'nth', 'nah', 'ap', 'av', 'ah',
          'natoms', 'box', 'pos')
@@ -44,7 +43,8 @@ def main():
         open(pre + '.thrm', 'w').write(thrm_txt)
         open(pre + '.traj', 'w').write(traj_txt)
         env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-        subprocess.run([sys.executable, REF, '-n', 'g', '-e', 'LJ'], cwd=d, check=True, env=env)
+        ref = os.path.join(os.environ['NM_REFERENCE'], 'scripts', 'lammps_parse.py')
+        subprocess.run([sys.executable, ref, '-n', 'g', '-e', 'LJ'], cwd=d, check=True, env=env)
         for n in NAMES:
             out['ref_' + n] = np.load(pre + '.%s.npy' % n)
     np.savez_compressed(os.path.join(HERE, 'ref_parse.npz'), **out)

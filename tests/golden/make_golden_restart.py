@@ -1,5 +1,5 @@
 """Golden fixture for the restart interchange: the REFERENCE's own dump_samples_restart
-(/root/reference/scripts/lammps_remcmc.py:821-828; module imported as tests/golden/make_golden.py does) writes a state list of
+(scripts/lammps_remcmc.py:821-828; module imported as tests/golden/make_golden.py does) writes a state list of
 the shape its gen_mc_param returns (remcmc:743-745) and the file's bytes are stored in ref_restart.npz together with the numbers
 that went in.  tests/test_driver.py::test_restart_file_written_by_the_reference_loads replays it."""
 import os

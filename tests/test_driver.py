@@ -1,15 +1,11 @@
 """the driver (neuralmelting_amd.remcmc): flags, row partition, file formats, restart"""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from helpers import OracleEngine
 from neuralmelting_amd import remcmc
-
-REF_PARSE = '/root/reference/scripts/lammps_parse.py'
 
 
 def test_parse_args_defaults_and_order():
@@ -78,20 +74,37 @@ def check_outputs(tmp_path, run, nrec):
     return cols
 
 
-def test_driver_formats_with_oracle_engine(tmp_path, oracle):
+def test_driver_formats_with_oracle_engine(tmp_path, oracle, monkeypatch):
     """host logic + file layout on a machine without a GPU: the engine is replaced by the oracle IN THIS TEST ONLY"""
+    from neuralmelting_amd import parse
     argv = '-bm -n t1 -e LJ -ss 4 -pn 2 -tn 2 -sn 3 -sm 4 -sc 1 -rd 2'.split()
     run = run_driver(tmp_path, argv, lambda r: OracleEngine(oracle, r))
     cols = check_outputs(tmp_path, run, nrec=2)          # STEP+1 > CUTOFF: cycles 2 and 3 are recorded
     assert os.path.isfile(run.restart_file('t1', 2))
-    if os.path.isfile(REF_PARSE):
-        # the reference's own consumer, unmodified, run as a script on the files just written
-        env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-        subprocess.check_call([sys.executable, REF_PARSE, '-n', 't1', '-e', 'LJ'], cwd=str(tmp_path), env=env)
-        pe = np.load(run.PREF + '.pe.npy')
-        pos = np.load(run.PREF + '.pos.npy')
-        assert pe.shape == (2, 2, 2) and pos.shape == (2, 2, 2, 256, 3)
-        np.testing.assert_array_equal(pe, cols[1])
+    # the consumer (lammps_parse.py's command line and files) on the files just written
+    monkeypatch.chdir(tmp_path)
+    parse.main(['-n', 't1', '-e', 'LJ'])
+    pe = np.load(run.PREF + '.pe.npy')
+    pos = np.load(run.PREF + '.pos.npy')
+    assert pe.shape == (2, 2, 2) and pos.shape == (2, 2, 2, 256, 3)
+    np.testing.assert_array_equal(pe, cols[1])
+    # tests/golden/ref_driver_parse.npz: the files the same run left and what the REFERENCE's own lammps_parse.py, run unmodified on
+    # them, wrote (tests/golden/make_golden_driver_parse.py); the consumer must write the same 20 files, bit for bit
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_driver_parse.npz'))
+    gold = tmp_path / 'gold'
+    gold.mkdir()
+    monkeypatch.chdir(gold)
+    pre = str(gold / os.path.basename(run.PREF))
+    np.save(pre + '.virial.trgt.npy', g['P'])
+    np.save(pre + '.temp.trgt.npy', g['T'])
+    open(pre + '.thrm', 'wb').write(g['thrm_txt'].tobytes())
+    open(pre + '.traj', 'wb').write(g['traj_txt'].tobytes())
+    parse.main(['-n', 't1', '-e', 'LJ'])
+    for n in parse.COLUMNS + ('natoms', 'box', 'pos'):
+        got, want = np.load(pre + '.%s.npy' % n), g['ref_' + n]
+        assert got.dtype == want.dtype and got.shape == want.shape, n
+        assert got.tobytes() == want.tobytes(), n
+    assert g['ref_pos'].shape == pos.shape and g['ref_pe'].shape == pe.shape
 
 
 def test_cycles_that_write_nothing_go_to_the_engine_as_one_call(tmp_path, oracle):

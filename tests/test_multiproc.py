@@ -165,3 +165,66 @@ def test_bench_under_torchrun_uses_rccl(tmp_path):
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d['n_gpus'] == 1 and d['config']['backend'] == 'nccl' and d['config']['world_size_seen_by_backend'] == 1
     assert d['scaling'] == 'strong' and d['config']['replicas_total'] == 64 and d['value'] > 1e5
+
+
+DUMP_NAMES = ['box.npy', 'dxdvdt.npy', 'slot.npy', 'thermo.npy', 'v.npy', 'x.npy']
+
+
+def _same_dumps(a, b, ns, natoms):
+    shapes = {'box.npy': (ns,), 'dxdvdt.npy': (ns, 3), 'slot.npy': (ns,), 'thermo.npy': (ns, 17), 'v.npy': (ns, 3 * natoms),
+              'x.npy': (ns, 3 * natoms)}
+    assert sorted(os.listdir(str(a))) == sorted(os.listdir(str(b))) == DUMP_NAMES
+    for n in DUMP_NAMES:
+        xa, xb = np.load(str(a / n)), np.load(str(b / n))
+        assert xa.dtype == np.float64 and xa.shape == shapes[n] and np.isfinite(xa).all(), n
+        assert np.array_equal(xa, xb), n
+    assert np.array_equal(np.load(str(a / 'slot.npy')), np.arange(ns))
+
+
+def test_bench_dump_outputs_are_the_same_for_the_same_arguments(tmp_path, oracle):
+    """--dump-outputs DIR: what the last of the `--steps` timed cycles left (state and thermo rows of every replica), float64; two runs
+    with the same arguments write the same arrays (CPU, the oracle stand-in as the engine)"""
+    argv = '--sz 4 --rows 2 --tn 2 --mod 2 --steps 3 --warmup 1 --equil 0 --no-cpu --dump-outputs'.split()
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    d = _bench_line(tmp_path, 1, argv + [str(a)])
+    _bench_line(tmp_path, 1, argv + [str(b)])
+    assert d['steps'] == 3 and d['roofline']['launches'] == 3          # the stand-in counts one launch per cycle
+    _same_dumps(a, b, 4, 256)
+
+
+def test_bench_dump_outputs_sample_a_large_grid(tmp_path, monkeypatch):
+    """beyond bench.DUMP_BYTES the dump holds a fixed, seeded sample of the replicas, named by `slot`, the same every time"""
+    import bench
+
+    class Eng:
+        def get_state(self):
+            x = np.arange(40 * 6, dtype=np.float64).reshape(40, 6)
+            return x, -x, np.arange(40.0), np.ones((40, 3))
+
+        def thermo(self):
+            return np.arange(40 * 17, dtype=np.float64).reshape(40, 17)
+
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 10 * (8 * (6 + 6 + 1 + 3 + 17) + 8))
+    bench.dump_outputs(Eng(), str(tmp_path / 'a'), 100)
+    bench.dump_outputs(Eng(), str(tmp_path / 'b'), 100)
+    slot = np.load(str(tmp_path / 'a' / 'slot.npy'))
+    assert len(slot) == 10 and (np.diff(slot) > 0).all() and slot.min() >= 100 and slot.max() < 140
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'box.npy')), slot - 100)
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'thermo.npy'))[:, 0], (slot - 100) * 17)
+    for n in DUMP_NAMES:
+        assert np.array_equal(np.load(str(tmp_path / 'a' / n)), np.load(str(tmp_path / 'b' / n))), n
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_gpu(tmp_path):
+    """bench.py --dump-outputs on the HIP engine, two fresh processes with the same arguments: the same arrays, bit for bit"""
+    import json
+    lines = []
+    for name in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+               '--equil', '0', '--no-cpu', '--dump-outputs', str(tmp_path / name)]
+        r = subprocess.run(cmd, timeout=600, cwd=str(tmp_path), capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    assert lines[0]['steps'] == 3 and lines[0]['window']['cycles_per_launch'] * lines[0]['roofline']['launches'] == 3
+    _same_dumps(tmp_path / 'a', tmp_path / 'b', 64, 256)
