@@ -157,6 +157,12 @@ int nm_synchronize(nm_ctx *ctx);
 #define NM_ST_NONFINITE 8       /* non-finite energy                                                          */
 #define NM_ST_SYNC_TIMEOUT 16   /* a hand-over between the workgroups of a replica timed out                  */
 #define NM_ST_NOT_RESIDENT 32   /* the launch's workgroups were not resident together; nothing was changed    */
+#define NM_ST_FORCE_RANGE 64    /* a force left the fixed-point range of the half-list kernels (one workgroup per replica, N > 256; a pair
+                                   closer than ~0.604 sigma).  nm_eval: the forces are not valid, NM_ERR_STATE.  nm_run_md: the run stops,
+                                   the replica keeps the state it started from, NM_ERR_STATE.  Inside a block it is never reported: such a
+                                   trajectory is rejected as an HMC move (counted in nth, not in nah; trace criterion +inf) and the chain
+                                   goes on — its energy error would be far beyond any Metropolis acceptance (the exact forces of the oracle
+                                   give > 10^3 kT); U and W stay exact (fp64 sums).  Never set by the other kernels. */
 int nm_get_status(nm_ctx *ctx, int *status);
 
 /* measurement: HIP-event time of the nm_run_block kernel launches since the last reset */
@@ -190,7 +196,7 @@ int nm_get_trace(nm_ctx *ctx, double *trace, int mod);
 int nm_set_counters(nm_ctx *ctx, const double *count, const float *ratio);
 /* slot -> buffer map after exchanges (which initial configuration sits in slot k) */
 int nm_get_perm(nm_ctx *ctx, int *perm);
-/* dh of every pair visited by the last nm_exchange, sweep order */
+/* dh of every pair visited by the last exchange sweep (nm_exchange, or the last cycle of nm_run_cycles), sweep order */
 int nm_get_exchange_crit(nm_ctx *ctx, double *crit, int n);
 
 #ifdef __cplusplus

@@ -307,16 +307,17 @@ void harvest(nm_ctx *c, EvPair &e)
 
 std::string status_text(const nm_ctx *c, int k, int bits)
 {
-    char buf[640];
+    char buf[768];
     std::snprintf(buf, sizeof buf,
-                  "replica slot %d (global %d) left the supported regime:%s%s%s%s%s%s", k, c->slot0 + k,
+                  "replica slot %d (global %d) left the supported regime:%s%s%s%s%s%s%s", k, c->slot0 + k,
                   (bits & ST_LIST_OVERFLOW) ? " neighbour list overflow;" : "",
                   (bits & ST_BOX_TOO_SMALL) ? " box edge < 2*rc (minimum image invalid);" : "",
                   (bits & ST_TAPE_EXHAUSTED) ? " rng tape exhausted;" : "",
                   (bits & ST_NONFINITE) ? " non-finite energy;" : "",
                   (bits & ST_SYNC_TIMEOUT) ? " cluster hand-off timed out (workgroups not co-resident?);" : "",
                   (bits & ST_NOT_RESIDENT) ? " the launch's workgroups were not resident together (CUs taken by another process, stream or a CU "
-                                             "mask): nothing was changed;" : "");
+                                             "mask): nothing was changed;" : "",
+                  (bits & ST_FORCE_RANGE) ? " force outside the fixed-point range of the half-list kernel (a pair closer than 0.604 sigma);" : "");
     return buf;
 }
 
@@ -441,7 +442,7 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed)
     c->step = keep;
     p.launch_id = first_id;
     p.mod = mod; p.ncycles = ncycles; p.nt = c->cfg.nt; p.row0 = c->cfg.row0;
-    p.rowbar = c->d_rowsync; p.rowgo = c->d_rowsync + nrows; p.cyc_abort = (int *)(c->d_rowsync + 2 * nrows); p.nswaps = c->d_nswaps;
+    p.rowbar = c->d_rowsync; p.rowgo = c->d_rowsync + nrows; p.cyc_abort = (int *)(c->d_rowsync + 2 * nrows); p.nswaps = c->d_nswaps; p.xcrit = c->d_xcrit;
     p.order = nullptr; p.tape = nullptr; p.trace = nullptr;
     if (testing())
         if (const char *e = std::getenv("NM_INJECT_CENSUS"))

@@ -15,7 +15,8 @@ enum : uint32_t { S_ROLL = 0, S_ACC = 1, S_VOL = 2, S_DISP_XY = 3, S_DISP_Z = 4,
                   S_EXCH = 7, S_ITER_XY = 8, S_ITER_Z = 9, S_ITER_ACC = 10 };
 
 // status bits per slot
-enum : int { ST_LIST_OVERFLOW = 1, ST_BOX_TOO_SMALL = 2, ST_TAPE_EXHAUSTED = 4, ST_NONFINITE = 8, ST_SYNC_TIMEOUT = 16, ST_NOT_RESIDENT = 32 };
+enum : int { ST_LIST_OVERFLOW = 1, ST_BOX_TOO_SMALL = 2, ST_TAPE_EXHAUSTED = 4, ST_NONFINITE = 8, ST_SYNC_TIMEOUT = 16, ST_NOT_RESIDENT = 32,
+             ST_FORCE_RANGE = 64 };
 
 struct KParams {
     int N, nslots, slot0;          // atoms, local replicas, global index of local slot 0
@@ -70,6 +71,7 @@ struct KParams {
     unsigned int *rowbar, *rowgo;  // per local row: workgroups arrived (monotonic within the launch), cycles released by the row's leader
     int *cyc_abort;                // set by whoever leaves the launch early: nobody waits for a row that will not complete
     int *nswaps;                   // accepted swaps of the launch (atomic)
+    double *xcrit;                 // dh of every pair the exchange sweeps visit, [local row][pair] in sweep order (nm_get_exchange_crit)
 };
 
 // status bits reach the host through status[] (last launch) and status_acc[] (everything since the host last looked); a block

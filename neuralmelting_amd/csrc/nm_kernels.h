@@ -1057,6 +1057,22 @@ struct Replica {
     // HALF: the force array of the own atoms as 64-bit fixed point while a pair loop runs.  fma(t, scale, 1.5 * 2^52) leaves
     // round(t * scale) in the low mantissa bits (|t * scale| < 2^51); the difference of the bit patterns is that integer.
     static constexpr double FIX_SCALE = 68719476736.0 /* 2^36 */, FIX_MAGIC = 6755399441055744.0 /* 1.5 * 2^52 */;
+    // The trick holds while |addend| < 2^15 force units; beyond it the integer is garbage.  Checked by a compare, not prevented: a pair's
+    // addend is at most its force, |F(r)| = 24 (2 r^-13 - r^-7), which grows as r shrinks below 1.12 sigma and reaches 2^15 at
+    // r = 0.604173 sigma (r^2 = 0.365025): every interacting pair is compared with FIX_R2 (a little above, so the test errs on the side of
+    // reporting), every row total with 2^15.  The pair's compare costs nothing: it takes the place of the own-range compare, which the
+    // shipped half-list configurations do not need (ONE_WG below).
+    static constexpr double FIX_RANGE = 32768.0 /* 2^15 */, FIX_R2 = 0.36503;
+    // CfgMidH and CfgLargeH run at one workgroup per replica only (launch_kind picks them at Q = 1): every listed atom is an own atom.
+    // (-DNM_HALF_LIST=2 builds half lists for the cluster configurations too: there the own-range compare stays.)
+    static constexpr bool ONE_WG = C::HALF && NM_HALF_LIST == 1;
+    int fr_bad = 0;    // HALF: this thread met an addend or a row total outside the fixed-point range since the last energy evaluation
+    int fr_hit = 0;    // HALF, uniform over the cluster: an evaluation since the current move started met one (take_sums); the forces are not
+                       // to be trusted
+    // The flag rides along in the pair-count sum of the energy evaluation: every flagged thread adds FR_TAG.  The counts are integers below
+    // 2^25 and at most 512 threads x 8 workgroups add the tag (2^52 at most), so the sums stay exact in any order, over the workgroup and
+    // over the cluster (finish_sums): every workgroup of a replica takes the same decision.
+    static constexpr double FR_TAG = 1099511627776.0; // 2^40
     __device__ __forceinline__ void fixed_add(unsigned int byte_off, double t, double scale) const
     {
         const double y = __builtin_fma(t, scale, FIX_MAGIC);
@@ -1113,7 +1129,8 @@ struct Replica {
         for (int q = 0; q < W; ++q) {
             r2[q] = dx[q] * dx[q] + dy[q] * dy[q] + dz[q] * dz[q];
             in[q] = ok[q] && r2[q] < rc2;
-            own[q] = ((unsigned int)j[q] - own8) < ownn8;
+            own[q] = ONE_WG || ((unsigned int)j[q] - own8) < ownn8;
+            fr_bad |= (in[q] && r2[q] < FIX_R2) ? 1 : 0; // (the fixed-point range, FIX_R2)
         }
 #pragma unroll
         for (int q = 0; q < W; ++q) y[q] = __builtin_amdgcn_rcp(r2[q]);
@@ -1308,6 +1325,8 @@ struct Replica {
                 // an integer, the total does not depend on the order); integration waits for the barrier behind the loop (half_end)
                 if (i < a1) {
                     eacc += e; wacc += w; nacc += np;
+                    // (a NaN total fails the compares too)
+                    fr_bad |= !(fabs(ax) < FIX_RANGE) | !(fabs(ay) < FIX_RANGE) | !(fabs(az) < FIX_RANGE);
                     fixed_add((unsigned int)C::OFF_FRC + 8u * (unsigned int)i, ax, FIX_SCALE);
                     fixed_add((unsigned int)(C::OFF_FRC + A1) + 8u * (unsigned int)i, ay, FIX_SCALE);
                     fixed_add((unsigned int)(C::OFF_FRC + 2 * A1) + 8u * (unsigned int)i, az, FIX_SCALE);
@@ -1684,7 +1703,10 @@ struct Replica {
         TLINE(3);
         PROF_BEGIN();
         st_evals += 1.0;
+        // HALF: whether a thread left the fixed-point range rides along with the pair count (FR_TAG; the force-only evaluations of a
+        // trajectory leave their threads' flags to the energy evaluation that ends it)
         double s[4] = { eacc, wacc, nacc, kacc };
+        if constexpr (C::HALF) { s[2] += fr_bad ? FR_TAG : 0.0; fr_bad = 0; }
         block_sum<4, NW, NVMAX>(s, red, parity); // over this workgroup's atoms
         PROF_END(4);
         TLINE(4);
@@ -1730,6 +1752,11 @@ struct Replica {
     __device__ void take_sums()
     {
         U = 0.5 * psum[0]; W = 0.5 * psum[1];
+        if constexpr (C::HALF)
+            if (psum[2] >= FR_TAG) { // (garbage forces: a Hamiltonian move that would start from them evaluates again)
+                fr_hit = 1; set_fresh(false);
+                psum[2] = fmod(psum[2], FR_TAG);
+            }
         st_eevals += 1.0; st_pairs += 0.5 * psum[2];
         if (!(U == U) || isinf(U)) status |= ST_NONFINITE;
     }
@@ -2164,7 +2191,8 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
     for (int i = tid; i < N; i += BLOCK) {
         const double sr = sqrt(rho[i]);
         if (i >= a0 && i < a1) sq_own += sr;
-        rho[i] = 1.0 / sr;
+        rho[i] = sr > 0.0 ? 1.0 / sr : 0.0; // (an atom with nothing inside rc: no pair inside rc reads it, and a listed pair beyond rc
+                                             //  multiplies it by an exact zero — 1 / sqrt(0) = inf would make that 0 x inf = NaN)
     }
     __syncthreads();
     // pass 2: forces (and energy, virial) of this workgroup's atoms.  1/r comes from v_rsq_f64 + two Newton steps (~1 ulp), which
@@ -2425,7 +2453,8 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     U0 = 0.0; W0 = 0.0; c_pe = 0.0; c_vol = 0.0; c_volnew = 0.0; c_boxl = 0.0;
     double &nth_entry = R.ust(22); // (stats column 7)
     nth_entry = nth;
-    const int fatal = ST_BOX_TOO_SMALL | ST_LIST_OVERFLOW | ST_SYNC_TIMEOUT;
+    // (ST_FORCE_RANGE is set here only by nm_run_md: a plain NVE run has no move to reject, so it stops)
+    const int fatal = ST_BOX_TOO_SMALL | ST_LIST_OVERFLOW | ST_SYNC_TIMEOUT | ST_FORCE_RANGE;
 
     // state carried across the evaluation of a move
     int phase = PH_INIT, m = 0;
@@ -2465,7 +2494,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         if (phase == PH_INIT) {
             if (p.eval_only) { // nm_eval: batched lj_energy_force on the resident states
                 if (writer) {
-                    p.evalU[slot] = R.U; p.evalW[slot] = R.W; report_status(p, slot, R.status, false);
+                    p.evalU[slot] = R.U; p.evalW[slot] = R.W; report_status(p, slot, R.status | ((C::HALF && R.fr_hit) ? ST_FORCE_RANGE : 0), false);
                     double *st = p.stats + NM_STATS_COLS * (size_t)slot;
                     st[0] += R.st_evals; st[1] += R.st_rebuilds; st[2] += R.st_eevals; st[3] += R.st_pairs;
                 }
@@ -2523,9 +2552,16 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         } else { // PH_HMC_STEP: the trajectory is complete, energies at its end are in
             const double etotnew = R.U / et + 0.5 * p.mvv2e * mv2new / et; // remcmc:618-622
             crit = etotnew - c_pe;
-            if (p.md_mode) acc = true; // plain NVE run (init_sample -is, remcmc:421-425): nothing to accept
-            else {
-                acc = R.metropolis(crit, S_ACC, (uint32_t)m, 0);
+            // HALF: a trajectory whose forces left the fixed-point range is rejected: criterion +inf (the uniform is drawn as for any
+            // criterion > 0), and no draw accepts it
+            bool out_of_range = false;
+            if constexpr (C::HALF) out_of_range = R.fr_hit != 0;
+            if (out_of_range) crit = __builtin_huge_val();
+            if (p.md_mode) { // plain NVE run (init_sample -is, remcmc:421-425): nothing to accept.  Forces out of range stop it: the replica
+                acc = true;  // keeps the state it started from and the host reports the reason (nm_run_md returns NM_ERR_STATE)
+                if (out_of_range) R.status |= ST_FORCE_RANGE;
+            } else {
+                acc = R.metropolis(crit, S_ACC, (uint32_t)m, 0) && !out_of_range;
                 if (acc) nah += 1.0;
                 else { R.restore(true); R.wrap(); R.U = U0; R.W = W0; }
             }
@@ -2595,6 +2631,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 PROF_END(11);
             } else { // hamiltonian_mc, remcmc:598-608
                 if (!p.md_mode) nth += 1.0;
+                if constexpr (C::HALF) R.fr_hit = 0; // (the move's own evaluations decide; a start from forces that were out of range evaluates again: take_sums)
                 const uint32_t tag = R.draw_tag((uint32_t)m);
                 mv2_0 = R.hmc_velocities(q6(t), tag, R.gauss_for == m ? 1 : 0);
                 c_h = uniform(q6(dt)); // timestep %f
@@ -2880,6 +2917,7 @@ __global__ void __launch_bounds__(C::BLOCK NM_MIN_WAVES) nm_cycles_kernel(const 
                     for (int vv = nt - 1; vv >= 0; --vv)
                         for (int w = 0; w < vv; ++w, ++q) {
                             const double dh = (E[vv] - E[w]) * (IE[vv] - IE[w]) + (PF[vv] - PF[w]) * (V[vv] - V[w]);
+                            if (p.xcrit) p.xcrit[row * ppr + q] = dh; // (exchange_row's index: local row, pair in sweep order)
                             const double e = exp(dh);
                             const double mm = (e != e) ? e : (e < 1.0 ? e : 1.0);
                             if (Uu[q] <= mm) {

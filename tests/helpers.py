@@ -34,21 +34,28 @@ class OracleLoop:
     """gen_samples / gen_mc_params / replica_exchange on the oracle, holding STATE like the reference does"""
 
     def __init__(self, O, sz, P, T, *, dx=0.03125, dv=0.03125, ppos=0.125, pvol=0.125, nstps=8, bulk=True, seed=256,
-                 row0=0, nrows=None, iter_revert=False, nthreads=0, el='LJ', k0=None, nk=None):
+                 row0=0, nrows=None, iter_revert=False, nthreads=0, el='LJ', k0=None, nk=None, states=None):
+        """states: explicit (x[ns][3N], v[ns][3N], box[ns], dxdvdt[ns][3]) of any N instead of the lattice states of sz^3 cells
+        (sz is then ignored)"""
         self.O = O
         self.P, self.T = P, T
         self.nt = len(T)
         self.row0 = row0
         self.nrows = len(P) - row0 if nrows is None else nrows
         self.ns = self.nrows * self.nt
-        self.natoms = 4 * sz ** 3
+        self.natoms = 4 * sz ** 3 if states is None else np.asarray(states[0]).reshape(self.ns, -1).shape[1] // 3
         self.el = el
         self.kw = dict(natoms=self.natoms, nstps=nstps, bulk=bulk, ppos=ppos, pvol=pvol, lat=lattice.LAT[el][1], seed=seed,
                        iter_revert=iter_revert, nthreads=nthreads)
         if el == 'Al':
             self.kw.update(units=1, mass=lattice.MASS['Al'], pot=1)
         self.seed = seed
-        self.x, self.v, self.box, self.d = lattice.init_states(sz, P, T, dx, dv, el=el, seed=seed, row0=row0, nrows=self.nrows)
+        if states is None:
+            self.x, self.v, self.box, self.d = lattice.init_states(sz, P, T, dx, dv, el=el, seed=seed, row0=row0, nrows=self.nrows)
+        else:
+            self.x, self.v = (np.array(a, dtype=np.float64).reshape(self.ns, 3 * self.natoms) for a in states[:2])
+            self.box = np.array(states[2], dtype=np.float64).reshape(self.ns)
+            self.d = np.array(states[3], dtype=np.float64).reshape(self.ns, 3)
         self.et, self.pf, self.tq = (constants_lj if el == 'LJ' else constants_metal)(P, T, row0, self.nrows)
         self.slot0 = row0 * self.nt
         if nk is not None:  # an arbitrary slot range inside the covering rows (a pressure row split across ranks)
@@ -67,6 +74,22 @@ class OracleLoop:
                                 slot0=self.slot0, step=step, **self.kw)
         self.x, self.v, self.box = out['x'], out['v'], out['box']
         self.thermo, self.counters, self.ratios = out['thermo'], out['counters'], out['ratios']
+
+    def run_block_traced(self, mod, step):
+        """run_block one replica at a time through Sim.run_block, which also records the per-move trace: returns trace[ns][mod][4]"""
+        kw = self.kw
+        tr = np.zeros((self.ns, mod, 4))
+        for k in range(self.ns):
+            s = self.O.Sim(self.natoms, kw.get('units', 0), kw.get('mass', 1.0), kw.get('pot', 0))
+            s.set_rng(self.seed, self.slot0 + k, step)
+            o = s.run_block(self.x[k], self.v[k], self.box[k], self.d[k], mod=mod, nstps=kw['nstps'], bulk=kw['bulk'], ppos=kw['ppos'],
+                            pvol=kw['pvol'], lat=kw['lat'], t=self.tq[k], et=self.et[k], pf=self.pf[k], iter_revert=kw['iter_revert'],
+                            trace=True)
+            s.close()
+            self.x[k], self.v[k], self.box[k] = o['x'], o['v'], o['box']
+            self.thermo[k], self.counters[k], self.ratios[k] = o['thermo'], o['counters'], o['ratios']
+            tr[k] = o['trace']
+        return tr
 
     def rows(self):
         """the 17 .thrm columns (remcmc:235-245)"""

@@ -26,10 +26,16 @@ def _single(e, step0, ncyc, mod):
         e.exchange(count=False)
 
 
+# nm_stats_get columns that are neither times nor placements: all but 4 (ticks of the 100 MHz clock) and 5 (blocks whose cluster handed
+# over inside one XCD, a property of where the workgroups landed)
+STATS_WORK_COLS = [0, 1, 2, 3, 6, 7, 8, 9]
+
+
 def _everything(e):
     e.synchronize()
     x, v, box, d = e.get_state()
-    return dict(x=x, v=v, box=box, d=d, thermo=e.thermo(), perm=e.perm(), status=e.status())
+    return dict(x=x, v=v, box=box, d=d, thermo=e.thermo(), perm=e.perm(), status=e.status(), crit=e.exchange_crit(),
+                stats=e.stats()[:, STATS_WORK_COLS])
 
 
 # (element, sz, pressure rows, temperatures, workgroups per replica the grid gets, has a fused kernel?)

@@ -13,7 +13,7 @@ RTOL = 1e-6  # north_star tolerance for floating point
 
 def make_engine(loop, sz, P, T, **kw):
     import neuralmelting_amd as nm
-    e = nm.Engine(4 * sz ** 3, P, T, row0=loop.row0, nrows=loop.nrows, seed=loop.seed, **kw)
+    e = nm.Engine(loop.natoms, P, T, row0=loop.row0, nrows=loop.nrows, seed=loop.seed, **kw)
     e.set_state(loop.x, loop.v, loop.box, loop.d)
     return e
 
@@ -227,7 +227,7 @@ def test_tape_replay_parity(oracle):
 
 
 # every instantiation nm_api.hip's launch_kind can pick: 5^3 / 6^3 -> CfgMidH (Q = 1: half lists), CfgMid (Q = 2), CfgMidQ4, CfgMidQ8; 8^3 -> CfgLargeH (Q = 1: half lists), CfgLarge (Q = 2, 4)
-LARGE_CELL_CASES = [(sz, q) for sz in (5, 6) for q in (1, 2, 4, 8)] + [(8, 1), (8, 2), (8, 4)]
+LARGE_CELL_CASES = [(sz, q) for sz in (5, 6) for q in (1, 2, 4, 8)] + [(7, 1), (7, 2), (7, 4), (8, 1), (8, 2), (8, 4)]
 
 
 @pytest.mark.parametrize('bulk', [True, False])
@@ -237,10 +237,16 @@ def test_block_parity_large_cells(oracle, monkeypatch, sz, cus, bulk):
     8^3: 2048 atoms) against the oracle, bulk and iterative position moves, at every workgroups-per-replica setting the size
     has an instantiation for"""
     monkeypatch.setenv('NM_CUS_PER_REPLICA', str(cus))
+    _block_parity(oracle, cus, bulk, sz=sz)
+
+
+def _block_parity(oracle, cus, bulk, sz=None, states=None):
+    """one block of bulk or iterative position moves and volume moves against the oracle: counters and decisions exact, energies
+    1e-6, x 1e-8, v 1e-7"""
     mod = 6
     P, T = grids(1, 2)
     kw = dict(bulk=bulk, ppos=0.3, pvol=0.2)
-    loop = OracleLoop(oracle, sz, P, T, **kw)
+    loop = OracleLoop(oracle, sz, P, T, states=states, **kw)
     e = make_engine(loop, sz, P, T, **kw)
     assert e.cus_per_replica == cus
     e.set_trace(True)
@@ -264,10 +270,15 @@ def test_short_trajectories_parity_large_cells(oracle, monkeypatch, sz, cus, nst
     outside the pair loop, fused middle steps, last evaluation carrying the kinetic energy) at every workgroups-per-replica
     setting, two blocks so that the second starts from velocities and step sizes the first one left"""
     monkeypatch.setenv('NM_CUS_PER_REPLICA', str(cus))
+    _short_trajectories_parity(oracle, cus, nstps, sz=sz)
+
+
+def _short_trajectories_parity(oracle, cus, nstps, sz=None, states=None):
+    """two HMC-heavy blocks of one- or three-step trajectories with adapt between them, against the oracle"""
     mod = 5
     P, T = grids(1, 2)
     kw = dict(bulk=True, ppos=0.1, pvol=0.1, nstps=nstps)
-    loop = OracleLoop(oracle, sz, P, T, **kw)
+    loop = OracleLoop(oracle, sz, P, T, states=states, **kw)
     e = make_engine(loop, sz, P, T, **kw)
     assert e.cus_per_replica == cus
     for step in range(2):
@@ -283,6 +294,43 @@ def test_short_trajectories_parity_large_cells(oracle, monkeypatch, sz, cus, nst
         e.adapt()
         loop.adapt()
     e.close()
+
+
+# atom counts that are not 4 sz^3, at every workgroups-per-replica setting of their kind: ragged waves and rows, own ranges that are not a
+# multiple of anything (100 / 8), one past a kind boundary (257: CfgMidH's rows, 865: CfgLarge), one short of a full kind (255, 2047)
+RAGGED_CASES = [(n, q) for n, qs in ((100, (1, 2, 4, 8)), (255, (1, 2, 4, 8)), (257, (1, 2, 4, 8)), (865, (1, 2, 4)), (2047, (1, 2, 4)))
+                for q in qs]
+
+
+def ragged_states(n, P, T):
+    """n atoms of the lattice states of the smallest fcc cell that holds them, 4^3 at least (its box is above 2 rc), each replica
+    keeping its own random subset: a crystal with vacancies, at the box the lattice start relaxed to (the oracle's run_blocks takes
+    any natoms)"""
+    from neuralmelting_amd import lattice
+    sz = 4
+    while 4 * sz ** 3 < n:
+        sz += 1
+    x, v, box, d = lattice.init_states(sz, P, T, 0.03125, 0.03125)
+    rng = np.random.default_rng(n)
+    ns = len(box)
+    keep = [np.sort(rng.permutation(4 * sz ** 3)[:n]) for _ in range(ns)]
+    x = np.stack([x[k].reshape(-1, 3)[keep[k]].reshape(-1) for k in range(ns)])
+    v = np.stack([v[k].reshape(-1, 3)[keep[k]].reshape(-1) for k in range(ns)])
+    return x, v, box, d
+
+
+@pytest.mark.parametrize('bulk', [True, False])
+@pytest.mark.parametrize('n,cus', RAGGED_CASES)
+def test_block_parity_ragged_atom_counts(oracle, monkeypatch, n, cus, bulk):
+    monkeypatch.setenv('NM_CUS_PER_REPLICA', str(cus))
+    _block_parity(oracle, cus, bulk, states=ragged_states(n, *grids(1, 2)))
+
+
+@pytest.mark.parametrize('nstps', [1, 3])
+@pytest.mark.parametrize('n,cus', RAGGED_CASES)
+def test_short_trajectories_parity_ragged_atom_counts(oracle, monkeypatch, n, cus, nstps):
+    monkeypatch.setenv('NM_CUS_PER_REPLICA', str(cus))
+    _short_trajectories_parity(oracle, cus, nstps, states=ragged_states(n, *grids(1, 2)))
 
 
 @pytest.mark.parametrize('sz,cus', [(4, 2), (4, 4), (4, 8)] + [(sz, q) for (sz, q) in LARGE_CELL_CASES if q > 1])
@@ -375,4 +423,77 @@ def test_failure_is_loud():
     e.set_state(x, np.zeros_like(x), [4.0], [[0.03, 0.03, 0.004]])
     with pytest.raises(nm.NMError):
         e.eval()
+    e.close()
+
+
+@pytest.mark.parametrize('sz,cus', [(5, 1), (8, 1), (5, 2)])
+def test_hmc_block_from_a_close_contact(oracle, monkeypatch, sz, cus):
+    """HMC-only blocks that start with a pair at 0.58 sigma (|F| = 4.6e4 > 2^15: beyond the fixed-point range of the half-list kernels
+    CfgMidH (5^3, one workgroup) and CfgLargeH (8^3, one workgroup); CfgMid (5^3, two workgroups) sums full lists in fp64).  A half-list
+    kernel rejects every trajectory that met such a force (trace criterion +inf); the oracle integrates it exactly and rejects it for its
+    energy error (> 10^3 kT).  Decisions, counters, energies and the end state must be the oracle's (before the fix the half-list kernels
+    rejected these trajectories for a criterion computed from wrapped fixed-point forces, 1e13-1e14 where the exact one is 1e21-1e36)."""
+    monkeypatch.setenv('NM_CUS_PER_REPLICA', str(cus))
+    mod = 3
+    kw = dict(bulk=True, ppos=0.0, pvol=0.0)
+    loop, P, T = close_contact_loop(oracle, sz, **kw)
+    e = make_engine(loop, sz, P, T, **kw)
+    assert e.cus_per_replica == cus
+    e.set_trace(True)
+    e.run_block(mod)
+    rows, tr = e.thermo(), e.trace(mod)
+    to = loop.run_block_traced(mod, 0)
+    ro = loop.rows()
+    np.testing.assert_array_equal(tr[:, :, :2], to[:, :, :2])               # branch (all HMC), accepted
+    assert (tr[:, :, 1] == 0).all()                                         # every trajectory rejected
+    assert (to[:, :, 2] > 1e3).all()                                        # the oracle's reason: the energy error
+    if cus == 1:
+        assert np.isinf(tr[:, :, 2]).all()                                  # the half-list kernels: out of range, rejected as such
+    else:
+        # the full-list kernel integrates the same exploding trajectory in fp64 (atoms driven into one another at |F| ~ 1e7 and beyond):
+        # it amplifies the last-bit differences of the summation order to O(1), so its criterion is compared by what decides the move
+        assert np.isfinite(tr[:, :, 2]).all() and (tr[:, :, 2] > 1e3).all()
+    np.testing.assert_allclose(tr[:, :, 3], to[:, :, 3], rtol=RTOL)
+    np.testing.assert_array_equal(rows[:, 8:], ro[:, 8:])
+    np.testing.assert_allclose(rows[:, :8], ro[:, :8], rtol=RTOL)
+    assert (e.status() == 0).all()
+    x, v, box, d = e.get_state()
+    np.testing.assert_allclose(x, loop.x, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(v, loop.v, rtol=0, atol=1e-7)
+    e.close()
+
+
+def close_contact_loop(oracle, sz, **kw):
+    """the lattice states of sz^3 cells with atom 1 moved to 0.58 sigma of atom 0 in every replica"""
+    P, T = grids(1, 2)
+    loop = OracleLoop(oracle, sz, P, T, **kw)
+    u = np.array([1.0, 2.0, 2.0]) / 3.0
+    for k in range(loop.ns):
+        loop.x[k, 3:6] = loop.x[k, 0:3] + 0.58 * u
+    return loop, P, T
+
+
+@pytest.mark.parametrize('sz,cus', [(5, 1), (8, 1), (5, 2)])
+def test_md_from_a_close_contact(oracle, monkeypatch, sz, cus):
+    """nm_run_md (plain NVE, nothing to reject) from a 0.58 sigma contact: the half-list kernels stop with NM_ST_FORCE_RANGE and leave the
+    state as it was; the full-list kernel integrates it"""
+    from neuralmelting_amd.engine import NMError
+    monkeypatch.setenv('NM_CUS_PER_REPLICA', str(cus))
+    loop, P, T = close_contact_loop(oracle, sz)
+    e = make_engine(loop, sz, P, T)
+    assert e.cus_per_replica == cus
+    e.run_md(4)
+    if cus == 1:
+        with pytest.raises(NMError, match='fixed-point range'):
+            e.synchronize()
+        assert (e.status() == 64).all()                                     # NM_ST_FORCE_RANGE
+        x, v, box, d = e.get_state()
+        np.testing.assert_array_equal(x, loop.x)
+        np.testing.assert_array_equal(v, loop.v)
+        np.testing.assert_array_equal(box, loop.box)
+    else:
+        e.synchronize()
+        assert (e.status() == 0).all()
+        x, v, box, d = e.get_state()
+        assert np.isfinite(x).all() and np.isfinite(v).all() and not np.array_equal(x, loop.x)
     e.close()
