@@ -134,6 +134,21 @@ int nm_get_thermo(nm_ctx *ctx, double *rows);
    Neither call looks at the queue's outcome: an error is reported by the next synchronising call as always. */
 int nm_snapshot(nm_ctx *ctx);
 int nm_snapshot_fetch(nm_ctx *ctx, double *rows, double *x, double *box);
+/* `ncycles` cycles of the main loop WITH outputs (remcmc:977-995 with write_outputs, remcmc:983-985): what nm_run_cycles does, plus for every cycle the
+   record nm_snapshot would have taken behind that cycle's block (17 thermo columns, positions, box; slot order), asynchronous.  The chains and every
+   record equal, bit for bit, ncycles times nm_run_block + nm_snapshot + nm_adapt + nm_exchange, on the fused launch (nm_cycles_kernel writes the records
+   itself, behind each completed block) and on the loop of single launches (a copy behind each block) alike.  The records of a call fill a ring in device
+   memory that one D2H on the side stream brings to pinned host memory behind the call's last launch; they join the queue nm_snapshot_fetch drains, in the
+   order they were queued, interleaved with nm_snapshot's own.  Two rings: a driver queues call i + 1 before it fetches call i; a third call while two
+   have records pending is NM_ERR_STATE and queues nothing.  More cycles than nm_record_capacity: NM_ERR_ARG.  Whole pressure rows only
+   (NM_ERR_UNSUPPORTED).  A record is handed out only if the block it was taken behind completed: every slot's record carries a tag (call, cycle) that only
+   such a block writes; when one is wrong nm_snapshot_fetch settles the queue (a launch that can be healed is re-issued at a lower number of workgroups per
+   replica and records into the same ring), copies the ring again, and returns the queue's error if it has one (the call's remaining records are then
+   dropped).  A halt in the middle of a fused launch is NM_ERR_STATE, as for nm_run_cycles. */
+int nm_run_cycles_recorded(nm_ctx *ctx, int ncycles, int mod);
+int nm_record_capacity(const nm_ctx *ctx);   /* the most cycles one nm_run_cycles_recorded call may hold (>= 1, <= 64): a ring of nslots x (3N + 19)
+                                                doubles per cycle within 64 MiB */
+int nm_snapshot_pending(const nm_ctx *ctx);  /* records queued and not yet fetched, from either source */
 /* gen_mc_params: adapt dx, dv, dt, zero counters and ratios */
 int nm_adapt(nm_ctx *ctx);
 /* replica_exchange over the local pressure rows.  nswaps may be NULL (stays asynchronous). */

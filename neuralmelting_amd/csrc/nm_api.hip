@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <string>
 #include <thread>
 #include <vector>
@@ -93,7 +94,7 @@ struct nm_ctx {
     // Calls queued on the stream since the host last looked at the outcome (settle): if a block of them stopped because its
     // cluster grid was not resident or a hand-over timed out, nothing after it has run (KParams::halt) and the same calls are
     // issued again with fewer workgroups per replica.
-    struct Op { int kind, arg, trace; uint32_t step, launch_id; };
+    struct Op { int kind, arg, trace; uint32_t step, launch_id; int rec = -1, rec0 = 0; }; // rec, rec0: ring and first cycle it records into (-1: none)
     std::vector<Op> journal;
     int heals = 0;              // blocks re-issued at a lower Q so far
     int cluster_launches = 0;   // (NM_INJECT_CENSUS counts these)
@@ -109,6 +110,15 @@ struct nm_ctx {
     struct Snap { double *d = nullptr, *h = nullptr; hipEvent_t taken = nullptr, landed = nullptr; bool pending = false; } snap[2];
     size_t snap_doubles = 0;
     int snap_head = 0, snap_count = 0; // oldest pending slot, number pending
+    // recorded cycles (nm_run_cycles_recorded): two rings, each a device buffer of rec_cap cycles' records (nslots x (3N + NM_REC_HEAD) doubles
+    // per cycle) and its pinned host copy, which lands in one D2H on the side stream behind the call's last launch.  n: records of the call in it,
+    // next: the next one nm_snapshot_fetch hands out (the ring is free when next == n); tag0: the tag of its first record; dirty: settle re-issued
+    // launches that write it, the host copy is stale
+    struct Ring { double *d = nullptr, *h = nullptr; hipEvent_t taken = nullptr, landed = nullptr; int n = 0, next = 0; uint32_t tag0 = 0;
+                  bool dirty = false; } ring[2];
+    int rec_cap = 0;
+    uint32_t rec_calls = 0;
+    std::deque<int> fetchq; // what nm_snapshot_fetch hands out next, oldest first: -1 an nm_snapshot, r >= 0 the next record of ring r
     double *h_stage = nullptr;   // pinned host staging area (nm_set_state / nm_get_state)
     size_t stage_cap = 0;
     size_t trace_cap;
@@ -230,14 +240,17 @@ int blocks_per_cu()
     return n;
 }
 
-template <class C>
-hipError_t launch_cycles(const nm_ctx *c, const KParams &p)
+template <class C, bool REC>
+hipError_t launch_cycles_rec(const nm_ctx *c, const KParams &p)
 {
-    hipError_t e = hipFuncSetAttribute((const void *)nm_cycles_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void *)nm_cycles_kernel<C, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(nm_cycles_kernel<C>, dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
+    hipLaunchKernelGGL((nm_cycles_kernel<C, REC>), dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
     return hipGetLastError();
 }
+// the recording instantiation where the launch has a ring (KParams::rec), the outputs-off one elsewhere: the same configurations have both
+template <class C>
+hipError_t launch_cycles(const nm_ctx *c, const KParams &p) { return p.rec ? launch_cycles_rec<C, true>(c, p) : launch_cycles_rec<C, false>(c, p); }
 
 // nm_cycles_kernel is instantiated for the 4^3 clusters (LJ and Al) and the 6^3 cluster of eight.  nm_run_cycles uses it where it measured faster
 // than the loop of single launches: the 4^3 clusters of 2 and 4 workgroups (64-128 replicas: +2.4 to +2.9 % LJ, +0.5 % Al).  Clusters of 8 run 32 replicas
@@ -321,7 +334,8 @@ std::string status_text(const nm_ctx *c, int k, int bits)
     return buf;
 }
 
-enum : int { OP_BLOCK = 0, OP_ADAPT = 1, OP_EXCHANGE = 2, OP_MD = 3, OP_CYCLES = 4 }; // OP_CYCLES: arg = MOD, trace = number of cycles
+enum : int { OP_BLOCK = 0, OP_ADAPT = 1, OP_EXCHANGE = 2, OP_MD = 3, OP_CYCLES = 4, OP_RECORD = 5 }; // OP_CYCLES: arg = MOD, trace = number of cycles;
+// OP_RECORD: the record of cycle rec0 into ring rec (nm_run_cycles_recorded on the loop of single launches)
 
 // ---- the queued calls (nm_run_block, nm_run_md, nm_adapt, nm_exchange) as stream operations; issued by the API call and, after a
 // block had to be given up, again by settle()
@@ -405,15 +419,34 @@ int issue_exchange(nm_ctx *c, uint32_t step)
     return NM_OK;
 }
 
+size_t rec_cycle_doubles(const nm_ctx *c) { return (size_t)c->nslots * ((size_t)3 * c->N + NM_REC_HEAD); } // one cycle's records
+
+// the record of cycle j of ring r, copied on the stream behind that cycle's block (the loop of single launches)
+int issue_record(nm_ctx *c, int r, int j)
+{
+    const nm_ctx::Ring &g = c->ring[r];
+    RecArgs a;
+    a.x = c->d_x; a.box = c->d_box; a.therm = c->d_therm; a.steps = c->d_steps; a.count = c->d_count; a.ratio = c->d_ratio; a.slot2buf = c->d_slot2buf;
+    a.halt = c->d_halt; a.dst = g.d + (size_t)j * rec_cycle_doubles(c); a.nslots = c->nslots; a.N = c->N; a.tag = g.tag0 + (uint32_t)j;
+    hipLaunchKernelGGL(nm_record_kernel, dim3(c->nslots), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    nm_ctx::Op o{ OP_RECORD, 0, 0, 0u, 0u };
+    o.rec = r; o.rec0 = j;
+    c->journal.push_back(o);
+    return NM_OK;
+}
+
 // nm_run_cycles as stream operations: ONE launch of nm_cycles_kernel where the configuration has one and the whole grid is resident and checked by the
-// census (clusters), else the same cycles as single blocks, adapts and exchanges
-int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed)
+// census (clusters), else the same cycles as single blocks, adapts and exchanges.  rec >= 0 (nm_run_cycles_recorded): cycle k's record goes to cycle
+// rec0 + k of ring rec — written by the fused kernel itself, or copied behind each block of the loop
+int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed, int rec, int rec0)
 {
     const bool fused = c->whole_rows && c->cus > 1 && !c->over && cycles_kind_ok(c) && !c->d_tape && !c->xtape_n && !c->trace_on &&
                        !(c->use_order && (c->cus == 1 || c->over));
     if (!fused) {
         for (int k = 0; k < ncycles; ++k) {
             int rc = issue_block(c, OP_BLOCK, mod, step + (uint32_t)k, 0, nullptr, timed);
+            if (!rc && rec >= 0) rc = issue_record(c, rec, rec0 + k);
             if (!rc) rc = issue_adapt(c);
             if (!rc) rc = issue_exchange(c, step + (uint32_t)k);
             if (rc) return rc;
@@ -424,7 +457,7 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed)
     constexpr int MAX_PER_LAUNCH = 64;
     if (ncycles > MAX_PER_LAUNCH) {
         for (int k = 0; k < ncycles; k += MAX_PER_LAUNCH) {
-            const int rc = issue_cycles(c, std::min(MAX_PER_LAUNCH, ncycles - k), mod, step + (uint32_t)k, timed);
+            const int rc = issue_cycles(c, std::min(MAX_PER_LAUNCH, ncycles - k), mod, step + (uint32_t)k, timed, rec, rec >= 0 ? rec0 + k : 0);
             if (rc) return rc;
         }
         return NM_OK;
@@ -444,6 +477,7 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed)
     p.mod = mod; p.ncycles = ncycles; p.nt = c->cfg.nt; p.row0 = c->cfg.row0;
     p.rowbar = c->d_rowsync; p.rowgo = c->d_rowsync + nrows; p.cyc_abort = (int *)(c->d_rowsync + 2 * nrows); p.nswaps = c->d_nswaps; p.xcrit = c->d_xcrit;
     p.order = nullptr; p.tape = nullptr; p.trace = nullptr;
+    if (rec >= 0) { p.rec = c->ring[rec].d + (size_t)rec0 * rec_cycle_doubles(c); p.rec_tag0 = c->ring[rec].tag0 + (uint32_t)rec0; }
     if (testing())
         if (const char *e = std::getenv("NM_INJECT_CENSUS"))
             if (std::atoi(e) == c->cluster_launches) p.inj_census = 1;
@@ -459,7 +493,9 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed)
         c->ev_next = (c->ev_next + 1) % (int)c->ev.size();
     } else HIPCHK(c, launch_cycles_kind(c, p));
     census_advance(c);
-    c->journal.push_back({ OP_CYCLES, mod, ncycles, step, first_id });
+    nm_ctx::Op o{ OP_CYCLES, mod, ncycles, step, first_id };
+    o.rec = rec; o.rec0 = rec0; // (a re-issue records into the same ring)
+    c->journal.push_back(o);
     return NM_OK;
 }
 
@@ -600,10 +636,15 @@ int settle(nm_ctx *c)
                 if (e.used && e.launch_id >= c->journal[at].launch_id) { hipEventSynchronize(e.b); e.used = false; }
             std::vector<nm_ctx::Op> todo(c->journal.begin() + at, c->journal.end());
             c->journal.clear();
+            // records re-taken into a ring: its host copy (whose D2H must not overlap the re-issue) is stale, nm_snapshot_fetch copies again
+            if (c->side) HIPCHK(c, hipStreamSynchronize(c->side));
+            for (const nm_ctx::Op &o : todo)
+                if (o.rec >= 0) c->ring[o.rec].dirty = true;
             for (size_t k = 0; k < todo.size(); ++k) {
                 const nm_ctx::Op &o = todo[k];
                 if (o.kind == OP_BLOCK || o.kind == OP_MD) rc = issue_block(c, o.kind, o.arg, o.step, o.trace, k == 0 ? c->d_rerun : nullptr, o.kind == OP_BLOCK);
-                else if (o.kind == OP_CYCLES) rc = issue_cycles(c, o.trace, o.arg, o.step, true); // (its census failed: nothing had run)
+                else if (o.kind == OP_CYCLES) rc = issue_cycles(c, o.trace, o.arg, o.step, true, o.rec, o.rec0); // (its census failed: nothing had run)
+                else if (o.kind == OP_RECORD) rc = issue_record(c, o.rec, o.rec0);
                 else if (o.kind == OP_ADAPT) rc = issue_adapt(c);
                 else rc = issue_exchange(c, o.step);
                 if (rc) return rc;
@@ -650,6 +691,12 @@ void free_ctx(nm_ctx *c)
         if (sn.h) hipHostFree(sn.h);
         if (sn.taken) hipEventDestroy(sn.taken);
         if (sn.landed) hipEventDestroy(sn.landed);
+    }
+    for (auto &g : c->ring) {
+        if (g.d) hipFree(g.d);
+        if (g.h) hipHostFree(g.h);
+        if (g.taken) hipEventDestroy(g.taken);
+        if (g.landed) hipEventDestroy(g.landed);
     }
     if (c->side) hipStreamDestroy(c->side);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -1117,8 +1164,8 @@ int nm_snapshot(nm_ctx *c)
     if (c->snap_count == 2) return fail(c, NM_ERR_STATE, "nm_snapshot: two snapshots are pending; fetch one first (nm_snapshot_fetch)");
     size_t off[8];
     const size_t nd = snap_layout(c, off);
-    if (!c->side) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+    if (!c->snap_doubles) {
+        if (!c->side) HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)); // (nm_run_cycles_recorded may have made it)
         c->snap_doubles = nd;
         for (auto &sn : c->snap) {
             HIPCHK(c, dalloc(&sn.d, nd));
@@ -1143,14 +1190,99 @@ int nm_snapshot(nm_ctx *c)
     HIPCHK(c, hipEventRecord(sn.landed, c->side));
     sn.pending = true;
     ++c->snap_count;
+    c->fetchq.push_back(-1);
+    return NM_OK;
+}
+
+// ---- recorded cycles (nm_run_cycles_recorded): the records of a call fill a ring, one D2H brings the ring to the host behind the call's last
+// launch, and nm_snapshot_fetch hands them out one by one in the queue it shares with nm_snapshot.  A record carries a tag (call, cycle) that only
+// a block which completed writes: a record whose tag is wrong was not taken (its block stopped, or was re-issued behind the copy), and the fetch then
+// settles the queue — which re-issues a launch that can be healed, into the same ring — and copies the ring again.
+static const size_t REC_BUDGET = (size_t)64 << 20; // bytes of one ring: 64 cycles of the 8 x 8 grid at 256 atoms (26 MB), 5 of 1024 x 500 atoms
+
+static int record_capacity(const nm_ctx *c)
+{
+    const size_t per = rec_cycle_doubles(c) * sizeof(double);
+    return (int)std::max<size_t>(1, std::min<size_t>(64, REC_BUDGET / per));
+}
+
+// both rings, the side stream and the events, all or nothing
+static int rec_alloc(nm_ctx *c)
+{
+    const int cap = record_capacity(c);
+    const size_t nd = (size_t)cap * rec_cycle_doubles(c);
+    nm_ctx::Ring g[2];
+    hipStream_t side = nullptr;
+    hipError_t e = c->side ? hipSuccess : hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
+    for (int r = 0; r < 2 && e == hipSuccess; ++r) {
+        e = dalloc(&g[r].d, nd);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&g[r].h, nd * sizeof(double), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&g[r].taken, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&g[r].landed, hipEventDisableTiming);
+    }
+    if (e != hipSuccess) {
+        for (auto &q : g) {
+            if (q.d) hipFree(q.d);
+            if (q.h) hipHostFree(q.h);
+            if (q.taken) hipEventDestroy(q.taken);
+            if (q.landed) hipEventDestroy(q.landed);
+        }
+        if (side) hipStreamDestroy(side);
+        return fail(c, NM_ERR_HIP, std::string("nm_run_cycles_recorded: ring allocation: ") + hipGetErrorString(e));
+    }
+    if (side) c->side = side;
+    c->ring[0] = g[0]; c->ring[1] = g[1];
+    c->rec_cap = cap;
+    return NM_OK;
+}
+
+// the records of ring r still queued are dropped (a fetch that reports an error)
+static void drop_ring(nm_ctx *c, int r)
+{
+    c->ring[r].n = c->ring[r].next = 0;
+    c->fetchq.erase(std::remove(c->fetchq.begin(), c->fetchq.end(), r), c->fetchq.end());
+}
+
+static int fetch_record(nm_ctx *c, int r, double *rows, double *x, double *box)
+{
+    nm_ctx::Ring &g = c->ring[r];
+    HIPCHK(c, hipEventSynchronize(g.landed));
+    const size_t n3 = (size_t)3 * c->N, rs = n3 + NM_REC_HEAD, ns = c->nslots;
+    const int j = g.next;
+    const double *const rec = g.h + (size_t)j * rec_cycle_doubles(c);
+    const double tag = (double)(g.tag0 + (uint32_t)j);
+    auto taken = [&]() {
+        for (size_t k = 0; k < ns; ++k)
+            if (rec[k * rs + NM_REC_TAG] != tag) return false;
+        return true;
+    };
+    if (g.dirty || !taken()) {
+        const int rc = check_status(c); // the queue's outcome: a healable stop is re-issued (into this ring), an error is reported
+        if (rc) { drop_ring(c, r); return rc; }
+        HIPCHK(c, hipMemcpy(g.h, g.d, (size_t)g.n * rec_cycle_doubles(c) * sizeof(double), hipMemcpyDeviceToHost));
+        g.dirty = false;
+        if (!taken()) {
+            drop_ring(c, r);
+            return fail(c, NM_ERR_STATE, "nm_snapshot_fetch: the record of a recorded cycle was never taken (its block did not complete)");
+        }
+    }
+    for (size_t k = 0; k < ns; ++k) {
+        const double *s = rec + k * rs;
+        if (rows) std::memcpy(rows + k * NM_THERMO_COLS, s, NM_THERMO_COLS * sizeof(double));
+        if (x) std::memcpy(x + k * n3, s + NM_REC_HEAD, n3 * sizeof(double));
+        if (box) box[k] = s[NM_REC_BOX];
+    }
+    c->fetchq.pop_front();
+    if (++g.next == g.n) g.n = g.next = 0;
     return NM_OK;
 }
 
 int nm_snapshot_fetch(nm_ctx *c, double *rows, double *x, double *box)
 {
     if (!c) return NM_ERR_ARG;
-    if (c->snap_count == 0) return fail(c, NM_ERR_STATE, "nm_snapshot_fetch: no snapshot is pending");
+    if (c->fetchq.empty()) return fail(c, NM_ERR_STATE, "nm_snapshot_fetch: no snapshot is pending");
     HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (c->fetchq.front() >= 0) return fetch_record(c, c->fetchq.front(), rows, x, box);
     nm_ctx::Snap &sn = c->snap[c->snap_head];
     HIPCHK(c, hipEventSynchronize(sn.landed));
     size_t off[8];
@@ -1174,6 +1306,38 @@ int nm_snapshot_fetch(nm_ctx *c, double *rows, double *x, double *box)
     sn.pending = false;
     c->snap_head ^= 1;
     --c->snap_count;
+    c->fetchq.pop_front();
+    return NM_OK;
+}
+
+int nm_record_capacity(const nm_ctx *c) { return c ? record_capacity(c) : NM_ERR_ARG; }
+int nm_snapshot_pending(const nm_ctx *c) { return c ? (int)c->fetchq.size() : NM_ERR_ARG; }
+
+int nm_run_cycles_recorded(nm_ctx *c, int ncycles, int mod)
+{
+    if (!c || ncycles < 1 || mod < 0) return fail(c, NM_ERR_ARG, "nm_run_cycles_recorded: bad argument");
+    if (!c->whole_rows) return fail(c, NM_ERR_UNSUPPORTED, "nm_run_cycles_recorded: this context holds a partial pressure row (the exchange spans contexts)");
+    if (ncycles > record_capacity(c))
+        return fail(c, NM_ERR_ARG, "nm_run_cycles_recorded: " + std::to_string(ncycles) + " cycles, more than one call holds (nm_record_capacity: " +
+                                       std::to_string(record_capacity(c)) + ")");
+    const int r = c->ring[0].n == 0 ? 0 : c->ring[1].n == 0 ? 1 : -1;
+    if (r < 0) return fail(c, NM_ERR_STATE, "nm_run_cycles_recorded: the records of two calls are pending; fetch them first (nm_snapshot_fetch)");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (!c->ring[0].d) {
+        const int rc = rec_alloc(c);
+        if (rc) return rc;
+    }
+    nm_ctx::Ring &g = c->ring[r];
+    g.tag0 = ((++c->rec_calls & 0xFFFFFFu) << 7) + 1; // (a record left from an earlier call of this ring never matches)
+    g.dirty = false;
+    int rc = issue_cycles(c, ncycles, mod, c->step, true, r, 0);
+    if (rc) return rc;
+    HIPCHK(c, hipEventRecord(g.taken, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->side, g.taken, 0));
+    HIPCHK(c, hipMemcpyAsync(g.h, g.d, (size_t)ncycles * rec_cycle_doubles(c) * sizeof(double), hipMemcpyDeviceToHost, c->side));
+    HIPCHK(c, hipEventRecord(g.landed, c->side));
+    g.n = ncycles; g.next = 0;
+    for (int k = 0; k < ncycles; ++k) c->fetchq.push_back(r);
     return NM_OK;
 }
 
@@ -1196,7 +1360,7 @@ int nm_run_cycles(nm_ctx *c, int ncycles, int mod)
     if (!c || ncycles < 1 || mod < 0) return fail(c, NM_ERR_ARG, "nm_run_cycles: bad argument");
     if (!c->whole_rows) return fail(c, NM_ERR_UNSUPPORTED, "nm_run_cycles: this context holds a partial pressure row (the exchange spans contexts)");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    return issue_cycles(c, ncycles, mod, c->step, true);
+    return issue_cycles(c, ncycles, mod, c->step, true, -1, 0);
 }
 
 int nm_get_thermo(nm_ctx *c, double *rows)

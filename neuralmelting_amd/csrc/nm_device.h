@@ -72,7 +72,14 @@ struct KParams {
     int *cyc_abort;                // set by whoever leaves the launch early: nobody waits for a row that will not complete
     int *nswaps;                   // accepted swaps of the launch (atomic)
     double *xcrit;                 // dh of every pair the exchange sweeps visit, [local row][pair] in sweep order (nm_get_exchange_crit)
+    // nm_run_cycles_recorded (nm_cycles_kernel<C, true>): the record of cycle c of this launch for slot k is rec[(c nslots + k) (3N + NM_REC_HEAD)],
+    // tagged rec_tag0 + c once the slot's block of that cycle has completed
+    double *rec;
+    uint32_t rec_tag0;
 };
+
+// one slot's record of a recorded cycle: the 17 thermo columns (remcmc:208), box, tag, then x[3N]
+enum : int { NM_REC_HEAD = 19, NM_REC_BOX = 17, NM_REC_TAG = 18 };
 
 // status bits reach the host through status[] (last launch) and status_acc[] (everything since the host last looked); a block
 // that stopped (stops) arms the halt word with its launch id

@@ -2756,6 +2756,27 @@ __global__ void nm_snapshot_kernel(const SnapArgs a)
     for (size_t i = t; i < a.n[6]; i += nt) mi[i] = a.slot2buf[i];
 }
 
+// nm_run_cycles_recorded on the loop of single launches: the record of one cycle (nm_cycles_kernel<C, true>'s layout), queued behind its block.
+// Workgroup k copies slot k.  Nothing, and no tag, when a block stopped on an error (halt word armed): that record was never taken.
+struct RecArgs { const double *x, *box, *therm, *steps, *count; const float *ratio; const int *slot2buf, *halt; double *dst; int nslots, N; uint32_t tag; };
+__global__ void nm_record_kernel(const RecArgs a)
+{
+    const int k = blockIdx.x;
+    if (k >= a.nslots || *a.halt) return;
+    const int b = a.slot2buf[k];
+    const size_t n3 = (size_t)3 * a.N;
+    double *const r = a.dst + (size_t)k * (n3 + NM_REC_HEAD);
+    for (size_t i = threadIdx.x; i < n3; i += blockDim.x) r[NM_REC_HEAD + i] = a.x[(size_t)b * n3 + i];
+    if (threadIdx.x == 0) {
+        for (int q = 0; q < 5; ++q) r[q] = a.therm[5 * b + q];
+        for (int q = 0; q < 3; ++q) r[5 + q] = a.steps[3 * b + q];
+        for (int q = 0; q < 6; ++q) r[8 + q] = a.count[6 * k + q];
+        for (int q = 0; q < 3; ++q) r[14 + q] = (double)a.ratio[3 * k + q];
+        r[NM_REC_BOX] = a.box[b];
+        r[NM_REC_TAG] = (double)a.tag;
+    }
+}
+
 // gen_mc_param (remcmc:726-745) of one slot
 __device__ __forceinline__ void adapt_slot(int k, const int *slot2buf, double *steps, double *count, float *ratio)
 {
@@ -2809,7 +2830,10 @@ __device__ __forceinline__ int exchange_row(int r, int nt, int row0, uint32_t se
 // i.e. a block's time scatters by 3.5 %, and a launch of 64 replicas waited for the slowest of 64 at every cycle.  Spins are bounded (2 s) and leave
 // through cyc_abort, which also whoever stops on an error sets: nobody waits for a row that will not complete.  Requires whole rows, no launch
 // order table, no tapes, no trace (nm_api.hip nm_run_cycles falls back to single cycles otherwise).
-template <class C>
+// REC (nm_run_cycles_recorded): behind a block that completed, and in front of the row barrier, every slot writes what nm_snapshot would have taken
+// there into its record of the cycle (p.rec): the writer thread the 17 columns, the box and the tag, each of the Q workgroups its own atoms' positions
+// from LDS.  The row's leader zeroes the counters and swaps slot2buf only behind its acquire on rowbar, so these reads come first.
+template <class C, bool REC = false>
 __global__ void __launch_bounds__(C::BLOCK NM_MIN_WAVES) nm_cycles_kernel(const KParams p0)
 {
     const int ncycles = p0.ncycles;
@@ -2855,6 +2879,26 @@ __global__ void __launch_bounds__(C::BLOCK NM_MIN_WAVES) nm_cycles_kernel(const 
         if (rc != 0) {                               // stopped (or nothing to run): the rows must not wait for this workgroup
             if (tid == 0) __hip_atomic_store(p.cyc_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
+        }
+        if constexpr (REC) { // this cycle's record of the slot (pointers and sizes from this cycle's copy of the arguments, as everything here)
+            const int N = p.N;
+            const size_t rs = (size_t)3 * N + NM_REC_HEAD;
+            double *const r = p.rec + ((size_t)cyc * p.nslots + slot) * rs;
+            const double *const lx = (const double *)(nm_lds + C::OFF_POS); // px, py, pz: every workgroup of the cluster holds all positions
+            const int a0 = (N * qq) / Q, a1 = (N * (qq + 1)) / Q;
+            for (int a = 3 * a0 + tid; a < 3 * a1; a += C::BLOCK) {
+                const int i = a / 3, c3 = a - 3 * i;
+                r[NM_REC_HEAD + a] = lx[(size_t)c3 * C::NMAX + i];
+            }
+            if (qq == 0 && tid == 0) { // nm_block_body's writer: it stored therm, box, count and ratio itself
+                const int bq = p.slot2buf[slot];
+                for (int q = 0; q < 5; ++q) r[q] = p.therm[5 * bq + q];
+                for (int q = 0; q < 3; ++q) r[5 + q] = p.steps[3 * bq + q];
+                for (int q = 0; q < 6; ++q) r[8 + q] = p.count[6 * slot + q];
+                for (int q = 0; q < 3; ++q) r[14 + q] = (double)p.ratio[3 * slot + q];
+                r[NM_REC_BOX] = p.box[bq];
+                r[NM_REC_TAG] = (double)(p.rec_tag0 + (uint32_t)cyc);
+            }
         }
         __syncthreads();                             // every thread's stores of this block are issued
         int abort_ = 0;

@@ -166,6 +166,21 @@ class Engine:
         which only the replicas of a pressure row wait for one another, where the configuration has the kernel for it; the same chains either way"""
         self._chk(self.lib.nm_run_cycles(self.h, int(ncycles), int(mod)))
 
+    def run_cycles_recorded(self, ncycles, mod):
+        """run_cycles with outputs on: every cycle also keeps what snapshot() would have kept behind its block (nm_run_cycles_recorded); the
+        ncycles records join the queue snapshot_fetch drains, in cycle order.  At most record_capacity cycles per call, records of two calls pending"""
+        self._chk(self.lib.nm_run_cycles_recorded(self.h, int(ncycles), int(mod)))
+
+    @property
+    def record_capacity(self):
+        """the most cycles one run_cycles_recorded call may hold (nm_record_capacity)"""
+        return int(self.lib.nm_record_capacity(self.h))
+
+    @property
+    def snapshot_pending(self):
+        """records queued by snapshot / run_cycles_recorded and not yet fetched (nm_snapshot_pending)"""
+        return int(self.lib.nm_snapshot_pending(self.h))
+
     def run_md(self, nsteps):
         """init_sample's -is dynamics (remcmc:421-425): velocities at T, then nsteps of NVE"""
         self._chk(self.lib.nm_run_md(self.h, int(nsteps)))
@@ -186,7 +201,7 @@ class Engine:
         rows = np.empty((self.nslots, B.NM_THERMO_COLS))
         x = np.empty((self.nslots, 3 * self.natoms)) if positions else None
         box = np.empty(self.nslots)
-        self._chk(self.lib.nm_snapshot_fetch(self.h, _dp(rows), _dp(x) if positions else None, _dp(box)))
+        self._settled(self.lib.nm_snapshot_fetch(self.h, _dp(rows), _dp(x) if positions else None, _dp(box)))  # (a record's fetch may settle)
         return rows, x, box
 
     def adapt(self):

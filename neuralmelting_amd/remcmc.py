@@ -229,8 +229,8 @@ class Run:
         if rc != 0:
             raise IOError('nm_append_outputs failed (%d)' % rc)
 
-    def _write_async(self, rows, x, box):
-        """write a recorded cycle on a helper thread (the C call releases the GIL) while the host drives the next block;
+    def _write_async(self, recs):
+        """write recorded cycles [(rows, x, box), ...] on a helper thread (the C call releases the GIL) while the host drives the next blocks;
         cycles are written in order: the previous write is joined first"""
         import threading
         self._write_join()
@@ -238,7 +238,8 @@ class Run:
 
         def work():
             try:
-                self.write_outputs(rows, x, box)
+                for r in recs:
+                    self.write_outputs(*r)
             except BaseException as e:  # surfaced by the next join
                 self._writer_err = e
         self._writer = threading.Thread(target=work)
@@ -339,6 +340,20 @@ class Run:
             s += 1
         return n
 
+    def _recorded_cycles(self):
+        """how many cycles from STEP on record (remcmc:983-985) but neither dump the restart file nor are the run's last — those go to the engine
+        as one call (Engine.run_cycles_recorded); 0 where a pressure row is split across ranks or the engine has no such call.  A call holds at most
+        record_capacity cycles and at most half of the cycles left in the run (but 2): the records of a call are written while the NEXT call runs, so
+        the last call's are written behind the GPU's last cycle, and calls that shrink towards the end keep that tail to a cycle or two"""
+        if getattr(self, 'split_rows', False) or not hasattr(self.engine, 'run_cycles_recorded'):
+            return 0
+        cap = min(self.engine.record_capacity, max(2, (self.NSMPL - self.STEP + 1) // 2))
+        n, s = 0, self.STEP
+        while n < cap and (s + 1) > self.CUTOFF and (s + 1) % self.REFREQ != 0 and (s + 1) != self.NSMPL:
+            n += 1
+            s += 1
+        return n
+
     def replica_exchange(self, step):
         """replica_exchange (remcmc:776-803): on the device when this rank owns whole rows, else all-gather + identical sweep"""
         eng = self.engine
@@ -412,6 +427,20 @@ class Run:
                     self.log('cycles %d-%d: outputs off' % (self.STEP, self.STEP + quiet - 1))
                 self.STEP += quiet
                 continue
+            rec = self._recorded_cycles()
+            if rec > 1:                                   # recorded cycles without a dump: one call, their records in the snapshot queue
+                eng.run_cycles_recorded(rec, self.MOD)    # (nm_run_cycles_recorded) — the same chains and records as the single path
+                snaps += rec
+                if self.VERBOSE:
+                    self.log('cycles %d-%d: recorded' % (self.STEP, self.STEP + rec - 1))
+                older = []                                # what was queued before this call: fetched while it runs, written on the helper thread
+                while snaps > rec:
+                    older.append(eng.snapshot_fetch())
+                    snaps -= 1
+                if older:
+                    self._write_async(older)
+                self.STEP += rec
+                continue
             eng.run_block(self.MOD)                       # gen_samples (asynchronous)
             record = (self.STEP + 1) > self.CUTOFF        # remcmc:983-985
             if record:
@@ -424,14 +453,20 @@ class Run:
                 n = self.replica_exchange(self.STEP)
                 if self.VERBOSE:
                     self.log('%d replica exchanges performed' % n)
-            while snaps > (1 if record else 0):           # the cycle before this one: write_outputs (remcmc:259-286), in cycle order
-                self._write_async(*eng.snapshot_fetch())
+            older = []                                    # the cycles before this one: write_outputs (remcmc:259-286), in cycle order,
+            while snaps > (1 if record else 0):           # on the helper thread (a recorded call leaves many)
+                older.append(eng.snapshot_fetch())
                 snaps -= 1
+            if older:
+                self._write_async(older)
             self.STEP += 1
         self.STEP = self.NSMPL - 1
+        older = []
         while snaps:
-            self._write_async(*eng.snapshot_fetch())
+            older.append(eng.snapshot_fetch())
             snaps -= 1
+        if older:
+            self._write_async(older)
         self._write_join()
         eng.synchronize()
         self.loop_seconds = time.perf_counter() - t_loop   # the metric's clock: main loop, remcmc:977-995
