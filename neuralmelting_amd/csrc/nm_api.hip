@@ -46,6 +46,13 @@ typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 192, unsigned char, true, true, 0
 typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 256, unsigned char, true, true, 1> CfgSmallSC;
 typedef Cfg<NM_SMALL_BLOCK, 2 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 1, 128, true, true> CfgSmallSCQ2; // (own rows, two lists)
 typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 1, 64, true, true> CfgSmallSCQ4;
+// element Al at 5^3 to 8^3 cells: 16-bit lists in HBM/L2, chunked as CfgMid's and CfgLarge's, full lists (Cfg::HALF stays lj/cut's).  256 slots
+// per atom: the crystal has 134 neighbours within rc + skin = 8.1 A, and the longest row over bench's Al grid (8 x 8, P 1 .. 8 bar, T 256 .. 2560 K,
+// 40 cycles from the lattice) was 149 at 5^3 and 151 at 8^3; more is reported as ST_LIST_OVERFLOW.  Densities in LDS at 864 atoms (141.5 KB in all), in the spill at 2048
+// (Cfg::RHO_LDS: positions, velocities and forces alone take 144 KB there).  Dispatched by launch_kind_eam.
+typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 1> CfgMidSC;     // 1 and 2 workgroups per replica
+typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 1> CfgMidSCQ4;   // 4
+typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 1> CfgLargeSC; // 1, 2 and 4
 typedef Cfg<512, 1, 864, 192, unsigned short, false, true> CfgMid;     // N <= 864: list in HBM/L2, saved copies in LDS (here: at 2 workgroups per replica)
 // the same at ONE workgroup per replica (more replicas than CUs: the reference's run.sh setting): every pair lies inside the workgroup and
 // is listed once (Cfg::HALF, nm_kernels.h)
@@ -275,8 +282,16 @@ hipError_t launch_cycles_kind(const nm_ctx *c, const KParams &p)
     return launch_cycles<CfgMidQ8>(c, p);
 }
 
+// element Al above 256 atoms (kinds 1 and 2)
+hipError_t launch_kind_eam(const nm_ctx *c, const KParams &p)
+{
+    if (c->kind == 1) return c->cus == 4 ? launch_block<CfgMidSCQ4>(c, p) : launch_block<CfgMidSC>(c, p);
+    return launch_block<CfgLargeSC>(c, p);
+}
+
 hipError_t launch_kind(const nm_ctx *c, const KParams &p)
 {
+    if (c->pot == 1 && c->kind > 0) return launch_kind_eam(c, p);
     switch (c->kind) {
     case 0:
         if (c->pot == 1) return c->cus == 4 ? launch_block<CfgSmallSCQ4>(c, p) : c->cus == 2 ? launch_block<CfgSmallSCQ2>(c, p) : launch_block<CfgSmallSC>(c, p);
@@ -288,6 +303,7 @@ hipError_t launch_kind(const nm_ctx *c, const KParams &p)
 
 int blocks_per_cu_kind(int kind, int pot, int q)
 {
+    if (pot == 1 && kind > 0) return kind == 1 ? (q == 4 ? blocks_per_cu<CfgMidSCQ4>() : blocks_per_cu<CfgMidSC>()) : blocks_per_cu<CfgLargeSC>();
     switch (kind) {
     case 0:
         if (pot == 1) return q == 4 ? blocks_per_cu<CfgSmallSCQ4>() : q == 2 ? blocks_per_cu<CfgSmallSCQ2>() : blocks_per_cu<CfgSmallSC>();
@@ -299,6 +315,7 @@ int blocks_per_cu_kind(int kind, int pot, int q)
 
 hipError_t probe_kind(const nm_ctx *c, const KParams &p)
 {
+    if (c->pot == 1 && c->kind > 0) return c->kind == 1 ? (c->cus == 4 ? launch_probe<CfgMidSCQ4>(c, p) : launch_probe<CfgMidSC>(c, p)) : launch_probe<CfgLargeSC>(c, p);
     switch (c->kind) {
     case 0:
         if (c->pot == 1) return c->cus == 4 ? launch_probe<CfgSmallSCQ4>(c, p) : c->cus == 2 ? launch_probe<CfgSmallSCQ2>(c, p) : launch_probe<CfgSmallSC>(c, p);
@@ -510,7 +527,7 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
     int cu = prop.multiProcessorCount;
     if (testing())
         if (const char *e = std::getenv("NM_ASSUME_CUS")) { const int v = std::atoi(e); if (v > 0) cu = v; } // tests of the fallback
-    const int maxq = c->kind == 0 ? (c->pot == 0 ? 8 : 4) : c->kind == 1 ? 8 : 4; // own-atom ranges the instantiated thread mappings cover
+    const int maxq = (c->pot == 1 || c->kind == 2) ? 4 : 8; // own-atom ranges the instantiated thread mappings cover
     c->cus = 1; c->over = false;
     // The large cells (N > 864) at 4 workgroups per replica when that makes a grid of (nearly) TWICE the chip: the clusters run in
     // two rounds, longest block first, each with its own census.  Their blocks differ by more than 2x across an equilibrated PxT grid
@@ -559,6 +576,7 @@ int alloc_cluster_buffers(nm_ctx *c)
     const size_t ns = c->nslots;
     size_t aux_doubles, lds_bytes = c->lds_bytes;
     if (c->kind == 0) aux_doubles = CfgSmall::AUX_DOUBLES;
+    else if (c->pot == 1) { aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES; lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; }
     else if (c->kind == 1) { aux_doubles = c->cus == 8 ? CfgMidQ8::AUX_DOUBLES : CfgMid::AUX_DOUBLES; lds_bytes = c->cus == 8 ? CfgMidQ8::LDS_BYTES : CfgMid::LDS_BYTES; }
     else aux_doubles = CfgLarge::AUX_DOUBLES;
     // the new buffers first, swapped in only when both exist: a failure leaves the context with the buffers (and the workgroups per
@@ -730,8 +748,6 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
         return fail(nullptr, NM_ERR_ARG, "nm_create: bad move parameters");
     if (cfg->element != NM_EL_LJ && cfg->element != NM_EL_AL)
         return fail(nullptr, NM_ERR_UNSUPPORTED, "nm_create: elements LJ and Al have device force kernels in this build");
-    if (cfg->element == NM_EL_AL && cfg->natoms > 256)
-        return fail(nullptr, NM_ERR_UNSUPPORTED, "nm_create: element Al (EAM) is built for up to 256 atoms (4^3 cells)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, NM_ERR_HIP, "nm_create: no HIP device available (this engine has no CPU fallback)");
@@ -789,6 +805,11 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
 
     size_t nbr_elems;
     if (c->N <= CfgSmall::NMAX) { c->kind = 0; c->lds_bytes = c->pot == 1 ? CfgSmallSC::LDS_BYTES : CfgSmall::LDS_BYTES; /* Q8 variant: set at launch */ c->aux_doubles = CfgSmall::AUX_DOUBLES; nbr_elems = CfgSmall::NBR_G_ELEMS; }
+    else if (c->pot == 1) { // element Al above 256 atoms (launch_kind_eam)
+        c->kind = c->N <= CfgMidSC::NMAX ? 1 : 2;
+        c->lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; c->aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES;
+        nbr_elems = c->kind == 1 ? CfgMidSC::NBR_G_ELEMS : CfgLargeSC::NBR_G_ELEMS;
+    }
     else if (c->N <= CfgMid::NMAX) { c->kind = 1; c->lds_bytes = CfgMid::LDS_BYTES; c->aux_doubles = CfgMid::AUX_DOUBLES; nbr_elems = CfgMid::NBR_G_ELEMS; }
     else { c->kind = 2; c->lds_bytes = CfgLarge::LDS_BYTES; c->aux_doubles = CfgLarge::AUX_DOUBLES; nbr_elems = CfgLarge::NBR_G_ELEMS; }
 
@@ -883,6 +904,15 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
         CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSCQ2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSCQ2::LDS_BYTES));
         CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSCQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSCQ4::LDS_BYTES));
         static_assert(CfgSmallSCQ2::LDS_BYTES <= 160 * 1024 && CfgSmallSC::LDS_BYTES <= 160 * 1024, "");
+    }
+    else if (c->pot == 1) {
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC::LDS_BYTES));
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSCQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSCQ4::LDS_BYTES));
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgLargeSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgLargeSC::LDS_BYTES));
+        static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");
+        static_assert(CfgMidSC::LDS_BYTES <= 160 * 1024 && CfgMidSCQ4::LDS_BYTES <= 160 * 1024 && CfgLargeSC::LDS_BYTES <= 160 * 1024, "");
+        static_assert(CfgMidSC::XBUF_DOUBLES == CfgMid::XBUF_DOUBLES && CfgLargeSC::XBUF_DOUBLES == CfgLarge::XBUF_DOUBLES, "alloc_cluster_buffers sizes the granules by kind");
+        static_assert(CfgMidSC::AUX_DOUBLES == CfgMidSCQ4::AUX_DOUBLES, "");
     }
     else if (c->kind == 1) {
         CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMid>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMid::LDS_BYTES));

@@ -188,7 +188,10 @@ struct Cfg {
     static constexpr size_t OFF_NBR = SAVE_LDS ? OFF_WN + pad8((size_t)3 * NMAX) : OFF_IMG;
     static constexpr size_t LIST_BYTES = LIST_LDS ? pad8((size_t)MAXNB * NLIST * sizeof(IdxT)) : 0; // one LDS list
     static constexpr size_t OFF_RHO = OFF_NBR + (LDS_LIST2 ? 2 : 1) * LIST_BYTES; // EAM densities
-    static constexpr size_t OFF_X0S = OFF_RHO + (POT ? (size_t)NMAX * sizeof(double) : 0); // LDS_LIST2: reference positions of the saved list
+    // RHO_LDS: the EAM densities sit in LDS where they fit beside everything else (every 4^3 and 5^3 configuration); the 2048-atom one,
+    // whose positions, velocities and forces alone take 144 KB, keeps them in its per-workgroup global spill instead (AUX_RHO)
+    static constexpr bool RHO_LDS = POT_ != 0 && OFF_RHO + (size_t)NMAX * sizeof(double) <= (size_t)160 * 1024;
+    static constexpr size_t OFF_X0S = OFF_RHO + (RHO_LDS ? (size_t)NMAX * sizeof(double) : 0); // LDS_LIST2: reference positions of the saved list
     static constexpr size_t OFF_CNTS = OFF_X0S + (LDS_LIST2 ? A3 : 0);                     //            and its row lengths
     // PREFETCH: the gaussians of the NEXT move's `velocity create` are drawn while the closing exchange of the current move's
     // energy sums is in flight (Replica::prefetch_gaussians) and wait here, 3 NMAX doubles
@@ -212,7 +215,8 @@ struct Cfg {
     // of that list (3 NMAX doubles + NMAX 16-bit counts per workgroup)
     static constexpr bool LIST2 = !LIST_LDS_ || LDS_LIST2_;
     static constexpr size_t AUX_LIST2 = !LIST_LDS_ ? (size_t)3 * NMAX + ((size_t)NMAX + 3) / 4 : 0;
-    static constexpr size_t AUX_DOUBLES = AUX_SAVES + (SAVEF_LDS ? 0 : (size_t)3 * NMAX) + AUX_LIST2; // ... + the saved forces + LIST2
+    static constexpr size_t AUX_RHO = (POT_ != 0 && !RHO_LDS) ? (size_t)NMAX : 0;                     // EAM densities outside LDS
+    static constexpr size_t AUX_DOUBLES = AUX_SAVES + (SAVEF_LDS ? 0 : (size_t)3 * NMAX) + AUX_RHO + AUX_LIST2; // ... + the saved forces + densities + LIST2
     static constexpr size_t NBR_G_ELEMS = LIST_LDS ? 0 : (size_t)MAXNB * NMAX; // per-slot global list
     // Lists that live in HBM/L2 are stored in chunks of CH consecutive neighbours of one atom ([chunk][atom][CH]) so that one
     // 8-byte load brings four indices: the dependent L2 round trip per neighbour was the cost there.  LDS lists stay [slot][atom].
@@ -388,7 +392,7 @@ struct Replica {
     LdsArr<unsigned short, C::OFF_CNT> cnt;
     typename ArrSel<C::LIST_LDS, IdxT, C::OFF_NBR>::type nbr;
     LdsArr<double, C::OFF_RED> red;
-    LdsArr<double, C::OFF_RHO> rho; // EAM: densities, then 1/sqrt(density)
+    typename ArrSel<C::RHO_LDS || C::POT == 0, double, C::OFF_RHO>::type rho; // EAM: densities, then 1/sqrt(density) (LDS, or the spill: Cfg::RHO_LDS)
     int parity = 0;
     // block-uniform scalars
     double L = 0.0, L0 = 0.0, U = 0.0, W = 0.0;
@@ -452,6 +456,10 @@ struct Replica {
             double *a = p.aux_g + ((size_t)slot * p.cus + q_) * C::AUX_DOUBLES + C::AUX_SAVES;
             sfx.g = a; sfy.g = a + NMAX; sfz.g = a + 2 * (size_t)NMAX;
             NM_BOUND(sfx, NMAX); NM_BOUND(sfy, NMAX); NM_BOUND(sfz, NMAX);
+        }
+        if constexpr (C::AUX_RHO != 0) {
+            rho.g = p.aux_g + ((size_t)slot * p.cus + q_) * C::AUX_DOUBLES + C::AUX_SAVES + (C::SAVEF_LDS ? 0 : 3 * (size_t)NMAX);
+            NM_BOUND(rho, NMAX);
         }
         if constexpr (!C::LIST_LDS) {
             nbr.g = (IdxT *)p.nbr_g + (size_t)slot * 2 * C::NBR_G_ELEMS; // two lists per slot, list_cur = 0
@@ -1390,6 +1398,103 @@ struct Replica {
     // fp = eps [ 7 (a/r)^7 - 6 (c/2)(1/sqrt(rho_i) + 1/sqrt(rho_j)) (a/r)^6 ] / r^2.
     template <bool WANT_E>
     __device__ __forceinline__ void pair_loop_sc(double invL, double &eacc, double &wacc, double &nacc, double &kacc, bool fuse, double dtfm, double h);
+    // a listed neighbour's coordinate / density: j is the atom index, or (BYTES: the lists in HBM/L2) 8 x the atom index
+    template <bool BYTES, class A>
+    static __device__ __forceinline__ double sc_at(const A &a, int j)
+    {
+#ifdef NM_PROF
+        return a[BYTES ? (j >> 3) : j]; // (diagnostic build: through the bounds-checked index of a spill array, the densities of CfgLargeSC)
+#else
+        if constexpr (BYTES) return *(const double *)((const char *)a.ptr() + j);
+        else return a[j];
+#endif
+    }
+    // pass 1 of pair_loop_sc for W listed neighbours at once: r += (a/r)^6 of those inside rc.  `in` enters as "the entry exists"
+    // (a missing one holds a finite stand-in) and is switched off by zeroing 1 / r^2 after the reciprocal, as in pair_pre.
+    template <int W, bool BYTES>
+    __device__ __forceinline__ void sc_rho_vec(const int (&j)[W], bool (&in)[W], double xi, double yi, double zi, double invL, double rc2,
+                                               double a2, double mhL, double &r)
+    {
+        double dx[W], dy[W], dz[W], r2[W], y[W], t[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            dx[u] = __builtin_fma(-sc_at<BYTES>(px, j[u]), invL, xi); dy[u] = __builtin_fma(-sc_at<BYTES>(py, j[u]), invL, yi);
+            dz[u] = __builtin_fma(-sc_at<BYTES>(pz, j[u]), invL, zi);
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            dx[u] = __builtin_fma(__builtin_amdgcn_fract(dx[u]), L, mhL); dy[u] = __builtin_fma(__builtin_amdgcn_fract(dy[u]), L, mhL);
+            dz[u] = __builtin_fma(__builtin_amdgcn_fract(dz[u]), L, mhL);
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            r2[u] = dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u];
+            in[u] = in[u] && r2[u] < rc2;
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) y[u] = __builtin_amdgcn_rcp(r2[u]);
+#pragma unroll
+        for (int u = 0; u < W; ++u) t[u] = __builtin_fma(-r2[u], y[u], 1.0);
+#pragma unroll
+        for (int u = 0; u < W; ++u) y[u] = __builtin_fma(y[u], t[u], y[u]);
+#pragma unroll
+        for (int u = 0; u < W; ++u) t[u] = __builtin_fma(-r2[u], y[u], 1.0);
+#pragma unroll
+        for (int u = 0; u < W; ++u) y[u] = in[u] ? __builtin_fma(y[u], t[u], y[u]) * a2 : 0.0; // (a/r)^2
+#pragma unroll
+        for (int u = 0; u < W; ++u) r += y[u] * y[u] * y[u];
+    }
+    // pass 2 for W listed neighbours: forces (and energy, virial, pair count) of row i, isi = 1/sqrt(rho_i)
+    template <bool WANT_E, int W, bool BYTES>
+    __device__ __forceinline__ void sc_force_vec(const int (&j)[W], bool (&in)[W], double xi, double yi, double zi, double isi, double invL,
+                                                 double rc2, double a2, double a1r, double eps, double cc, double mhL, double &ax, double &ay,
+                                                 double &az, double &e, double &w, double &np)
+    {
+        double dx[W], dy[W], dz[W], r2[W], y[W], t[W], hh[W], rj[W], q2[W], rm[W], rn[W], fp[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            dx[u] = __builtin_fma(-sc_at<BYTES>(px, j[u]), invL, xi); dy[u] = __builtin_fma(-sc_at<BYTES>(py, j[u]), invL, yi);
+            dz[u] = __builtin_fma(-sc_at<BYTES>(pz, j[u]), invL, zi);
+            rj[u] = sc_at<BYTES>(rho, j[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            dx[u] = __builtin_fma(__builtin_amdgcn_fract(dx[u]), L, mhL); dy[u] = __builtin_fma(__builtin_amdgcn_fract(dy[u]), L, mhL);
+            dz[u] = __builtin_fma(__builtin_amdgcn_fract(dz[u]), L, mhL);
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            r2[u] = dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u];
+            in[u] = in[u] && r2[u] < rc2;
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) y[u] = __builtin_amdgcn_rsq(r2[u]);
+#pragma unroll
+        for (int u = 0; u < 2 * W; ++u) { // two Newton steps per neighbour: y <- y + y (1/2 - (r2 y)(y/2))
+            const int v = u % W;
+            t[v] = r2[v] * y[v]; hh[v] = 0.5 * y[v];
+            t[v] = __builtin_fma(-t[v], hh[v], 0.5);
+            y[v] = __builtin_fma(y[v], t[v], y[v]);
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) y[u] = in[u] ? y[u] : 0.0; // 1 / r, or nothing at all
+#pragma unroll
+        for (int u = 0; u < W; ++u) { t[u] = y[u] * y[u]; q2[u] = a2 * t[u]; } // t = 1/r^2, q2 = (a/r)^2
+#pragma unroll
+        for (int u = 0; u < W; ++u) { rm[u] = q2[u] * q2[u] * q2[u]; }         // (a/r)^6
+#pragma unroll
+        for (int u = 0; u < W; ++u) { rn[u] = rm[u] * (a1r * y[u]); }           // (a/r)^7
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            const double dF = 0.5 * cc * (isi + rj[u]);
+            fp[u] = eps * (7.0 * rn[u] - 6.0 * dF * rm[u]) * t[u];
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            ax += dx[u] * fp[u]; ay += dy[u] * fp[u]; az += dz[u] * fp[u];
+            if (WANT_E) { e += eps * rn[u]; w += r2[u] * fp[u]; np += in[u] ? 1.0 : 0.0; }
+        }
+    }
 
     // ------------------------------------------------------------------ cluster hand-off (Q workgroups per replica)
     // Data-tagged granules (MI355X guide, hand-off price list "handoff-1to1"): every exchanged double travels as ONE
@@ -1876,25 +1981,63 @@ struct Replica {
         rho_k_new = s[2];
         dE = p.sc_eps * (s[0] - p.sc_c * (s[1] + sqrt(s[2]) - sqrt(rho[k])));
     }
+    // N > BLOCK: the same with atom j on thread j mod BLOCK (the elementwise owner), which keeps the drho_j of each of the NJ atoms it
+    // owns in registers until the decision.  The old density of atom k reaches the others through the reduction (s[3], added by k's
+    // owner alone: the sum is that value exactly), so nobody but j's owner reads or writes rho[j] or the coordinates of j, and a trial
+    // needs no barrier beyond the one inside its reduction.
+    static constexpr int NJ = (NMAX + BLOCK - 1) / BLOCK;
+    __device__ void delta_single_sc_strided(int k, double ox, double oy, double oz, double nx, double ny, double nz, double &dE,
+                                            double (&drho)[NJ], double &rho_k_new)
+    {
+        box_consts();
+        const double invL = bc_invL, rc2 = p.rc * p.rc, a2 = p.sc_a2;
+        double s[4] = { 0.0, 0.0, 0.0, 0.0 };
+#pragma unroll
+        for (int m = 0; m < NJ; ++m) {
+            const int j = tid + m * BLOCK;
+            drho[m] = 0.0;
+            if (j < N && j != k) {
+                const double xj = px[j], yj = py[j], zj = pz[j];
+                double ax = nx - xj, ay = ny - yj, az = nz - zj, bx = ox - xj, by = oy - yj, bz = oz - zj;
+                ax -= L * rint(ax * invL); ay -= L * rint(ay * invL); az -= L * rint(az * invL);
+                bx -= L * rint(bx * invL); by -= L * rint(by * invL); bz -= L * rint(bz * invL);
+                const double ra = ax * ax + ay * ay + az * az, rb = bx * bx + by * by + bz * bz;
+                const bool ina = ra < rc2, inb = rb < rc2;
+                const double qa = a2 * recip(ina ? ra : 1.0), qb = a2 * recip(inb ? rb : 1.0); // (a/r)^2
+                const double ga = ina ? qa * qa * qa : 0.0, gb = inb ? qb * qb * qb : 0.0;     // (a/r)^6
+                s[0] += ga * sqrt(qa) - gb * sqrt(qb);                                         // (a/r)^7, new - old
+                drho[m] = ga - gb;
+                const double rj = rho[j];
+                s[1] += sqrt(rj + drho[m]) - sqrt(rj);
+                s[2] += ga;
+            }
+            if (j == k) s[3] = sqrt(rho[k]);
+        }
+        block_sum<4, NW, NVMAX>(s, red, parity);
+        rho_k_new = s[2];
+        dE = p.sc_eps * (s[0] - p.sc_c * (s[1] + sqrt(s[2]) - s[3]));
+    }
     // densities of all atoms of the current configuration, O(N^2), one thread per atom (start of an iterative EAM position move)
     __device__ void iter_densities()
     {
         box_consts();
         const double invL = bc_invL, rc2 = p.rc * p.rc, a2 = p.sc_a2;
         __syncthreads(); // rho[] may still be read by the evaluation that ended last
-        if (tid < N) {
-            const double xj = px[tid], yj = py[tid], zj = pz[tid];
+        auto density = [&](int t) {
+            const double xj = px[t], yj = py[t], zj = pz[t];
             double r = 0.0;
             for (int i = 0; i < N; ++i) {
                 double dx = xj - px[i], dy = yj - py[i], dz = zj - pz[i];
                 dx -= L * rint(dx * invL); dy -= L * rint(dy * invL); dz -= L * rint(dz * invL);
                 const double r2 = dx * dx + dy * dy + dz * dz;
-                const bool in = r2 < rc2 && i != tid;
+                const bool in = r2 < rc2 && i != t;
                 const double q = a2 * recip(in ? r2 : 1.0);
                 r += in ? q * q * q : 0.0;
             }
-            rho[tid] = r;
-        }
+            rho[t] = r;
+        };
+        if constexpr (NMAX <= BLOCK) { if (tid < N) density(tid); }
+        else for (int t = tid; t < N; t += BLOCK) density(t); // (atom t on its elementwise owner, as in the trials)
         __syncthreads();
     }
 
@@ -2064,7 +2207,9 @@ struct Replica {
             }
             double dE, dW = 0.0;
             [[maybe_unused]] double drho = 0.0, rho_k_new = 0.0;
-            if constexpr (C::POT == 1) delta_single_sc(k, ox, oy, oz, nx, ny, nz, dE, drho, rho_k_new);
+            [[maybe_unused]] double drho_n[NJ];
+            if constexpr (C::POT == 1 && NMAX > BLOCK) delta_single_sc_strided(k, ox, oy, oz, nx, ny, nz, dE, drho_n, rho_k_new);
+            else if constexpr (C::POT == 1) delta_single_sc(k, ox, oy, oz, nx, ny, nz, dE, drho, rho_k_new);
             else delta_single(k, ox, oy, oz, nx, ny, nz, dE, dW);
             const double Unew = U + dE;
             const double de = Unew / et - pe;
@@ -2085,14 +2230,21 @@ struct Replica {
                         im[3 * k + 2] = (short)(im[3 * k + 2] + runs * wn[3 * k + 2]);
                     }
                 }
-                if constexpr (C::POT == 1) { // the densities follow the move
+                if constexpr (C::POT == 1 && NMAX > BLOCK) { // the densities follow the move, each on its owner
+#pragma unroll
+                    for (int m = 0; m < NJ; ++m) {
+                        const int j = tid + m * BLOCK;
+                        if (j < N && j != k) rho[j] += drho_n[m];
+                    }
+                    if (tid == (k % BLOCK)) rho[k] = rho_k_new;
+                } else if constexpr (C::POT == 1) {
                     if (tid < N && tid != k) rho[tid] += drho;
                     if (tid == (k % BLOCK)) rho[k] = rho_k_new;
                 }
                 U = Unew; W += dW;
                 set_fresh(false);
             }
-            if constexpr (C::POT == 1) __syncthreads(); // the next trial reads rho[k+1] in every thread
+            if constexpr (C::POT == 1 && NMAX <= BLOCK) __syncthreads(); // the next trial reads rho[k+1] in every thread
             runs += acc ? 1 : 2;
         }
         __syncthreads();
@@ -2109,10 +2261,12 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
     const double rc2 = p.rc * p.rc, a2 = p.sc_a2, eps = p.sc_eps, cc = p.sc_c, mhL = -0.5 * L;
     double *xg = xb ? xb + (size_t)(gen & 1) * C::XBUF_DOUBLES : nullptr;
     const unsigned long long mg = magic();
-    // pass 1: densities of this workgroup's atoms.  Both passes walk the byte list like pair_loop does: one conflict-free 8-byte
-    // read = eight neighbours, two neighbours' dependency chains interleaved stage by stage.
+    // pass 1: densities of this workgroup's atoms.  Both passes walk the list like pair_loop does — the byte lists in LDS one
+    // conflict-free 8-byte read = eight neighbours, the 16-bit lists in HBM/L2 in chunks of four, three chunks ahead —
+    // two neighbours' dependency chains interleaved stage by stage (sc_rho_vec, sc_force_vec: the 16-bit lists; the byte loops
+    // below are the same arithmetic written out, as the 4^3 kernels have always compiled it).
     constexpr int W = NM_PAIR_W;
-    static_assert(sizeof(IdxT) == 1, "the EAM loops read byte lists");
+    static_assert(C::LIST_LDS ? sizeof(IdxT) == 1 : (sizeof(IdxT) == 2 && C::CH == 4), "the EAM loops read byte lists in LDS or chunked 16-bit lists");
     const unsigned long long *nb64 = (const unsigned long long *)nbr_cur();
     for (int i0 = a0; i0 < a1; i0 += G) {
         const int i = i0 + g;
@@ -2121,46 +2275,70 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
         if (i < a1) {
             const double xi = __builtin_fma(px[i], invL, 0.5), yi = __builtin_fma(py[i], invL, 0.5), zi = __builtin_fma(pz[i], invL, 0.5); // (minimum image as in pair_pre)
             const int c = cnt[i];
-            const int mine = (c - sub + TPA - 1) / TPA;
-            unsigned long long wn = nb64[(size_t)lrow(i) * TPA + sub];
-            for (int k0 = 0; k0 < mine; k0 += 8) {
-                const unsigned long long wd = wn; // (the next word one word ahead, as in pair_loop)
-                wn = nb64[((size_t)(min(k0 + 8, MAXNB / TPA - 8) >> 3) * C::NLIST + lrow(i)) * TPA + sub];
+            if constexpr (C::LIST_LDS) {
+                const int mine = (c - sub + TPA - 1) / TPA;
+                unsigned long long wn = nb64[(size_t)lrow(i) * TPA + sub];
+                for (int k0 = 0; k0 < mine; k0 += 8) {
+                    const unsigned long long wd = wn; // (the next word one word ahead, as in pair_loop)
+                    wn = nb64[((size_t)(min(k0 + 8, MAXNB / TPA - 8) >> 3) * C::NLIST + lrow(i)) * TPA + sub];
 #pragma unroll
-                for (int e0 = 0; e0 < 8; e0 += W) {
-                    if (k0 + e0 == PRIO_SW) prio_swap();
-                    if (k0 + e0 < mine) {
-                        double dx[W], dy[W], dz[W], r2[W], y[W], t[W];
-                        bool in[W]; // (switched off by zeroing 1 / r^2 after the reciprocal, as in pair_pre)
+                    for (int e0 = 0; e0 < 8; e0 += W) {
+                        if (k0 + e0 == PRIO_SW) prio_swap();
+                        if (k0 + e0 < mine) {
+                            double dx[W], dy[W], dz[W], r2[W], y[W], t[W];
+                            bool in[W]; // (switched off by zeroing 1 / r^2 after the reciprocal, as in pair_pre)
 #pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            in[u] = (k0 + e0 + u) < mine;
-                            const int j = in[u] ? (int)((wd >> (8 * (e0 + u))) & 0xFFull) : i;
-                            dx[u] = __builtin_fma(-px[j], invL, xi); dy[u] = __builtin_fma(-py[j], invL, yi); dz[u] = __builtin_fma(-pz[j], invL, zi);
+                            for (int u = 0; u < W; ++u) {
+                                in[u] = (k0 + e0 + u) < mine;
+                                const int j = in[u] ? (int)((wd >> (8 * (e0 + u))) & 0xFFull) : i;
+                                dx[u] = __builtin_fma(-px[j], invL, xi); dy[u] = __builtin_fma(-py[j], invL, yi); dz[u] = __builtin_fma(-pz[j], invL, zi);
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                dx[u] = __builtin_fma(__builtin_amdgcn_fract(dx[u]), L, mhL); dy[u] = __builtin_fma(__builtin_amdgcn_fract(dy[u]), L, mhL);
+                                dz[u] = __builtin_fma(__builtin_amdgcn_fract(dz[u]), L, mhL);
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                r2[u] = dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u];
+                                in[u] = in[u] && r2[u] < rc2;
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) y[u] = __builtin_amdgcn_rcp(r2[u]);
+#pragma unroll
+                            for (int u = 0; u < W; ++u) t[u] = __builtin_fma(-r2[u], y[u], 1.0);
+#pragma unroll
+                            for (int u = 0; u < W; ++u) y[u] = __builtin_fma(y[u], t[u], y[u]);
+#pragma unroll
+                            for (int u = 0; u < W; ++u) t[u] = __builtin_fma(-r2[u], y[u], 1.0);
+#pragma unroll
+                            for (int u = 0; u < W; ++u) y[u] = in[u] ? __builtin_fma(y[u], t[u], y[u]) * a2 : 0.0; // (a/r)^2
+#pragma unroll
+                            for (int u = 0; u < W; ++u) r += y[u] * y[u] * y[u];
                         }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            dx[u] = __builtin_fma(__builtin_amdgcn_fract(dx[u]), L, mhL); dy[u] = __builtin_fma(__builtin_amdgcn_fract(dy[u]), L, mhL);
-                            dz[u] = __builtin_fma(__builtin_amdgcn_fract(dz[u]), L, mhL);
-                        }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            r2[u] = dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u];
-                            in[u] = in[u] && r2[u] < rc2;
-                        }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) y[u] = __builtin_amdgcn_rcp(r2[u]);
-#pragma unroll
-                        for (int u = 0; u < W; ++u) t[u] = __builtin_fma(-r2[u], y[u], 1.0);
-#pragma unroll
-                        for (int u = 0; u < W; ++u) y[u] = __builtin_fma(y[u], t[u], y[u]);
-#pragma unroll
-                        for (int u = 0; u < W; ++u) t[u] = __builtin_fma(-r2[u], y[u], 1.0);
-#pragma unroll
-                        for (int u = 0; u < W; ++u) y[u] = in[u] ? __builtin_fma(y[u], t[u], y[u]) * a2 : 0.0; // (a/r)^2
-#pragma unroll
-                        for (int u = 0; u < W; ++u) r += y[u] * y[u] * y[u];
                     }
+                }
+            } else {
+                constexpr int LA = 3; // chunks sub, sub+TPA, ... of atom i; the word LA chunks ahead is asked for before a chunk's arithmetic,
+                // so the L2 latency is paid once and hidden behind 4 LA neighbours (as pair_loop's PF, with one chunk's code instead of four)
+                const int nch = (c + C::CH - 1) / C::CH, mych = (nch - sub + TPA - 1) / TPA;
+                auto word = [&](int k) { return k < mych ? nb64[NM_CHECK_INDEX((size_t)(sub + k * TPA) * NMAX + i, C::NBR_G_ELEMS / 4)] : 0ull; };
+                unsigned long long w0 = word(0), w1 = word(1), w2 = word(2);
+                for (int k = 0; k < mych; ++k) {
+                    const unsigned long long w3 = word(k + LA);
+                    const int first = (sub + k * TPA) * C::CH;
+#pragma unroll
+                    for (int e0 = 0; e0 < C::CH; e0 += W) {
+                        int jj[W];
+                        bool in[W];
+#pragma unroll
+                        for (int u = 0; u < W; ++u) {
+                            in[u] = (first + e0 + u) < c; // (the tail entries of a row's last chunk are zero: atom 0, masked)
+                            jj[u] = (int)((w0 >> (16 * (e0 + u))) & 0xFFFFull); // 8 x the atom index
+                        }
+                        sc_rho_vec<W, true>(jj, in, xi, yi, zi, invL, rc2, a2, mhL, r);
+                    }
+                    w0 = w1; w1 = w2; w2 = w3;
                 }
             }
         }
@@ -2208,62 +2386,86 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
             const double xi = __builtin_fma(px[i], invL, 0.5), yi = __builtin_fma(py[i], invL, 0.5), zi = __builtin_fma(pz[i], invL, 0.5), isi = rho[i];
             const int c = cnt[i];
             if constexpr (SPREAD) { if (fuse && sub < 3) { vpre = vx.ptr()[sub * NMAX + i]; ppre = px.ptr()[sub * NMAX + i]; } } // (as pair_loop)
-            const int mine = (c - sub + TPA - 1) / TPA;
-            unsigned long long wn = nb64[(size_t)lrow(i) * TPA + sub];
-            for (int k0 = 0; k0 < mine; k0 += 8) {
-                const unsigned long long wd = wn; // (the next word one word ahead, as in pair_loop)
-                wn = nb64[((size_t)(min(k0 + 8, MAXNB / TPA - 8) >> 3) * C::NLIST + lrow(i)) * TPA + sub];
+            if constexpr (C::LIST_LDS) {
+                const int mine = (c - sub + TPA - 1) / TPA;
+                unsigned long long wn = nb64[(size_t)lrow(i) * TPA + sub];
+                for (int k0 = 0; k0 < mine; k0 += 8) {
+                    const unsigned long long wd = wn; // (the next word one word ahead, as in pair_loop)
+                    wn = nb64[((size_t)(min(k0 + 8, MAXNB / TPA - 8) >> 3) * C::NLIST + lrow(i)) * TPA + sub];
 #pragma unroll
-                for (int e0 = 0; e0 < 8; e0 += W) {
-                    if (k0 + e0 == PRIO_SW) prio_swap();
-                    if (k0 + e0 < mine) {
-                        double dx[W], dy[W], dz[W], r2[W], y[W], t[W], hh[W], rj[W], q2[W], rm[W], rn[W], fp[W];
+                    for (int e0 = 0; e0 < 8; e0 += W) {
+                        if (k0 + e0 == PRIO_SW) prio_swap();
+                        if (k0 + e0 < mine) {
+                            double dx[W], dy[W], dz[W], r2[W], y[W], t[W], hh[W], rj[W], q2[W], rm[W], rn[W], fp[W];
+                            bool in[W];
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                in[u] = (k0 + e0 + u) < mine;
+                                const int j = in[u] ? (int)((wd >> (8 * (e0 + u))) & 0xFFull) : i;
+                                dx[u] = __builtin_fma(-px[j], invL, xi); dy[u] = __builtin_fma(-py[j], invL, yi); dz[u] = __builtin_fma(-pz[j], invL, zi);
+                                rj[u] = rho[j];
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                dx[u] = __builtin_fma(__builtin_amdgcn_fract(dx[u]), L, mhL); dy[u] = __builtin_fma(__builtin_amdgcn_fract(dy[u]), L, mhL);
+                                dz[u] = __builtin_fma(__builtin_amdgcn_fract(dz[u]), L, mhL);
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                r2[u] = dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u];
+                                in[u] = in[u] && r2[u] < rc2;
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) y[u] = __builtin_amdgcn_rsq(r2[u]);
+#pragma unroll
+                            for (int u = 0; u < 2 * W; ++u) { // two Newton steps per neighbour: y <- y + y (1/2 - (r2 y)(y/2))
+                                const int v = u % W;
+                                t[v] = r2[v] * y[v]; hh[v] = 0.5 * y[v];
+                                t[v] = __builtin_fma(-t[v], hh[v], 0.5);
+                                y[v] = __builtin_fma(y[v], t[v], y[v]);
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) y[u] = in[u] ? y[u] : 0.0; // 1 / r, or nothing at all
+#pragma unroll
+                            for (int u = 0; u < W; ++u) { t[u] = y[u] * y[u]; q2[u] = a2 * t[u]; } // t = 1/r^2, q2 = (a/r)^2
+#pragma unroll
+                            for (int u = 0; u < W; ++u) { rm[u] = q2[u] * q2[u] * q2[u]; }         // (a/r)^6
+#pragma unroll
+                            for (int u = 0; u < W; ++u) { rn[u] = rm[u] * (a1r * y[u]); }           // (a/r)^7
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                const double dF = 0.5 * cc * (isi + rj[u]);
+                                fp[u] = eps * (7.0 * rn[u] - 6.0 * dF * rm[u]) * t[u];
+                            }
+#pragma unroll
+                            for (int u = 0; u < W; ++u) {
+                                ax += dx[u] * fp[u]; ay += dy[u] * fp[u]; az += dz[u] * fp[u];
+                                if (WANT_E) { e += eps * rn[u]; w += r2[u] * fp[u]; np += in[u] ? 1.0 : 0.0; }
+                            }
+                        }
+                    }
+                }
+            } else {
+                constexpr int LA = 3; // chunks sub, sub+TPA, ... of atom i; the word LA chunks ahead is asked for before a chunk's arithmetic,
+                // so the L2 latency is paid once and hidden behind 4 LA neighbours (as pair_loop's PF, with one chunk's code instead of four)
+                const int nch = (c + C::CH - 1) / C::CH, mych = (nch - sub + TPA - 1) / TPA;
+                auto word = [&](int k) { return k < mych ? nb64[NM_CHECK_INDEX((size_t)(sub + k * TPA) * NMAX + i, C::NBR_G_ELEMS / 4)] : 0ull; };
+                unsigned long long w0 = word(0), w1 = word(1), w2 = word(2);
+                for (int k = 0; k < mych; ++k) {
+                    const unsigned long long w3 = word(k + LA);
+                    const int first = (sub + k * TPA) * C::CH;
+#pragma unroll
+                    for (int e0 = 0; e0 < C::CH; e0 += W) {
+                        int jj[W];
                         bool in[W];
 #pragma unroll
                         for (int u = 0; u < W; ++u) {
-                            in[u] = (k0 + e0 + u) < mine;
-                            const int j = in[u] ? (int)((wd >> (8 * (e0 + u))) & 0xFFull) : i;
-                            dx[u] = __builtin_fma(-px[j], invL, xi); dy[u] = __builtin_fma(-py[j], invL, yi); dz[u] = __builtin_fma(-pz[j], invL, zi);
-                            rj[u] = rho[j];
+                            in[u] = (first + e0 + u) < c; // (the tail entries of a row's last chunk are zero: atom 0, masked)
+                            jj[u] = (int)((w0 >> (16 * (e0 + u))) & 0xFFFFull); // 8 x the atom index
                         }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            dx[u] = __builtin_fma(__builtin_amdgcn_fract(dx[u]), L, mhL); dy[u] = __builtin_fma(__builtin_amdgcn_fract(dy[u]), L, mhL);
-                            dz[u] = __builtin_fma(__builtin_amdgcn_fract(dz[u]), L, mhL);
-                        }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            r2[u] = dx[u] * dx[u] + dy[u] * dy[u] + dz[u] * dz[u];
-                            in[u] = in[u] && r2[u] < rc2;
-                        }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) y[u] = __builtin_amdgcn_rsq(r2[u]);
-#pragma unroll
-                        for (int u = 0; u < 2 * W; ++u) { // two Newton steps per neighbour: y <- y + y (1/2 - (r2 y)(y/2))
-                            const int v = u % W;
-                            t[v] = r2[v] * y[v]; hh[v] = 0.5 * y[v];
-                            t[v] = __builtin_fma(-t[v], hh[v], 0.5);
-                            y[v] = __builtin_fma(y[v], t[v], y[v]);
-                        }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) y[u] = in[u] ? y[u] : 0.0; // 1 / r, or nothing at all
-#pragma unroll
-                        for (int u = 0; u < W; ++u) { t[u] = y[u] * y[u]; q2[u] = a2 * t[u]; } // t = 1/r^2, q2 = (a/r)^2
-#pragma unroll
-                        for (int u = 0; u < W; ++u) { rm[u] = q2[u] * q2[u] * q2[u]; }         // (a/r)^6
-#pragma unroll
-                        for (int u = 0; u < W; ++u) { rn[u] = rm[u] * (a1r * y[u]); }           // (a/r)^7
-#pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            const double dF = 0.5 * cc * (isi + rj[u]);
-                            fp[u] = eps * (7.0 * rn[u] - 6.0 * dF * rm[u]) * t[u];
-                        }
-#pragma unroll
-                        for (int u = 0; u < W; ++u) {
-                            ax += dx[u] * fp[u]; ay += dy[u] * fp[u]; az += dz[u] * fp[u];
-                            if (WANT_E) { e += eps * rn[u]; w += r2[u] * fp[u]; np += in[u] ? 1.0 : 0.0; }
-                        }
+                        sc_force_vec<WANT_E, W, true>(jj, in, xi, yi, zi, isi, invL, rc2, a2, a1r, eps, cc, mhL, ax, ay, az, e, w, np);
                     }
+                    w0 = w1; w1 = w2; w2 = w3;
                 }
             }
         }

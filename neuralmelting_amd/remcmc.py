@@ -44,7 +44,7 @@ _FLAGS = (
     ('-nt', '--threads', int, 1, 'ignored'),
     ('-mt', '--method', str, 'fork', 'ignored'),
     ('-n', '--name', str, 'remcmc_init', 'run name (prefix of every file)'),
-    ('-e', '--element', str, 'LJ', 'LJ or Al'),
+    ('-e', '--element', str, 'LJ', 'LJ or Al (Sutton-Chen EAM); both at any -ss from 1 to 8 (2048 atoms)'),
     ('-ss', '--supercell_size', int, 5, 'fcc cells per box edge'),
     ('-pn', '--pressure_number', int, 16, 'points of the pressure grid'),
     ('-pr', '--pressure_range', (float, 2), [1, 8], 'lowest and highest pressure'),
