@@ -16,6 +16,9 @@ The reference cannot be imported as is: `numba` and `lammps` are not installed (
 
 Outputs: ref_scalars.json (G1 constants, G2 adaptive steps, G3 exchange sweeps, G4 strings) and
 ref_blocks.npz (G5: gen_sample traces: inputs, the recorded np.random stream, outputs).
+Element Al (metal units; FakeLammps builds the oracle with units=1, the reference's mass and Sutton-Chen): ref_blocks_al.npz holds
+the G5 traces of the three tags at 4^3 and 5^3 ('<tag>_<sz>_<slot>_*'), ref_scalars.json their command strings
+(G5_command_strings_al) and G3 sweeps on synthetic metal-unit states (G3_exchange_al).  The LJ outputs do not depend on them.
 """
 import ctypes
 import importlib.util
@@ -74,6 +77,7 @@ class FakeLammps:
     """the 8 methods / 10 command patterns remcmc uses, answered by the oracle"""
     natoms = 256
     sz = 4
+    el = 'LJ'             # metal units (units=1, the reference's mass, Sutton-Chen) for every other element
     rng = (256, 0, 0)     # (seed, slot, step) of the per-atom Philox streams
     calls = None          # optional list collecting the command strings
 
@@ -81,10 +85,10 @@ class FakeLammps:
         self.sim = None
 
     def file(self, path):
-        n = FakeLammps.natoms
-        self.sim = O.Sim(n)
+        n, el = FakeLammps.natoms, FakeLammps.el
+        self.sim = O.Sim(n) if el == 'LJ' else O.Sim(n, units=1, mass=lattice.MASS[el], pot=1)
         self.sim.set_rng(*FakeLammps.rng)
-        box = FakeLammps.sz * lattice.lattice_constant('LJ')
+        box = FakeLammps.sz * lattice.lattice_constant(el)
         self.sim.set_box(box)
         self.sim.set_x((lattice.fcc_fractional(FakeLammps.sz) * box).ravel())
         self.sim.set_v(np.zeros(3 * n))
@@ -195,6 +199,108 @@ def set_globals(mod, *, el='LJ', sz=4, npn=2, ntn=2, pr=(1.0, 8.0), tr=(0.25, 2.
     return P32, T32
 
 
+def gen_traces(mod, rec, blocks, name, kw, el, sz, dx, dv):
+    """gen_sample (remcmc:665-691) for the four slots of a 2x2 grid, each from its own np.random seed: inputs, the recorded
+    np.random stream and outputs go into blocks under '<name>_<slot>_*'; returns the first 40 command strings of slot 0"""
+    grid = {} if el == 'LJ' else dict(el=el, sz=sz, pr=(1.0, 8.0), tr=(300.0, 900.0))
+    P32, T32 = set_globals(mod, npn=2, ntn=2, **grid, **kw)
+    mod.CONST = mod.init_constants()
+    x, v, box, d = lattice.init_states(sz, P32, T32, dx, dv, **({} if el == 'LJ' else dict(el=el)))
+    n = 4 * sz ** 3
+    FakeLammps.natoms, FakeLammps.sz, FakeLammps.el = n, sz, el
+    for k in range(4):
+        np.random.seed(256 + k)
+        FakeLammps.rng = (256, k, 3)
+        FakeLammps.calls = [] if k == 0 else None
+        state = [n, x[k].copy(), v[k].copy(), 0.0, 0.0, 0.0, 0.0, float(box[k]), float(box[k]) ** 3,
+                 float(d[k, 0]), float(d[k, 1]), float(d[k, 2])] + [0.0] * 9
+        rec.install()
+        try:
+            out = mod.gen_sample(k, mod.CONST[k], state)
+        finally:
+            rec.remove()
+        tape = np.array(rec.take())
+        if k == 0:
+            calls = FakeLammps.calls[:40]
+        pre = '%s_%d_' % (name, k)
+        blocks[pre + 'x_in'], blocks[pre + 'v_in'] = x[k], v[k]
+        blocks[pre + 'scal_in'] = np.array([box[k], d[k, 0], d[k, 1], d[k, 2], mod.CONST[k][0], mod.CONST[k][1], mod.T[k % 2]])
+        blocks[pre + 'tape'] = tape
+        blocks[pre + 'x_out'], blocks[pre + 'v_out'] = np.array(out[1]), np.array(out[2])
+        blocks[pre + 'row_out'] = np.array([float(q) for q in out[3:7]] + [float(out[8])] + [float(q) for q in out[9:21]])
+        blocks[pre + 'box_out'] = np.array([float(out[7])])
+    blocks[name + '_params'] = np.array([kw['mod_'], kw.get('ppos', 0.125), kw.get('pvol', 0.125), 8, int(kw['bm'])], dtype=np.float64)
+    FakeLammps.el, FakeLammps.calls = 'LJ', None
+    return calls
+
+
+# element Al: (tag, move mix, dx[sz], dv[sz]) per tag, at the production timestep of 1/256 ps.  The production dx = dv = 1/32 rejects
+# every bulk position move of a crystal at 300-900 K (a whole-crystal displacement of 0.126 A costs many kT), and a volume step of
+# that size costs several kT, so each tag gets steps at which every kind of move it draws is accepted and rejected within its four slots
+# (check_moves)
+AL_TAGS = (('bulk', dict(bm=True, mod_=24, ppos=0.25, pvol=0.25), {4: 0.004, 5: 0.003}, {4: 0.004, 5: 0.003}),
+           ('iter', dict(bm=False, mod_=10, ppos=0.2, pvol=0.3), {4: 0.03125, 5: 0.03125}, {4: 0.004, 5: 0.003}),
+           ('default_mix', dict(bm=True, mod_=32), {4: 0.004, 5: 0.003}, {4: 0.004, 5: 0.003}))
+
+
+def check_moves(blocks, name, bm):
+    """every kind of move the tag draws (bulk or iterative position, volume, HMC) is accepted and rejected at least once over
+    its four slots: counters ntp, nap, ntv, nav, nth, nah of the reference's output rows"""
+    c = np.array([blocks['%s_%d_row_out' % (name, k)][8:14] for k in range(4)]).sum(0)
+    for kind, (tries, acc) in zip(('position', 'volume', 'hmc'), c.reshape(3, 2)):
+        assert 0 < acc < tries, (name, kind, c.tolist())
+    print('%-16s bm=%d  tries/accepted: position %d/%d  volume %d/%d  hmc %d/%d' % ((name, bm) + tuple(int(q) for q in c)))
+
+
+def sweep_accepts(g):
+    """the number of swaps replica_exchange accepted: its sweep (remcmc:782-798) replayed on the recorded uniforms"""
+    nt = g['nt']
+    etot = np.array(g['pe']) + np.array(g['ke'])
+    ident, u, n = list(range(g['np'] * nt)), iter(g['uniforms']), 0
+    for r in range(g['np']):
+        for v in range(nt - 1, -1, -1):
+            for w in range(v):
+                i, j = r * nt + v, r * nt + w
+                a, b = ident[i], ident[j]
+                dh = (etot[a] - etot[b]) * (1.0 / g['et'][i] - 1.0 / g['et'][j]) + (g['pf'][i] - g['pf'][j]) * (g['vol'][a] - g['vol'][b])
+                if next(u) <= min(1.0, np.exp(dh)):
+                    ident[i], ident[j] = b, a
+                    n += 1
+    assert ident == g['perm']
+    return n
+
+
+def gen_exchange_al(mod, rec):
+    """replica_exchange (remcmc:776-803) on synthetic metal-unit states of 256 atoms: energies ~ -3.4 eV and volumes ~ 16.6 A^3
+    per atom, constants of init_constants() for el='Al' on a GPa-scale pressure grid, so that both terms of the criterion count"""
+    g3 = []
+    for npn, ntn, seed in ((2, 2, 256), (2, 8, 256), (3, 5, 7)):
+        P32, T32 = set_globals(mod, el='Al', npn=npn, ntn=ntn, pr=(1e4, 5e4), tr=(300.0, 900.0))
+        ns = npn * ntn
+        mod.CONST = mod.init_constants()
+        rs = np.random.RandomState(2000 + ns)
+        # 1/kT differs by up to 26 /eV across the grid and P/kT by up to 0.8 /A^3: spreads of 0.1 eV and 1 A^3 give a mix of
+        # accepted and rejected swaps
+        pe = -3.4 * 256 + 0.1 * rs.rand(ns)
+        ke = 0.0388 * 256 + 0.05 * rs.rand(ns)
+        vol = 16.6 * 256 + 1.0 * rs.rand(ns)
+        mod.STATE = [[k, None, None, 0.0, float(pe[k]), float(ke[k]), 0.0, 0.0, float(vol[k]), 0.1, 0.2, 0.3] + [0.0] * 9
+                     for k in range(ns)]
+        np.random.seed(seed)
+        rec.install()
+        try:
+            mod.replica_exchange()
+        finally:
+            rec.remove()
+        g3.append(dict(np=npn, nt=ntn, P=[float(q) for q in P32], T=[float(q) for q in T32], pe=pe.tolist(), ke=ke.tolist(),
+                       vol=vol.tolist(), et=[float(a) for a, b in mod.CONST], pf=[float(b) for a, b in mod.CONST],
+                       uniforms=rec.take(), perm=[int(s[0]) for s in mod.STATE]))
+        acc, tries = sweep_accepts(g3[-1]), len(g3[-1]['uniforms'])
+        assert 0 < acc < tries, ('G3 Al: no mix of accepted and rejected swaps', npn, ntn, acc, tries)
+        print('G3 Al %dx%d: %d of %d swaps accepted' % (npn, ntn, acc, tries))
+    return g3
+
+
 def main():
     mod = load_reference()
     scal = {}
@@ -270,44 +376,29 @@ def main():
     scal['G4_formats'] = g4
 
     # ---------------- G5: gen_sample traces (remcmc:665-691) with the reference's control flow
-    blocks = {}
-    cmdlog = {}
+    blocks, cmdlog = {}, {}
     for tag, kw in (('bulk', dict(bm=True, mod_=24, ppos=0.25, pvol=0.25)),
                     ('iter', dict(bm=False, mod_=10, ppos=0.2, pvol=0.3)),
                     ('default_mix', dict(bm=True, mod_=32))):
-        P32, T32 = set_globals(mod, npn=2, ntn=2, **kw)
-        mod.CONST = mod.init_constants()
-        x, v, box, d = lattice.init_states(4, P32, T32, 0.03125, 0.03125)
-        FakeLammps.natoms, FakeLammps.sz = 256, 4
-        for k in range(4):
-            np.random.seed(256 + k)
-            FakeLammps.rng = (256, k, 3)
-            FakeLammps.calls = [] if k == 0 else None
-            state = [256, x[k].copy(), v[k].copy(), 0.0, 0.0, 0.0, 0.0, float(box[k]), float(box[k]) ** 3,
-                     float(d[k, 0]), float(d[k, 1]), float(d[k, 2])] + [0.0] * 9
-            rec.install()
-            try:
-                out = mod.gen_sample(k, mod.CONST[k], state)
-            finally:
-                rec.remove()
-            tape = np.array(rec.take())
-            if k == 0:
-                cmdlog[tag] = FakeLammps.calls[:40]
-            pre = '%s_%d_' % (tag, k)
-            blocks[pre + 'x_in'], blocks[pre + 'v_in'] = x[k], v[k]
-            blocks[pre + 'scal_in'] = np.array([box[k], d[k, 0], d[k, 1], d[k, 2], mod.CONST[k][0], mod.CONST[k][1], mod.T[k % 2]])
-            blocks[pre + 'tape'] = tape
-            blocks[pre + 'x_out'], blocks[pre + 'v_out'] = np.array(out[1]), np.array(out[2])
-            blocks[pre + 'row_out'] = np.array([float(q) for q in out[3:7]] + [float(out[8])] + [float(q) for q in out[9:21]])
-            blocks[pre + 'box_out'] = np.array([float(out[7])])
-        blocks[tag + '_params'] = np.array([kw['mod_'], kw.get('ppos', 0.125), kw.get('pvol', 0.125), 8, int(kw['bm'])], dtype=np.float64)
+        cmdlog[tag] = gen_traces(mod, rec, blocks, tag, kw, 'LJ', 4, 0.03125, 0.03125)
     scal['G5_command_strings'] = cmdlog
+
+    # ---------------- G3 / G5 for element Al (metal units)
+    scal['G3_exchange_al'] = gen_exchange_al(mod, rec)
+    blocks_al, cmdlog_al = {}, {}
+    for sz in (4, 5):
+        for tag, kw, dx, dv in AL_TAGS:
+            name = '%s_%d' % (tag, sz)
+            cmdlog_al[name] = gen_traces(mod, rec, blocks_al, name, kw, 'Al', sz, dx[sz], dv[sz])
+            check_moves(blocks_al, name, kw['bm'])
+    scal['G5_command_strings_al'] = cmdlog_al
 
     with open(os.path.join(HERE, 'ref_scalars.json'), 'w') as f:
         json.dump(scal, f, indent=1)
     np.savez_compressed(os.path.join(HERE, 'ref_blocks.npz'), **blocks)
-    print('wrote ref_scalars.json (%d bytes) and ref_blocks.npz (%d bytes)'
-          % (os.path.getsize(os.path.join(HERE, 'ref_scalars.json')), os.path.getsize(os.path.join(HERE, 'ref_blocks.npz'))))
+    np.savez_compressed(os.path.join(HERE, 'ref_blocks_al.npz'), **blocks_al)
+    print('wrote ref_scalars.json (%d bytes), ref_blocks.npz (%d bytes) and ref_blocks_al.npz (%d bytes)'
+          % tuple(os.path.getsize(os.path.join(HERE, f)) for f in ('ref_scalars.json', 'ref_blocks.npz', 'ref_blocks_al.npz')))
 
 
 if __name__ == '__main__':

@@ -9,6 +9,11 @@ touches oracle/:
   C5 thermo_temp, thermo_press      test_velocity_create_semantics..., test_npt_virial_pressure_equals_imposed_pressure
   C6 fix nve = kick-drift-kick      test_hmc_energy_error_is_second_order_in_dt
   volume_mc's weight (remcmc:576)   test_dilute_gas_volume_follows_the_npt_ideal_gas_law
+These run in lj units, where kB, mvv2e, ftm2v and nktv2p all equal 1.  The metal-unit rows (element Al) are in
+test_physics_metal_gpu.py:
+  C4, C5 in metal units, N 256-2048  test_velocity_create_semantics_metal (also LJ at N = 2048)
+  C6 with ftm2v and the mass         test_hmc_energy_error_is_second_order_in_dt_al
+  C5 press in bar, pf in the VMC     test_npt_pressure_in_bar_equals_imposed_pressure_al
 """
 import numpy as np
 import pytest
