@@ -20,7 +20,12 @@ extern "C" {
  *   rdf[s][0] = 0 (rd[1:] += np.histogram(d, r)[0]);
  * rv_edges[cbins+1] float64 = RV[0] of calculate_spatial (lammps_distr.py:111-113), the same edges in x, y and z;
  * rdf[ns][sbins], cdf[ns][cbins][cbins][cbins] float32 counts summed over the 27 images, NOT yet divided by natoms.
- * Either output may be NULL.  Returns 0 or a negative NM_ERR_* code (include/nm.h); message via nm_distr_last_error(). */
+ * Either output may be NULL: that histogram is neither computed nor written, and its edges and bin count are not read.
+ * Returns 0 or a negative NM_ERR_* code (include/nm.h); message via nm_distr_last_error().  NM_ERR_ARG for bad arguments
+ * (natoms outside 1..4095, sbins outside 2..256, cbins outside 1..32, a working set beyond 160 KiB of LDS, a bad device
+ * ordinal): the outputs are left untouched.  NM_ERR_ARG also when a returned count reaches 2^24 (a bin can hold more than
+ * natoms^2 counts, because a displacement on +-l/2 lies in two periodic images per axis): float32 counts are no longer
+ * exact there, and the outputs hold unspecified values. */
 int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const float *box, int sbins,
                         const double *r_edges, int cbins, const double *rv_edges, float *rdf, float *cdf);
 const char *nm_distr_last_error(void);

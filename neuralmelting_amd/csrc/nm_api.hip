@@ -1667,7 +1667,9 @@ int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const 
     const size_t lds = (((size_t)3 * (natoms + npad) * sizeof(float) + 7) & ~(size_t)7) + (size_t)(sb + cb + 1) * sizeof(double)
                      + ((size_t)sb + nc) * sizeof(unsigned int);
     if (lds > 160 * 1024) return dfail(NM_ERR_ARG, "nm_distr_histograms: working set exceeds LDS");
-    if (natoms >= 4096) return dfail(NM_ERR_ARG, "nm_distr_histograms: natoms^2 must stay below 2^24 (float32 counts, as in the reference)");
+    // one image block's count of a bin is at most natoms^2, exact as a float below 2^24; the sum of the 27 blocks can exceed
+    // natoms^2 (a displacement on +-l/2 lies in the closed cube in two images per axis) and is checked after the copy-back
+    if (natoms >= 4096) return dfail(NM_ERR_ARG, "nm_distr_histograms: natoms^2 must stay below 2^24 (float32 counts of one periodic image)");
     DCHK(hipFuncSetAttribute((const void *)nm_distr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int chunk = 4096; // samples per launch: bounds device memory (pos 12 N B + counts) for long trajectories
     float *d_pos = nullptr, *d_box = nullptr;
@@ -1691,6 +1693,15 @@ int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const 
         DCHK(hipDeviceSynchronize());
         if (rdf) DCHK(hipMemcpy(rdf + (size_t)s0 * sbins, d_r, (size_t)n * sbins * sizeof(float), hipMemcpyDeviceToHost));
         if (cdf) DCHK(hipMemcpy(cdf + (size_t)s0 * nc, d_c, (size_t)n * nc * sizeof(float), hipMemcpyDeviceToHost));
+        // every partial sum below 2^24 is exact, so a total reaches 2^24 exactly when the returned float does; from there on
+        // the float atomics round in the order they land, and the counts are no longer the reference's
+        bool big = false;
+        if (rdf) for (size_t i = 0; i < (size_t)n * sbins; ++i) big |= rdf[(size_t)s0 * sbins + i] >= 16777216.0f;
+        if (cdf) for (size_t i = 0; i < (size_t)n * nc; ++i) big |= cdf[(size_t)s0 * nc + i] >= 16777216.0f;
+        if (big) {
+            hipFree(d_pos); hipFree(d_box); hipFree(d_re); hipFree(d_ve); hipFree(d_r); hipFree(d_c);
+            return dfail(NM_ERR_ARG, "nm_distr_histograms: a bin holds 2^24 counts or more, beyond what float32 counts hold exactly");
+        }
     }
     hipFree(d_pos); hipFree(d_box); hipFree(d_re); hipFree(d_ve); hipFree(d_r); hipFree(d_c);
 #undef DCHK

@@ -1,7 +1,7 @@
 // nm_distr.h — histogram kernels for lammps_distr.py's calculate_rdf / calculate_cdf (lammps_distr.py:123-171).
 // One workgroup per (sample, periodic image): positions staged in LDS, float32 displacement arithmetic identical to
 // numpy's (no contraction), float64 edge comparisons, integer counts in LDS, one float atomic (exact below 2^24) per non-empty bin
-// at the end.
+// at the end; the host refuses a result with a count of 2^24 or more.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,10 +72,12 @@ nm_distr_kernel(int natoms, const float *__restrict__ pos, const float *__restri
         } else { qx[a] = 3.0e38f; qy[a] = 3.0e38f; qz[a] = 3.0e38f; }
     }
     for (int k = tid; k < sbins; k += DISTR_BLOCK) { re[k] = r_edges[k]; hr[k] = 0u; }
-    for (int k = tid; k <= cbins; k += DISTR_BLOCK) ve[k] = rv_edges[k];
+    const bool do_r = rdf_cnt != nullptr, do_c = cdf_cnt != nullptr;
+    // an rdf-only call passes cbins = 0 and no cdf edges: nothing to stage then (ve[0] would be read from a null pointer)
+    if (do_c)
+        for (int k = tid; k <= cbins; k += DISTR_BLOCK) ve[k] = rv_edges[k];
     for (int k = tid; k < nc; k += DISTR_BLOCK) hc[k] = 0u;
     __syncthreads();
-    const bool do_r = rdf_cnt != nullptr, do_c = cdf_cnt != nullptr;
     double far = 0.0;
     if (do_r) far = fmax(far, fmax(fabs(re[0]), fabs(re[sbins - 1])));
     if (do_c) far = fmax(far, fmax(fabs(ve[0]), fabs(ve[cbins])));
@@ -101,7 +103,9 @@ nm_distr_kernel(int natoms, const float *__restrict__ pos, const float *__restri
                     float d2 = dx * dx;      // np.sum(np.square(dvm), -1): sequential float32 sum of three terms
                     d2 = d2 + dy * dy;
                     d2 = d2 + dz * dz;
-                    const float d = __fsqrt_rn(d2);
+                    // np.sqrt is correctly rounded; so is sqrtf under hipcc's default fp32 sqrt, while __fsqrt_rn is
+                    // the bare v_sqrt_f32 (1 ulp), which moves a pair next to an edge into the neighbouring bin
+                    const float d = sqrtf(d2);
                     const int k = bin_near(re, sbins, (double)d, rinv);
                     if (k >= 0) atomicAdd(&hr[k + 1], 1u);
                 }
@@ -115,8 +119,10 @@ nm_distr_kernel(int natoms, const float *__restrict__ pos, const float *__restri
         }
     }
     __syncthreads();
-    // the 27 image blocks of a sample meet in global memory; counts stay below 2^24, so float atomics are exact and
-    // the result is what the reference holds in its float32 `rd` / `cd` arrays before the division by natoms
+    // the 27 image blocks of a sample meet in global memory.  A block's own count is at most natoms^2 < 2^24 and exact as a
+    // float; the float atomics are exact as long as the sum stays below 2^24, and the host refuses a result that reaches it
+    // (displacements on +-l/2 count in two images per axis, so a bin can exceed natoms^2).  Below that, the result is what
+    // the reference holds in its float32 `rd` / `cd` arrays before the division by natoms
     if (do_r)
         for (int k = tid; k < sbins; k += DISTR_BLOCK) if (hr[k]) atomicAdd(&rdf_cnt[(size_t)s * sbins + k], (float)hr[k]);
     if (do_c)

@@ -22,6 +22,49 @@ def test_oracle_matches_reference_outputs(key):
 
 
 @pytest.mark.parametrize('key', KEYS)
+def test_bounded_reference_matches_reference_outputs(key):
+    """tests/distr_ref.py (the chunked reference of the GPU edge tests) on every golden key, in blocks of a few rows b and,
+    where the rows fit, several samples: bit-equal to what the reference returns"""
+    import distr_ref as R
+    pos, box, natoms, r, rv = (G[key + '_' + n] for n in ('pos', 'box', 'natoms', 'r', 'rv'))
+    for budget in (1 << 12, 1 << 22):
+        rd, cd = R.counts(pos, box, r, rv[0], budget=budget)
+        assert (rd[:, 0] == 0).all()
+        np.testing.assert_array_equal(R.normalized(rd, natoms), G[key + '_rdf'])
+        np.testing.assert_array_equal(R.normalized(cd, natoms), G[key + '_cdf'])
+
+
+def test_bounded_reference_matches_oracle_on_arbitrary_edges():
+    """arbitrary increasing edges (geometric r edges, cdf edges not centred on 0, edges that sit on grid displacements),
+    positions outside [0, L), coincident atoms and boxes that differ per sample: the chunked reference == the oracle"""
+    import distr_ref as R
+    from oracle import distr_oracle as D
+    rng = np.random.default_rng(11)
+    ns, n = 5, 37
+    box = np.array([4.0, 4.0, 5.5, 3.25, 4.0], dtype=np.float32)
+    pos = (rng.random((ns, n, 3)) * box[:, None, None]).astype(np.float32)
+    pos[0] = (rng.integers(0, 16, (n, 3)) * 0.25).astype(np.float32)      # dyadic grid: displacements on the edges below
+    pos[1] = pos[0] + (rng.integers(-2, 3, (n, 3)) * 4.0).astype(np.float32)  # the same frame, unwrapped
+    pos[2, 5] = pos[2, 9]                                                  # d = 0
+    pos[3] -= np.float32(1.5)
+    edges = [(np.geomspace(0.01, 2.0, 23), np.linspace(-1.5, 2.25, 8)),
+             (np.linspace(1e-16, 0.5, 17) * 4.0, np.linspace(0, 4.0, 9) - 2.0),
+             (np.concatenate([[0.0], np.geomspace(0.25, 2.0, 4)]), np.array([-2.0, -1.75, -0.5, 0.0, 0.25, 1.0, 2.0])),
+             (np.array([0.5, 0.5000001, 2.0]), np.array([-0.25, 0.0]))]
+    for r, ve in edges:
+        rd, cd = R.counts(pos, box, r, ve, budget=1 << 10)
+        rv = np.array([ve, ve, ve])
+        na = np.full(ns, n, dtype=np.uint16)
+        for i in range(ns):
+            np.testing.assert_array_equal(R.normalized(rd, na)[i], D.calculate_rdf(na[i], box[i], pos[i], r))
+            np.testing.assert_array_equal(R.normalized(cd, na)[i], D.calculate_cdf(na[i], box[i], pos[i], rv))
+        rd1, _ = R.counts(pos, box, r, None)
+        _, cd1 = R.counts(pos, box, None, ve)
+        np.testing.assert_array_equal(rd1, rd)
+        np.testing.assert_array_equal(cd1, cd)
+
+
+@pytest.mark.parametrize('key', KEYS)
 def test_spatial_domains_match(key):
     from neuralmelting_amd import distr
     sb = len(G[key + '_r']); cb = G[key + '_rv'].shape[1] - 1
@@ -44,7 +87,8 @@ def test_hip_histograms_bit_exact(key):
 
 @pytest.mark.gpu
 def test_hip_histograms_many_samples_vs_oracle():
-    """more samples than one launch chunk would need + totals: every pair of every image lands in exactly one cdf bin or outside"""
+    """40 samples in one launch (the host launches up to 4096 per chunk; tests/test_distr_edges_gpu.py covers several chunks),
+    three of them checked against the oracle, and the totals: every pair of every image lands in at most one cdf bin"""
     from neuralmelting_amd import distr
     from oracle import distr_oracle as D
     rng = np.random.default_rng(3)
