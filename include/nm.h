@@ -131,7 +131,9 @@ int nm_get_thermo(nm_ctx *ctx, double *rows);
    recorded cycle writes (the 17 thermo columns, positions, box) as of that point; a side stream brings it to the host while the context's stream goes on with
    nm_adapt, nm_exchange and the next block.  nm_snapshot_fetch hands the OLDEST pending snapshot out — rows[nslots][17], x[nslots][3N], box[nslots], any
    of them NULL — and waits for that copy only.  At most two may be pending (a driver fetches cycle s - 1 after queueing cycle s); NM_ERR_STATE otherwise.
-   Neither call looks at the queue's outcome: an error is reported by the next synchronising call as always. */
+   A snapshot is a record as nm_run_cycles_recorded takes them, with the same guarantee: a snapshot of a block that did not complete is never handed out.
+   A block that stopped in a way the library heals is re-issued and the snapshot taken again; any other error is returned by the fetch as NM_ERR_STATE,
+   with the reason. */
 int nm_snapshot(nm_ctx *ctx);
 int nm_snapshot_fetch(nm_ctx *ctx, double *rows, double *x, double *box);
 /* `ncycles` cycles of the main loop WITH outputs (remcmc:977-995 with write_outputs, remcmc:983-985): what nm_run_cycles does, plus for every cycle the

@@ -111,21 +111,16 @@ struct nm_ctx {
     void *d_nbr;
     unsigned long long *d_prof; // diagnostic build only (NM_PROF)
     unsigned long long *d_tline; // experiment build only
-    // output snapshots (nm_snapshot / nm_snapshot_fetch): two slots, each a device copy and a pinned host copy of everything a recorded
-    // cycle writes (x, box, therm, steps, count, ratio, slot2buf); the D2H runs on a side stream so that the main stream never waits
+    // recorded cycles: rings 0 and 1 hold the records of nm_run_cycles_recorded calls, rings 2 and 3 those of nm_snapshot (one cycle each).  A ring
+    // is a device buffer of cap cycles' records (nslots x (3N + NM_REC_HEAD) doubles per cycle) and its pinned host copy, which lands in one D2H on
+    // the side stream (the main stream never waits for it) behind the ring's last record.  n: records of the call in it, next: the next one
+    // nm_snapshot_fetch hands out (the ring is free when n == 0); tag0: the tag of its first record; dirty: settle re-issued launches that write it,
+    // the host copy is stale
     hipStream_t side = nullptr;
-    struct Snap { double *d = nullptr, *h = nullptr; hipEvent_t taken = nullptr, landed = nullptr; bool pending = false; } snap[2];
-    size_t snap_doubles = 0;
-    int snap_head = 0, snap_count = 0; // oldest pending slot, number pending
-    // recorded cycles (nm_run_cycles_recorded): two rings, each a device buffer of rec_cap cycles' records (nslots x (3N + NM_REC_HEAD) doubles
-    // per cycle) and its pinned host copy, which lands in one D2H on the side stream behind the call's last launch.  n: records of the call in it,
-    // next: the next one nm_snapshot_fetch hands out (the ring is free when next == n); tag0: the tag of its first record; dirty: settle re-issued
-    // launches that write it, the host copy is stale
-    struct Ring { double *d = nullptr, *h = nullptr; hipEvent_t taken = nullptr, landed = nullptr; int n = 0, next = 0; uint32_t tag0 = 0;
-                  bool dirty = false; } ring[2];
-    int rec_cap = 0;
+    struct Ring { double *d = nullptr, *h = nullptr; hipEvent_t taken = nullptr, landed = nullptr; int cap = 0, n = 0, next = 0; uint32_t tag0 = 0;
+                  bool dirty = false; } ring[4];
     uint32_t rec_calls = 0;
-    std::deque<int> fetchq; // what nm_snapshot_fetch hands out next, oldest first: -1 an nm_snapshot, r >= 0 the next record of ring r
+    std::deque<int> fetchq; // the rings whose next records nm_snapshot_fetch hands out, oldest first
     double *h_stage = nullptr;   // pinned host staging area (nm_set_state / nm_get_state)
     size_t stage_cap = 0;
     size_t trace_cap;
@@ -438,7 +433,7 @@ int issue_exchange(nm_ctx *c, uint32_t step)
 
 size_t rec_cycle_doubles(const nm_ctx *c) { return (size_t)c->nslots * ((size_t)3 * c->N + NM_REC_HEAD); } // one cycle's records
 
-// the record of cycle j of ring r, copied on the stream behind that cycle's block (the loop of single launches)
+// the record of cycle j of ring r, copied on the stream behind that cycle's block (nm_snapshot, the loop of single launches)
 int issue_record(nm_ctx *c, int r, int j)
 {
     const nm_ctx::Ring &g = c->ring[r];
@@ -692,6 +687,14 @@ int check_status(nm_ctx *c)
     return settle(c);
 }
 
+void free_ring(nm_ctx::Ring &g)
+{
+    if (g.d) hipFree(g.d);
+    if (g.h) hipHostFree(g.h);
+    if (g.taken) hipEventDestroy(g.taken);
+    if (g.landed) hipEventDestroy(g.landed);
+}
+
 // everything a context owns; safe on a half-built one (nm_create's failure paths: `new nm_ctx()` zero-initialises the pointers)
 void free_ctx(nm_ctx *c)
 {
@@ -704,18 +707,7 @@ void free_ctx(nm_ctx *c)
     for (void *q : ptrs) if (q) hipFree(q);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->side) hipStreamSynchronize(c->side);
-    for (auto &sn : c->snap) {
-        if (sn.d) hipFree(sn.d);
-        if (sn.h) hipHostFree(sn.h);
-        if (sn.taken) hipEventDestroy(sn.taken);
-        if (sn.landed) hipEventDestroy(sn.landed);
-    }
-    for (auto &g : c->ring) {
-        if (g.d) hipFree(g.d);
-        if (g.h) hipHostFree(g.h);
-        if (g.taken) hipEventDestroy(g.taken);
-        if (g.landed) hipEventDestroy(g.landed);
-    }
+    for (auto &g : c->ring) free_ring(g);
     if (c->side) hipStreamDestroy(c->side);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -1166,69 +1158,16 @@ int nm_set_slots(nm_ctx *c, int nk, const int *slots, const double *x, const dou
     return NM_OK;
 }
 
-// ---- output snapshots: write_outputs (remcmc:259-286) without stopping the stream.  nm_snapshot, queued right behind nm_run_block, copies what
-// a recorded cycle writes — positions, box, the 17 thermo columns' sources — device to device on the context's stream (behind the block, in front of
-// nm_adapt), and a side stream brings the copy to pinned host memory while the main stream goes on with nm_adapt, nm_exchange and the next block.
-// nm_snapshot_fetch hands the OLDEST pending snapshot out; it waits for that snapshot's copy only, never for the main stream.  Two slots: a driver
-// fetches cycle s - 1 after it has queued cycle s.  (nm_get_thermo + nm_get_state, the synchronous way, stop the GPU between two blocks for the
-// copies and the host's turn-around: 7 % of a recorded C2 run.)  Neither call looks at the queue's outcome: a block that stopped on an error is
-// reported by the next synchronising call as always, and its snapshot holds the state the block started from.
-static size_t snap_layout(const nm_ctx *c, size_t off[8])
-{
-    const size_t ns = c->nslots, n3 = (size_t)3 * c->N;
-    size_t o = 0;
-    off[0] = o; o += ns * n3;        // x
-    off[1] = o; o += ns;             // box
-    off[2] = o; o += 5 * ns;         // therm
-    off[3] = o; o += 3 * ns;         // steps
-    off[4] = o; o += 6 * ns;         // count
-    off[5] = o; o += (3 * ns + 1) / 2; // ratio (float)
-    off[6] = o; o += (ns + 1) / 2;   // slot2buf (int)
-    return o;
-}
-
-int nm_snapshot(nm_ctx *c)
-{
-    if (!c) return NM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->snap_count == 2) return fail(c, NM_ERR_STATE, "nm_snapshot: two snapshots are pending; fetch one first (nm_snapshot_fetch)");
-    size_t off[8];
-    const size_t nd = snap_layout(c, off);
-    if (!c->snap_doubles) {
-        if (!c->side) HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)); // (nm_run_cycles_recorded may have made it)
-        c->snap_doubles = nd;
-        for (auto &sn : c->snap) {
-            HIPCHK(c, dalloc(&sn.d, nd));
-            HIPCHK(c, hipHostMalloc((void **)&sn.h, nd * sizeof(double), hipHostMallocDefault));
-            HIPCHK(c, hipEventCreateWithFlags(&sn.taken, hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&sn.landed, hipEventDisableTiming));
-        }
-    }
-    nm_ctx::Snap &sn = c->snap[(c->snap_head + c->snap_count) & 1];
-    const size_t ns = c->nslots, n3 = (size_t)3 * c->N;
-    SnapArgs a;
-    a.x = c->d_x; a.box = c->d_box; a.therm = c->d_therm; a.steps = c->d_steps; a.count = c->d_count; a.ratio = c->d_ratio; a.slot2buf = c->d_slot2buf;
-    a.dst = sn.d;
-    const size_t cnt[7] = { ns * n3, ns, 5 * ns, 3 * ns, 6 * ns, 3 * ns, ns };
-    for (int q = 0; q < 7; ++q) { a.off[q] = off[q]; a.n[q] = cnt[q]; }
-    const unsigned int blocks = (unsigned int)std::min<size_t>((ns * n3 + 1023) / 1024, 64); // (a handful of CUs for a few microseconds, between two blocks)
-    hipLaunchKernelGGL(nm_snapshot_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(sn.taken, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->side, sn.taken, 0));
-    HIPCHK(c, hipMemcpyAsync(sn.h, sn.d, nd * sizeof(double), hipMemcpyDeviceToHost, c->side));
-    HIPCHK(c, hipEventRecord(sn.landed, c->side));
-    sn.pending = true;
-    ++c->snap_count;
-    c->fetchq.push_back(-1);
-    return NM_OK;
-}
-
-// ---- recorded cycles (nm_run_cycles_recorded): the records of a call fill a ring, one D2H brings the ring to the host behind the call's last
-// launch, and nm_snapshot_fetch hands them out one by one in the queue it shares with nm_snapshot.  A record carries a tag (call, cycle) that only
-// a block which completed writes: a record whose tag is wrong was not taken (its block stopped, or was re-issued behind the copy), and the fetch then
-// settles the queue — which re-issues a launch that can be healed, into the same ring — and copies the ring again.
-static const size_t REC_BUDGET = (size_t)64 << 20; // bytes of one ring: 64 cycles of the 8 x 8 grid at 256 atoms (26 MB), 5 of 1024 x 500 atoms
+// ---- recorded cycles and output snapshots: write_outputs (remcmc:259-286) without stopping the stream.  A record holds what a recorded cycle writes
+// (the 17 thermo columns, the box and the positions of every slot) as of the point of the queue where it is taken.  The records of one call fill a
+// ring on the device, one D2H on the side stream brings the ring to pinned host memory behind the call's last record while the main stream goes on,
+// and nm_snapshot_fetch hands the records out one by one, oldest first, waiting for that ring's copy only.  nm_run_cycles_recorded takes a record
+// behind each of its cycles into ring 0 or 1; nm_snapshot, queued right behind nm_run_block (in front of nm_adapt, which zeroes the counters), takes
+// one into ring 2 or 3 — two of each, so that a driver fetches cycle s - 1 after it has queued cycle s.  (nm_get_thermo + nm_get_state, the
+// synchronous way, stop the GPU between two blocks for the copies and the host's turn-around: 7 % of a recorded C2 run.)  A record carries a tag
+// (call, cycle) that only a block which completed writes: a record whose tag is wrong was not taken (its block stopped, or was re-issued behind the
+// copy), and the fetch then settles the queue — which re-issues a launch that can be healed, into the same ring — and copies the ring again.
+static const size_t REC_BUDGET = (size_t)64 << 20; // bytes of one call ring: 64 cycles of the 8 x 8 grid at 256 atoms (26 MB), 5 of 1024 x 500 atoms
 
 static int record_capacity(const nm_ctx *c)
 {
@@ -1236,34 +1175,63 @@ static int record_capacity(const nm_ctx *c)
     return (int)std::max<size_t>(1, std::min<size_t>(64, REC_BUDGET / per));
 }
 
-// both rings, the side stream and the events, all or nothing
-static int rec_alloc(nm_ctx *c)
+// rings r0 and r0 + 1 of cap cycles each, and the side stream if there is none: all or nothing
+static int ring_alloc(nm_ctx *c, int r0, int cap, const char *who)
 {
-    const int cap = record_capacity(c);
     const size_t nd = (size_t)cap * rec_cycle_doubles(c);
     nm_ctx::Ring g[2];
     hipStream_t side = nullptr;
     hipError_t e = c->side ? hipSuccess : hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
-    for (int r = 0; r < 2 && e == hipSuccess; ++r) {
-        e = dalloc(&g[r].d, nd);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&g[r].h, nd * sizeof(double), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&g[r].taken, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&g[r].landed, hipEventDisableTiming);
+    for (auto &q : g) {
+        if (e == hipSuccess) e = dalloc(&q.d, nd);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&q.h, nd * sizeof(double), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&q.taken, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&q.landed, hipEventDisableTiming);
     }
     if (e != hipSuccess) {
-        for (auto &q : g) {
-            if (q.d) hipFree(q.d);
-            if (q.h) hipHostFree(q.h);
-            if (q.taken) hipEventDestroy(q.taken);
-            if (q.landed) hipEventDestroy(q.landed);
-        }
+        for (auto &q : g) free_ring(q);
         if (side) hipStreamDestroy(side);
-        return fail(c, NM_ERR_HIP, std::string("nm_run_cycles_recorded: ring allocation: ") + hipGetErrorString(e));
+        return fail(c, NM_ERR_HIP, std::string(who) + ": ring allocation: " + hipGetErrorString(e));
     }
     if (side) c->side = side;
-    c->ring[0] = g[0]; c->ring[1] = g[1];
-    c->rec_cap = cap;
+    g[0].cap = g[1].cap = cap;
+    c->ring[r0] = g[0]; c->ring[r0 + 1] = g[1];
     return NM_OK;
+}
+
+// the records of one call go to the free ring r: a fresh tag, set before they are issued
+static void open_ring(nm_ctx *c, int r)
+{
+    c->ring[r].tag0 = ((++c->rec_calls & 0xFFFFFFu) << 7) + 1; // (a record left from an earlier call of this ring never matches)
+    c->ring[r].dirty = false;
+}
+
+// behind the n records just issued into ring r: one D2H on the side stream, and the records join the fetch queue
+static int land_ring(nm_ctx *c, int r, int n)
+{
+    nm_ctx::Ring &g = c->ring[r];
+    HIPCHK(c, hipEventRecord(g.taken, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->side, g.taken, 0));
+    HIPCHK(c, hipMemcpyAsync(g.h, g.d, (size_t)n * rec_cycle_doubles(c) * sizeof(double), hipMemcpyDeviceToHost, c->side));
+    HIPCHK(c, hipEventRecord(g.landed, c->side));
+    g.n = n; g.next = 0;
+    for (int k = 0; k < n; ++k) c->fetchq.push_back(r);
+    return NM_OK;
+}
+
+int nm_snapshot(nm_ctx *c)
+{
+    if (!c) return NM_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int r = c->ring[2].n == 0 ? 2 : c->ring[3].n == 0 ? 3 : -1;
+    if (r < 0) return fail(c, NM_ERR_STATE, "nm_snapshot: two snapshots are pending; fetch one first (nm_snapshot_fetch)");
+    if (!c->ring[2].cap) {
+        const int rc = ring_alloc(c, 2, 1, "nm_snapshot");
+        if (rc) return rc;
+    }
+    open_ring(c, r);
+    const int rc = issue_record(c, r, 0);
+    return rc ? rc : land_ring(c, r, 1);
 }
 
 // the records of ring r still queued are dropped (a fetch that reports an error)
@@ -1293,7 +1261,7 @@ static int fetch_record(nm_ctx *c, int r, double *rows, double *x, double *box)
         g.dirty = false;
         if (!taken()) {
             drop_ring(c, r);
-            return fail(c, NM_ERR_STATE, "nm_snapshot_fetch: the record of a recorded cycle was never taken (its block did not complete)");
+            return fail(c, NM_ERR_STATE, "nm_snapshot_fetch: a snapshot or recorded cycle was never taken (the block in front of it did not complete)");
         }
     }
     for (size_t k = 0; k < ns; ++k) {
@@ -1312,32 +1280,7 @@ int nm_snapshot_fetch(nm_ctx *c, double *rows, double *x, double *box)
     if (!c) return NM_ERR_ARG;
     if (c->fetchq.empty()) return fail(c, NM_ERR_STATE, "nm_snapshot_fetch: no snapshot is pending");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->fetchq.front() >= 0) return fetch_record(c, c->fetchq.front(), rows, x, box);
-    nm_ctx::Snap &sn = c->snap[c->snap_head];
-    HIPCHK(c, hipEventSynchronize(sn.landed));
-    size_t off[8];
-    snap_layout(c, off);
-    const size_t ns = c->nslots, n3 = (size_t)3 * c->N;
-    const double *hx = sn.h + off[0], *hb = sn.h + off[1], *th = sn.h + off[2], *st = sn.h + off[3], *cn = sn.h + off[4];
-    const float *ra = (const float *)(sn.h + off[5]);
-    const int *m = (const int *)(sn.h + off[6]);
-    for (size_t k = 0; k < ns; ++k) {
-        const size_t b = (size_t)m[k];
-        if (rows) {
-            double *r = rows + k * NM_THERMO_COLS;
-            for (int q = 0; q < 5; ++q) r[q] = th[5 * b + q];
-            for (int q = 0; q < 3; ++q) r[5 + q] = st[3 * b + q];
-            for (int q = 0; q < 6; ++q) r[8 + q] = cn[6 * k + q];
-            for (int q = 0; q < 3; ++q) r[14 + q] = (double)ra[3 * k + q];
-        }
-        if (x) std::memcpy(x + k * n3, hx + b * n3, n3 * sizeof(double));
-        if (box) box[k] = hb[b];
-    }
-    sn.pending = false;
-    c->snap_head ^= 1;
-    --c->snap_count;
-    c->fetchq.pop_front();
-    return NM_OK;
+    return fetch_record(c, c->fetchq.front(), rows, x, box);
 }
 
 int nm_record_capacity(const nm_ctx *c) { return c ? record_capacity(c) : NM_ERR_ARG; }
@@ -1353,22 +1296,13 @@ int nm_run_cycles_recorded(nm_ctx *c, int ncycles, int mod)
     const int r = c->ring[0].n == 0 ? 0 : c->ring[1].n == 0 ? 1 : -1;
     if (r < 0) return fail(c, NM_ERR_STATE, "nm_run_cycles_recorded: the records of two calls are pending; fetch them first (nm_snapshot_fetch)");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (!c->ring[0].d) {
-        const int rc = rec_alloc(c);
+    if (!c->ring[0].cap) {
+        const int rc = ring_alloc(c, 0, record_capacity(c), "nm_run_cycles_recorded");
         if (rc) return rc;
     }
-    nm_ctx::Ring &g = c->ring[r];
-    g.tag0 = ((++c->rec_calls & 0xFFFFFFu) << 7) + 1; // (a record left from an earlier call of this ring never matches)
-    g.dirty = false;
-    int rc = issue_cycles(c, ncycles, mod, c->step, true, r, 0);
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(g.taken, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->side, g.taken, 0));
-    HIPCHK(c, hipMemcpyAsync(g.h, g.d, (size_t)ncycles * rec_cycle_doubles(c) * sizeof(double), hipMemcpyDeviceToHost, c->side));
-    HIPCHK(c, hipEventRecord(g.landed, c->side));
-    g.n = ncycles; g.next = 0;
-    for (int k = 0; k < ncycles; ++k) c->fetchq.push_back(r);
-    return NM_OK;
+    open_ring(c, r);
+    const int rc = issue_cycles(c, ncycles, mod, c->step, true, r, 0);
+    return rc ? rc : land_ring(c, r, ncycles);
 }
 
 int nm_run_block(nm_ctx *c, int mod)

@@ -1,7 +1,7 @@
 """nm_run_cycles_recorded: recorded cycles of the main loop (remcmc:977-995 with write_outputs) as one call.  The bar: the chains and every record
 equal, bit for bit, the single path — nm_run_block + nm_snapshot + nm_adapt + nm_exchange per cycle — on the fused launch and on the loop of single
 launches, for every instantiation of the recording kernel; the records share the snapshot queue in cycle order; a healed launch records again; a record
-of a block that did not complete is never handed out."""
+of a block that did not complete is never handed out, and neither is a snapshot, which is a record of one cycle."""
 import time
 
 import numpy as np
@@ -211,6 +211,58 @@ def test_a_recorded_launch_that_is_not_resident_records_again_when_reissued(monk
     b.close()
     _same(got, want)
     _same_state(g, w)
+
+
+def test_a_snapshot_behind_a_block_that_did_not_complete_is_taken_again_or_reported(monkeypatch):
+    """a snapshot is a record: behind a block whose census fails (NM_INJECT_CENSUS), with the next cycle queued before the fetch as the driver does,
+    the fetch settles the queue, which re-issues both cycles at 2 workgroups per replica — snapshots and chains are those of a context at 2 from the
+    start; behind a block that stops on an injected list overflow, the fetch is NM_ERR_STATE with the reason, never the state from before the block"""
+    import neuralmelting_amd as nm
+    from neuralmelting_amd import _lib as B
+    P, T = grids(8, 8)
+    st = _states(4, P, T)
+    ncyc, mod = 4, 12
+    monkeypatch.setenv('NM_INJECT_CENSUS', '0')
+    a = _engine(4, P, T, 'LJ', st)
+    assert a.cus_per_replica == 4
+    got = []
+    for s in range(3, 3 + ncyc):
+        a.set_step(s)
+        a.run_block(mod)
+        a.snapshot()
+        a.adapt()
+        a.exchange(count=False)
+        if s > 3:
+            got.append(a.snapshot_fetch())                   # the cycle before this one
+    got.append(a.snapshot_fetch())
+    monkeypatch.delenv('NM_INJECT_CENSUS')
+    assert a.cus_per_replica == 2 and a.heals == 1 and a.snapshot_pending == 0
+    g = _everything(a)
+    a.close()
+    monkeypatch.setenv('NM_CUS_PER_REPLICA', '2')
+    b = _engine(4, P, T, 'LJ', st)
+    want = _single_rec(b, 3, ncyc, mod)
+    w = _everything(b)
+    b.close()
+    _same(got, want)
+    _same_state(g, w)
+    monkeypatch.delenv('NM_CUS_PER_REPLICA')
+
+    e = _engine(4, P, T, 'LJ', st)
+    e.run_block(8)
+    e.synchronize()
+    monkeypatch.setenv('NM_INJECT_OVERFLOW', '3,1')
+    e.set_step(1)
+    e.run_block(48)
+    e.snapshot()
+    e.adapt()
+    e.exchange(count=False)
+    monkeypatch.delenv('NM_INJECT_OVERFLOW')
+    with pytest.raises(nm.NMError) as ei:
+        e.snapshot_fetch()
+    assert ei.value.code == B.NM_ERR_STATE and 'neighbour list overflow' in str(ei.value)
+    assert e.snapshot_pending == 0
+    e.close()
 
 
 def test_a_record_of_a_block_that_did_not_complete_is_never_handed_out(monkeypatch):
