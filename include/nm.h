@@ -38,6 +38,9 @@ extern "C" {
 
 #define NM_EL_LJ 0            /* units lj, fcc, lattice 1.122, mass 1     (remcmc:873-889) */
 #define NM_EL_AL 1            /* units metal, fcc, 4.046 A, mass 29.982  (remcmc:880,886); Sutton-Chen EAM, 2 to 2048 atoms */
+#define NM_EL_NI 2            /* units metal, fcc, 3.524 A, mass 58.693  (remcmc:881,887); Sutton-Chen EAM (n = 9), 2 to 2048 atoms */
+#define NM_EL_CU 3            /* units metal, fcc, 3.615 A, mass 63.546  (remcmc:882,888); Sutton-Chen EAM (n = 9), 2 to 2048 atoms.
+                                 Any other element (Ti: bcc, no Sutton-Chen set) is NM_ERR_UNSUPPORTED in nm_create */
 
 #define NM_THERMO_COLS 17     /* temp pe ke virial vol dx dv dt ntp nap ntv nav nth nah ap av ah (remcmc:208) */
 #define NM_TRACE_COLS 4       /* branch (0 bulk PMC, 1 VMC, 2 HMC, 3 iter PMC), accepted, criterion, U after */

@@ -11,7 +11,7 @@ c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 
 NM_OK, NM_ERR_ARG, NM_ERR_HIP, NM_ERR_STATE, NM_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
-NM_EL_LJ, NM_EL_AL = 0, 1
+NM_EL_LJ, NM_EL_AL, NM_EL_NI, NM_EL_CU = 0, 1, 2, 3
 NM_THERMO_COLS, NM_TRACE_COLS, NM_STATS_COLS = 17, 4, 10
 
 # every symbol include/nm.h declares (tests check that the library exports all of them)

@@ -53,6 +53,15 @@ typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, tru
 typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 1> CfgMidSC;     // 1 and 2 workgroups per replica
 typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 1> CfgMidSCQ4;   // 4
 typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 1> CfgLargeSC; // 1, 2 and 4
+// elements Cu and Ni: every Al configuration again with the Sutton-Chen exponent n = 9 (Cfg POT 2), dispatched by launch_kind_sc9.  Their cutoff and
+// skin are Al's in units of the lattice constant (nm_lattice.h sc_element), so the list lengths, the 256 slots, the LDS plans and the size thresholds
+// above hold for them unchanged (nm_create asserts the equal sizes; the sizing code below names the Al twins).
+typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2> CfgSmallSC9;
+typedef Cfg<NM_SMALL_BLOCK, 2 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2, 128, true, true> CfgSmallSC9Q2;
+typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2, 64, true, true> CfgSmallSC9Q4;
+typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 2> CfgMidSC9;
+typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 2> CfgMidSC9Q4;
+typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 2> CfgLargeSC9;
 typedef Cfg<512, 1, 864, 192, unsigned short, false, true> CfgMid;     // N <= 864: list in HBM/L2, saved copies in LDS (here: at 2 workgroups per replica)
 // the same at ONE workgroup per replica (more replicas than CUs: the reference's run.sh setting): every pair lies inside the workgroup and
 // is listed once (Cfg::HALF, nm_kernels.h)
@@ -85,7 +94,8 @@ struct nm_ctx {
     uint32_t launch_id;
     size_t lds_bytes, aux_doubles;
     double lat, mass, kB, mvv2e, ftm2v, nktv2p, skin, rc;
-    int pot; // 0 lj/cut, 1 Sutton-Chen EAM
+    int pot; // 0 lj/cut, 1 Sutton-Chen EAM n = 7 (Al), 2 Sutton-Chen EAM n = 9 (Cu, Ni): the kernels' Cfg POT
+    double sc_eps, sc_a2, sc_c; // Sutton-Chen constants of the element (nm_lattice.h sc_element); unused by lj/cut
     uint32_t step;
     hipStream_t stream;
     // device
@@ -170,7 +180,7 @@ void fill_params(const nm_ctx *c, KParams &p)
     p.ppos = c->cfg.ppos; p.pvol = c->cfg.pvol; p.lat = c->lat; p.mass = c->mass;
     p.kB = c->kB; p.mvv2e = c->mvv2e; p.ftm2v = c->ftm2v; p.nktv2p = c->nktv2p;
     p.rc = c->rc; p.skin = c->skin;
-    p.sc_eps = 0.033147; p.sc_a2 = 4.05 * 4.05; p.sc_c = 16.399; // Sutton & Chen, Phil. Mag. Lett. 61 (1990) 139: Al
+    p.sc_eps = c->sc_eps; p.sc_a2 = c->sc_a2; p.sc_c = c->sc_c; // Sutton & Chen, Phil. Mag. Lett. 61 (1990) 139 (nm_lattice.h sc_element)
     p.x = c->d_x; p.v = c->d_v; p.box = c->d_box; p.steps = c->d_steps; p.therm = c->d_therm;
     p.count = c->d_count; p.ratio = c->d_ratio; p.slot2buf = c->d_slot2buf;
     p.et = c->d_et; p.pf = c->d_pf; p.tq = c->d_tq;
@@ -272,6 +282,7 @@ hipError_t launch_cycles_kind(const nm_ctx *c, const KParams &p)
 {
     if (c->kind == 0) {
         if (c->pot == 1) return c->cus == 4 ? launch_cycles<CfgSmallSCQ4>(c, p) : launch_cycles<CfgSmallSCQ2>(c, p);
+        if (c->pot == 2) return c->cus == 4 ? launch_cycles<CfgSmallSC9Q4>(c, p) : launch_cycles<CfgSmallSC9Q2>(c, p);
         return c->cus == 8 ? launch_cycles<CfgSmallQ8>(c, p) : c->cus == 4 ? launch_cycles<CfgSmallQ4>(c, p) : launch_cycles<CfgSmallQ2>(c, p);
     }
     return launch_cycles<CfgMidQ8>(c, p);
@@ -284,8 +295,17 @@ hipError_t launch_kind_eam(const nm_ctx *c, const KParams &p)
     return launch_block<CfgLargeSC>(c, p);
 }
 
+// elements Cu and Ni (Sutton-Chen n = 9), every kind: the n = 7 dispatch with the twins
+hipError_t launch_kind_sc9(const nm_ctx *c, const KParams &p)
+{
+    if (c->kind == 1) return c->cus == 4 ? launch_block<CfgMidSC9Q4>(c, p) : launch_block<CfgMidSC9>(c, p);
+    if (c->kind == 2) return launch_block<CfgLargeSC9>(c, p);
+    return c->cus == 4 ? launch_block<CfgSmallSC9Q4>(c, p) : c->cus == 2 ? launch_block<CfgSmallSC9Q2>(c, p) : launch_block<CfgSmallSC9>(c, p);
+}
+
 hipError_t launch_kind(const nm_ctx *c, const KParams &p)
 {
+    if (c->pot == 2) return launch_kind_sc9(c, p);
     if (c->pot == 1 && c->kind > 0) return launch_kind_eam(c, p);
     switch (c->kind) {
     case 0:
@@ -298,6 +318,10 @@ hipError_t launch_kind(const nm_ctx *c, const KParams &p)
 
 int blocks_per_cu_kind(int kind, int pot, int q)
 {
+    if (pot == 2) {
+        if (kind > 0) return kind == 1 ? (q == 4 ? blocks_per_cu<CfgMidSC9Q4>() : blocks_per_cu<CfgMidSC9>()) : blocks_per_cu<CfgLargeSC9>();
+        return q == 4 ? blocks_per_cu<CfgSmallSC9Q4>() : q == 2 ? blocks_per_cu<CfgSmallSC9Q2>() : blocks_per_cu<CfgSmallSC9>();
+    }
     if (pot == 1 && kind > 0) return kind == 1 ? (q == 4 ? blocks_per_cu<CfgMidSCQ4>() : blocks_per_cu<CfgMidSC>()) : blocks_per_cu<CfgLargeSC>();
     switch (kind) {
     case 0:
@@ -310,6 +334,10 @@ int blocks_per_cu_kind(int kind, int pot, int q)
 
 hipError_t probe_kind(const nm_ctx *c, const KParams &p)
 {
+    if (c->pot == 2) {
+        if (c->kind > 0) return c->kind == 1 ? (c->cus == 4 ? launch_probe<CfgMidSC9Q4>(c, p) : launch_probe<CfgMidSC9>(c, p)) : launch_probe<CfgLargeSC9>(c, p);
+        return c->cus == 4 ? launch_probe<CfgSmallSC9Q4>(c, p) : c->cus == 2 ? launch_probe<CfgSmallSC9Q2>(c, p) : launch_probe<CfgSmallSC9>(c, p);
+    }
     if (c->pot == 1 && c->kind > 0) return c->kind == 1 ? (c->cus == 4 ? launch_probe<CfgMidSCQ4>(c, p) : launch_probe<CfgMidSC>(c, p)) : launch_probe<CfgLargeSC>(c, p);
     switch (c->kind) {
     case 0:
@@ -522,7 +550,7 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
     int cu = prop.multiProcessorCount;
     if (testing())
         if (const char *e = std::getenv("NM_ASSUME_CUS")) { const int v = std::atoi(e); if (v > 0) cu = v; } // tests of the fallback
-    const int maxq = (c->pot == 1 || c->kind == 2) ? 4 : 8; // own-atom ranges the instantiated thread mappings cover
+    const int maxq = (c->pot != 0 || c->kind == 2) ? 4 : 8; // own-atom ranges the instantiated thread mappings cover
     c->cus = 1; c->over = false;
     // The large cells (N > 864) at 4 workgroups per replica when that makes a grid of (nearly) TWICE the chip: the clusters run in
     // two rounds, longest block first, each with its own census.  Their blocks differ by more than 2x across an equilibrated PxT grid
@@ -571,7 +599,7 @@ int alloc_cluster_buffers(nm_ctx *c)
     const size_t ns = c->nslots;
     size_t aux_doubles, lds_bytes = c->lds_bytes;
     if (c->kind == 0) aux_doubles = CfgSmall::AUX_DOUBLES;
-    else if (c->pot == 1) { aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES; lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; }
+    else if (c->pot != 0) { aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES; lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; }
     else if (c->kind == 1) { aux_doubles = c->cus == 8 ? CfgMidQ8::AUX_DOUBLES : CfgMid::AUX_DOUBLES; lds_bytes = c->cus == 8 ? CfgMidQ8::LDS_BYTES : CfgMid::LDS_BYTES; }
     else aux_doubles = CfgLarge::AUX_DOUBLES;
     // the new buffers first, swapped in only when both exist: a failure leaves the context with the buffers (and the workgroups per
@@ -738,8 +766,8 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     if (!cfg->P || !cfg->T) return fail(nullptr, NM_ERR_ARG, "nm_create: P and T grids are required");
     if (cfg->nstps < 1 || cfg->ppos < 0 || cfg->pvol < 0 || cfg->ppos + cfg->pvol > 1.0)
         return fail(nullptr, NM_ERR_ARG, "nm_create: bad move parameters");
-    if (cfg->element != NM_EL_LJ && cfg->element != NM_EL_AL)
-        return fail(nullptr, NM_ERR_UNSUPPORTED, "nm_create: elements LJ and Al have device force kernels in this build");
+    if (cfg->element != NM_EL_LJ && !lat::sc_element(cfg->element))
+        return fail(nullptr, NM_ERR_UNSUPPORTED, "nm_create: elements LJ (0), Al (1), Ni (2) and Cu (3) have device force kernels in this build");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, NM_ERR_HIP, "nm_create: no HIP device available (this engine has no CPU fallback)");
@@ -770,12 +798,14 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     //  0.40 / 0.45 / 0.50 / 0.55: the O(N^2) rebuild of the larger cells wants fewer rebuilds; 0.45 for both until then)
     if (const char *e = std::getenv("NM_SKIN")) { const double v = std::atof(e); if (v > 0.0 && v < 1.0) c->skin = v; }
     c->lat = 1.122; c->mass = 1.0; c->kB = 1.0; c->mvv2e = 1.0; c->ftm2v = 1.0; c->nktv2p = 1.0;
-    c->rc = 2.5; c->pot = 0;
-    if (cfg->element == NM_EL_AL) { // units metal (LAMMPS update.cpp constants), remcmc:880,886
-        c->lat = 4.046; c->mass = 29.982; c->kB = 8.617343e-5; c->mvv2e = 1.0364269e-4; c->ftm2v = 1.0 / 1.0364269e-4;
-        c->nktv2p = 1.6021765e6; c->rc = 7.5; c->skin = 0.6; c->pot = 1; // (skin: 0.8 until the rebuild's scan and append got cheaper in round 3;
-        // equilibrated C4 on one box: 685 / 690 / 706 k sweeps/s at 0.8 / 0.7 / 0.6 A, 2.64 / 2.73 / 2.95 rebuilds per sweep)
-        if (const char *e = std::getenv("NM_SKIN_AL")) { const double v = std::atof(e); if (v > 0.0 && v < 3.0) c->skin = v; }
+    c->rc = 2.5; c->pot = 0; c->sc_eps = 0.0; c->sc_a2 = 0.0; c->sc_c = 0.0;
+    if (const lat::ScElement *s = lat::sc_element(cfg->element)) { // units metal (LAMMPS update.cpp constants), remcmc:880-889
+        c->lat = s->lat; c->mass = s->mass; c->kB = 8.617343e-5; c->mvv2e = 1.0364269e-4; c->ftm2v = 1.0 / 1.0364269e-4;
+        c->nktv2p = 1.6021765e6; c->rc = s->rc; c->skin = s->skin; c->pot = s->pot; // (Al's skin: 0.8 until the rebuild's scan and append got cheaper
+        // in round 3; equilibrated C4 on one box: 685 / 690 / 706 k sweeps/s at 0.8 / 0.7 / 0.6 A, 2.64 / 2.73 / 2.95 rebuilds per sweep)
+        c->sc_eps = s->eps; c->sc_a2 = s->a * s->a; c->sc_c = s->c;
+        if (cfg->element == NM_EL_AL) // (Al only)
+            if (const char *e = std::getenv("NM_SKIN_AL")) { const double v = std::atof(e); if (v > 0.0 && v < 3.0) c->skin = v; }
     }
 
     // init_constant (remcmc:114-132) in float64 on the float32-rounded grid values (NumPy-1.x promotion)
@@ -783,7 +813,7 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     for (int k = 0; k < c->nslots; ++k) {
         const int i = (c->slot0 + k) / cfg->nt, j = (c->slot0 + k) % cfg->nt;
         const double Pi = (double)cfg->P[i], Tj = (double)cfg->T[j];
-        if (cfg->element == NM_EL_AL) { // remcmc:124-127
+        if (cfg->element != NM_EL_LJ) { // units metal, remcmc:124-127
             const double kb = 8.61733e-5;
             c->h_et[k] = kb * Tj;
             c->h_pf[k] = 1e-30 * (1e5 * Pi) / (1.60218e-19 * kb * Tj);
@@ -796,8 +826,8 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     }
 
     size_t nbr_elems;
-    if (c->N <= CfgSmall::NMAX) { c->kind = 0; c->lds_bytes = c->pot == 1 ? CfgSmallSC::LDS_BYTES : CfgSmall::LDS_BYTES; /* Q8 variant: set at launch */ c->aux_doubles = CfgSmall::AUX_DOUBLES; nbr_elems = CfgSmall::NBR_G_ELEMS; }
-    else if (c->pot == 1) { // element Al above 256 atoms (launch_kind_eam)
+    if (c->N <= CfgSmall::NMAX) { c->kind = 0; c->lds_bytes = c->pot != 0 ? CfgSmallSC::LDS_BYTES : CfgSmall::LDS_BYTES; /* Q8 variant: set at launch */ c->aux_doubles = CfgSmall::AUX_DOUBLES; nbr_elems = CfgSmall::NBR_G_ELEMS; }
+    else if (c->pot != 0) { // elements Al, Cu and Ni above 256 atoms (launch_kind_eam, launch_kind_sc9: the n = 9 twins have these sizes)
         c->kind = c->N <= CfgMidSC::NMAX ? 1 : 2;
         c->lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; c->aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES;
         nbr_elems = c->kind == 1 ? CfgMidSC::NBR_G_ELEMS : CfgLargeSC::NBR_G_ELEMS;
@@ -896,6 +926,20 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
         CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSCQ2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSCQ2::LDS_BYTES));
         CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSCQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSCQ4::LDS_BYTES));
         static_assert(CfgSmallSCQ2::LDS_BYTES <= 160 * 1024 && CfgSmallSC::LDS_BYTES <= 160 * 1024, "");
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC9::LDS_BYTES));
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC9Q2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC9Q2::LDS_BYTES));
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC9Q4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC9Q4::LDS_BYTES));
+        static_assert(CfgSmallSC9::LDS_BYTES == CfgSmallSC::LDS_BYTES && CfgSmallSC9Q2::LDS_BYTES == CfgSmallSCQ2::LDS_BYTES &&
+                      CfgSmallSC9Q4::LDS_BYTES == CfgSmallSCQ4::LDS_BYTES, "the n = 9 twins have Al's LDS plans");
+    }
+    else if (c->pot == 2) {
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC9::LDS_BYTES));
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC9Q4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC9Q4::LDS_BYTES));
+        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgLargeSC9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgLargeSC9::LDS_BYTES));
+        static_assert(CfgMidSC9::LDS_BYTES == CfgMidSC::LDS_BYTES && CfgMidSC9Q4::LDS_BYTES == CfgMidSCQ4::LDS_BYTES && CfgLargeSC9::LDS_BYTES == CfgLargeSC::LDS_BYTES &&
+                      CfgMidSC9::AUX_DOUBLES == CfgMidSC::AUX_DOUBLES && CfgMidSC9Q4::AUX_DOUBLES == CfgMidSC::AUX_DOUBLES &&
+                      CfgLargeSC9::AUX_DOUBLES == CfgLargeSC::AUX_DOUBLES && CfgMidSC9::NBR_G_ELEMS == CfgMidSC::NBR_G_ELEMS &&
+                      CfgLargeSC9::NBR_G_ELEMS == CfgLargeSC::NBR_G_ELEMS, "the n = 9 twins have Al's LDS plans and spill sizes");
     }
     else if (c->pot == 1) {
         CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC::LDS_BYTES));
@@ -1028,7 +1072,7 @@ int nm_set_state(nm_ctx *c, int k0, int nk, const double *x, const double *v, co
 int nm_lattice_state(int element, int sz, int np, int nt, const float *P, uint32_t seed, int gslot, double dx, int interpolate, double *x,
                      double *box)
 {
-    if ((element != NM_EL_LJ && element != NM_EL_AL) || sz < 1 || np < 1 || nt < 1 || !P || gslot < 0 || gslot >= np * nt || !x || !box)
+    if ((element != NM_EL_LJ && !lat::sc_element(element)) || sz < 1 || np < 1 || nt < 1 || !P || gslot < 0 || gslot >= np * nt || !x || !box)
         return fail(nullptr, NM_ERR_ARG, "nm_lattice_state: bad argument");
     std::vector<double> frac;
     lat::fcc_fractional(sz, frac);

@@ -149,7 +149,13 @@ struct Cfg {
     static constexpr int NLIST = NLIST_;
     static constexpr bool SAVEV_LDS = SAVEV_LDS_;
     static_assert(SAVE_LDS_ || !SAVEV_LDS_, "saved velocities in LDS only together with the saved positions");
-    static constexpr int POT = POT_; // 0 = lj/cut 2.5, 1 = Sutton-Chen EAM (two-pass: densities, then forces)
+    // 0 = lj/cut 2.5; 1 and 2 = Sutton-Chen EAM (two-pass: densities, then forces) with the repulsive exponent n = 7 (element Al) and
+    // n = 9 (elements Cu and Ni).  The exponent is the only compile-time difference between the EAM elements: eps, a^2, c, rc and the
+    // skin travel in KParams.
+    static constexpr int POT = POT_;
+    static_assert(POT_ >= 0 && POT_ <= 2, "POT: 0 lj/cut, 1 Sutton-Chen n = 7, 2 Sutton-Chen n = 9");
+    static constexpr bool EAM = POT_ != 0;
+    static constexpr int SC_N = POT_ == 2 ? 9 : 7;
     // HALF (round 4): the configurations whose lists live in HBM / L2 with one thread per row evaluate a pair of two atoms of the SAME
     // workgroup once instead of twice.  The row that holds the pair — chosen by a checkerboard rule, (j > i) == ((i + j) even), so that
     // every row keeps about half of its own-range neighbours whatever its index — adds the force to its own sum and the opposite force
@@ -392,7 +398,7 @@ struct Replica {
     LdsArr<unsigned short, C::OFF_CNT> cnt;
     typename ArrSel<C::LIST_LDS, IdxT, C::OFF_NBR>::type nbr;
     LdsArr<double, C::OFF_RED> red;
-    typename ArrSel<C::RHO_LDS || C::POT == 0, double, C::OFF_RHO>::type rho; // EAM: densities, then 1/sqrt(density) (LDS, or the spill: Cfg::RHO_LDS)
+    typename ArrSel<C::RHO_LDS || !C::EAM, double, C::OFF_RHO>::type rho; // EAM: densities, then 1/sqrt(density) (LDS, or the spill: Cfg::RHO_LDS)
     int parity = 0;
     // block-uniform scalars
     double L = 0.0, L0 = 0.0, U = 0.0, W = 0.0;
@@ -1391,13 +1397,19 @@ struct Replica {
         }
     }
 
-    // ------------------------------------------------------------------ Sutton-Chen EAM (element Al; the build's own choice
-    // for BASELINE config 4: the reference's MEAM parameter files are not part of its tree)
-    // E = eps [ 1/2 sum_ij (a/r)^7 - c sum_i sqrt(rho_i) ],  rho_i = sum_j (a/r)^6,  r < rc.
+    // ------------------------------------------------------------------ Sutton-Chen EAM (elements Al, Cu and Ni; the build's own
+    // choice for BASELINE config 4: the reference's MEAM parameter files are not part of its tree)
+    // E = eps [ 1/2 sum_ij (a/r)^n - c sum_i sqrt(rho_i) ],  rho_i = sum_j (a/r)^6,  r < rc;  n = Cfg::SC_N (7: Al, 9: Cu and Ni).
     // Two passes over the same full list: densities of the own atoms, (cluster: exchange them,) then forces with
-    // fp = eps [ 7 (a/r)^7 - 6 (c/2)(1/sqrt(rho_i) + 1/sqrt(rho_j)) (a/r)^6 ] / r^2.
+    // fp = eps [ n (a/r)^n - 6 (c/2)(1/sqrt(rho_i) + 1/sqrt(rho_j)) (a/r)^6 ] / r^2.
     template <bool WANT_E>
     __device__ __forceinline__ void pair_loop_sc(double invL, double &eacc, double &wacc, double &nacc, double &kacc, bool fuse, double dtfm, double h);
+    // (a/r)^n from (a/r)^6, (a/r)^2 and a/r: n = 7 is g6 * a/r as it always was; n = 9 one multiply more, (g6 (a/r)^2) a/r
+    static __device__ __forceinline__ double sc_rep(double g6, double q2, double ar)
+    {
+        if constexpr (C::SC_N == 9) return g6 * q2 * ar;
+        else return g6 * ar;
+    }
     // a listed neighbour's coordinate / density: j is the atom index, or (BYTES: the lists in HBM/L2) 8 x the atom index
     template <bool BYTES, class A>
     static __device__ __forceinline__ double sc_at(const A &a, int j)
@@ -1483,11 +1495,11 @@ struct Replica {
 #pragma unroll
         for (int u = 0; u < W; ++u) { rm[u] = q2[u] * q2[u] * q2[u]; }         // (a/r)^6
 #pragma unroll
-        for (int u = 0; u < W; ++u) { rn[u] = rm[u] * (a1r * y[u]); }           // (a/r)^7
+        for (int u = 0; u < W; ++u) rn[u] = sc_rep(rm[u], q2[u], a1r * y[u]); // (a/r)^n
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             const double dF = 0.5 * cc * (isi + rj[u]);
-            fp[u] = eps * (7.0 * rn[u] - 6.0 * dF * rm[u]) * t[u];
+            fp[u] = eps * ((double)C::SC_N * rn[u] - 6.0 * dF * rm[u]) * t[u];
         }
 #pragma unroll
         for (int u = 0; u < W; ++u) {
@@ -1801,7 +1813,7 @@ struct Replica {
         PROF_BEGIN();
         if constexpr (C::HALF) half_begin();
         if (NM_DBG(16)) { }
-        else if constexpr (C::POT == 1) pair_loop_sc<true>(invL, eacc, wacc, nacc, kacc, final_kick, dtfm, 0.0);
+        else if constexpr (C::EAM) pair_loop_sc<true>(invL, eacc, wacc, nacc, kacc, final_kick, dtfm, 0.0);
         else pair_loop<true>(invL, eacc, wacc, nacc, kacc, final_kick, dtfm, 0.0);
         if constexpr (C::HALF) half_end(final_kick, dtfm, kacc);
         PROF_END(3);
@@ -1839,7 +1851,7 @@ struct Replica {
         PROF_BEGIN();
         if constexpr (C::HALF) half_begin();
         if (NM_DBG(16)) { }
-        else if constexpr (C::POT == 1) pair_loop_sc<false>(invL, eacc, wacc, nacc, kacc, true, dtfm, h);
+        else if constexpr (C::EAM) pair_loop_sc<false>(invL, eacc, wacc, nacc, kacc, true, dtfm, h);
         else pair_loop<false>(invL, eacc, wacc, nacc, kacc, true, dtfm, h);
         PROF_END(3);
         TLINE(3);
@@ -1949,14 +1961,14 @@ struct Replica {
     }
 
     // The same for the Sutton-Chen EAM: moving atom k changes its pair terms AND the density of every neighbour, old or new:
-    //   dE = eps [ sum_j ((a/r'_kj)^7 - (a/r_kj)^7) - c ( sum_j (sqrt(rho_j + drho_j) - sqrt(rho_j)) + sqrt(rho'_k) - sqrt(rho_k) ) ],
+    //   dE = eps [ sum_j ((a/r'_kj)^n - (a/r_kj)^n) - c ( sum_j (sqrt(rho_j + drho_j) - sqrt(rho_j)) + sqrt(rho'_k) - sqrt(rho_k) ) ],
     //   drho_j = (a/r'_kj)^6 - (a/r_kj)^6,  rho'_k = sum_j (a/r'_kj)^6.
     // rho[] holds the densities of the current configuration (iter_densities at move start, kept up to date by the trial loop); thread
     // j keeps its drho_j until the decision is known.  One work item per atom (N <= BLOCK), one block reduction.
     __device__ void delta_single_sc(int k, double ox, double oy, double oz, double nx, double ny, double nz, double &dE, double &drho_mine,
                                     double &rho_k_new)
     {
-        static_assert(C::POT != 1 || NMAX <= BLOCK, "one thread per atom");
+        static_assert(!C::EAM || NMAX <= BLOCK, "one thread per atom");
         box_consts();
         const double invL = bc_invL, rc2 = p.rc * p.rc, a2 = p.sc_a2;
         double s[3] = { 0.0, 0.0, 0.0 };
@@ -1971,7 +1983,7 @@ struct Replica {
             const bool ina = ra < rc2, inb = rb < rc2;
             const double qa = a2 * recip(ina ? ra : 1.0), qb = a2 * recip(inb ? rb : 1.0); // (a/r)^2
             const double ga = ina ? qa * qa * qa : 0.0, gb = inb ? qb * qb * qb : 0.0;     // (a/r)^6
-            s[0] = ga * sqrt(qa) - gb * sqrt(qb);                                          // (a/r)^7, new - old
+            s[0] = sc_rep(ga, qa, sqrt(qa)) - sc_rep(gb, qb, sqrt(qb));                    // (a/r)^n, new - old
             drho_mine = ga - gb;
             const double rj = rho[j];
             s[1] = sqrt(rj + drho_mine) - sqrt(rj);
@@ -2005,7 +2017,7 @@ struct Replica {
                 const bool ina = ra < rc2, inb = rb < rc2;
                 const double qa = a2 * recip(ina ? ra : 1.0), qb = a2 * recip(inb ? rb : 1.0); // (a/r)^2
                 const double ga = ina ? qa * qa * qa : 0.0, gb = inb ? qb * qb * qb : 0.0;     // (a/r)^6
-                s[0] += ga * sqrt(qa) - gb * sqrt(qb);                                         // (a/r)^7, new - old
+                s[0] += sc_rep(ga, qa, sqrt(qa)) - sc_rep(gb, qb, sqrt(qb));                   // (a/r)^n, new - old
                 drho[m] = ga - gb;
                 const double rj = rho[j];
                 s[1] += sqrt(rj + drho[m]) - sqrt(rj);
@@ -2193,7 +2205,7 @@ struct Replica {
         if constexpr (C::POT == 0) {
             if (pre && !p.iter_revert) return iter_pmc_all(et, nt, na, crit);
         }
-        if constexpr (C::POT == 1) iter_densities();
+        if constexpr (C::EAM) iter_densities();
         for (int k = 0; k < N; ++k) {
             nt += 1.0;
             const double pe = U / et;
@@ -2208,8 +2220,8 @@ struct Replica {
             double dE, dW = 0.0;
             [[maybe_unused]] double drho = 0.0, rho_k_new = 0.0;
             [[maybe_unused]] double drho_n[NJ];
-            if constexpr (C::POT == 1 && NMAX > BLOCK) delta_single_sc_strided(k, ox, oy, oz, nx, ny, nz, dE, drho_n, rho_k_new);
-            else if constexpr (C::POT == 1) delta_single_sc(k, ox, oy, oz, nx, ny, nz, dE, drho, rho_k_new);
+            if constexpr (C::EAM && NMAX > BLOCK) delta_single_sc_strided(k, ox, oy, oz, nx, ny, nz, dE, drho_n, rho_k_new);
+            else if constexpr (C::EAM) delta_single_sc(k, ox, oy, oz, nx, ny, nz, dE, drho, rho_k_new);
             else delta_single(k, ox, oy, oz, nx, ny, nz, dE, dW);
             const double Unew = U + dE;
             const double de = Unew / et - pe;
@@ -2230,21 +2242,21 @@ struct Replica {
                         im[3 * k + 2] = (short)(im[3 * k + 2] + runs * wn[3 * k + 2]);
                     }
                 }
-                if constexpr (C::POT == 1 && NMAX > BLOCK) { // the densities follow the move, each on its owner
+                if constexpr (C::EAM && NMAX > BLOCK) { // the densities follow the move, each on its owner
 #pragma unroll
                     for (int m = 0; m < NJ; ++m) {
                         const int j = tid + m * BLOCK;
                         if (j < N && j != k) rho[j] += drho_n[m];
                     }
                     if (tid == (k % BLOCK)) rho[k] = rho_k_new;
-                } else if constexpr (C::POT == 1) {
+                } else if constexpr (C::EAM) {
                     if (tid < N && tid != k) rho[tid] += drho;
                     if (tid == (k % BLOCK)) rho[k] = rho_k_new;
                 }
                 U = Unew; W += dW;
                 set_fresh(false);
             }
-            if constexpr (C::POT == 1 && NMAX <= BLOCK) __syncthreads(); // the next trial reads rho[k+1] in every thread
+            if constexpr (C::EAM && NMAX <= BLOCK) __syncthreads(); // the next trial reads rho[k+1] in every thread
             runs += acc ? 1 : 2;
         }
         __syncthreads();
@@ -2431,11 +2443,11 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
 #pragma unroll
                             for (int u = 0; u < W; ++u) { rm[u] = q2[u] * q2[u] * q2[u]; }         // (a/r)^6
 #pragma unroll
-                            for (int u = 0; u < W; ++u) { rn[u] = rm[u] * (a1r * y[u]); }           // (a/r)^7
+                            for (int u = 0; u < W; ++u) rn[u] = sc_rep(rm[u], q2[u], a1r * y[u]); // (a/r)^n
 #pragma unroll
                             for (int u = 0; u < W; ++u) {
                                 const double dF = 0.5 * cc * (isi + rj[u]);
-                                fp[u] = eps * (7.0 * rn[u] - 6.0 * dF * rm[u]) * t[u];
+                                fp[u] = eps * ((double)C::SC_N * rn[u] - 6.0 * dF * rm[u]) * t[u];
                             }
 #pragma unroll
                             for (int u = 0; u < W; ++u) {
@@ -2805,7 +2817,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 double c2 = 0.0;
                 const int na = R.iter_pmc((uint32_t)m, et, dx, ntp, nap, c2);
                 if (__builtin_amdgcn_readfirstlane(R.status) & fatal) break; // (its exchange of energy differences failed)
-                if constexpr (C::POT == 1) { // close the move with a full evaluation (c_vol, c_volnew are free during a position move)
+                if constexpr (C::EAM) { // close the move with a full evaluation (c_vol, c_volnew are free during a position move)
                     c_vol = (double)na; c_volnew = c2;
                     phase = PH_ITER_END; pending = true;
                 } else {

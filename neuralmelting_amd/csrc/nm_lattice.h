@@ -44,6 +44,21 @@ struct Philox4x64 {
     }
 };
 
+// The metal-unit elements (NM_EL_AL, NM_EL_NI, NM_EL_CU): Sutton-Chen EAM (Sutton & Chen, Phil. Mag. Lett. 61 (1990) 139),
+// E = eps [ 1/2 sum_ij (a/r)^n - c sum_i sqrt(sum_j (a/r)^6) ], unshifted at rc; lat and mass are the reference's (remcmc:880-889).
+// Cu and Ni take Al's cutoff and skin in units of a (7.5 A and 0.6 A x a / 4.05): the same geometry in units of the lattice constant, hence
+// the same list lengths, LDS plans and size thresholds as Al.  pot: the kernels' Cfg POT (the exponent is compile-time).
+struct ScElement { double eps, a, c, rc, skin, lat, mass; int n, pot; };
+inline const ScElement *sc_element(int element)
+{
+    static const ScElement al = { 0.033147, 4.05, 16.399, 7.5, 0.6, 4.046, 29.982, 7, 1 };
+    static const ScElement ni = { 1.5707e-2, 3.52, 39.432, 7.5 * 3.52 / 4.05, 0.6 * 3.52 / 4.05, 3.524, 58.693, 9, 2 };
+    static const ScElement cu = { 1.2382e-2, 3.61, 39.432, 7.5 * 3.61 / 4.05, 0.6 * 3.61 / 4.05, 3.615, 63.546, 9, 2 };
+    return element == 1 ? &al : element == 2 ? &ni : element == 3 ? &cu : nullptr;
+}
+// the `lattice fcc X` edge of an element (remcmc:873-889); LJ's 1.122 is the reduced density, not an edge
+inline double lat_param(int element) { return element == 0 ? 1.122 : sc_element(element)->lat; }
+
 // fractional coordinates in create_atoms order: k outer, j, i inner, basis innermost
 inline void fcc_fractional(int sz, std::vector<double> &f)
 {
@@ -73,8 +88,9 @@ inline double static_pressure(int element, const std::vector<double> &f, double 
             }
         return w / (3.0 * box * box * box);
     }
-    // Sutton-Chen Al (nm_api.hip fill_params): densities, then the pair part of r.f; returned in bar (LAMMPS metal units)
-    const double eps = 0.033147, a2 = 4.05 * 4.05, cc = 16.399, rc2 = 7.5 * 7.5;
+    // Sutton-Chen (sc_element, as nm_api.hip fill_params): densities, then the pair part of r.f; returned in bar (LAMMPS metal units)
+    const ScElement &s = *sc_element(element);
+    const double eps = s.eps, a2 = s.a * s.a, cc = s.c, rc2 = s.rc * s.rc;
     std::vector<double> rho((size_t)n, 0.0);
     for (int a = 0; a < n; ++a)
         for (int b = 0; b < n; ++b) {
@@ -91,9 +107,9 @@ inline double static_pressure(int element, const std::vector<double> &f, double 
             for (int c = 0; c < 3; ++c) { double d = f[3 * a + c] - f[3 * b + c]; d -= std::nearbyint(d); r2 += d * d; }
             r2 *= box * box;
             if (r2 < rc2) {
-                const double q2 = a2 / r2, rm = q2 * q2 * q2, rn = rm * std::sqrt(q2);
+                const double q2 = a2 / r2, rm = q2 * q2 * q2, rn = (s.n == 9 ? rm * q2 : rm) * std::sqrt(q2);
                 const double dF = 0.5 * cc * (1.0 / std::sqrt(rho[a]) + 1.0 / std::sqrt(rho[b]));
-                w += 0.5 * eps * (7.0 * rn - 6.0 * dF * rm);
+                w += 0.5 * eps * ((double)s.n * rn - 6.0 * dF * rm);
             }
         }
     return w / (3.0 * box * box * box) * 1.6021765e6;
@@ -105,7 +121,7 @@ inline double relax_box(int element, int sz, double press)
 {
     std::vector<double> f;
     fcc_fractional(4, f); // the perfect lattice's pressure depends on the lattice constant only: 4^3 root, scaled
-    const double a0 = 4.0 * (element == 0 ? std::cbrt(4.0 / 1.122) : 4.046);
+    const double a0 = 4.0 * (element == 0 ? std::cbrt(4.0 / 1.122) : lat_param(element));
     auto g = [&](double b) { return static_pressure(element, f, b) - press; };
     double lo = (element == 0 ? 0.9 : 0.97) * a0, hi = (element == 0 ? 1.05 : 1.03) * a0;
     while (g(lo) < 0.0) lo *= (element == 0 ? 0.97 : 0.99);
@@ -126,7 +142,7 @@ inline void init_state(int element, int sz, double box_row, uint32_t seed, int g
                        const std::vector<double> &frac, double *x, double *box)
 {
     const int n = (int)(frac.size() / 3);
-    const double amp = dx * (element == 0 ? 1.122 : 4.046);
+    const double amp = dx * lat_param(element);
     Philox4x64 rng((uint64_t)seed, (uint64_t)gslot);
     double bk = box_row;
     for (int a = 0; a < 3 * n; ++a) {

@@ -21,7 +21,7 @@ def _dp(a):
 class Engine:
     """batched replica engine on one MI355X"""
 
-    ELEMENTS = {'LJ': B.NM_EL_LJ, 'Al': B.NM_EL_AL}
+    ELEMENTS = {'LJ': B.NM_EL_LJ, 'Al': B.NM_EL_AL, 'Ni': B.NM_EL_NI, 'Cu': B.NM_EL_CU}
 
     def __init__(self, natoms, P, T, *, element='LJ', ppos=0.125, pvol=0.125, nstps=8, bulk=True, seed=256,
                  device=0, row0=0, nrows=None, iter_revert=False, slot0=None, nslots=None):

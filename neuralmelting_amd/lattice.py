@@ -43,22 +43,28 @@ def lj_static(frac, box):
 # Sutton-Chen Al (Phil. Mag. Lett. 61 (1990) 139), the engine's EAM for element Al; rc as in the kernels
 SC_EPS, SC_A, SC_C, SC_RC = 0.033147, 4.05, 16.399, 7.5
 NKTV2P_METAL = 1.6021765e6  # eV/A^3 -> bar (LAMMPS metal units)
+# the same paper's sets for the metal-unit elements the engine runs (nm_lattice.h sc_element): eps [eV], a [A], c, n (m = 6), cutoff rc [A].
+# Cu and Ni take Al's cutoff in units of a (7.5 A x a / 4.05), so their lattices and liquids have Al's geometry in units of a.
+SC = {'Al': (SC_EPS, SC_A, SC_C, 7, SC_RC),
+      'Ni': (1.5707e-2, 3.52, 39.432, 9, 7.5 * 3.52 / 4.05),
+      'Cu': (1.2382e-2, 3.61, 39.432, 9, 7.5 * 3.61 / 4.05)}
 
 
-def sc_static(frac, box):
-    """U [eV] and W = sum r.f [eV] of the Sutton-Chen potential for fractional coordinates in a cubic box (numpy, O(N^2))"""
+def sc_static(frac, box, el='Al'):
+    """U [eV] and W = sum r.f [eV] of the Sutton-Chen potential of element `el` for fractional coordinates in a cubic box (numpy, O(N^2))"""
+    eps, a, c, n, rc = SC[el]
     d = frac[:, None, :] - frac[None, :, :]
     d -= np.rint(d)
     r2 = (d * d).sum(-1) * box * box
     np.fill_diagonal(r2, np.inf)
-    q2 = np.where(r2 < SC_RC * SC_RC, SC_A * SC_A / r2, 0.0)
+    q2 = np.where(r2 < rc * rc, a * a / r2, 0.0)
     rm = q2 ** 3
-    rn = rm * np.sqrt(q2)
+    rn = (rm * q2 if n == 9 else rm) * np.sqrt(q2)
     rho = rm.sum(1)
     isr = 1.0 / np.sqrt(rho)
-    u = SC_EPS * (0.5 * rn.sum() - SC_C * np.sqrt(rho).sum())
-    dF = 0.5 * SC_C * (isr[:, None] + isr[None, :])
-    w = 0.5 * (SC_EPS * (7.0 * rn - 6.0 * dF * rm)).sum()     # r2*fp summed over pairs once
+    u = eps * (0.5 * rn.sum() - c * np.sqrt(rho).sum())
+    dF = 0.5 * c * (isr[:, None] + isr[None, :])
+    w = 0.5 * (eps * (float(n) * rn - 6.0 * dF * rm)).sum()     # r2*fp summed over pairs once
     return float(u), float(w)
 
 
@@ -72,11 +78,11 @@ def relax_box(sz, press, el='LJ'):
     frac = fcc_fractional(sz)
     a0 = sz * lattice_constant(el)
     if UNITS[el] == 'metal':
-        if el != 'Al':
-            raise NotImplementedError('only Al has a potential among the metal-unit elements')
+        if el not in SC:
+            raise NotImplementedError('%s has no potential in this engine: the metal-unit elements are %s' % (el, ', '.join(SC)))
 
         def f(box):
-            return sc_static(frac, box)[1] / (3.0 * box ** 3) * NKTV2P_METAL - press
+            return sc_static(frac, box, el)[1] / (3.0 * box ** 3) * NKTV2P_METAL - press
         lo, hi = 0.97 * a0, 1.03 * a0
         while f(lo) < 0:
             lo *= 0.99

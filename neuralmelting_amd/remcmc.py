@@ -44,7 +44,7 @@ _FLAGS = (
     ('-nt', '--threads', int, 1, 'ignored'),
     ('-mt', '--method', str, 'fork', 'ignored'),
     ('-n', '--name', str, 'remcmc_init', 'run name (prefix of every file)'),
-    ('-e', '--element', str, 'LJ', 'LJ or Al (Sutton-Chen EAM); both at any -ss from 1 to 8 (2048 atoms)'),
+    ('-e', '--element', str, 'LJ', 'LJ, or Al, Ni or Cu (Sutton-Chen EAM); each at any -ss from 1 to 8 (2048 atoms); Ti (bcc) is not built'),
     ('-ss', '--supercell_size', int, 5, 'fcc cells per box edge'),
     ('-pn', '--pressure_number', int, 16, 'points of the pressure grid'),
     ('-pr', '--pressure_range', (float, 2), [1, 8], 'lowest and highest pressure'),
@@ -127,6 +127,8 @@ class Run:
         self.PHMC = 1 - self.PPOS - self.PVOL
         self.P = np.linspace(self.LP, self.HP, self.NP, dtype=np.float32)  # remcmc:895
         self.T = np.linspace(self.LT, self.HT, self.NT, dtype=np.float32)  # remcmc:897
+        if self.EL not in ('LJ',) + tuple(lattice.SC):   # Ti: bcc, and Sutton-Chen has no set for it
+            raise NotImplementedError('element %s is not supported: this engine runs LJ, %s' % (self.EL, ', '.join(lattice.SC)))
         self.DT = TIMESTEP[UNITS[self.EL]]
         self.PREF = self.cwd + '/%s.%s.%s.lammps' % (self.NAME, self.EL.lower(), LAT[self.EL][0])
         if LAT[self.EL][0] != 'fcc':

@@ -1,10 +1,12 @@
-"""Diagnostic build (make prof) only: scripts/check_bounds.py for element Al above 256 atoms — the 16-bit-list EAM kernels (CfgMidSC,
-CfgMidSCQ4, CfgLargeSC; the densities of the last in the global spill).  5^3, 6^3 and 8^3 cells at 1, 2 and 4 workgroups per replica, bulk
-and iterative position moves, on bench's Al temperatures: every index into the spill and list arrays checked inside the kernel, every
-rebuilt list row checked against exact separations.  Prints the counts; all must be 0.
+"""Diagnostic build (make prof) only: scripts/check_bounds.py for the EAM elements above 256 atoms — the 16-bit-list EAM kernels (CfgMidSC,
+CfgMidSCQ4, CfgLargeSC, and their n = 9 twins for Cu and Ni; the densities of the last in the global spill).  5^3, 6^3 and 8^3 cells at 1, 2
+and 4 workgroups per replica, bulk and iterative position moves, on bench's metal temperatures: every index into the spill and list arrays
+checked inside the kernel, every rebuilt list row checked against exact separations.  Prints the counts; all must be 0.  --el Cu / Ni: the
+n = 9 kernels; --sizes 4,5,6,8 adds the 4^3 byte-list kernels.
 
-    NM_HIP_LIB=$PWD/neuralmelting_amd/libnm_hip_prof.so python scripts/check_bounds_al.py
+    NM_HIP_LIB=$PWD/neuralmelting_amd/libnm_hip_prof.so python scripts/check_bounds_al.py [--el Al|Cu|Ni] [--sizes 5,6,8]
 """
+import argparse
 import ctypes as C
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,7 +15,12 @@ import numpy as np
 os.environ['NM_DBG'] = '8'   # the exact list self-check of the diagnostic build
 
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--el', default='Al', choices=('Al', 'Cu', 'Ni'))
+    ap.add_argument('--sizes', default='5,6,8')
+    a = ap.parse_args(argv)
+    el, sizes = a.el, [int(s) for s in a.sizes.split(',')]
     import neuralmelting_amd as nm
     from neuralmelting_amd import lattice, _lib
     assert 'prof' in _lib.LIB_PATH, 'run with NM_HIP_LIB pointing at libnm_hip_prof.so'
@@ -21,12 +28,12 @@ def main():
     total = 0
     P = np.linspace(1.0, 8.0, 2, dtype=np.float32)
     T = np.linspace(256.0, 2560.0, 4, dtype=np.float32)
-    for sz in (5, 6, 8):
+    for sz in sizes:
         for q in (1, 2, 4):
             for bulk in (True, False):
                 os.environ['NM_CUS_PER_REPLICA'] = str(q)
-                x, v, box, d = lattice.init_states(sz, P, T, 0.03125, 0.03125, el='Al')
-                e = nm.Engine(4 * sz ** 3, P, T, element='Al', bulk=bulk, ppos=0.2, pvol=0.2)
+                x, v, box, d = lattice.init_states(sz, P, T, 0.03125, 0.03125, el=el)
+                e = nm.Engine(4 * sz ** 3, P, T, element=el, bulk=bulk, ppos=0.2, pvol=0.2)
                 assert e.cus_per_replica == q
                 e.set_state(x, v, box, d)
                 for step in range(4):
@@ -35,8 +42,8 @@ def main():
                 st = e.stats()
                 n, m = C.c_uint(0), C.c_uint(0)
                 assert L.nm_prof_oob(e.h, C.byref(n)) == 0 and L.nm_prof_list_miss(e.h, C.byref(m)) == 0
-                print('Al %d^3 Q=%d %-9s rebuilds %4d  evaluations %5d  longest row %3d  out-of-range indices %d  incomplete list rows %d'
-                      % (sz, q, 'bulk' if bulk else 'iterative', st[:, 1].sum(), st[:, 0].sum(), st[:, 8].max(), n.value, m.value), flush=True)
+                print('%s %d^3 Q=%d %-9s rebuilds %4d  evaluations %5d  longest row %3d  out-of-range indices %d  incomplete list rows %d'
+                      % (el, sz, q, 'bulk' if bulk else 'iterative', st[:, 1].sum(), st[:, 0].sum(), st[:, 8].max(), n.value, m.value), flush=True)
                 total += n.value + m.value
                 e.close()
     print('total', total)
