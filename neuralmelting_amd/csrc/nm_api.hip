@@ -18,6 +18,7 @@
 #include <deque>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace nm;
@@ -49,13 +50,12 @@ typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, tru
 // element Al at 5^3 to 8^3 cells: 16-bit lists in HBM/L2, chunked as CfgMid's and CfgLarge's, full lists (Cfg::HALF stays lj/cut's).  256 slots
 // per atom: the crystal has 134 neighbours within rc + skin = 8.1 A, and the longest row over bench's Al grid (8 x 8, P 1 .. 8 bar, T 256 .. 2560 K,
 // 40 cycles from the lattice) was 149 at 5^3 and 151 at 8^3; more is reported as ST_LIST_OVERFLOW.  Densities in LDS at 864 atoms (141.5 KB in all), in the spill at 2048
-// (Cfg::RHO_LDS: positions, velocities and forces alone take 144 KB there).  Dispatched by launch_kind_eam.
+// (Cfg::RHO_LDS: positions, velocities and forces alone take 144 KB there).
 typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 1> CfgMidSC;     // 1 and 2 workgroups per replica
 typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 1> CfgMidSCQ4;   // 4
 typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 1> CfgLargeSC; // 1, 2 and 4
-// elements Cu and Ni: every Al configuration again with the Sutton-Chen exponent n = 9 (Cfg POT 2), dispatched by launch_kind_sc9.  Their cutoff and
-// skin are Al's in units of the lattice constant (nm_lattice.h sc_element), so the list lengths, the 256 slots, the LDS plans and the size thresholds
-// above hold for them unchanged (nm_create asserts the equal sizes; the sizing code below names the Al twins).
+// elements Cu and Ni: every Al configuration again with the Sutton-Chen exponent n = 9 (Cfg POT 2).  Their cutoff and skin are Al's in units of
+// the lattice constant (nm_lattice.h sc_element), so the list lengths, the 256 slots, the LDS plans and the size thresholds above hold for them unchanged.
 typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2> CfgSmallSC9;
 typedef Cfg<NM_SMALL_BLOCK, 2 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2, 128, true, true> CfgSmallSC9Q2;
 typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2, 64, true, true> CfgSmallSC9Q4;
@@ -79,6 +79,57 @@ typedef Cfg<512, 1, 2048, 224, unsigned short, false, false> CfgLarge;
 // against 231 k sweeps/s sustained (+10 %)
 typedef Cfg<512, 1, 2048, 224, unsigned short, false, false, 0, 2048, false, false, true> CfgLargeH;
 
+// The configuration a context runs: X(pot, kind, Q, Cfg, FUSED) for the potential (nm_ctx::pot), the size class (nm_ctx::kind: the first
+// kind whose NMAX holds N) and the workgroups per replica (nm_ctx::cus).  FUSED: nm_cycles_kernel is instantiated for the row (cycles_kind_ok
+// decides where it runs).  Block launches, the occupancy query, the residency probe, the fused launch and the buffer sizes all find their
+// configuration here (with_row), and pick_q only picks a Q that has a row.  One row per line: tests/helpers.py reads the table.
+#define NM_CFG_ROWS(X)                  \
+    X(0, 0, 1, CfgSmall,          0)    \
+    X(0, 0, 2, CfgSmallQ2,        1)    \
+    X(0, 0, 4, CfgSmallQ4,        1)    \
+    X(0, 0, 8, CfgSmallQ8,        1)    \
+    X(0, 1, 1, CfgMidH,           0)    \
+    X(0, 1, 2, CfgMid,            0)    \
+    X(0, 1, 4, CfgMidQ4,          0)    \
+    X(0, 1, 8, CfgMidQ8,          1)    \
+    X(0, 2, 1, CfgLargeH,         0)    \
+    X(0, 2, 2, CfgLarge,          0)    \
+    X(0, 2, 4, CfgLarge,          0)    \
+    X(1, 0, 1, CfgSmallSC,        0)    \
+    X(1, 0, 2, CfgSmallSCQ2,      1)    \
+    X(1, 0, 4, CfgSmallSCQ4,      1)    \
+    X(1, 1, 1, CfgMidSC,          0)    \
+    X(1, 1, 2, CfgMidSC,          0)    \
+    X(1, 1, 4, CfgMidSCQ4,        0)    \
+    X(1, 2, 1, CfgLargeSC,        0)    \
+    X(1, 2, 2, CfgLargeSC,        0)    \
+    X(1, 2, 4, CfgLargeSC,        0)    \
+    X(2, 0, 1, CfgSmallSC9,       0)    \
+    X(2, 0, 2, CfgSmallSC9Q2,     1)    \
+    X(2, 0, 4, CfgSmallSC9Q4,     1)    \
+    X(2, 1, 1, CfgMidSC9,         0)    \
+    X(2, 1, 2, CfgMidSC9,         0)    \
+    X(2, 1, 4, CfgMidSC9Q4,       0)    \
+    X(2, 2, 1, CfgLargeSC9,       0)    \
+    X(2, 2, 2, CfgLargeSC9,       0)    \
+    X(2, 2, 4, CfgLargeSC9,       0)
+
+// f(Cfg(), std::bool_constant<FUSED>()) for the row (pot, kind, q); `none` where the table has no such row
+template <class R, class F>
+R with_row(int pot, int kind, int q, R none, F &&f)
+{
+#define NM_ROW(P, K, Q, C, FUSED) if (pot == P && kind == K && q == Q) return f(C(), std::bool_constant<FUSED>());
+    NM_CFG_ROWS(NM_ROW)
+#undef NM_ROW
+    return none;
+}
+
+// every row fits the CU's LDS and holds the atoms of its kind (nm_create picks the kind by the Q = 1 row's NMAX)
+#define NM_ROW(P, K, Q, C, FUSED) static_assert(C::LDS_BYTES <= 160 * 1024 && C::NMAX == (K == 0 ? 256 : K == 1 ? 864 : 2048), #C);
+NM_CFG_ROWS(NM_ROW)
+#undef NM_ROW
+static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");
+
 thread_local std::string g_create_error;
 
 struct EvPair { hipEvent_t a, b; bool used; uint32_t launch_id; };
@@ -92,7 +143,6 @@ struct nm_ctx {
     bool whole_rows;            // the slot range is made of whole pressure rows (nm_exchange can run on the device)
     double *d_xbuf;
     uint32_t launch_id;
-    size_t lds_bytes, aux_doubles;
     double lat, mass, kB, mvv2e, ftm2v, nktv2p, skin, rc;
     int pot; // 0 lj/cut, 1 Sutton-Chen EAM n = 7 (Al), 2 Sutton-Chen EAM n = 9 (Cu, Ni): the kernels' Cfg POT
     double sc_eps, sc_a2, sc_c; // Sutton-Chen constants of the element (nm_lattice.h sc_element); unused by lj/cut
@@ -242,12 +292,16 @@ hipError_t launch_probe(const nm_ctx *c, KParams p)
     return hipGetLastError();
 }
 
-// workgroups of the block kernel one CU admits (LDS, registers), for the configuration launch_kind would pick at q per replica
+// dynamic LDS above 64 KiB has to be requested per kernel
+template <class C>
+hipError_t request_lds() { return hipFuncSetAttribute((const void *)nm_block_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES); }
+
+// workgroups of the block kernel one CU admits (LDS, registers)
 template <class C>
 int blocks_per_cu()
 {
     int n = 0;
-    if (hipFuncSetAttribute((const void *)nm_block_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES) != hipSuccess) return 0;
+    if (request_lds<C>() != hipSuccess) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, nm_block_kernel<C>, C::BLOCK, C::LDS_BYTES) != hipSuccess) return 0;
     return n;
 }
@@ -264,11 +318,11 @@ hipError_t launch_cycles_rec(const nm_ctx *c, const KParams &p)
 template <class C>
 hipError_t launch_cycles(const nm_ctx *c, const KParams &p) { return p.rec ? launch_cycles_rec<C, true>(c, p) : launch_cycles_rec<C, false>(c, p); }
 
-// nm_cycles_kernel is instantiated for the 4^3 clusters (LJ and Al) and the 6^3 cluster of eight.  nm_run_cycles uses it where it measured faster
+// nm_cycles_kernel is instantiated for the FUSED rows (the 4^3 clusters and the 6^3 cluster of eight).  nm_run_cycles uses it where it measured faster
 // than the loop of single launches: the 4^3 clusters of 2 and 4 workgroups (64-128 replicas: +2.4 to +2.9 % LJ, +0.5 % Al).  Clusters of 8 run 32 replicas
 // or fewer, whose rows have little spread to hide, and there the block compiled inside the loop over cycles (~1 % slower) costs more than the rows gain
 // (-0.8 % at 4^3, -2.9 % at 6^3): the loop of single launches, unless NM_FUSED_CYCLES=all.  NM_FUSED_CYCLES=0: never.  DESIGN.md §7.4 (6).
-bool cycles_kind_built(const nm_ctx *c) { return (c->kind == 0 && c->cus >= 2) || (c->kind == 1 && c->cus == 8); }
+bool cycles_kind_built(const nm_ctx *c) { return with_row(c->pot, c->kind, c->cus, false, [](auto, auto fused) { return decltype(fused)::value; }); }
 bool cycles_kind_ok(const nm_ctx *c)
 {
     if (!cycles_kind_built(c)) return false;
@@ -280,72 +334,23 @@ bool cycles_kind_ok(const nm_ctx *c)
 
 hipError_t launch_cycles_kind(const nm_ctx *c, const KParams &p)
 {
-    if (c->kind == 0) {
-        if (c->pot == 1) return c->cus == 4 ? launch_cycles<CfgSmallSCQ4>(c, p) : launch_cycles<CfgSmallSCQ2>(c, p);
-        if (c->pot == 2) return c->cus == 4 ? launch_cycles<CfgSmallSC9Q4>(c, p) : launch_cycles<CfgSmallSC9Q2>(c, p);
-        return c->cus == 8 ? launch_cycles<CfgSmallQ8>(c, p) : c->cus == 4 ? launch_cycles<CfgSmallQ4>(c, p) : launch_cycles<CfgSmallQ2>(c, p);
-    }
-    return launch_cycles<CfgMidQ8>(c, p);
-}
-
-// element Al above 256 atoms (kinds 1 and 2)
-hipError_t launch_kind_eam(const nm_ctx *c, const KParams &p)
-{
-    if (c->kind == 1) return c->cus == 4 ? launch_block<CfgMidSCQ4>(c, p) : launch_block<CfgMidSC>(c, p);
-    return launch_block<CfgLargeSC>(c, p);
-}
-
-// elements Cu and Ni (Sutton-Chen n = 9), every kind: the n = 7 dispatch with the twins
-hipError_t launch_kind_sc9(const nm_ctx *c, const KParams &p)
-{
-    if (c->kind == 1) return c->cus == 4 ? launch_block<CfgMidSC9Q4>(c, p) : launch_block<CfgMidSC9>(c, p);
-    if (c->kind == 2) return launch_block<CfgLargeSC9>(c, p);
-    return c->cus == 4 ? launch_block<CfgSmallSC9Q4>(c, p) : c->cus == 2 ? launch_block<CfgSmallSC9Q2>(c, p) : launch_block<CfgSmallSC9>(c, p);
+    return with_row(c->pot, c->kind, c->cus, hipErrorInvalidDeviceFunction, [&](auto cfg, auto fused) {
+        if constexpr (decltype(fused)::value) return launch_cycles<decltype(cfg)>(c, p);
+        else return hipErrorInvalidDeviceFunction;
+    });
 }
 
 hipError_t launch_kind(const nm_ctx *c, const KParams &p)
 {
-    if (c->pot == 2) return launch_kind_sc9(c, p);
-    if (c->pot == 1 && c->kind > 0) return launch_kind_eam(c, p);
-    switch (c->kind) {
-    case 0:
-        if (c->pot == 1) return c->cus == 4 ? launch_block<CfgSmallSCQ4>(c, p) : c->cus == 2 ? launch_block<CfgSmallSCQ2>(c, p) : launch_block<CfgSmallSC>(c, p);
-        return c->cus == 8 ? launch_block<CfgSmallQ8>(c, p) : c->cus == 4 ? launch_block<CfgSmallQ4>(c, p) : c->cus == 2 ? launch_block<CfgSmallQ2>(c, p) : launch_block<CfgSmall>(c, p);
-    case 1: return c->cus == 8 ? launch_block<CfgMidQ8>(c, p) : c->cus == 4 ? launch_block<CfgMidQ4>(c, p) : c->cus == 2 ? launch_block<CfgMid>(c, p) : launch_block<CfgMidH>(c, p);
-    default: return c->cus == 1 ? launch_block<CfgLargeH>(c, p) : launch_block<CfgLarge>(c, p);
-    }
+    return with_row(c->pot, c->kind, c->cus, hipErrorInvalidDeviceFunction, [&](auto cfg, auto) { return launch_block<decltype(cfg)>(c, p); });
 }
 
-int blocks_per_cu_kind(int kind, int pot, int q)
-{
-    if (pot == 2) {
-        if (kind > 0) return kind == 1 ? (q == 4 ? blocks_per_cu<CfgMidSC9Q4>() : blocks_per_cu<CfgMidSC9>()) : blocks_per_cu<CfgLargeSC9>();
-        return q == 4 ? blocks_per_cu<CfgSmallSC9Q4>() : q == 2 ? blocks_per_cu<CfgSmallSC9Q2>() : blocks_per_cu<CfgSmallSC9>();
-    }
-    if (pot == 1 && kind > 0) return kind == 1 ? (q == 4 ? blocks_per_cu<CfgMidSCQ4>() : blocks_per_cu<CfgMidSC>()) : blocks_per_cu<CfgLargeSC>();
-    switch (kind) {
-    case 0:
-        if (pot == 1) return q == 4 ? blocks_per_cu<CfgSmallSCQ4>() : q == 2 ? blocks_per_cu<CfgSmallSCQ2>() : blocks_per_cu<CfgSmallSC>();
-        return q == 8 ? blocks_per_cu<CfgSmallQ8>() : q == 4 ? blocks_per_cu<CfgSmallQ4>() : q == 2 ? blocks_per_cu<CfgSmallQ2>() : blocks_per_cu<CfgSmall>();
-    case 1: return q == 8 ? blocks_per_cu<CfgMidQ8>() : q == 4 ? blocks_per_cu<CfgMidQ4>() : q == 2 ? blocks_per_cu<CfgMid>() : blocks_per_cu<CfgMidH>();
-    default: return q == 1 ? blocks_per_cu<CfgLargeH>() : blocks_per_cu<CfgLarge>();
-    }
-}
+// 0 where the table has no configuration at q: pick_q then finds no room for such a grid
+int blocks_per_cu_kind(const nm_ctx *c, int q) { return with_row(c->pot, c->kind, q, 0, [](auto cfg, auto) { return blocks_per_cu<decltype(cfg)>(); }); }
 
 hipError_t probe_kind(const nm_ctx *c, const KParams &p)
 {
-    if (c->pot == 2) {
-        if (c->kind > 0) return c->kind == 1 ? (c->cus == 4 ? launch_probe<CfgMidSC9Q4>(c, p) : launch_probe<CfgMidSC9>(c, p)) : launch_probe<CfgLargeSC9>(c, p);
-        return c->cus == 4 ? launch_probe<CfgSmallSC9Q4>(c, p) : c->cus == 2 ? launch_probe<CfgSmallSC9Q2>(c, p) : launch_probe<CfgSmallSC9>(c, p);
-    }
-    if (c->pot == 1 && c->kind > 0) return c->kind == 1 ? (c->cus == 4 ? launch_probe<CfgMidSCQ4>(c, p) : launch_probe<CfgMidSC>(c, p)) : launch_probe<CfgLargeSC>(c, p);
-    switch (c->kind) {
-    case 0:
-        if (c->pot == 1) return c->cus == 4 ? launch_probe<CfgSmallSCQ4>(c, p) : c->cus == 2 ? launch_probe<CfgSmallSCQ2>(c, p) : launch_probe<CfgSmallSC>(c, p);
-        return c->cus == 8 ? launch_probe<CfgSmallQ8>(c, p) : c->cus == 4 ? launch_probe<CfgSmallQ4>(c, p) : c->cus == 2 ? launch_probe<CfgSmallQ2>(c, p) : launch_probe<CfgSmall>(c, p);
-    case 1: return c->cus == 8 ? launch_probe<CfgMidQ8>(c, p) : c->cus == 4 ? launch_probe<CfgMidQ4>(c, p) : c->cus == 2 ? launch_probe<CfgMid>(c, p) : launch_probe<CfgMidH>(c, p);
-    default: return c->cus == 1 ? launch_probe<CfgLargeH>(c, p) : launch_probe<CfgLarge>(c, p);
-    }
+    return with_row(c->pot, c->kind, c->cus, hipErrorInvalidDeviceFunction, [&](auto cfg, auto) { return launch_probe<decltype(cfg)>(c, p); });
 }
 
 // drain one event pair into the timing accumulators
@@ -540,7 +545,7 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed, int
 }
 
 // Workgroups per replica.  A cluster spins on its peers, so every workgroup of the grid must be resident at once.  The candidates
-// are the Q <= qmax for which the occupancy query admits the whole grid (workgroups per CU x CUs); the first one whose grid
+// are the Q <= qmax with a row in NM_CFG_ROWS for which the occupancy query admits the whole grid (workgroups per CU x CUs); the first one whose grid
 // actually gathers in a residency census (nm_probe_kernel: the block kernel's launch shape, census only, nm_kernels.h) is taken,
 // so a masked or busy CU lowers Q instead of stalling every block.  Leaves c->cus set; 1 when no cluster gathers.
 int pick_q(nm_ctx *c, int qmax, std::string &note)
@@ -550,7 +555,6 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
     int cu = prop.multiProcessorCount;
     if (testing())
         if (const char *e = std::getenv("NM_ASSUME_CUS")) { const int v = std::atoi(e); if (v > 0) cu = v; } // tests of the fallback
-    const int maxq = (c->pot != 0 || c->kind == 2) ? 4 : 8; // own-atom ranges the instantiated thread mappings cover
     c->cus = 1; c->over = false;
     // The large cells (N > 864) at 4 workgroups per replica when that makes a grid of (nearly) TWICE the chip: the clusters run in
     // two rounds, longest block first, each with its own census.  Their blocks differ by more than 2x across an equilibrated PxT grid
@@ -565,8 +569,8 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
     if (const char *e = std::getenv("NM_OVERSUBSCRIBE")) try_over = c->kind == 2 && qmax >= 4 && std::atoi(e) != 0;
     for (int pass = try_over ? 0 : 1; pass < 2; ++pass)
     for (int qq : { 8, 4, 2 }) {
-        if (qq > maxq || qq > qmax) continue;
-        const int per_cu = blocks_per_cu_kind(c->kind, c->pot, qq);
+        if (qq > qmax) continue;
+        const int per_cu = blocks_per_cu_kind(c, qq); // (0 where the table has no configuration at qq)
         const long grid = (long)nm_grid(c->nslots, qq), room = (long)per_cu * cu;
         const bool over = pass == 0;
         if (over) { if (qq != 4 || grid > 2 * room || 4 * grid < 7 * room) continue; } // 1.75 .. 2 chips' worth of workgroups
@@ -597,15 +601,11 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
 int alloc_cluster_buffers(nm_ctx *c)
 {
     const size_t ns = c->nslots;
-    size_t aux_doubles, lds_bytes = c->lds_bytes;
-    if (c->kind == 0) aux_doubles = CfgSmall::AUX_DOUBLES;
-    else if (c->pot != 0) { aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES; lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; }
-    else if (c->kind == 1) { aux_doubles = c->cus == 8 ? CfgMidQ8::AUX_DOUBLES : CfgMid::AUX_DOUBLES; lds_bytes = c->cus == 8 ? CfgMidQ8::LDS_BYTES : CfgMid::LDS_BYTES; }
-    else aux_doubles = CfgLarge::AUX_DOUBLES;
+    const size_t aux_doubles = with_row(c->pot, c->kind, c->cus, (size_t)0, [](auto cfg, auto) { return decltype(cfg)::AUX_DOUBLES; });
+    const size_t xbd = with_row(c->pot, c->kind, c->cus, (size_t)0, [](auto cfg, auto) { return decltype(cfg)::XBUF_DOUBLES; });
     // the new buffers first, swapped in only when both exist: a failure leaves the context with the buffers (and the workgroups per
     // replica) it can still run with
     double *aux = nullptr, *xbuf = nullptr;
-    const size_t xbd = c->kind == 0 ? CfgSmall::XBUF_DOUBLES : c->kind == 1 ? CfgMid::XBUF_DOUBLES : CfgLarge::XBUF_DOUBLES;
     hipError_t e = hipSuccess;
     if (aux_doubles) e = dalloc(&aux, ns * c->cus * aux_doubles);
     if (e == hipSuccess && c->cus > 1) {
@@ -620,7 +620,7 @@ int alloc_cluster_buffers(nm_ctx *c)
     }
     if (c->d_aux) hipFree(c->d_aux);
     if (c->d_xbuf) hipFree(c->d_xbuf);
-    c->d_aux = aux; c->d_xbuf = xbuf; c->aux_doubles = aux_doubles; c->lds_bytes = lds_bytes;
+    c->d_aux = aux; c->d_xbuf = xbuf;
     return NM_OK;
 }
 
@@ -825,15 +825,11 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
         c->h_tq[k] = Tj;
     }
 
-    size_t nbr_elems;
-    if (c->N <= CfgSmall::NMAX) { c->kind = 0; c->lds_bytes = c->pot != 0 ? CfgSmallSC::LDS_BYTES : CfgSmall::LDS_BYTES; /* Q8 variant: set at launch */ c->aux_doubles = CfgSmall::AUX_DOUBLES; nbr_elems = CfgSmall::NBR_G_ELEMS; }
-    else if (c->pot != 0) { // elements Al, Cu and Ni above 256 atoms (launch_kind_eam, launch_kind_sc9: the n = 9 twins have these sizes)
-        c->kind = c->N <= CfgMidSC::NMAX ? 1 : 2;
-        c->lds_bytes = c->kind == 1 ? CfgMidSC::LDS_BYTES : CfgLargeSC::LDS_BYTES; c->aux_doubles = c->kind == 1 ? CfgMidSC::AUX_DOUBLES : CfgLargeSC::AUX_DOUBLES;
-        nbr_elems = c->kind == 1 ? CfgMidSC::NBR_G_ELEMS : CfgLargeSC::NBR_G_ELEMS;
-    }
-    else if (c->N <= CfgMid::NMAX) { c->kind = 1; c->lds_bytes = CfgMid::LDS_BYTES; c->aux_doubles = CfgMid::AUX_DOUBLES; nbr_elems = CfgMid::NBR_G_ELEMS; }
-    else { c->kind = 2; c->lds_bytes = CfgLarge::LDS_BYTES; c->aux_doubles = CfgLarge::AUX_DOUBLES; nbr_elems = CfgLarge::NBR_G_ELEMS; }
+    // size class: the first kind whose configurations hold N atoms (every potential's kind 2 holds the 2048 checked above)
+    for (c->kind = 0; c->kind < 2 && with_row(c->pot, c->kind, 1, 0, [](auto cfg, auto) { return decltype(cfg)::NMAX; }) < c->N; ++c->kind) {}
+    // the neighbour lists in HBM, per slot: the largest of the kind's rows (a heal can take a 6^3 context from Q = 8, whose lists are in LDS, to Q = 4)
+    size_t nbr_elems = 0;
+    for (int q : { 1, 2, 4, 8 }) nbr_elems = std::max(nbr_elems, with_row(c->pot, c->kind, q, (size_t)0, [](auto cfg, auto) { return decltype(cfg)::NBR_G_ELEMS; }));
 
 #define CHK(call)                                                                                     \
     do {                                                                                              \
@@ -915,52 +911,7 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     CHK(hipMemcpy(c->d_et, c->h_et.data(), ns * sizeof(double), hipMemcpyHostToDevice));
     CHK(hipMemcpy(c->d_pf, c->h_pf.data(), ns * sizeof(double), hipMemcpyHostToDevice));
     CHK(hipMemcpy(c->d_tq, c->h_tq.data(), ns * sizeof(double), hipMemcpyHostToDevice));
-    // dynamic LDS above 64 KiB has to be requested per kernel
-    if (c->kind == 0) {
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmall>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmall::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallQ2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallQ2::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallQ4::LDS_BYTES));
-        static_assert(CfgSmall::LDS_BYTES <= 160 * 1024 && CfgSmallQ2::LDS_BYTES <= 160 * 1024, "two byte lists per workgroup must fit the CU's LDS");
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallQ8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallQ8::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSCQ2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSCQ2::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSCQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSCQ4::LDS_BYTES));
-        static_assert(CfgSmallSCQ2::LDS_BYTES <= 160 * 1024 && CfgSmallSC::LDS_BYTES <= 160 * 1024, "");
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC9::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC9Q2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC9Q2::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgSmallSC9Q4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgSmallSC9Q4::LDS_BYTES));
-        static_assert(CfgSmallSC9::LDS_BYTES == CfgSmallSC::LDS_BYTES && CfgSmallSC9Q2::LDS_BYTES == CfgSmallSCQ2::LDS_BYTES &&
-                      CfgSmallSC9Q4::LDS_BYTES == CfgSmallSCQ4::LDS_BYTES, "the n = 9 twins have Al's LDS plans");
-    }
-    else if (c->pot == 2) {
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC9::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC9Q4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC9Q4::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgLargeSC9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgLargeSC9::LDS_BYTES));
-        static_assert(CfgMidSC9::LDS_BYTES == CfgMidSC::LDS_BYTES && CfgMidSC9Q4::LDS_BYTES == CfgMidSCQ4::LDS_BYTES && CfgLargeSC9::LDS_BYTES == CfgLargeSC::LDS_BYTES &&
-                      CfgMidSC9::AUX_DOUBLES == CfgMidSC::AUX_DOUBLES && CfgMidSC9Q4::AUX_DOUBLES == CfgMidSC::AUX_DOUBLES &&
-                      CfgLargeSC9::AUX_DOUBLES == CfgLargeSC::AUX_DOUBLES && CfgMidSC9::NBR_G_ELEMS == CfgMidSC::NBR_G_ELEMS &&
-                      CfgLargeSC9::NBR_G_ELEMS == CfgLargeSC::NBR_G_ELEMS, "the n = 9 twins have Al's LDS plans and spill sizes");
-    }
-    else if (c->pot == 1) {
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSC::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidSCQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidSCQ4::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgLargeSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgLargeSC::LDS_BYTES));
-        static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");
-        static_assert(CfgMidSC::LDS_BYTES <= 160 * 1024 && CfgMidSCQ4::LDS_BYTES <= 160 * 1024 && CfgLargeSC::LDS_BYTES <= 160 * 1024, "");
-        static_assert(CfgMidSC::XBUF_DOUBLES == CfgMid::XBUF_DOUBLES && CfgLargeSC::XBUF_DOUBLES == CfgLarge::XBUF_DOUBLES, "alloc_cluster_buffers sizes the granules by kind");
-        static_assert(CfgMidSC::AUX_DOUBLES == CfgMidSCQ4::AUX_DOUBLES, "");
-    }
-    else if (c->kind == 1) {
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMid>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMid::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidH::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidQ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidQ4::LDS_BYTES));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgMidQ8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgMidQ8::LDS_BYTES));
-        static_assert(CfgMidQ8::LDS_BYTES <= 160 * 1024, "the 6^3 cluster configuration must fit the CU's LDS");
-    }
-    else {
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgLarge>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes));
-        CHK(hipFuncSetAttribute((const void *)nm_block_kernel<CfgLargeH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CfgLargeH::LDS_BYTES));
-    }
+    for (int q : { 1, 2, 4, 8 }) CHK(with_row(c->pot, c->kind, q, hipSuccess, [](auto cfg, auto) { return request_lds<decltype(cfg)>(); }));
     c->ev.assign(32, EvPair{ nullptr, nullptr, false, 0u });
     for (auto &e : c->ev) { CHK(hipEventCreate(&e.a)); CHK(hipEventCreate(&e.b)); }
 #undef CHK

@@ -1,9 +1,26 @@
 """shared helpers of the parity tests: the reference's main loop (remcmc:977-995) driven on the oracle"""
+import os
+import re
+
 import numpy as np
 
 from neuralmelting_amd import lattice
 
 LAT_LJ = 1.122
+NM_API = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'neuralmelting_amd', 'csrc', 'nm_api.hip')
+
+
+def cfg_rows():
+    """nm_api.hip's table of kernel configurations (NM_CFG_ROWS): {(pot, kind, Q): (Cfg typedef, fused)}; pot 0 lj/cut, 1 Al, 2 Cu and Ni"""
+    rows = {}
+    for line in open(NM_API).read().split('#define NM_CFG_ROWS(X)', 1)[1].split('\n')[1:]:
+        m = re.fullmatch(r'\s*X\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(Cfg\w+)\s*,\s*([01])\s*\)\s*(\\?)', line)
+        assert m, 'not a row of NM_CFG_ROWS: %r' % line
+        key = tuple(int(v) for v in m.group(1, 2, 3))
+        assert key not in rows, key
+        rows[key] = (m.group(4), m.group(5) == '1')
+        if not m.group(6):
+            return rows
 
 
 def grids(npn, ntn, pr=(1.0, 8.0), tr=(0.25, 2.5)):

@@ -2,13 +2,13 @@
 (eval_allpairs) on every edge state the GPU edge tests use.  Pins the reference, and the oracle at the edges: pairs at the cutoff
 and at the list radius, through every periodic image, on the faces, unwrapped, close contacts, boxes from 2 rc to 2 (rc + skin), and
 EAM atoms with nothing inside rc."""
-import os
 import re
 
 import numpy as np
 import pytest
 
 import exact_ref as X
+from helpers import NM_API, cfg_rows
 
 REL = 1e-12
 
@@ -73,13 +73,26 @@ def test_edge_states_are_what_they_claim():
         assert Ls[0] == 2 * rc and Ls[-1] > 2 * (rc + sk)
 
 
-def test_the_gpu_edge_matrix_covers_every_instantiation_launch_kind_can_pick():
-    """tests/test_eval_edges_gpu.py names a configuration for every (element, kind, workgroups per replica); the set of names must be the
-    set of block-kernel instantiations in nm_api.hip's launch_kind, so that a new one cannot go untested"""
+def test_the_gpu_edge_matrix_covers_every_lj_and_4cubed_al_row():
+    """tests/test_eval_edges_gpu.py names a configuration for every (element, kind, workgroups per replica) of lj/cut and of Al at 4^3:
+    the row of nm_api.hip's configuration table (NM_CFG_ROWS) for each, so that a new row cannot go untested"""
     import test_eval_edges_gpu as G
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'neuralmelting_amd', 'csrc', 'nm_api.hip')).read()
-    body = src[src.index('hipError_t launch_kind('):]
-    body = body[:body.index('\n}\n')]
-    launched = set(re.findall(r'launch_block<(\w+)>', body))
-    tested = {G.qs(el, n)[q] for el, n, q in (c.values for c in G.CASES)}
-    assert launched and tested == launched
+    tested = {({'LJ': 0, 'Al': 1}[el], G.kind(n), q): G.qs(el, n)[q] for el, n, q in (c.values for c in G.CASES)}
+    assert tested == {k: name for k, (name, _) in cfg_rows().items() if k[0] == 0 or k[:2] == (1, 0)}
+
+
+def test_every_launch_finds_its_configuration_in_the_table():
+    """nm_api.hip picks the kernel configuration of a context in one place, NM_CFG_ROWS through with_row: no launcher, occupancy query or
+    kernel reference names a Cfg typedef, so the block launch, the occupancy query and the residency probe cannot disagree.  The rows with a
+    fused nm_cycles_kernel and the workgroups per replica of each (potential, kind) are the measured and tested ones."""
+    src = open(NM_API).read()
+    launcher = r'launch_block|launch_probe|blocks_per_cu|request_lds|launch_cycles(?:_rec)?|nm_(?:block|probe|cycles)_kernel'
+    named = re.findall(r'\b(?:%s)\s*<\s*Cfg\w*' % launcher, src)
+    assert not named, named
+    rows = cfg_rows()
+    fused = {k for k, (_, f) in rows.items() if f}
+    assert fused == {(0, 0, 2), (0, 0, 4), (0, 0, 8), (0, 1, 8), (1, 0, 2), (1, 0, 4), (2, 0, 2), (2, 0, 4)}
+    qs = {}
+    for pot, kind, q in sorted(rows):
+        qs.setdefault((pot, kind), []).append(q)
+    assert qs == {(0, 0): [1, 2, 4, 8], (0, 1): [1, 2, 4, 8], (0, 2): [1, 2, 4], **{(p, k): [1, 2, 4] for p in (1, 2) for k in range(3)}}

@@ -137,23 +137,13 @@ def test_driver_refuses_ti_by_name(tmp_path):
         remcmc.Run('-e Ti -ss 4 -pn 2 -tn 2'.split(), cwd=str(tmp_path))
 
 
-def test_the_gpu_matrix_covers_every_n9_instantiation():
-    """tests/test_metals_gpu.py names a configuration for every (kind, workgroups per replica) of launch_kind_sc9 (nm_api.hip), and the
-    occupancy query and the residency probe ask about the same choice for Cu and Ni"""
-    import os
-    import re
+def test_the_gpu_matrix_covers_every_n9_row():
+    """tests/test_metals_gpu.py names a configuration for every (kind, workgroups per replica) of Cu and Ni: the row of nm_api.hip's
+    configuration table (NM_CFG_ROWS) for each.  Those rows are Al's with the n = 9 twins, fused where Al's are."""
     import test_metals_gpu as G
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'neuralmelting_amd', 'csrc', 'nm_api.hip')).read()
-
-    def body(sig):
-        b = src[src.index(sig):]
-        return b[:b.index('\n}\n')]
-    launched = set(re.findall(r'launch_block<(\w+)>', body('hipError_t launch_kind_sc9(')))
-    tested = {G.qs(n)[q] for el, n, q in (c.values for c in G.CASES)}
-    assert launched and tested == launched
-    assert 'if (c->pot == 2) return launch_kind_sc9(c, p);' in body('hipError_t launch_kind(')
-    occ = set(re.findall(r'blocks_per_cu<(\w+)>', body('int blocks_per_cu_kind(').split('if (pot == 2)')[1].split('\n    }')[0]))
-    prb = set(re.findall(r'launch_probe<(\w+)>', body('hipError_t probe_kind(').split('if (c->pot == 2)')[1].split('\n    }')[0]))
-    assert occ == launched and prb == launched
-    cyc = set(re.findall(r'launch_cycles<(\w+)>', [ln for ln in body('hipError_t launch_cycles_kind(').split('\n') if 'pot == 2' in ln][0]))
-    assert cyc == {'CfgSmallSC9Q2', 'CfgSmallSC9Q4'}
+    from helpers import cfg_rows
+    rows = cfg_rows()
+    tested = {(2, 0 if n <= 256 else 1 if n <= 864 else 2, q): G.qs(n)[q] for el, n, q in (c.values for c in G.CASES)}
+    assert tested == {k: name for k, (name, _) in rows.items() if k[0] == 2}
+    al_twins = {k[1:]: (name.replace('SC', 'SC9'), fused) for k, (name, fused) in rows.items() if k[0] == 1}
+    assert {k[1:]: v for k, v in rows.items() if k[0] == 2} == al_twins

@@ -27,7 +27,7 @@ NKTV2P = 1.6021765e6
 
 
 def qs(n):
-    """workgroups per replica launch_kind has an n = 9 instantiation for (nm_api.hip): the names are the Cfg typedefs"""
+    """workgroups per replica with an n = 9 row in the configuration table (nm_api.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
     if n <= 256:
         return {1: 'CfgSmallSC9', 2: 'CfgSmallSC9Q2', 4: 'CfgSmallSC9Q4'}
     if n <= 864:
