@@ -30,6 +30,28 @@ int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const 
                         const double *r_edges, int cbins, const double *rv_edges, float *rdf, float *cdf);
 const char *nm_distr_last_error(void);
 
+/* Angular (bond-angle) distribution: the quantity lammps_distr.py names .a.npy / .adf.npy but leaves switched off.
+ * Definition (the build's own; the reference's disabled code is not well-defined), for sample s and centre atom c:
+ *   neighbours  (j, a) over the 27 image shifts br[j] (lammps_distr.py:99-102) and all atoms a, with
+ *               v = pos[a] - (pos[c] + box*br[j]) in float32, d = float32 sqrt of the sequential float32 sum of the three
+ *               squares (as the rdf), and r_lo < (double)d <= r_hi;
+ *   triplets    every unordered pair of distinct neighbours (v1, v2) of the same centre; in float64 from the float32
+ *               components n_i = (x_i*x_i + y_i*y_i) + z_i*z_i, dot = (x1*x2 + y1*y2) + z1*z2,
+ *               cth = clip(dot / sqrt(n1*n2), -1, 1);
+ *   bins        in cosine space: cos_edges[abins] = cos(a[k]) for the angle edges a, strictly decreasing; bin k
+ *               (0 <= k <= abins-2) holds cos_edges[k] >= cth > cos_edges[k+1], the last bin also cth == cos_edges[abins-1]
+ *               (np.histogram(theta, a) without an acos); outside is dropped;
+ *   result      adf[s][k+1] += 1, adf[s][0] = 0 (ad[1:] += histogram, lammps_distr.py:107): raw counts, each unordered pair
+ *               once, NOT divided by natoms.
+ * pos[ns][natoms][3], box[ns] float32; adf[ns][abins] unsigned 64-bit (one bin can hold natoms * M^2 / 2 counts for M
+ * neighbours per centre).  Any number of neighbours per centre is handled.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_angles:".  NM_ERR_ARG,
+ * checked before the device is looked for and with adf left untouched, for: ns < 0, natoms outside 1..4095, abins outside
+ * 2..256, edges not strictly decreasing, not 0 <= r_lo < r_hi, r_hi > min(box)/2 over the batch (an atom could neighbour its
+ * own image), a null pointer, a bad device ordinal.  ns == 0 is NM_OK. */
+int nm_distr_angles(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int abins,
+                    const double *cos_edges, uint64_t *adf);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1637,6 +1637,61 @@ int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const 
     return NM_OK;
 }
 
+int nm_distr_angles(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int abins,
+                    const double *cos_edges, uint64_t *adf)
+{
+    if (ns < 0 || !pos || !box || !cos_edges || !adf) return dfail(NM_ERR_ARG, "nm_distr_angles: bad argument");
+    if (natoms < 1 || natoms > 4095) return dfail(NM_ERR_ARG, "nm_distr_angles: natoms must lie in 1..4095");
+    if (abins < 2 || abins > ADF_MAXB) return dfail(NM_ERR_ARG, "nm_distr_angles: abins must lie in 2..256");
+    for (int k = 0; k + 1 < abins; ++k)
+        if (!(cos_edges[k] > cos_edges[k + 1])) return dfail(NM_ERR_ARG, "nm_distr_angles: cos_edges must decrease strictly");
+    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return dfail(NM_ERR_ARG, "nm_distr_angles: the shell needs 0 <= r_lo < r_hi");
+    // beyond half the smallest box an atom could neighbour its own image (a zero angle that is no bond angle)
+    for (int s = 0; s < ns; ++s)
+        if (!(r_hi <= 0.5 * (double)box[s])) return dfail(NM_ERR_ARG, "nm_distr_angles: r_hi exceeds half the smallest box");
+    if (device < 0) return dfail(NM_ERR_ARG, "nm_distr_angles: device ordinal out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_angles: no HIP device available");
+    if (device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_angles: device ordinal out of range");
+    if (ns == 0) return NM_OK;
+    // the image pre-test of the scan compares float components with a float at or above r_hi; it is switched off for shells
+    // so small that the squares of such components could underflow
+    const float cube = r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY);
+    const int chunk = 4096; // samples per launch, as nm_distr_histograms
+    const int cs = ns < chunk ? ns : chunk;
+    const int groups = (natoms + ADF_CPB - 1) / ADF_CPB;
+    float *d_pos = nullptr, *d_box = nullptr;
+    double *d_e = nullptr;
+    unsigned long long *d_a = nullptr;
+    auto release = [&]() { hipFree(d_pos); hipFree(d_box); hipFree(d_e); hipFree(d_a); };
+#define ACHK(call)                                                                                     \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) { release(); return dfail(NM_ERR_HIP, std::string("nm_distr_angles: ") + #call + ": " + hipGetErrorString(e_)); } \
+    } while (0)
+    ACHK(hipSetDevice(device));
+    const size_t lds = adf_lds_bytes(natoms, abins); // at most 109,652 B (natoms 4095, abins 256)
+    ACHK(hipFuncSetAttribute((const void *)nm_adf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ACHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
+    ACHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
+    ACHK(hipMalloc((void **)&d_e, (size_t)abins * sizeof(double)));
+    ACHK(hipMalloc((void **)&d_a, (size_t)cs * abins * sizeof(unsigned long long)));
+    ACHK(hipMemcpy(d_e, cos_edges, (size_t)abins * sizeof(double), hipMemcpyHostToDevice));
+    for (int s0 = 0; s0 < ns; s0 += cs) {
+        const int n = (ns - s0) < cs ? (ns - s0) : cs;
+        ACHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
+        ACHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        ACHK(hipMemset(d_a, 0, (size_t)n * abins * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(nm_adf_kernel, dim3(n * groups), dim3(ADF_BLOCK), lds, 0, natoms, d_pos, d_box, r_lo, r_hi, cube, abins, d_e, d_a);
+        ACHK(hipGetLastError());
+        ACHK(hipDeviceSynchronize());
+        ACHK(hipMemcpy(adf + (size_t)s0 * abins, d_a, (size_t)n * abins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    release();
+#undef ACHK
+    return NM_OK;
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -129,4 +129,262 @@ nm_distr_kernel(int natoms, const float *__restrict__ pos, const float *__restri
         for (int k = tid; k < nc; k += DISTR_BLOCK) if (hc[k]) atomicAdd(&cdf_cnt[(size_t)s * nc + k], (float)hc[k]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Angular distribution (include/nm_distr.h, nm_distr_angles): for every centre atom c the angle between every unordered
+// pair of its neighbours, a neighbour being an (image, atom) whose float32 displacement length lies in (r_lo, r_hi].
+//
+// A workgroup takes ADF_CPB consecutive centres of one sample; the sample's positions are staged in LDS once.  Each wave
+// works through its centres on its own (no workgroup barrier after the staging):
+//   scan   the 27 images x natoms candidates, 64 at a time, with numpy's float32 arithmetic; survivors are appended to
+//          the wave's LDS neighbour list (ballot + prefix count): the float32 components and 1/|v| in float64.  An image
+//          whose shift puts the whole sample outside the cube |component| <= cube around the centre is skipped first.
+//   pairs  every unordered pair of the list, spread evenly over the lanes (the numbering is given at the loop), binned in cosine
+//          space into one of ADF_REP copies of the wave's LDS histogram (crystal frames put nearly all counts into four
+//          bins; the copies cut that contention by ADF_REP).
+//   tiles  a list longer than ADF_TILE is processed in tiles: tile A against itself, then against every later tile B,
+//          which is produced by scanning again.  Any number of neighbours is handled.
+// The LDS histograms are 32-bit; a wave adds them to the 64-bit global counts before they could overflow and at its end.
+constexpr int ADF_BLOCK = 256;
+constexpr int ADF_WAVES = ADF_BLOCK / 64;
+constexpr int ADF_TILE = 256;   // neighbours per LDS tile (two tiles per wave)
+constexpr int ADF_CPB = 32;     // centres per workgroup
+constexpr int ADF_REP = 4;      // copies of a wave's histogram, chosen by lane
+constexpr int ADF_LUT = 4096;   // cells of the bin-guess table over cos(theta) in [-1, 1]
+constexpr int ADF_MAXB = 256;   // most edges (a bin index fits the table's bytes)
+static_assert(ADF_LUT % ADF_BLOCK == 0 && ADF_MAXB <= 256, "each thread fills ADF_LUT / ADF_BLOCK cells with byte-sized bins");
+
+// The estimate est = dot * (r1 * r2), r_i = 1 / sqrt(n_i), against the definition's cth = clip(dot / sqrt(n1 * n2)):
+// with u = 2^-53 and every operation correctly rounded, cth carries a relative error of at most (1/2 + 1 + 1) u = 2.5 u
+// against the real quotient t (the product, its root, the division); r_i carries 2 u (root, reciprocal), r1 * r2 5 u and est
+// 6 u.  No operand can underflow or overflow: the n_i are sums of squares of float32 values, not all zero, so they lie in
+// [2^-298, 2^257].  |t| <= 1 up to the rounding of dot and n_i (a few u), so |est - cth| < 9 u (1 + 4 u) < 2^-49, and
+// ADF_MARGIN = 2^-48 is twice that.  If no edge lies within the margin of est and |est| < 1 - margin (so that the clip is
+// the identity), est and cth lie strictly between the same two edges, or outside on the same side: same bin.  Otherwise the
+// definition's expression is evaluated.
+constexpr double ADF_MARGIN = 0x1p-48;
+
+__host__ __device__ inline size_t adf_lds_bytes(int natoms, int abins)
+{
+    return (size_t)(abins + 1 + ADF_WAVES * 2 * ADF_TILE) * sizeof(double)                // edges and their sentinel, 1/|v| of the tiles
+         + ((size_t)3 * natoms + (size_t)ADF_WAVES * 2 * 3 * ADF_TILE + ADF_WAVES * 6) * sizeof(float) // positions, tiles, bounding box partials
+         + (size_t)ADF_WAVES * ADF_REP * abins * sizeof(unsigned int) + ADF_LUT;           // histograms, guess table
+}
+
+// bin k (0 <= k <= n-2) holds e[k] >= c > e[k+1] for strictly decreasing e, the last bin also c == e[n-1]; -1 = outside.
+// The walk starts from any k in [0, n-2] and is exact for every start.
+__device__ __forceinline__ int adf_walk(const double *e, int n, double c, int k)
+{
+    if (!(c <= e[0]) || !(c >= e[n - 1])) return -1;
+    while (k > 0 && c > e[k]) --k;            // now c <= e[k]
+    while (k < n - 2 && c <= e[k + 1]) ++k;   // now k == n-2 or c > e[k+1]
+    return k;
+}
+
+// The bin of one neighbour pair, -1 = dropped.  e holds one sentinel behind the last edge (e[n] = -inf), so the three edges
+// around the guessed bin are read at once: the guess k0 = lut[cell of est] is the bin of the cell's largest value, and est lies in
+// bin k0 or k0 + 1 unless the cell holds two edges.  If est is then inside its bin by more than the margin (see ADF_MARGIN), that
+// is the definition's bin; everything else (an edge within the margin, a wrong guess, outside, |est| within the margin of 1)
+// takes the general path: the walk, the margin test against the bin found, and the definition's own expression where it fails.
+__device__ __forceinline__ int adf_bin(const double *e, int n, const unsigned char *lut, float x1, float y1, float z1, double r1,
+                                       float x2, float y2, float z2, double r2)
+{
+    // float64 from the float32 components.  A product of two float32 is exact in float64, so the fma chain rounds exactly
+    // where (x1*x2 + y1*y2) + z1*z2 does: the same bits.
+    const double X1 = x1, Y1 = y1, Z1 = z1, X2 = x2, Y2 = y2, Z2 = z2;
+    const double dot = fma(Z1, Z2, fma(Y1, Y2, X1 * X2));
+    const double est = dot * (r1 * r2);
+    int g = (int)((1.0 - est) * (double)(ADF_LUT / 2));
+    g = g < 0 ? 0 : (g > ADF_LUT - 1 ? ADF_LUT - 1 : g);
+    const int k0 = (int)lut[g];
+    const double ea = e[k0], eb = e[k0 + 1], ec = e[k0 + 2];
+    const bool up = est <= eb;
+    const double hi = up ? eb : ea, lo = up ? ec : eb;
+    int k = up ? k0 + 1 : k0;
+    if (k <= n - 2 && hi - est > ADF_MARGIN && est - lo > ADF_MARGIN && fabs(est) < 1.0 - ADF_MARGIN) return k;
+    k = adf_walk(e, n, est, k <= n - 2 ? k : n - 2);
+    bool near = !(fabs(est) < 1.0 - ADF_MARGIN);
+    if (k >= 0) near = near || e[k] - est <= ADF_MARGIN || est - e[k + 1] <= ADF_MARGIN;
+    else near = near || (est > e[0] ? est - e[0] <= ADF_MARGIN : e[n - 1] - est <= ADF_MARGIN);
+    if (near) {
+        const double n1 = fma(Z1, Z1, fma(Y1, Y1, X1 * X1)), n2 = fma(Z2, Z2, fma(Y2, Y2, X2 * X2));
+        double c = dot / sqrt(n1 * n2); // IEEE division and square root (hipcc's defaults for float64)
+        c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+        k = adf_walk(e, n, c, k >= 0 ? k : (est > e[0] ? 0 : n - 2));
+    }
+    return k;
+}
+
+// A wave's lanes exchange the neighbour tiles through LDS without a workgroup barrier: a wave's LDS operations complete in
+// program order, and this keeps the compiler from moving them across the hand-over.
+__device__ __forceinline__ void adf_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One scan of the candidates of centre (cx, cy, cz): neighbours number t0 .. t0+ADF_TILE-1 (in scan order) go to the tile.
+// Returns the number of neighbours seen; the scan ends early once that reaches `stop`.
+__device__ __forceinline__ int adf_fill(const float *px, const float *py, const float *pz, int natoms, float cx, float cy, float cz,
+                                        float L, float cube, const float *bb, double r_lo, double r_hi, int t0, int stop, float *tx,
+                                        float *ty, float *tz, double *tr, int lane)
+{
+#pragma clang fp contract(off)
+    int base = 0;
+    for (int img = 0; img < 27; ++img) {
+        // br[j] = (b[i], b[j], b[k]) for i, j, k in range(3), b = [-1, 0, 1]  (lammps_distr.py:99-102)
+        const float bx = (float)(img / 9 - 1), by = (float)((img / 3) % 3 - 1), bz = (float)(img % 3 - 1);
+        const float qx = cx + L * bx, qy = cy + L * by, qz = cz + L * bz; // pos[c] + box*br[j]
+        // float subtraction is monotone, so every atom's component lies between those of the bounding box; a component beyond
+        // cube >= r_hi in magnitude gives d >= |component| > r_hi (sqrt(x*x) rounds to |x|, the further terms only add)
+        if (bb[0] - qx > cube || bb[1] - qx < -cube || bb[2] - qy > cube || bb[3] - qy < -cube || bb[4] - qz > cube || bb[5] - qz < -cube)
+            continue;
+        for (int a0 = 0; a0 < natoms; a0 += 64) {
+            const int a = a0 + lane;
+            bool in = false;
+            float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+            if (a < natoms) {
+                vx = px[a] - qx; vy = py[a] - qy; vz = pz[a] - qz;
+                float d2 = vx * vx;      // sequential float32 sum of three terms, as the rdf path
+                d2 = d2 + vy * vy;
+                d2 = d2 + vz * vz;
+                const double d = (double)sqrtf(d2); // correctly rounded (see nm_distr_kernel)
+                in = r_lo < d && d <= r_hi;
+            }
+            const unsigned long long m = __ballot(in);
+            if (in) {
+                const int o = base + __popcll(m & ((1ull << lane) - 1ull)) - t0;
+                if (o >= 0 && o < ADF_TILE) {
+                    const double X = vx, Y = vy, Z = vz;
+                    tx[o] = vx; ty[o] = vy; tz[o] = vz;
+                    tr[o] = 1.0 / sqrt(fma(Z, Z, fma(Y, Y, X * X)));
+                }
+            }
+            base += __popcll(m);
+            if (base >= stop) return base;
+        }
+    }
+    return base;
+}
+
+__global__ void __launch_bounds__(ADF_BLOCK)
+nm_adf_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+              int abins, const double *__restrict__ cos_edges, unsigned long long *__restrict__ adf)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + ADF_CPB - 1) / ADF_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * ADF_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double *e = (double *)smem, *tr_all = e + abins + 1;
+    float *px = (float *)(tr_all + ADF_WAVES * 2 * ADF_TILE), *py = px + natoms, *pz = py + natoms;
+    float *txyz_all = pz + natoms, *part = txyz_all + ADF_WAVES * 2 * 3 * ADF_TILE;
+    unsigned int *h_all = (unsigned int *)(part + ADF_WAVES * 6);
+    unsigned char *lut = (unsigned char *)(h_all + ADF_WAVES * ADF_REP * abins);
+    const float L = box[s];
+    const float *ps = pos + (size_t)s * natoms * 3;
+    // stage the positions, their bounding box, the edges, the guess table; clear the histograms
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    for (int a = tid; a < natoms; a += ADF_BLOCK) {
+        const float x = ps[3 * a], y = ps[3 * a + 1], z = ps[3 * a + 2];
+        px[a] = x; py[a] = y; pz[a] = z;
+        lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
+        lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
+        lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
+    }
+    for (int d = 0; d < 3; ++d) {
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[d] = fminf(lo[d], __shfl_xor(lo[d], o));
+            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o));
+        }
+        if (lane == 0) { part[wave * 6 + 2 * d] = lo[d]; part[wave * 6 + 2 * d + 1] = hi[d]; }
+    }
+    for (int k = tid; k <= abins; k += ADF_BLOCK) e[k] = k < abins ? cos_edges[k] : -INFINITY;
+    for (int k = tid; k < ADF_WAVES * ADF_REP * abins; k += ADF_BLOCK) h_all[k] = 0u;
+    __syncthreads();
+    {
+        // the bin of each cell's largest value (cells in decreasing order of cos: the bin never decreases along a thread's
+        // consecutive cells); a hint only, adf_bin is exact for any table
+        int k = 0;
+        for (int g = tid * (ADF_LUT / ADF_BLOCK); g < (tid + 1) * (ADF_LUT / ADF_BLOCK); ++g) {
+            const double top = 1.0 - (double)g * (2.0 / ADF_LUT);
+            while (k < abins - 2 && top <= e[k + 1]) ++k;
+            lut[g] = (unsigned char)k;
+        }
+    }
+    float bb[6];
+    for (int d = 0; d < 3; ++d) {
+        float l = part[2 * d], u = part[2 * d + 1];
+        for (int w = 1; w < ADF_WAVES; ++w) { l = fminf(l, part[w * 6 + 2 * d]); u = fmaxf(u, part[w * 6 + 2 * d + 1]); }
+        bb[2 * d] = l; bb[2 * d + 1] = u;
+    }
+    __syncthreads();
+    // this wave's tiles and histogram copies
+    float *ax = txyz_all + (size_t)wave * 2 * 3 * ADF_TILE, *ay = ax + ADF_TILE, *az = ay + ADF_TILE;
+    float *bx = az + ADF_TILE, *by = bx + ADF_TILE, *bz = by + ADF_TILE;
+    double *ar = tr_all + (size_t)wave * 2 * ADF_TILE, *br = ar + ADF_TILE;
+    unsigned int *hw = h_all + (size_t)wave * ADF_REP * abins;
+    unsigned int *h = hw + (lane & (ADF_REP - 1)) * abins;
+    unsigned long long *out = adf + (size_t)s * abins;
+    unsigned long long held = 0ull; // upper bound of the counts this wave's LDS histograms hold
+    auto flush = [&]() {
+        for (int k = lane; k < abins; k += 64) {
+            unsigned long long t = 0ull;
+            for (int r = 0; r < ADF_REP; ++r) { t += hw[r * abins + k]; hw[r * abins + k] = 0u; }
+            if (t) atomicAdd(&out[k], t);
+        }
+        held = 0ull;
+    };
+    const int cend = c0 + ADF_CPB < natoms ? c0 + ADF_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += ADF_WAVES) {
+        adf_wave_sync(); // the previous centre's pair loops are done with the tiles
+        // wave-uniform values in scalar registers
+        const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px[c])));
+        const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py[c])));
+        const float cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pz[c])));
+        const int M = adf_fill(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, 0, 0x7fffffff, ax, ay, az, ar, lane);
+        adf_wave_sync();
+        const int nt = (M + ADF_TILE - 1) / ADF_TILE;
+        for (int ta = 0; ta < nt; ++ta) {
+            if (ta > 0) {
+                adf_wave_sync(); // the pair loops of the previous tile are done with A
+                adf_fill(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, ta * ADF_TILE, (ta + 1) * ADF_TILE, ax, ay, az, ar, lane);
+                adf_wave_sync();
+            }
+            const int ma = M - ta * ADF_TILE < ADF_TILE ? M - ta * ADF_TILE : ADF_TILE;
+            if (held + (unsigned long long)ADF_TILE * ADF_TILE > 0xffffffffull) flush();
+            // all unordered pairs of the tile, each once: pair number q = (d - 1) * ma + i is (i, (i + d) mod ma) for the offsets
+            // d = 1 .. ma/2 (for even ma the last offset only with i < ma/2): ma (ma - 1) / 2 pairs, lanes take q = lane, lane + 64, ..
+            {
+                const int Q = ma * (ma - 1) / 2;
+                int d = 1 + lane / ma, i = lane % ma;
+                for (int q = lane; q < Q; q += 64) {
+                    const int j = i + d < ma ? i + d : i + d - ma;
+                    const int k = adf_bin(e, abins, lut, ax[i], ay[i], az[i], ar[i], ax[j], ay[j], az[j], ar[j]);
+                    if (k >= 0) atomicAdd(&h[k + 1], 1u);
+                    i += 64;
+                    while (i >= ma) { i -= ma; ++d; }
+                }
+                held += (unsigned long long)Q;
+            }
+            for (int tb = ta + 1; tb < nt; ++tb) {
+                adf_wave_sync();
+                adf_fill(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, tb * ADF_TILE, (tb + 1) * ADF_TILE, bx, by, bz, br, lane);
+                adf_wave_sync();
+                const int mb = M - tb * ADF_TILE < ADF_TILE ? M - tb * ADF_TILE : ADF_TILE;
+                if (held + (unsigned long long)ADF_TILE * ADF_TILE > 0xffffffffull) flush();
+                const int Q = ma * mb; // every pair (i of A, j of B)
+                int j = lane / ma, i = lane % ma;
+                for (int q = lane; q < Q; q += 64) {
+                    const int k = adf_bin(e, abins, lut, ax[i], ay[i], az[i], ar[i], bx[j], by[j], bz[j], br[j]);
+                    if (k >= 0) atomicAdd(&h[k + 1], 1u);
+                    i += 64;
+                    while (i >= ma) { i -= ma; ++j; }
+                }
+                held += (unsigned long long)Q;
+            }
+        }
+    }
+    flush();
+}
+
 } // namespace nm

@@ -4,9 +4,11 @@ Mirrors the reference's scripts/lammps_distr.py ("distr"): loads <PREFIX>.natoms
 lammps_parse.py, computes the per-sample radial distribution over the 27 periodic images (calculate_rdf, distr:123-135)
 and the 3-D histogram of pair displacement vectors (calculate_cdf, distr:161-171) — here one kernel launch over all
 samples (include/nm_distr.h) instead of a Dask/joblib map of numpy calls — and writes the same .dni/.r/.rdf/.dn/.rv/.cdf
-files with the same shapes and dtypes.
+files with the same shapes and dtypes.  With -ad it also writes the angular (bond-angle) distribution the reference names
+.a.npy / .adf.npy but leaves switched off (definition: include/nm_distr.h, nm_distr_angles).
 
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
 """
 import argparse
 import ctypes as C
@@ -39,7 +41,17 @@ def parse_args(argv=None):
     p.add_argument('-e', '--element', type=str, default='LJ')
     p.add_argument('-sb', '--spherical_bins', type=int, default=64)
     p.add_argument('-cb', '--cartesian_bins', type=int, default=16)
-    return p.parse_args(argv)
+    p.add_argument('-ad', '--angular', action='store_true',
+                   help='also write <PREFIX>.a.npy and <PREFIX>.adf.npy: the distribution of the angles between the neighbours of '
+                        'each atom, on the domain a = linspace(1e-16, pi, spherical_bins)')
+    p.add_argument('-ac', '--angular_cutoff', type=float, default=0.5,
+                   help='outer radius of the neighbour shell of -ad as a fraction of the smallest box edge, in (0, 0.5]; '
+                        'default 0.5 (the last radial edge).  The first shell of an fcc crystal of SZ cells per edge ends at '
+                        'about 0.85/SZ')
+    a = p.parse_args(argv)
+    if not 0.0 < a.angular_cutoff <= 0.5:
+        p.error('-ac/--angular_cutoff must lie in (0, 0.5]')
+    return a
 
 
 def calculate_spatial(natoms, box, sbins, cbins):
@@ -88,6 +100,25 @@ def histograms(natoms, box, pos, r, rv, device=0, want_rdf=True, want_cdf=True):
     return rdf, cdf
 
 
+def angles(natoms, box, pos, a, r_lo, r_hi, device=0):
+    """angular distribution of all samples on the angle edges a (float64 [sbins], increasing from about 0 to pi), neighbour
+    shell r_lo < d <= r_hi: the raw counts of nm_distr_angles (each unordered neighbour pair of a centre once, unsigned 64-bit,
+    adf[:, 0] = 0) divided by natoms in float64 and cast to float32 [ns][sbins], the dtype of the other histogram files.  The
+    exact integers are available through the C-ABI."""
+    L = B.load()
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    box = np.ascontiguousarray(box, dtype=np.float32)
+    ns, n = pos.shape[0], pos.shape[1]
+    ce = np.ascontiguousarray(np.cos(np.asarray(a, dtype=np.float64)))   # bins are compared in cosine space
+    adf = np.zeros((ns, len(ce)), dtype=np.uint64)
+    rc = L.nm_distr_angles(device, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), float(r_lo), float(r_hi),
+                           len(ce), ce.ctypes.data_as(B.c_double_p), adf.ctypes.data_as(B.c_uint64_p))
+    if rc != 0:
+        raise RuntimeError('nm_distr_angles failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    na = np.asarray(natoms).reshape(-1).astype(np.float64)
+    return (adf.astype(np.float64) / na[:, None]).astype(np.float32)
+
+
 def main(argv=None):
     a = parse_args(argv)
     prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, a.element.lower(), LAT[a.element])
@@ -111,6 +142,12 @@ def main(argv=None):
     np.save(prefix + '.dn.npy', dn)
     np.save(prefix + '.rv.npy', rv)
     np.save(prefix + '.cdf.npy', c.reshape(pn, tn, rns, *(3 * (rv.shape[1] - 1,))))
+    if a.angular:
+        l = float(np.min(box))
+        ang = np.linspace(1e-16, np.pi, a.spherical_bins)                     # distr:88
+        adf = angles(natoms, box, pos, ang, 1e-16 * l, a.angular_cutoff * l, device=int(os.environ.get('LOCAL_RANK', '0')))
+        np.save(prefix + '.a.npy', ang)
+        np.save(prefix + '.adf.npy', adf.reshape(pn, tn, rns, ang.size))
     if a.verbose:
         print('all properties pickled')
 

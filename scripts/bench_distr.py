@@ -1,8 +1,70 @@
-"""throughput of nm_distr_histograms (row f-2) next to the numpy restatement of calculate_rdf / calculate_cdf"""
+"""throughput of nm_distr_histograms (row f-2) next to the numpy restatement of calculate_rdf / calculate_cdf
+
+    python scripts/bench_distr.py [ns=4096] [natoms=256]
+    python scripts/bench_distr.py --angles [ns=4096] [cells=4] [cutoff=0.5] [repeats=5]
+
+--angles: nm_distr_angles on displaced fcc frames of 4 cells^3 atoms (shell up to cutoff * l; the first shell is about
+0.85 / cells): the time of the whole call (copies + kernel, host clock around the synchronous call, median of the repeats
+after a warm-up), triplets/s, and the numpy restatement (tests/adf_ref.py) on one host core over a few centres.  The
+kernel's own time comes from `rocprofv3 --kernel-trace --stats -- python scripts/bench_distr.py --angles ...` (nm_adf_kernel)."""
 import os, sys, time
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from neuralmelting_amd import distr
+
+
+def bench_angles(argv):
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import adf_ref as A
+    from neuralmelting_amd import _lib as B, lattice
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    cells = int(argv[1]) if len(argv) > 1 else 4
+    cut = float(argv[2]) if len(argv) > 2 else 0.5
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    rng = np.random.default_rng(3)
+    n = 4 * cells ** 3
+    a0 = lattice.lattice_constant('LJ')
+    box = (cells * a0 * (1.0 + 0.05 * rng.random(ns))).astype(np.float32)
+    frac = lattice.fcc_fractional(cells)
+    pos = ((frac[None] + 0.08 / cells * rng.normal(size=(ns, n, 3))) % 1.0 * box[:, None, None]).astype(np.float32)
+    pos = np.minimum(pos, np.nextafter(box, np.float32(0))[:, None, None])
+    l = float(box.min())
+    ce = np.ascontiguousarray(np.cos(np.linspace(1e-16, np.pi, 64)))
+    L = B.load()
+    out = np.zeros((ns, 64), dtype=np.uint64)
+
+    def run(m):
+        rc = L.nm_distr_angles(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, 64,
+                               ce.ctypes.data_as(B.c_double_p), out.ctypes.data_as(B.c_uint64_p))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+    run(min(ns, 8))
+    run(ns)                                                                   # warm-up at the timed shape
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter(); run(ns); ts.append(time.perf_counter() - t)
+    trip = int(out.sum())
+    dt = float(np.median(ts))
+    print('angles: %d samples x %d atoms, cutoff %.4f l: %d triplets (%.1f neighbours per centre); call (H2D + kernel + D2H) median '
+          'of %d: %.4f s (min %.4f, max %.4f) = %.2f G triplets/s' % (ns, n, cut, trip, (1 + np.sqrt(1 + 8 * trip / (ns * n))) / 2,
+                                                                       reps, dt, min(ts), max(ts), trip / dt / 1e9))
+    kc = min(n, 16)
+    t = time.perf_counter()
+    nt = 0
+    for c in range(kc):
+        v = A.neighbours(pos[0], box[0], c, 1e-16 * l, cut * l)
+        k = A.cos_bins(ce, A.cosines(v)) if len(v) > 1 else np.zeros(0, dtype=np.int64)
+        np.bincount(k[k >= 0], minlength=63)
+        nt += len(v) * (len(v) - 1) // 2
+    dt = time.perf_counter() - t
+    print('numpy restatement, one core, %d centres of sample 0: %.4f s, %.4f G triplets/s, %.2f centres/s' % (kc, dt, nt / dt / 1e9, kc / dt))
+
+
+if '--angles' in sys.argv:
+    bench_angles([x for x in sys.argv[1:] if x != '--angles'])
+    sys.exit(0)
+
 from oracle import distr_oracle as D
 
 ns, n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096, int(sys.argv[2]) if len(sys.argv) > 2 else 256

@@ -1,10 +1,13 @@
 #!/bin/bash
 # The stages of the reference's run.sh (equilibrate, restart + collect, parse, structural histograms) on the MI355X
 # modules of this repository.  Same flags; the cluster flags of the reference (-c -nw -nt -mt ...) are accepted and ignored.
-#   scripts/run_mi355x.sh [supercell=5] [pressures=32] [temperatures=32] [cycles=1024]
+#   scripts/run_mi355x.sh [supercell=5] [pressures=32] [temperatures=32] [cycles=1024] [-ad [-ac CUTOFF]]
+# Anything after the fourth argument goes to the distr stage: -ad adds the angular distribution (.a.npy / .adf.npy), -ac its
+# neighbour shell as a fraction of the smallest box edge (first fcc shell: about 0.85 / supercell).
 # For several GPUs start the first two stages under  python -m torch.distributed.run --nproc-per-node N -m neuralmelting_amd.remcmc ...
 set -euo pipefail
 s=${1:-5}; pn=${2:-32}; tn=${3:-32}; sn=${4:-1024}
+if [ $# -gt 4 ]; then shift 4; else shift $#; fi
 root=$(cd "$(dirname "$0")/.." && pwd)
 export PYTHONPATH="$root${PYTHONPATH:+:$PYTHONPATH}"
 mkdir -p ./output/remcmc_$s
@@ -15,5 +18,5 @@ python -m neuralmelting_amd.remcmc -v -n remcmc_init_$s -ss $s -bm -pn $pn -tn $
 python -m neuralmelting_amd.remcmc -v -r -rn remcmc_init_$s -rs $sn -n remcmc_run_$s -ss $s -bm -pn $pn -tn $tn -sn $sn -rd $sn
 # text -> arrays
 python -m neuralmelting_amd.parse -v -n remcmc_run_$s
-# radial and cartesian pair histograms
-python -m neuralmelting_amd.distr -v -n remcmc_run_$s -cb 11
+# radial and cartesian pair histograms (and, with -ad, the angular distribution)
+python -m neuralmelting_amd.distr -v -n remcmc_run_$s -cb 11 "$@"
