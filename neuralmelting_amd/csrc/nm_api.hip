@@ -25,28 +25,17 @@ using namespace nm;
 
 namespace {
 
-#ifndef NM_SMALL_BLOCK
-#define NM_SMALL_BLOCK 512 // 8 waves: 256 VGPRs per lane, no spills (1024 threads cap at 128 and spilled ~200)
-#define NM_SMALL_TPA 2
-#endif
+// The small kernels run 512 threads, 8 waves: 256 VGPRs per lane, no spills (1024 threads cap at 128 and spilled ~200).
 // cluster variants of the small kernel: Q workgroups per replica, threads-per-atom scaled so that all 512 threads work
 // (a cluster stores the list rows of its own atoms only, and keeps the list twice: a rejected move goes back to the one it started from)
-typedef Cfg<NM_SMALL_BLOCK, 2 * NM_SMALL_TPA, 256, 192, unsigned char, true, true, 0, 128, true, true> CfgSmallQ2;
-#if NM_SMALL_BLOCK == 1024
-typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 0, 64, true, true> CfgSmallQ4;
-#else
-typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 192, unsigned char, true, true, 0, 64, true, true> CfgSmallQ4;
-#endif
-#if NM_SMALL_BLOCK == 1024 // (experiment: 16 waves per workgroup; 32 threads per row would not fit a DPP row)
-typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 0, 64, true, true> CfgSmallQ8;
-#else
-typedef Cfg<NM_SMALL_BLOCK, 8 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 0, 32, true, true> CfgSmallQ8; // grids of <= 32 replicas
-#endif
-typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 192, unsigned char, true, true, 0, 256, true, true> CfgSmall;     // N <= 256: everything incl. the byte lists in LDS
+typedef Cfg<512, 4, 256, 192, unsigned char, true, true, 0, 128, true, true> CfgSmallQ2;
+typedef Cfg<512, 8, 256, 192, unsigned char, true, true, 0, 64, true, true> CfgSmallQ4;
+typedef Cfg<512, 16, 256, 256, unsigned char, true, true, 0, 32, true, true> CfgSmallQ8; // grids of <= 32 replicas
+typedef Cfg<512, 2, 256, 192, unsigned char, true, true, 0, 256, true, true> CfgSmall;     // N <= 256: everything incl. the byte lists in LDS
 // element Al: Sutton-Chen EAM, 4^3 cells only (BASELINE config 4); 200 neighbour slots (134 within rc+skin in the crystal)
-typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 256, unsigned char, true, true, 1> CfgSmallSC;
-typedef Cfg<NM_SMALL_BLOCK, 2 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 1, 128, true, true> CfgSmallSCQ2; // (own rows, two lists)
-typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 1, 64, true, true> CfgSmallSCQ4;
+typedef Cfg<512, 2, 256, 256, unsigned char, true, true, 1> CfgSmallSC;
+typedef Cfg<512, 4, 256, 256, unsigned char, true, true, 1, 128, true, true> CfgSmallSCQ2; // (own rows, two lists)
+typedef Cfg<512, 8, 256, 256, unsigned char, true, true, 1, 64, true, true> CfgSmallSCQ4;
 // element Al at 5^3 to 8^3 cells: 16-bit lists in HBM/L2, chunked as CfgMid's and CfgLarge's, full lists (Cfg::HALF stays lj/cut's).  256 slots
 // per atom: the crystal has 134 neighbours within rc + skin = 8.1 A, and the longest row over bench's Al grid (8 x 8, P 1 .. 8 bar, T 256 .. 2560 K,
 // 40 cycles from the lattice) was 149 at 5^3 and 151 at 8^3; more is reported as ST_LIST_OVERFLOW.  Densities in LDS at 864 atoms (141.5 KB in all), in the spill at 2048
@@ -56,9 +45,9 @@ typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 1> CfgMidSCQ4;   // 4
 typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 1> CfgLargeSC; // 1, 2 and 4
 // elements Cu and Ni: every Al configuration again with the Sutton-Chen exponent n = 9 (Cfg POT 2).  Their cutoff and skin are Al's in units of
 // the lattice constant (nm_lattice.h sc_element), so the list lengths, the 256 slots, the LDS plans and the size thresholds above hold for them unchanged.
-typedef Cfg<NM_SMALL_BLOCK, NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2> CfgSmallSC9;
-typedef Cfg<NM_SMALL_BLOCK, 2 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2, 128, true, true> CfgSmallSC9Q2;
-typedef Cfg<NM_SMALL_BLOCK, 4 * NM_SMALL_TPA, 256, 256, unsigned char, true, true, 2, 64, true, true> CfgSmallSC9Q4;
+typedef Cfg<512, 2, 256, 256, unsigned char, true, true, 2> CfgSmallSC9;
+typedef Cfg<512, 4, 256, 256, unsigned char, true, true, 2, 128, true, true> CfgSmallSC9Q2;
+typedef Cfg<512, 8, 256, 256, unsigned char, true, true, 2, 64, true, true> CfgSmallSC9Q4;
 typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 2> CfgMidSC9;
 typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 2> CfgMidSC9Q4;
 typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 2> CfgLargeSC9;
@@ -124,8 +113,9 @@ R with_row(int pot, int kind, int q, R none, F &&f)
     return none;
 }
 
-// every row fits the CU's LDS and holds the atoms of its kind (nm_create picks the kind by the Q = 1 row's NMAX)
-#define NM_ROW(P, K, Q, C, FUSED) static_assert(C::LDS_BYTES <= 160 * 1024 && C::NMAX == (K == 0 ? 256 : K == 1 ? 864 : 2048), #C);
+// every row fits the CU's LDS and holds the atoms of its kind (nm_create picks the kind by the Q = 1 row's NMAX); a half list runs at one
+// workgroup per replica only (pair_vec_half takes every listed atom for an own atom)
+#define NM_ROW(P, K, Q, C, FUSED) static_assert(C::LDS_BYTES <= 160 * 1024 && C::NMAX == (K == 0 ? 256 : K == 1 ? 864 : 2048) && (!C::HALF || Q == 1), #C);
 NM_CFG_ROWS(NM_ROW)
 #undef NM_ROW
 static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");

@@ -16,39 +16,6 @@
 
 namespace nm {
 
-#ifndef NM_AB
-#define NM_AB 0 // A/B experiments: a variant library is built with -DNM_AB=k (scripts/ab_multi.sh), the shipped one with 0
-#endif
-#ifndef NM_POLL_SLEEP
-#define NM_POLL_SLEEP 1 // s_sleep units (64 clocks each) between two polls of a hand-over granule (0: none)
-#endif
-#ifndef NM_PAIR_W
-#define NM_PAIR_W 2 // listed neighbours a thread works on at once (pair_vec)
-#endif
-#ifndef NM_HALF_LIST
-#define NM_HALF_LIST 1 // one thread per row (lists in HBM/L2): a pair of two atoms of the same workgroup is listed ONCE (Cfg::HALF); 0 = full lists
-#endif
-#ifndef NM_SPREAD
-#define NM_SPREAD 1 // pair loop over LDS lists: the row's epilogue on three lanes, its operands prefetched (0: one lane, as in rounds 1-3)
-#endif
-// pair loop over LDS lists: list entry at which the two waves of a SIMD swap priorities (see pair_loop), by threads per row — a thread
-// holds (row length) / TPA entries, and the best swap point sits at ~0.6 of them.  Equilibrated, same box (round 4): TPA 8 (C2):
-// 1.415 / 1.420 / 1.409 / 1.403 M sweeps/s at 8 / 10 / 12 / 14 (12 in rounds 2-3); TPA 4 (C3 share): 360 k at 20 vs 354 k at 10 or 12,
-// 354 k at 26.  A swap point proportional to the row's own length — a run-time compare in every trip instead of one the compiler
-// folds — measured 3 % slower.
-#ifndef NM_PRIO_SW16
-#define NM_PRIO_SW16 6
-#endif
-#ifndef NM_PRIO_SW8
-#define NM_PRIO_SW8 10
-#endif
-#ifndef NM_PRIO_SW4
-#define NM_PRIO_SW4 20
-#endif
-#ifndef NM_PRIO_SW2
-#define NM_PRIO_SW2 40
-#endif
-
 constexpr int NVMAX = 16; // widest block reduction (the 16 raw moments of hmc_velocities)
 
 // Diagnostic build only (-DNM_PROF, never the shipped library): shader-clock stamps per section, summed by lane 0
@@ -168,8 +135,8 @@ struct Cfg {
     // bound by the LDS pipe already (64 unrelated atoms per gather instruction), three atomics per entry make 2.4 times the LDS work of an
     // entry, only the own range's pairs go away (75 % of the entries at two workgroups per replica), and a cluster loses the epilogue that
     // integrates and publishes a row's atom as soon as its force is known.  At ONE workgroup per replica it pays at 2048 atoms too (256 replicas:
-    // +10 %).  So HALF_ is set for the one-workgroup configurations of the lists in HBM only (CfgMidH, CfgLargeH, nm_api.hip); -DNM_HALF_LIST=2 builds every one-thread-per-row configuration with half lists for the A/B.
-    static constexpr bool HALF = !LIST_LDS_ && TPA_ == 1 && POT_ == 0 && (NM_HALF_LIST == 2 || (NM_HALF_LIST == 1 && HALF_));
+    // +10 %).  So HALF_ is set for the one-workgroup configurations of the lists in HBM only (CfgMidH, CfgLargeH, nm_api.hip).
+    static constexpr bool HALF = !LIST_LDS_ && TPA_ == 1 && POT_ == 0 && HALF_;
     static constexpr int BLOCK = BLOCK_, TPA = TPA_, NW = BLOCK_ / 64, G = BLOCK_ / TPA_, NMAX = NMAX_, MAXNB = MAXNB_;
     static constexpr bool LIST_LDS = LIST_LDS_, SAVE_LDS = SAVE_LDS_;
     using IdxT = IdxT_;
@@ -199,21 +166,11 @@ struct Cfg {
     static constexpr bool RHO_LDS = POT_ != 0 && OFF_RHO + (size_t)NMAX * sizeof(double) <= (size_t)160 * 1024;
     static constexpr size_t OFF_X0S = OFF_RHO + (RHO_LDS ? (size_t)NMAX * sizeof(double) : 0); // LDS_LIST2: reference positions of the saved list
     static constexpr size_t OFF_CNTS = OFF_X0S + (LDS_LIST2 ? A3 : 0);                     //            and its row lengths
-    // PREFETCH: the gaussians of the NEXT move's `velocity create` are drawn while the closing exchange of the current move's
-    // energy sums is in flight (Replica::prefetch_gaussians) and wait here, 3 NMAX doubles
-    // (measured 1.4 % SLOWER on C2 and C4, round 3: the 400 instructions per thread delay the poll more than the flight time they fill,
-    //  and the kernel spills 75 instead of 52 VGPRs.  Kept behind NM_AB == 6 for the record; off in the shipped build.)
-    static constexpr bool PREFETCH = (NM_AB == 6) && NMAX_ <= 256;
-    static constexpr size_t OFF_GAUSS = OFF_CNTS + (LDS_LIST2 ? pad8((size_t)NMAX * sizeof(unsigned short)) : 0);
-    static constexpr size_t LDS_NATURAL = OFF_GAUSS + (PREFETCH ? A3 : 0);
+    static constexpr size_t LDS_NATURAL = OFF_CNTS + (LDS_LIST2 ? pad8((size_t)NMAX * sizeof(unsigned short)) : 0);
     // One workgroup per CU, by construction: a cluster's census and the Q selection count on it (nm_probe_kernel asserts it), and
     // two workgroups of different replicas on one CU measured slower.  A configuration that would fit twice
     // into the CU's 160 KB asks for a little more than half of them.
-#if NM_AB == 4 // experiment: 256-thread workgroups (-DNM_SMALL_BLOCK=256 -DNM_SMALL_TPA=1), 8 per replica, two (of different replicas) per CU
-    static constexpr size_t LDS_BYTES = (BLOCK_ == 256 || LDS_NATURAL > (size_t)82 * 1024) ? LDS_NATURAL : (size_t)82 * 1024;
-#else
     static constexpr size_t LDS_BYTES = LDS_NATURAL > (size_t)82 * 1024 ? LDS_NATURAL : (size_t)82 * 1024;
-#endif
     // per-slot global spill when the saved copies do not fit in LDS: sav, savv, x0 (9 NMAX doubles) + images + wrap counts
     static constexpr size_t AUX_SAVES = SAVE_LDS ? (SAVEV_LDS ? 0 : (size_t)3 * NMAX) : (size_t)9 * NMAX + ((size_t)3 * NMAX * 3 + 7) / 8;
     // lists outside LDS are kept TWICE per slot (LIST2): a trial that rebuilt and is then rejected goes back to the list it started
@@ -248,17 +205,16 @@ struct Cfg {
 // touches is in LDS at constant offsets; scalars come and go by value.  Makes ONE block reduction (the caller flips its buffer
 // parity) and returns sum m |v|^2 of the velocities it leaves.
 // the gaussians of `velocity all create ... dist gaussian`, divided by sqrt(m): 2N work items over all threads — item w < N draws
-// (vx, vy) of atom w, item N + w draws vz — written to three arrays of NMAX doubles at byte offset `off` of the LDS block (the
-// velocities, or the prefetch area).  A function of its own (Philox, log, sin, cos: ~400 instructions), called from two places.
+// (vx, vy) of atom w, item N + w draws vz — written to the velocities.  A function of its own (Philox, log, sin, cos: ~400 instructions).
 template <class C>
-__device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int gslot, double mass, uint32_t seed, uint32_t step, int off)
+__device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int gslot, double mass, uint32_t seed, uint32_t step)
 {
     constexpr int BLOCK = C::BLOCK;
     const int tid = threadIdx.x;
-    N = __builtin_amdgcn_readfirstlane(N); gslot = __builtin_amdgcn_readfirstlane(gslot); off = __builtin_amdgcn_readfirstlane(off);
+    N = __builtin_amdgcn_readfirstlane(N); gslot = __builtin_amdgcn_readfirstlane(gslot);
     tag = __builtin_amdgcn_readfirstlane(tag); seed = __builtin_amdgcn_readfirstlane(seed); step = __builtin_amdgcn_readfirstlane(step);
     mass = uniform(mass);
-    double *const gx = (double *)(nm_lds + off), *const gy = gx + C::NMAX, *const gz = gy + C::NMAX;
+    double *const gx = (double *)(nm_lds + C::OFF_VEL), *const gy = gx + C::NMAX, *const gz = gy + C::NMAX;
     const double twopi = 6.283185307179586476925286766559;
     const double fac = 1.0 / sqrt(mass);
     for (int w = tid; w < 2 * N; w += BLOCK) {
@@ -276,7 +232,7 @@ __device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int
 
 template <class C>
 __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t tag, double L, int N, int gslot, int parity, double mass,
-                                                         double mvv2e, double kB, uint32_t seed, uint32_t step, short *im_g, int prefetched)
+                                                         double mvv2e, double kB, uint32_t seed, uint32_t step, short *im_g)
 {
     constexpr int BLOCK = C::BLOCK, NW = C::NW;
     constexpr size_t A1 = (size_t)C::NMAX * sizeof(double);
@@ -296,11 +252,7 @@ __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t t
     tag = __builtin_amdgcn_readfirstlane(tag); seed = __builtin_amdgcn_readfirstlane(seed); step = __builtin_amdgcn_readfirstlane(step);
     t = uniform(t); L = uniform(L); mass = uniform(mass); mvv2e = uniform(mvv2e); kB = uniform(kB);
     const double m = mass, mt = m * N;
-    prefetched = __builtin_amdgcn_readfirstlane(prefetched);
-    if (C::PREFETCH && prefetched) { // drawn while the previous move's energy sums were crossing the cluster (prefetch_gaussians)
-        const double *const g = (const double *)(nm_lds + C::OFF_GAUSS);
-        for (int i = tid; i < N; i += BLOCK) { vx[i] = g[i]; vy[i] = g[C::NMAX + i]; vz[i] = g[2 * C::NMAX + i]; }
-    } else gaussian_fill<C>(tag, N, gslot, mass, seed, step, (int)C::OFF_VEL);
+    gaussian_fill<C>(tag, N, gslot, mass, seed, step);
     __syncthreads();
     double a[16];
 #pragma unroll
@@ -321,11 +273,7 @@ __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t t
         a[14] -= m * Y * Z;
         a[15] -= m * X * Z;
     }
-#if NM_AB == 1
-    block_sum<16, NW, NVMAX>(a, red, parity);
-#else
     block_sum<16, NW, NVMAX>(a, red, parity, min(NW, (N + 63) >> 6)); // (atoms are dealt out by thread index: N <= 256 leaves half the waves empty)
-#endif
     const double imt = 1.0 / mt; // (one division instead of six, and one for the inertia tensor below instead of three: every thread does all of this)
     const double c0 = a[0] * imt, c1 = a[1] * imt, c2 = a[2] * imt;   // COM velocity
     const double cx = a[3] * imt, cy = a[4] * imt, cz = a[5] * imt;   // centre of mass (unwrapped)
@@ -1074,12 +1022,11 @@ struct Replica {
     // The trick holds while |addend| < 2^15 force units; beyond it the integer is garbage.  Checked by a compare, not prevented: a pair's
     // addend is at most its force, |F(r)| = 24 (2 r^-13 - r^-7), which grows as r shrinks below 1.12 sigma and reaches 2^15 at
     // r = 0.604173 sigma (r^2 = 0.365025): every interacting pair is compared with FIX_R2 (a little above, so the test errs on the side of
-    // reporting), every row total with 2^15.  The pair's compare costs nothing: it takes the place of the own-range compare, which the
-    // shipped half-list configurations do not need (ONE_WG below).
+    // reporting), every row total with 2^15.  The pair's compare is the only one beside the cutoff's: a half list needs no
+    // own-range compare (below).
     static constexpr double FIX_RANGE = 32768.0 /* 2^15 */, FIX_R2 = 0.36503;
-    // CfgMidH and CfgLargeH run at one workgroup per replica only (launch_kind picks them at Q = 1): every listed atom is an own atom.
-    // (-DNM_HALF_LIST=2 builds half lists for the cluster configurations too: there the own-range compare stays.)
-    static constexpr bool ONE_WG = C::HALF && NM_HALF_LIST == 1;
+    // CfgMidH and CfgLargeH run at one workgroup per replica only (launch_kind picks them at Q = 1; nm_api.hip asserts it for every row
+    // of its table): every listed atom is an own atom.
     int fr_bad = 0;    // HALF: this thread met an addend or a row total outside the fixed-point range since the last energy evaluation
     int fr_hit = 0;    // HALF, uniform over the cluster: an evaluation since the current move started met one (take_sums); the forces are not
                        // to be trusted
@@ -1118,17 +1065,16 @@ struct Replica {
     {
         return (double)__double_as_longlong(slot) * (1.0 / FIX_SCALE);
     }
-    // W listed neighbours of row i at once (lists in HBM/L2, j = 8 x the atom index); entries that are atoms of this workgroup
-    // (own8 = 8 a0, ownn8 = 8 (a1 - a0)) stand for the pair in BOTH directions: the opposite force goes to the partner, the pair's energy,
-    // virial and count are taken twice (the caller halves the cluster-wide sums as it does for a full list)
+    // W listed neighbours of row i at once (lists in HBM/L2, j = 8 x the atom index); every entry is an atom of this workgroup and
+    // stands for the pair in BOTH directions: the opposite force goes to the partner, the pair's energy, virial and count are taken twice
+    // (the caller halves the sums as it does for a full list)
     // (the neighbours' coordinates are handed in: the caller gathers those of the NEXT trip before it calls this for the current one,
     //  so that the gathers stand in front of this trip's atomics in the LDS queue, which returns in order — with the gathers behind
     //  them every trip waited for six atomics to drain before its coordinates arrived: C5 share -11 %, run.sh setting +5 %; round 4)
     template <bool WANT_E, int W>
     __device__ __forceinline__ void pair_vec_half(const int (&j)[W], const bool (&ok)[W], const double (&xj)[W], const double (&yj)[W],
                                                   const double (&zj)[W], double xi, double yi, double zi, double invL,
-                                                  double rc2, double &ax, double &ay, double &az, double &e, double &w, double &np,
-                                                  unsigned int own8, unsigned int ownn8)
+                                                  double rc2, double &ax, double &ay, double &az, double &e, double &w, double &np)
     {
         double dx[W], dy[W], dz[W], r2[W], y[W], t[W], fp[W];
         const double mhL = -0.5 * L;
@@ -1138,12 +1084,11 @@ struct Replica {
         for (int q = 0; q < W; ++q) { dx[q] = __builtin_amdgcn_fract(dx[q]); dy[q] = __builtin_amdgcn_fract(dy[q]); dz[q] = __builtin_amdgcn_fract(dz[q]); }
 #pragma unroll
         for (int q = 0; q < W; ++q) { dx[q] = __builtin_fma(dx[q], L, mhL); dy[q] = __builtin_fma(dy[q], L, mhL); dz[q] = __builtin_fma(dz[q], L, mhL); }
-        bool in[W], own[W];
+        bool in[W];
 #pragma unroll
         for (int q = 0; q < W; ++q) {
             r2[q] = dx[q] * dx[q] + dy[q] * dy[q] + dz[q] * dz[q];
             in[q] = ok[q] && r2[q] < rc2;
-            own[q] = ONE_WG || ((unsigned int)j[q] - own8) < ownn8;
             fr_bad |= (in[q] && r2[q] < FIX_R2) ? 1 : 0; // (the fixed-point range, FIX_R2)
         }
 #pragma unroll
@@ -1165,17 +1110,16 @@ struct Replica {
 #pragma unroll
         for (int q = 0; q < W; ++q) {
             fp[q] = t[q] * __builtin_fma(2.0, t[q], -1.0) * y[q]; // (pair_pre's units: 24 for force and virial, 4 for the energy)
-            if (WANT_E) { const double wg = own[q] ? 2.0 : 1.0; e += wg * (t[q] * (t[q] - 1.0)); np += in[q] ? wg : 0.0; w += wg * (r2[q] * fp[q]); }
+            if (WANT_E) { e += 2.0 * (t[q] * (t[q] - 1.0)); np += in[q] ? 2.0 : 0.0; w += 2.0 * (r2[q] * fp[q]); }
         }
 #pragma unroll
         for (int q = 0; q < W; ++q) {
             const double tx = dx[q] * fp[q], ty = dy[q] * fp[q], tz = dz[q] * fp[q];
             ax += tx; ay += ty; az += tz;
             // the partner's share, -24 t (the row's own sum is scaled by 24 at its end).  UNCONDITIONAL: an entry beyond the cutoff adds an
-            // exact zero (fp = 0), an atom of another workgroup gets a zero scale (its entry of the force array is not read by anybody).
-            // Guarded by `if (own && in)` the compiler gave every neighbour a basic block of its own and the two neighbours of a trip no
+            // exact zero (fp = 0).  Guarded by `if (in)` the compiler gave every neighbour a basic block of its own and the two neighbours of a trip no
             // longer overlapped: the half list then ran 8-14 % SLOWER than the full one (run.sh setting, C5 share; round 4).
-            const double sc = own[q] ? -24.0 * FIX_SCALE : 0.0;
+            const double sc = -24.0 * FIX_SCALE;
             fixed_add((unsigned int)C::OFF_FRC + (unsigned int)j[q], tx, sc);
             fixed_add((unsigned int)(C::OFF_FRC + A1) + (unsigned int)j[q], ty, sc);
             fixed_add((unsigned int)(C::OFF_FRC + 2 * A1) + (unsigned int)j[q], tz, sc);
@@ -1184,10 +1128,14 @@ struct Replica {
 
     // The two waves that share a SIMD (w and w + NW/2) do not share it evenly: the older one wins every arbitration it is
     // ready for, finishes its rows ~1 us before the other, and the younger one then runs alone below the SIMD's fp64 issue
-    // rate.  So in the loops over LDS lists the younger wave holds the higher priority for its first NM_PRIO_SW list entries and
+    // rate.  So in the loops over LDS lists the younger wave holds the higher priority for its first PRIO_SW list entries and
     // the older one after that: both stay in the loop to the end (measured +2.9 % on the 4^3 cluster; either wave favoured
     // throughout: no gain).
-    static constexpr int PRIO_SW = TPA >= 16 ? NM_PRIO_SW16 : TPA >= 8 ? NM_PRIO_SW8 : TPA >= 4 ? NM_PRIO_SW4 : NM_PRIO_SW2;
+    // PRIO_SW, by threads per row: a thread holds (row length) / TPA entries, and the best swap point sits at ~0.6 of them.  Equilibrated,
+    // same box (round 4): TPA 8 (C2): 1.415 / 1.420 / 1.409 / 1.403 M sweeps/s at 8 / 10 / 12 / 14 (12 in rounds 2-3); TPA 4 (C3 share):
+    // 360 k at 20 vs 354 k at 10 or 12, 354 k at 26.  A swap point proportional to the row's own length — a run-time compare in every
+    // trip instead of one the compiler folds — measured 3 % slower.
+    static constexpr int PRIO_SW = TPA >= 16 ? 6 : TPA >= 8 ? 10 : TPA >= 4 ? 20 : 40;
     __device__ __forceinline__ bool young() const { return (tid >> 6) >= NW / 2; }
     __device__ __forceinline__ void prio_begin() const { if constexpr (C::LIST_LDS) { if (young()) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); } }
     __device__ __forceinline__ void prio_swap() const { if constexpr (C::LIST_LDS) { if (young()) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); } }
@@ -1205,7 +1153,7 @@ struct Replica {
         const double rc2 = p.rc * p.rc;
         // SPREAD (round 4): the row's epilogue — integrate, publish, store — is done by three lanes, one component each, instead of
         // lane 0 doing all three in a row (TPA >= 4; the byte / 16-bit LDS lists)
-        constexpr bool SPREAD = (NM_SPREAD != 0) && TPA >= 4 && !C::HALF;
+        constexpr bool SPREAD = TPA >= 4 && !C::HALF;
         for (int i0 = a0; i0 < a1; i0 += G) { // uniform trip count keeps the shuffles below convergent
             const int i = i0 + g;
             double ax = 0.0, ay = 0.0, az = 0.0, e = 0.0, w = 0.0, np = 0.0;
@@ -1219,7 +1167,7 @@ struct Replica {
                 const double xi = __builtin_fma(px[i], invL, 0.5), yi = __builtin_fma(py[i], invL, 0.5), zi = __builtin_fma(pz[i], invL, 0.5); // (pair_pre)
                 if constexpr (SPREAD && !C::LIST_LDS) { if (fuse && sub < 3) { vpre = vx.ptr()[sub * NMAX + i]; ppre = px.ptr()[sub * NMAX + i]; } }
                 if constexpr (C::LIST_LDS) {
-                    constexpr int W = NM_PAIR_W, PW = C::PW, BITS = 8 * (int)sizeof(IdxT);
+                    constexpr int W = 2, PW = C::PW, BITS = 8 * (int)sizeof(IdxT); // W: listed neighbours a thread works on at once (pair_vec)
                     static_assert(PW % W == 0, "");
                     const unsigned long long *nb64 = (const unsigned long long *)nbr_cur();
                     const int mine = (c - sub + TPA - 1) / TPA; // neighbours of atom i that this thread handles: slots sub, sub+TPA, ...
@@ -1279,7 +1227,6 @@ struct Replica {
                             }
                         };
                         fetch(cur[0], 0);
-                        const unsigned int own8 = 8u * (unsigned int)a0, ownn8 = 8u * (unsigned int)(a1 - a0);
                         for (int k0 = 0; k0 < mych; k0 += PF) {
 #pragma unroll
                             for (int q = 0; q < PF; ++q) nxt[q] = (k0 + PF + q) < mych ? nb64[NM_CHECK_INDEX((size_t)(k0 + PF + q) * NMAX + i, C::NBR_G_ELEMS / 4)] : 0ull;
@@ -1295,7 +1242,7 @@ struct Replica {
                                         if (e0 + W < C::CH) fetch(cur[q], e0 + W);
                                         else if (q + 1 < PF) fetch(cur[q + 1], 0);
                                         else fetch(nxt[0], 0);
-                                        pair_vec_half<WANT_E, W>(jj, ok, xc, yc, zc, xi, yi, zi, invL, rc2, ax, ay, az, e, w, np, own8, ownn8);
+                                        pair_vec_half<WANT_E, W>(jj, ok, xc, yc, zc, xi, yi, zi, invL, rc2, ax, ay, az, e, w, np);
                                     }
                                 }
                             }
@@ -1576,9 +1523,8 @@ struct Replica {
                 poisoned |= po;
                 return true;
             }
-#if NM_POLL_SLEEP > 0
-            __builtin_amdgcn_s_sleep(NM_POLL_SLEEP); // a failed poll is not repeated at once: fewer loads in the way of the peers' stores
-#endif
+            static constexpr int POLL_SLEEP = 1; // s_sleep units (64 clocks each) between two polls of a hand-over granule
+            __builtin_amdgcn_s_sleep(POLL_SLEEP); // a failed poll is not repeated at once: fewer loads in the way of the peers' stores
             if ((++spins & 63) == 0) {
                 const unsigned long long now = wall_clock64();
                 if (t0 == 0) t0 = now | 1ull;
@@ -1634,44 +1580,6 @@ struct Replica {
         if (fl & 2) status |= ST_LIST_OVERFLOW; // a peer's list overflowed
 #pragma unroll
         for (int k = 0; k < K; ++k) s[k] = uniform(t[k]);
-    }
-
-    // the same in two halves, for work that can be done while the granules are in flight
-    __device__ __forceinline__ void exchange_put(const double (&s)[4])
-    {
-        double *xg = xb + (size_t)(gen & 1) * C::XBUF_DOUBLES;
-        if (tid < 4) {
-            double mine = s[0];
-#pragma unroll
-            for (int k = 1; k < 4; ++k) mine = (tid == k) ? s[k] : mine;
-            put_granule(xg + 2 * (size_t)(C::XG_PART + 4 * q + tid), mine, my_magic());
-        }
-    }
-    __device__ __forceinline__ void exchange_get(double (&s)[4])
-    {
-        double *xg = xb + (size_t)(gen & 1) * C::XBUF_DOUBLES;
-        const unsigned long long mg = magic();
-        int timeout = 0, poisoned = 0;
-        const int lane = tid & 63;
-        double v[4] = { 0.0, 0.0, 0.0, 0.0 };
-        if (lane < Q) {
-            double *gs[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) gs[k] = xg + 2 * (C::XG_PART + 4 * lane + k);
-            get_granules<4>(gs, mg, v, timeout, poisoned);
-        }
-        double t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            t[k] = 0.0;
-            for (int r = 0; r < Q; ++r) t[k] += __shfl(v[k], r, 64);
-        }
-        ++gen;
-        const int fl = block_any2<NW, NVMAX>(timeout != 0, poisoned != 0, red, parity);
-        if (fl & 1) status |= ST_SYNC_TIMEOUT;
-        if (fl & 2) status |= ST_LIST_OVERFLOW; // a peer's list overflowed
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = uniform(t[k]);
     }
 
     // a workgroup that leaves the block on its own finding (list overflow) marks everything its peers could be waiting for
@@ -1877,28 +1785,16 @@ struct Replica {
         st_eevals += 1.0; st_pairs += 0.5 * psum[2];
         if (!(U == U) || isinf(U)) status |= ST_NONFINITE;
     }
-    // completes an energy evaluation; `extra` is one more per-workgroup partial sum that rides along.  next_m >= 0: the move that
-    // follows is move next_m of the block; if it is going to be a Hamiltonian move its gaussians are drawn between the publication of
-    // this workgroup's partial sums and the poll for the peers' — the ~1 us the sums need to cross the cluster otherwise passes idle.
-    // Philox is counter-based, so the values are those velocity_create would draw: results do not change by a bit.
-    int gauss_for = -1; // move index whose gaussians wait in the prefetch area
-    __device__ double finish_sums(double extra, int next_m = -1)
+    // Read by nothing: four bytes of Replica's layout.  Without them the compiler assigns the registers of the eleven block kernels whose lists
+    // live in HBM/L2 differently — the same instructions, 2 to 28 more spilled VGPRs in the Sutton-Chen ones — and 864 Al atoms at four workgroups
+    // per replica ran 0.3 % slower sustained, 0.7 % in the window, in five of five alternations (profiles/r07_ab_retired_variants.txt).
+    // (Initialised to -1 and to nothing else: with 0 the eleven kernels move again.)
+    int layout_pad = -1;
+    // completes an energy evaluation; `extra` is one more per-workgroup partial sum that rides along.
+    __device__ double finish_sums(double extra)
     {
         double s[4] = { psum[0], psum[1], psum[2], extra };
-#if NM_AB == 5
-        next_m = -1;
-#endif
-        if (C::PREFETCH && Q > 1 && next_m >= 0 && next_m < p.mod && tape == nullptr && !p.md_mode) {
-            exchange_put(s);
-            uint32_t o[4];
-            philox4x32_10(0u, S_ROLL, (uint32_t)next_m, p.step, p.seed, (uint32_t)gslot, o);
-            const double roll = u01(o[0], o[1]); // (draw_scalar(S_ROLL, next_m, 0): block-uniform)
-            if (roll > p.ppos + p.pvol) {
-                gaussian_fill<C>((uint32_t)next_m, N, gslot, p.mass, p.seed, p.step, (int)C::OFF_GAUSS);
-                gauss_for = next_m; // (visible to every thread after exchange_get's barrier)
-            }
-            exchange_get(s);
-        } else exchange_sums<4>(s);
+        exchange_sums<4>(s);
         psum[0] = s[0]; psum[1] = s[1]; psum[2] = s[2];
         take_sums();
         return s[3];
@@ -1918,11 +1814,11 @@ struct Replica {
     //   I about the COM            = raw second moments - M (|Xc|^2 1 - Xc Xc^T)   (parallel axis)
     // and one pass that writes v = sc (v - c) - omega x (X - Xc).  The second "zero linear" would subtract the round-off of
     // sum m v' / M (~1e-17 relative); it is left out.  Differences to the four-pass arithmetic are ~1e-15 relative.
-    __device__ __forceinline__ double hmc_velocities(double t, uint32_t tag, int prefetched)
+    __device__ __forceinline__ double hmc_velocities(double t, uint32_t tag)
     {
         short *img = nullptr;
         if constexpr (!C::SAVE_LDS) img = im.g;
-        const double mv2 = velocity_create<C>(t, tag, L, N, gslot, parity, p.mass, p.mvv2e, p.kB, p.seed, p.step, img, prefetched);
+        const double mv2 = velocity_create<C>(t, tag, L, N, gslot, parity, p.mass, p.mvv2e, p.kB, p.seed, p.step, img);
         parity ^= 1;
         return uniform(mv2); // (the caller's barrier after wrap() orders these velocities for the threads that take the own atoms next)
     }
@@ -2277,7 +2173,7 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
     // conflict-free 8-byte read = eight neighbours, the 16-bit lists in HBM/L2 in chunks of four, three chunks ahead —
     // two neighbours' dependency chains interleaved stage by stage (sc_rho_vec, sc_force_vec: the 16-bit lists; the byte loops
     // below are the same arithmetic written out, as the 4^3 kernels have always compiled it).
-    constexpr int W = NM_PAIR_W;
+    constexpr int W = 2; // listed neighbours a thread works on at once
     static_assert(C::LIST_LDS ? sizeof(IdxT) == 1 : (sizeof(IdxT) == 2 && C::CH == 4), "the EAM loops read byte lists in LDS or chunked 16-bit lists");
     const unsigned long long *nb64 = (const unsigned long long *)nbr_cur();
     for (int i0 = a0; i0 < a1; i0 += G) {
@@ -2388,7 +2284,7 @@ __device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &ea
     // pass 2: forces (and energy, virial) of this workgroup's atoms.  1/r comes from v_rsq_f64 + two Newton steps (~1 ulp), which
     // gives (a/r)^2 and a/r at once: no separate division and square root.
     const double a1r = sqrt(a2);
-    constexpr bool SPREAD = (NM_SPREAD != 0) && TPA >= 4; // the row's epilogue on three lanes, operands prefetched (see pair_loop)
+    constexpr bool SPREAD = TPA >= 4; // the row's epilogue on three lanes, operands prefetched (see pair_loop)
     for (int i0 = a0; i0 < a1; i0 += G) {
         const int i = i0 + g;
         double ax = 0.0, ay = 0.0, az = 0.0, e = 0.0, w = 0.0, np = 0.0;
@@ -2581,9 +2477,7 @@ __device__ __forceinline__ bool residency_census(const KParams &p, int cluster)
 template <class C>
 __global__ void __launch_bounds__(C::BLOCK) nm_probe_kernel(const KParams p)
 {
-#if NM_AB != 4
     static_assert(2 * C::LDS_BYTES > 160 * 1024, "the probe stands in for the block kernel only while LDS limits both to one workgroup per CU");
-#endif
     const int Q = p.cus, b = blockIdx.x;
     const int slot = (b & 7) + 8 * ((b >> 3) / Q); // (the block kernel's mapping; a padding workgroup takes the census and leaves)
     if (p.over && slot >= p.nslots) return;        // (clusters that do not exist have no census of their own)
@@ -2597,11 +2491,6 @@ enum : int { PH_INIT = 0, PH_BULK = 1, PH_VMC = 2, PH_HMC_START = 3, PH_HMC_STEP
 // evaluation; PH_ITER_END: the evaluation that closes an iterative position move of the EAM (its virial is not carried through the trials)
 
 // one workgroup = one replica for MOD moves
-#if NM_AB == 4
-#define NM_MIN_WAVES , 2 // (256-thread workgroups: without it the compiler takes the 512 registers a lone wave per SIMD may have)
-#else
-#define NM_MIN_WAVES
-#endif
 // The block of one workgroup: returns 0 when the replica's block completed and was stored, 1 when this workgroup had nothing to run (halted
 // queue, padding workgroup, a slot the re-issue mask leaves out, nm_eval), 2 when the block stopped on an error (reported; state untouched).
 // CENSUS: the launch's residency census is taken here (nm_cycles_kernel takes it itself, once, in front of its cycles).
@@ -2687,8 +2576,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             R.eval(have_need, pre_need, phase == PH_HMC_STEP, c_dtfm);
             // cluster-wide U, W of an energy evaluation — ONE exchange site; the kinetic energy rides along.
             if (!(st_before & fatal) && !(R.status & (ST_BOX_TOO_SMALL | ST_SYNC_TIMEOUT)))
-                mv2new = R.finish_sums(phase == PH_HMC_STEP ? R.psum[3] : 0.0,
-                                       phase == PH_HMC_START || p.eval_only ? -1 : phase == PH_INIT ? m : m + 1); // the move that follows this evaluation
+                mv2new = R.finish_sums(phase == PH_HMC_STEP ? R.psum[3] : 0.0);
         }
         skip_eval = false;
         have_need = false;
@@ -2847,7 +2735,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 if (!p.md_mode) nth += 1.0;
                 if constexpr (C::HALF) R.fr_hit = 0; // (the move's own evaluations decide; a start from forces that were out of range evaluates again: take_sums)
                 const uint32_t tag = R.draw_tag((uint32_t)m);
-                mv2_0 = R.hmc_velocities(q6(t), tag, R.gauss_for == m ? 1 : 0);
+                mv2_0 = R.hmc_velocities(q6(t), tag);
                 c_h = uniform(q6(dt)); // timestep %f
                 c_dtfm = 0.5 * c_h * p.ftm2v / p.mass;
                 R.wrap(); // run 0
@@ -2918,9 +2806,6 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         const unsigned long long ticks = wall_clock64() - t_entry;
         if (p.last_ticks) p.last_ticks[slot] = ticks;
         st[4] += (double)ticks; st[5] += R.same_xcd ? 1.0 : 0.0; st[6] += 1.0; st[7] += nth - nth_entry; st[9] = (double)C::MAXNB;
-#if NM_AB == 8 // dev probe (scripts/probe_rounds.py): when did this slot's block start (100 MHz ticks)
-        st[9] = (double)t_entry;
-#endif
 #ifdef NM_PROF
         if (p.prof) for (int q = 0; q < NM_PROF_SLOTS; ++q) p.prof[(size_t)slot * NM_PROF_SLOTS + q] += R.prof_acc[q];
 #endif
@@ -2929,7 +2814,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
 }
 
 template <class C>
-__global__ void __launch_bounds__(C::BLOCK NM_MIN_WAVES) nm_block_kernel(const KParams p)
+__global__ void __launch_bounds__(C::BLOCK) nm_block_kernel(const KParams p)
 {
     (void)nm_block_body<C>(p);
 }
@@ -3033,7 +2918,7 @@ __device__ __forceinline__ int exchange_row(int r, int nt, int row0, uint32_t se
 // there into its record of the cycle (p.rec): the writer thread the 17 columns, the box and the tag, each of the Q workgroups its own atoms' positions
 // from LDS.  The row's leader zeroes the counters and swaps slot2buf only behind its acquire on rowbar, so these reads come first.
 template <class C, bool REC = false>
-__global__ void __launch_bounds__(C::BLOCK NM_MIN_WAVES) nm_cycles_kernel(const KParams p0)
+__global__ void __launch_bounds__(C::BLOCK) nm_cycles_kernel(const KParams p0)
 {
     const int ncycles = p0.ncycles;
     const uint32_t step0 = p0.step, id0 = p0.launch_id;

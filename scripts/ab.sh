@@ -1,8 +1,8 @@
 #!/bin/bash
 # A/B/C... on the SAME box (boxes differ by several per cent): bench lines of the shipped libnm_hip.so ("default") and of every variant
 # given, alternating, REPS rounds; window and sustained rate of each.  A variant is either a library path relative to the repo root
-# (built with `make -C neuralmelting_amd/csrc ab<k>` or any -D flag) or an environment setting VAR=VALUE (e.g. NM_SKIN=0.37).
-#   CFG=C2 REPS=3 STEPS=10 WARM=5 EXTRA="--rows 4" scripts/ab.sh neuralmelting_amd/libnm_hip_ab3.so NM_PLAIN_GRANULES=0
+# (another checkout's libnm_hip.so copied into the tree, or a build with any -D flag) or an environment setting VAR=VALUE (e.g. NM_SKIN=0.37).
+#   CFG=C2 REPS=3 STEPS=10 WARM=5 EXTRA="--rows 4" scripts/ab.sh build/variants/libnm_hip_other.so NM_PLAIN_GRANULES=0
 for i in $(seq 1 ${REPS:-3}); do
   for var in default "$@"; do
     unset NM_HIP_LIB; pre=""

@@ -3,7 +3,7 @@ the kernel (nm_kernels.h NM_CHECK_INDEX: counted and redirected, never dereferen
 instantiations that use those arrays — 5^3 / 6^3 at 1, 2, 4, 8 workgroups per replica, 8^3 at 1 and 2, bulk and iterative position
 moves, HMC-heavy blocks whose rejected trajectories go back to the saved copies and the second list — and prints the count.
 
-    NM_HIP_LIB=$PWD/neuralmelting_amd/libnm_hip_prof.so python scripts/check_bounds.py
+    NM_HIP_LIB=$PWD/build/variants/libnm_hip_prof.so python scripts/check_bounds.py
 """
 import ctypes as C
 import os, sys

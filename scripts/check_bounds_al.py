@@ -4,7 +4,7 @@ and 4 workgroups per replica, bulk and iterative position moves, on bench's meta
 checked inside the kernel, every rebuilt list row checked against exact separations.  Prints the counts; all must be 0.  --el Cu / Ni: the
 n = 9 kernels; --sizes 4,5,6,8 adds the 4^3 byte-list kernels.
 
-    NM_HIP_LIB=$PWD/neuralmelting_amd/libnm_hip_prof.so python scripts/check_bounds_al.py [--el Al|Cu|Ni] [--sizes 5,6,8]
+    NM_HIP_LIB=$PWD/build/variants/libnm_hip_prof.so python scripts/check_bounds_al.py [--el Al|Cu|Ni] [--sizes 5,6,8]
 """
 import argparse
 import ctypes as C

@@ -7,7 +7,7 @@ RND=${ROUND:-r04}; export ROUND=$RND; O=gpurun_out/final_$RND; mkdir -p $O
 if [ $PART = a ]; then
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-NM_HIP_LIB=$PWD/neuralmelting_amd/libnm_hip_prof.so timeout -k 10 400 python scripts/check_bounds.py > $O/check_bounds.txt 2>&1; echo "bounds rc=$?"; tail -1 $O/check_bounds.txt
+NM_HIP_LIB=$PWD/build/variants/libnm_hip_prof.so timeout -k 10 400 python scripts/check_bounds.py > $O/check_bounds.txt 2>&1; echo "bounds rc=$?"; tail -1 $O/check_bounds.txt
 for cfg in "C2 64" "C3 32" "C4 64" "C5 128" "runsh 1024"; do
   set -- $cfg
   timeout -k 10 300 bash scripts/profile_round.sh $1 $2 $C > $O/prof_$1.log 2>&1; echo "profile $1 rc=$?"

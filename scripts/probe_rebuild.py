@@ -4,7 +4,7 @@ evaluations: 0 entry, 3 conversion issued, 4 past the barrier, 5 tests done, 6 s
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ['NM_HIP_LIB'] = os.path.join(ROOT, 'neuralmelting_amd', 'libnm_hip_exp_rb.so')
+os.environ['NM_HIP_LIB'] = os.path.join(ROOT, 'build', 'variants', 'libnm_hip_exprb.so')
 import numpy as np
 import neuralmelting_amd as nm
 from neuralmelting_amd import lattice, _lib
