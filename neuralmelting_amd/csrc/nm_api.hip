@@ -250,6 +250,25 @@ void fill_params(const nm_ctx *c, KParams &p)
 unsigned int nm_grid(int nslots, int q) { return q == 1 ? (unsigned int)nslots : (unsigned int)(8 * q * ((nslots + 7) / 8)); }
 size_t census_words(int nslots) { return 1 + (size_t)8 * ((nslots + 7) / 8); } // the grid's counter + one per cluster
 
+// The production form of the block (nm_block_body's PLAIN) is instantiated for the 4^3 rows, kind 0, whose NMAX the static_assert above
+// ties to 256: block and fused kernels.  The 864- and 2048-atom rows keep the general form alone (build time).
+template <class C> constexpr bool has_plain = C::NMAX == 256;
+// ... and runs exactly where the call asks for nothing it leaves out: bulk position moves, no RNG tape, no trace, not nm_run_md, no forces
+// out of nm_eval.  NM_PLAIN_KERNELS=0 forces the general form (tests, A/B); both forms compute the same bits.
+bool plain_call(const KParams &p)
+{
+    const char *e = std::getenv("NM_PLAIN_KERNELS");
+    if (e && !std::strcmp(e, "0")) return false;
+    return p.bulk && !p.tape && !p.trace && !p.md_mode && !p.evalF;
+}
+
+template <class C, bool PLAIN>
+hipError_t launch_block_form(const nm_ctx *c, const KParams &p)
+{
+    hipLaunchKernelGGL((nm_block_kernel<C, PLAIN>), dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
+    return hipGetLastError();
+}
+
 template <class C>
 hipError_t launch_block(const nm_ctx *c, const KParams &p)
 {
@@ -258,8 +277,9 @@ hipError_t launch_block(const nm_ctx *c, const KParams &p)
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(nm_block_kernel<C>, dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
-    return hipGetLastError();
+    if constexpr (has_plain<C>)
+        if (plain_call(p)) return launch_block_form<C, true>(c, p);
+    return launch_block_form<C, false>(c, p);
 }
 
 // The census counters only grow (KParams::census_base): zero them and the bases.  At creation, around the residency probes, after a
@@ -284,7 +304,14 @@ hipError_t launch_probe(const nm_ctx *c, KParams p)
 
 // dynamic LDS above 64 KiB has to be requested per kernel
 template <class C>
-hipError_t request_lds() { return hipFuncSetAttribute((const void *)nm_block_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES); }
+hipError_t request_lds()
+{
+    if constexpr (has_plain<C>) {
+        const hipError_t e = hipFuncSetAttribute((const void *)nm_block_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
+        if (e != hipSuccess) return e;
+    }
+    return hipFuncSetAttribute((const void *)nm_block_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
+}
 
 // workgroups of the block kernel one CU admits (LDS, registers)
 template <class C>
@@ -296,13 +323,20 @@ int blocks_per_cu()
     return n;
 }
 
+template <class C, bool REC, bool PLAIN>
+hipError_t launch_cycles_form(const nm_ctx *c, const KParams &p)
+{
+    hipError_t e = hipFuncSetAttribute((const void *)nm_cycles_kernel<C, REC, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((nm_cycles_kernel<C, REC, PLAIN>), dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
+    return hipGetLastError();
+}
 template <class C, bool REC>
 hipError_t launch_cycles_rec(const nm_ctx *c, const KParams &p)
 {
-    hipError_t e = hipFuncSetAttribute((const void *)nm_cycles_kernel<C, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((nm_cycles_kernel<C, REC>), dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
-    return hipGetLastError();
+    if constexpr (has_plain<C>)
+        if (plain_call(p)) return launch_cycles_form<C, REC, true>(c, p);
+    return launch_cycles_form<C, REC, false>(c, p);
 }
 // the recording instantiation where the launch has a ring (KParams::rec), the outputs-off one elsewhere: the same configurations have both
 template <class C>

@@ -315,7 +315,9 @@ __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t t
 // none of them ordered — seen once, in round 3, as a stale velocity in a block's closing kinetic-energy sum.
 #define NM_FOR_OWN(i) for (int i = a0 + tid; i < a1; i += BLOCK)
 
-template <class C>
+// PLAIN: the form the production path runs (nm_block_body): no RNG tape, no iterative position move.  The tape members and the members of the
+// iterative move are then referenced nowhere and take no registers; they stay declared, so that the layout is the general form's (layout_pad below).
+template <class C, bool PLAIN = false>
 struct Replica {
     using IdxT = typename C::IdxT;
     static constexpr int BLOCK = C::BLOCK, TPA = C::TPA, NW = C::NW, G = C::G, NMAX = C::NMAX, MAXNB = C::MAXNB;
@@ -422,30 +424,33 @@ struct Replica {
             cnts.g = (unsigned short *)(a + 3 * (size_t)NMAX);
             NM_BOUND(x0s, NMAX); NM_BOUND(y0s, NMAX); NM_BOUND(z0s, NMAX); NM_BOUND(cnts, NMAX); NM_BOUND(nbr, C::NBR_G_ELEMS);
         }
-        if (p.tape) { tape = p.tape + p.tape_off[slot]; tlen = p.tape_off[slot + 1] - p.tape_off[slot]; }
+        if constexpr (!PLAIN)
+            if (p.tape) { tape = p.tape + p.tape_off[slot]; tlen = p.tape_off[slot + 1] - p.tape_off[slot]; }
     }
 
     // ------------------------------------------------------------------ random draws
     __device__ __forceinline__ double draw_scalar(uint32_t stream, uint32_t m, uint32_t index)
     {
-        if (tape) { // test-only: uniforms recorded from the reference's np.random stream
-            double v = 2.0;
-            if (tpos < tlen) v = tape[tpos]; else status |= ST_TAPE_EXHAUSTED;
-            ++tpos;
-            return v;
-        }
+        if constexpr (!PLAIN)
+            if (tape) { // test-only: uniforms recorded from the reference's np.random stream
+                double v = 2.0;
+                if (tpos < tlen) v = tape[tpos]; else status |= ST_TAPE_EXHAUSTED;
+                ++tpos;
+                return v;
+            }
         uint32_t o[4];
         philox4x32_10(index, stream, m, p.step, p.seed, (uint32_t)gslot, o);
         return u01(o[0], o[1]);
     }
     __device__ __forceinline__ uint32_t draw_tag(uint32_t m)
     {
-        if (tape) { // np.random.randint(1, 2**16), remcmc:482,603
-            uint32_t v = 0;
-            if (tpos < tlen) v = (uint32_t)(tape[tpos] * 65536.0); else status |= ST_TAPE_EXHAUSTED; // randint/65536
-            ++tpos;
-            return v;
-        }
+        if constexpr (!PLAIN)
+            if (tape) { // np.random.randint(1, 2**16), remcmc:482,603
+                uint32_t v = 0;
+                if (tpos < tlen) v = (uint32_t)(tape[tpos] * 65536.0); else status |= ST_TAPE_EXHAUSTED; // randint/65536
+                ++tpos;
+                return v;
+            }
         return m;
     }
     // remcmc:487-500: metcrit = exp(-c); +inf -> reject without drawing; else accept iff u <= min(1, metcrit)
@@ -2161,9 +2166,9 @@ struct Replica {
     }
 };
 
-template <class C>
+template <class C, bool PLAIN>
 template <bool WANT_E>
-__device__ __forceinline__ void Replica<C>::pair_loop_sc(double invL, double &eacc, double &wacc, double &nacc, double &kacc, bool fuse, double dtfm, double h)
+__device__ __forceinline__ void Replica<C, PLAIN>::pair_loop_sc(double invL, double &eacc, double &wacc, double &nacc, double &kacc, bool fuse, double dtfm, double h)
 {
     const int g = tid / TPA, sub = tid - g * TPA;
     const double rc2 = p.rc * p.rc, a2 = p.sc_a2, eps = p.sc_eps, cc = p.sc_c, mhL = -0.5 * L;
@@ -2494,7 +2499,12 @@ enum : int { PH_INIT = 0, PH_BULK = 1, PH_VMC = 2, PH_HMC_START = 3, PH_HMC_STEP
 // The block of one workgroup: returns 0 when the replica's block completed and was stored, 1 when this workgroup had nothing to run (halted
 // queue, padding workgroup, a slot the re-issue mask leaves out, nm_eval), 2 when the block stopped on an error (reported; state untouched).
 // CENSUS: the launch's residency census is taken here (nm_cycles_kernel takes it itself, once, in front of its cycles).
-template <class C, bool CENSUS = true>
+// PLAIN: the production form of the block.  What only tests, diagnostics and the reference modes ask for is compiled out instead of branched
+// around: the RNG tape (p.tape), the per-move trace (p.trace), the plain NVE run (p.md_mode), nm_eval's force output (p.evalF) and the whole
+// iterative position move (!p.bulk).  The launchers (nm_api.hip) pick it exactly when the call asks for none of them; the general form computes
+// the same bits.  The function is register-allocated as a whole, and these branches cost the hot loops 20 spilled vector registers and a fifth
+// of the instructions.  Fault injection, the census, stats and status reporting are in both forms.
+template <class C, bool CENSUS = true, bool PLAIN = false>
 __device__ __forceinline__ int nm_block_body(const KParams &p)
 {
     constexpr bool first = CENSUS;
@@ -2515,7 +2525,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     }
     const int buf = p.slot2buf[slot];
     const int tid = threadIdx.x;
-    Replica<C> R(p, slot, qq);
+    Replica<C, PLAIN> R(p, slot, qq);
     const bool writer = (tid == 0 && qq == 0); // one workgroup of the cluster writes the replica's results
     const int N = p.N;
     // status[] holds the bits of the LAST launch that ran: the writer, the only thread that ever reports for this slot, clears it first
@@ -2600,14 +2610,15 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                     double *st = p.stats + NM_STATS_COLS * (size_t)slot;
                     st[0] += R.st_evals; st[1] += R.st_rebuilds; st[2] += R.st_eevals; st[3] += R.st_pairs;
                 }
-                if (p.evalF) // every workgroup holds the forces of its own atoms
-                    for (int a = 3 * R.a0 + tid; a < 3 * R.a1; a += BLOCK) {
-                        const int i = a / 3, c = a - 3 * i;
-                        p.evalF[(size_t)slot * 3 * N + a] = (c == 0 ? R.fx : c == 1 ? R.fy : R.fz)[i];
-                    }
+                if constexpr (!PLAIN)
+                    if (p.evalF) // every workgroup holds the forces of its own atoms
+                        for (int a = 3 * R.a0 + tid; a < 3 * R.a1; a += BLOCK) {
+                            const int i = a / 3, c = a - 3 * i;
+                            p.evalF[(size_t)slot * 3 * N + a] = (c == 0 ? R.fx : c == 1 ? R.fy : R.fz)[i];
+                        }
                 return 1;
             }
-        } else if (phase == PH_ITER_END) { // iter_position_mc of the EAM: U, W of the final configuration are in (the reference's last `run 0`)
+        } else if (!PLAIN && phase == PH_ITER_END) { // iter_position_mc of the EAM: U, W of the final configuration are in (the reference's last `run 0`)
             if (p.trace && writer) {
                 double *tr = p.trace + ((size_t)slot * p.mod + m) * 4;
                 tr[0] = 3.0; tr[1] = c_vol; tr[2] = c_volnew; tr[3] = R.U;
@@ -2659,7 +2670,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             bool out_of_range = false;
             if constexpr (C::HALF) out_of_range = R.fr_hit != 0;
             if (out_of_range) crit = __builtin_huge_val();
-            if (p.md_mode) { // plain NVE run (init_sample -is, remcmc:421-425): nothing to accept.  Forces out of range stop it: the replica
+            if (!PLAIN && p.md_mode) { // plain NVE run (init_sample -is, remcmc:421-425): nothing to accept.  Forces out of range stop it: the replica
                 acc = true;  // keeps the state it started from and the host reports the reason (nm_run_md returns NM_ERR_STATE)
                 if (out_of_range) R.status |= ST_FORCE_RANGE;
             } else {
@@ -2670,10 +2681,11 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             branch = 2.0; move_done = true;
         }
         if (move_done) {
-            if (p.trace && writer) {
-                double *tr = p.trace + ((size_t)slot * p.mod + m) * 4;
-                tr[0] = branch; tr[1] = acc ? 1.0 : 0.0; tr[2] = crit; tr[3] = R.U;
-            }
+            if constexpr (!PLAIN)
+                if (p.trace && writer) {
+                    double *tr = p.trace + ((size_t)slot * p.mod + m) * 4;
+                    tr[0] = branch; tr[1] = acc ? 1.0 : 0.0; tr[2] = crit; tr[3] = R.U;
+                }
             ++m;
         }
 
@@ -2682,8 +2694,8 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         bool pending = false;
         while (m < p.mod && !pending) {
             PROF_BEGIN();
-            const double roll = p.md_mode ? 2.0 : R.draw_scalar(S_ROLL, (uint32_t)m, 0);
-            if (roll <= p.ppos && p.bulk) { // bulk_position_mc, remcmc:477-484
+            const double roll = (!PLAIN && p.md_mode) ? 2.0 : R.draw_scalar(S_ROLL, (uint32_t)m, 0);
+            if (roll <= p.ppos && (PLAIN || p.bulk)) { // bulk_position_mc, remcmc:477-484
                 ntp += 1.0;
                 R.save(false);
                 U0 = R.U; W0 = R.W; c_pe = R.U / et;
@@ -2701,21 +2713,23 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 R.wrap();
                 phase = PH_BULK; pending = true;
                 PROF_END(10);
-            } else if (roll <= p.ppos) { // iter_position_mc: local energy differences, no full evaluation
-                double c2 = 0.0;
-                const int na = R.iter_pmc((uint32_t)m, et, dx, ntp, nap, c2);
-                if (__builtin_amdgcn_readfirstlane(R.status) & fatal) break; // (its exchange of energy differences failed)
-                if constexpr (C::EAM) { // close the move with a full evaluation (c_vol, c_volnew are free during a position move)
-                    c_vol = (double)na; c_volnew = c2;
-                    phase = PH_ITER_END; pending = true;
-                } else {
-                    if (p.trace && writer) {
-                        double *tr = p.trace + ((size_t)slot * p.mod + m) * 4;
-                        tr[0] = 3.0; tr[1] = (double)na; tr[2] = c2; tr[3] = R.U;
+            } else if (!PLAIN && roll <= p.ppos) { // iter_position_mc: local energy differences, no full evaluation
+                if constexpr (!PLAIN) { // (not instantiated for the production form)
+                    double c2 = 0.0;
+                    const int na = R.iter_pmc((uint32_t)m, et, dx, ntp, nap, c2);
+                    if (__builtin_amdgcn_readfirstlane(R.status) & fatal) break; // (its exchange of energy differences failed)
+                    if constexpr (C::EAM) { // close the move with a full evaluation (c_vol, c_volnew are free during a position move)
+                        c_vol = (double)na; c_volnew = c2;
+                        phase = PH_ITER_END; pending = true;
+                    } else {
+                        if (p.trace && writer) {
+                            double *tr = p.trace + ((size_t)slot * p.mod + m) * 4;
+                            tr[0] = 3.0; tr[1] = (double)na; tr[2] = c2; tr[3] = R.U;
+                        }
+                        ++m;
                     }
-                    ++m;
+                    PROF_END(13);
                 }
-                PROF_END(13);
             } else if (roll <= p.ppos + p.pvol) { // volume_mc, remcmc:552-573
                 ntv += 1.0;
                 c_boxl = R.L; c_vol = uniform(pow(c_boxl, 3.0));
@@ -2732,7 +2746,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 phase = PH_VMC; pending = true;
                 PROF_END(11);
             } else { // hamiltonian_mc, remcmc:598-608
-                if (!p.md_mode) nth += 1.0;
+                if (PLAIN || !p.md_mode) nth += 1.0;
                 if constexpr (C::HALF) R.fr_hit = 0; // (the move's own evaluations decide; a start from forces that were out of range evaluates again: take_sums)
                 const uint32_t tag = R.draw_tag((uint32_t)m);
                 mv2_0 = R.hmc_velocities(q6(t), tag);
@@ -2799,7 +2813,8 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         r[0] = (ntp > 0.0) ? (float)nap / (float)ntp : 0.0f;
         r[1] = (ntv > 0.0) ? (float)nav / (float)ntv : 0.0f;
         r[2] = (nth > 0.0) ? (float)nah / (float)nth : 0.0f;
-        if (R.tape && R.tpos > R.tlen) R.status |= ST_TAPE_EXHAUSTED;
+        if constexpr (!PLAIN)
+            if (R.tape && R.tpos > R.tlen) R.status |= ST_TAPE_EXHAUSTED;
         report_status(p, slot, R.status, false);
         double *st = p.stats + NM_STATS_COLS * (size_t)slot;
         st[0] += R.st_evals; st[1] += R.st_rebuilds; st[2] += R.st_eevals; st[3] += R.st_pairs;
@@ -2813,10 +2828,10 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     return 0;
 }
 
-template <class C>
+template <class C, bool PLAIN = false>
 __global__ void __launch_bounds__(C::BLOCK) nm_block_kernel(const KParams p)
 {
-    (void)nm_block_body<C>(p);
+    (void)nm_block_body<C, true, PLAIN>(p);
 }
 
 // Launch order for grids with more one-workgroup replicas than the chip holds at once (the reference's run.sh setting: 1024 replicas
@@ -2917,7 +2932,7 @@ __device__ __forceinline__ int exchange_row(int r, int nt, int row0, uint32_t se
 // REC (nm_run_cycles_recorded): behind a block that completed, and in front of the row barrier, every slot writes what nm_snapshot would have taken
 // there into its record of the cycle (p.rec): the writer thread the 17 columns, the box and the tag, each of the Q workgroups its own atoms' positions
 // from LDS.  The row's leader zeroes the counters and swaps slot2buf only behind its acquire on rowbar, so these reads come first.
-template <class C, bool REC = false>
+template <class C, bool REC = false, bool PLAIN = false>
 __global__ void __launch_bounds__(C::BLOCK) nm_cycles_kernel(const KParams p0)
 {
     const int ncycles = p0.ncycles;
@@ -2949,7 +2964,7 @@ __global__ void __launch_bounds__(C::BLOCK) nm_cycles_kernel(const KParams p0)
         const KParams &p = pc;                       // (this cycle's copy)
         pc.step = step0 + (uint32_t)cyc;
         pc.launch_id = id0 + (uint32_t)cyc; // (distinguishes the hand-over granules of successive blocks)
-        const int rc = nm_block_body<C, false>(pc);
+        const int rc = nm_block_body<C, false, PLAIN>(pc);
         // the workgroup's place in the grid, worked out HERE from opaque copies of its indices: computed once in front of the loop, these values (and
         // whatever the compiler derives from them for the code below) would be alive all the way through every block
         int b = blockIdx.x, tid = threadIdx.x;
