@@ -52,6 +52,30 @@ const char *nm_distr_last_error(void);
 int nm_distr_angles(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int abins,
                     const double *cos_edges, uint64_t *adf);
 
+/* Static structure factor on the reciprocal lattice of each sample's box: the quantity lammps_distr.py names .q.npy / .sf.npy
+ * but leaves switched off (its Fourier transform of g(r) ends at r = l/2 and cannot resolve a Bragg peak).  Definition (the
+ * build's own), for sample s with N = natoms atoms and the cubic box L = box[s]:
+ *   coordinates  u_a = (double)pos[a] / (double)L per component, in float64; the caller need not wrap them;
+ *   vectors      every integer triple (h, k, l) with 1 <= n2 = h*h + k*k + l*l <= qmax*qmax  (q = 2 pi (h, k, l) / L);
+ *   density mode rho(hkl) = sum_a exp(-2 pi i (h u_ax + k u_ay + l u_az)), the phases h u, k u, l u each reduced in turns (the
+ *                nearest integer subtracted, in float64) before any sine or cosine, so that the accuracy depends on neither
+ *                qmax nor unwrapped coordinates beyond the bound below;
+ *   S(hkl)       = |rho(hkl)|^2 / N in float64; S(-q) = S(q), so one half space is evaluated;
+ *   sf_sum[s][n2] the sum of S(hkl) over all vectors of the full shell h*h + k*k + l*l = n2 (twice the half-space sum);
+ *   sf_max[s][n2] the maximum of S(hkl) over the shell: N on a Bragg peak of a perfect crystal, O(1) in a liquid;
+ *   empty        index 0 and the shells without a vector (n2 = 4^a (8 b + 7)) hold 0 in both.
+ * Error bound: every unit-magnitude term carries at most e = (6 pi qmax max|u| + 16) 2^-53 (the rounded products h u; the 16
+ * covers the three sines and cosines and the two complex products), so |S - exact| <= 2 N e for every vector.
+ * The result is the same bit for bit on every call: float64 accumulators in a fixed order, integer shell sums, no
+ * floating-point atomics.
+ * pos[ns][natoms][3], box[ns] float32; sf_sum, sf_max [ns][qmax*qmax + 1] float64.  Either output may be NULL (it is then not
+ * written), but not both.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_sfactor:".  NM_ERR_ARG,
+ * checked before the device is looked for and with the outputs left untouched, for: ns < 0, natoms outside 1..4095, qmax
+ * outside 1..32, a box that is not finite and positive, a null pos or box, both outputs null, a bad device ordinal.
+ * ns == 0 is NM_OK. */
+int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const float *box, int qmax, double *sf_sum, double *sf_max);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1716,6 +1716,61 @@ int nm_distr_angles(int device, int ns, int natoms, const float *pos, const floa
     return NM_OK;
 }
 
+int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const float *box, int qmax, double *sf_sum, double *sf_max)
+{
+    if (ns < 0 || !pos || !box) return dfail(NM_ERR_ARG, "nm_distr_sfactor: bad argument");
+    if (!sf_sum && !sf_max) return dfail(NM_ERR_ARG, "nm_distr_sfactor: sf_sum and sf_max are both null");
+    if (natoms < 1 || natoms > 4095) return dfail(NM_ERR_ARG, "nm_distr_sfactor: natoms must lie in 1..4095");
+    if (qmax < 1 || qmax > SF_QMAX) return dfail(NM_ERR_ARG, "nm_distr_sfactor: qmax must lie in 1..32");
+    for (int s = 0; s < ns; ++s)
+        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return dfail(NM_ERR_ARG, "nm_distr_sfactor: a box is not finite and positive");
+    if (device < 0) return dfail(NM_ERR_ARG, "nm_distr_sfactor: device ordinal out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_sfactor: no HIP device available");
+    if (device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_sfactor: device ordinal out of range");
+    if (ns == 0) return NM_OK;
+    // the work items (nm_distr.h): every (h >= 0, k >= 0, l0) whose chunk l0 .. l0 + SF_LB - 1 reaches into the sphere, l0 slowest
+    std::vector<unsigned int> items;
+    for (int l0 = 0; l0 <= qmax; l0 += SF_LB)
+        for (int h = 0; h <= qmax; ++h)
+            for (int k = 0; k <= qmax; ++k)
+                if (h * h + k * k + l0 * l0 <= qmax * qmax) items.push_back(sf_item(h, k, l0));
+    const int nitems = (int)items.size();
+    const size_t nsh = (size_t)qmax * qmax + 1;
+    const int chunk = 4096; // samples per launch, as nm_distr_histograms
+    const int cs = ns < chunk ? ns : chunk;
+    float *d_pos = nullptr, *d_box = nullptr;
+    unsigned int *d_it = nullptr;
+    double *d_sum = nullptr, *d_max = nullptr;
+    auto release = [&]() { hipFree(d_pos); hipFree(d_box); hipFree(d_it); hipFree(d_sum); hipFree(d_max); };
+#define SCHK(call)                                                                                     \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) { release(); return dfail(NM_ERR_HIP, std::string("nm_distr_sfactor: ") + #call + ": " + hipGetErrorString(e_)); } \
+    } while (0)
+    SCHK(hipSetDevice(device));
+    const size_t lds = sf_lds_bytes(qmax); // below the 64 KiB a kernel gets without asking
+    SCHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
+    SCHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
+    SCHK(hipMalloc((void **)&d_it, (size_t)nitems * sizeof(unsigned int)));
+    if (sf_sum) SCHK(hipMalloc((void **)&d_sum, (size_t)cs * nsh * sizeof(double)));
+    if (sf_max) SCHK(hipMalloc((void **)&d_max, (size_t)cs * nsh * sizeof(double)));
+    SCHK(hipMemcpy(d_it, items.data(), (size_t)nitems * sizeof(unsigned int), hipMemcpyHostToDevice));
+    for (int s0 = 0; s0 < ns; s0 += cs) {
+        const int n = (ns - s0) < cs ? (ns - s0) : cs;
+        SCHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
+        SCHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nm_sfac_kernel, dim3(n), dim3(SF_BLOCK), lds, 0, natoms, d_pos, d_box, qmax, nitems, d_it, d_sum, d_max);
+        SCHK(hipGetLastError());
+        SCHK(hipDeviceSynchronize());
+        if (sf_sum) SCHK(hipMemcpy(sf_sum + (size_t)s0 * nsh, d_sum, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
+        if (sf_max) SCHK(hipMemcpy(sf_max + (size_t)s0 * nsh, d_max, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    release();
+#undef SCHK
+    return NM_OK;
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------

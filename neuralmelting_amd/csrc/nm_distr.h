@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nm_math.h"
 
 namespace nm {
 
@@ -385,6 +386,135 @@ nm_adf_kernel(int natoms, const float *__restrict__ pos, const float *__restrict
         }
     }
     flush();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Static structure factor (include/nm_distr.h, nm_distr_sfactor): S(hkl) = |sum_a exp(-2 pi i (h, k, l) . u_a)|^2 / N on the
+// reciprocal lattice of each sample's box, summed and maximised over the shells h^2 + k^2 + l^2 = n2.
+//
+// One workgroup takes one sample.  A work item is (h >= 0, k >= 0, l0): a thread owns the up to 4 * SF_LB vectors
+// (h, +-k, +-l), l = l0 .. l0 + SF_LB - 1, that lie in the half space (h > 0, or h = 0 and k > 0, or h = k = 0 and l > 0) and
+// inside the sphere; the host lists the items that hold at least one, l0 slowest, so that a wave's lanes share l0.  The atoms
+// are walked in tiles of SF_TILE: for a tile the workgroup builds the per-axis tables E(m) = exp(-2 pi i m u), m = 0 .. qmax,
+// in LDS (the phase m u reduced to [-1/2, 1/2] turns in float64 first; the z table holds (cos, sin) instead), then every
+// thread adds the tile to its float64 accumulators.  With W = E_x(h) E_y(+-k) (negative k is the conjugate) the two sums
+//   P(l) = sum_a W cos(2 pi l u_z),  Q(l) = sum_a W sin(2 pi l u_z)    give   rho(h, +-k, +l) = P - i Q,  rho(h, +-k, -l) = P + i Q:
+// 8 real multiply-adds per atom for 4 vectors, where the direct product takes 8 for one.  The x and y factors are one LDS
+// gather per atom and item, the z factors broadcasts.  A sample of 4095 atoms needs the LDS of one tile.
+//
+// Shell reduction: S < 2^12 is split into two integers, S 2^28 = hi + lo 2^-52 (lo truncated at 2^-80), which are added to the
+// shell's two 64-bit LDS counters with integer atomics; the maximum is an integer maximum over the bit patterns (S >= 0).
+// Integer addition is associative, so the sums are exact to 2^-80 per vector and the same bits in whatever order the lanes
+// arrive: what a fixed reduction order gives, without one.  A shell of the sphere holds fewer than 2^10 vectors, so neither
+// counter can overflow (hi < 2^40, lo < 2^52 per vector).  The outputs are written with ordinary stores.
+constexpr int SF_BLOCK = 1024;
+constexpr int SF_TILE = 16;     // atoms per table tile
+constexpr int SF_LB = 4;        // consecutive l of a work item
+constexpr int SF_QMAX = 32;
+
+// table entries per atom and axis: m = 0 .. qmax, padded with zeros so that every item reads a whole chunk of l
+__host__ __device__ inline int sf_row(int qmax) { return (qmax / SF_LB + 1) * SF_LB; }
+
+__host__ __device__ inline size_t sf_lds_bytes(int qmax) // 52,632 B at qmax 32
+{
+    return (size_t)3 * SF_TILE * sf_row(qmax) * sizeof(double2) + (size_t)3 * SF_TILE * sizeof(double)
+         + (size_t)3 * (qmax * qmax + 1) * sizeof(unsigned long long);
+}
+
+__host__ __device__ inline unsigned int sf_item(int h, int k, int l0) { return (unsigned int)h | (unsigned int)k << 8 | (unsigned int)l0 << 16; }
+
+__device__ __forceinline__ void sf_add(unsigned long long *shi, unsigned long long *slo, unsigned long long *smx, int n2, double S)
+{
+    const double x = S * 0x1p28;
+    const unsigned long long hi = (unsigned long long)x;
+    const unsigned long long lo = (unsigned long long)((x - (double)hi) * 0x1p52); // x - hi is exact
+    atomicAdd(&shi[n2], hi);
+    atomicAdd(&slo[n2], lo);
+    atomicMax(&smx[n2], (unsigned long long)__double_as_longlong(S));
+}
+
+__global__ void __launch_bounds__(SF_BLOCK)
+nm_sfac_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, int qmax, int nitems,
+               const unsigned int *__restrict__ items, double *__restrict__ sf_sum, double *__restrict__ sf_max)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int row = sf_row(qmax), q2 = qmax * qmax, nsh = q2 + 1;
+    double2 *ex = (double2 *)smem, *ey = ex + SF_TILE * row, *ez = ey + SF_TILE * row;
+    double *ut = (double *)(ez + SF_TILE * row);                       // reduced coordinates of the tile, [atom][axis]
+    unsigned long long *shi = (unsigned long long *)(ut + 3 * SF_TILE), *slo = shi + nsh, *smx = slo + nsh;
+    const double L = (double)box[s], dn = (double)natoms;
+    const float *ps = pos + (size_t)s * natoms * 3;
+    for (int k = tid; k < 3 * nsh; k += SF_BLOCK) shi[k] = 0ull;         // all three arrays; the first barrier below orders it
+    for (int i0 = 0; i0 < nitems; i0 += SF_BLOCK) {
+        const bool have = i0 + tid < nitems;
+        const unsigned int it = have ? items[i0 + tid] : 0u;
+        const int h = (int)(it & 255u), k = (int)((it >> 8) & 255u), l0 = (int)(it >> 16);
+        const bool work = __ballot(have) != 0ull;                        // a wave without an item only builds tables
+        double acc[2][SF_LB][4];                                         // [+k, -k][l - l0][Re P, Im P, Re Q, Im Q]
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int j = 0; j < SF_LB; ++j) { acc[g][j][0] = 0.0; acc[g][j][1] = 0.0; acc[g][j][2] = 0.0; acc[g][j][3] = 0.0; }
+        for (int a0 = 0; a0 < natoms; a0 += SF_TILE) {
+            const int na = natoms - a0 < SF_TILE ? natoms - a0 : SF_TILE;
+            __syncthreads();                                             // the previous tile's readers are done
+            if (tid < 3 * na) ut[tid] = (double)ps[3 * a0 + tid] / L;
+            __syncthreads();
+            for (int e = tid; e < 3 * na * row; e += SF_BLOCK) {         // consecutive lanes, consecutive m: conflict-free stores
+                const int ad = e / row, m = e - ad * row;                // ad = 3 * atom + axis
+                const int ai = ad / 3, d = ad - 3 * ai;
+                double2 v = make_double2(0.0, 0.0);
+                if (m <= qmax) {
+                    const double x = (double)m * ut[ad];
+                    double sn, cs;
+                    sincos_turn(x - rint(x), sn, cs);                    // the difference is exact
+                    v = d == 2 ? make_double2(cs, sn) : make_double2(cs, -sn);
+                }
+                (d == 0 ? ex : d == 1 ? ey : ez)[ai * row + m] = v;
+            }
+            __syncthreads();
+            if (!work) continue;
+            for (int ai = 0; ai < na; ++ai) {
+                const double2 X = ex[ai * row + h], Y = ey[ai * row + k];
+                const double A = X.x * Y.x, B = X.y * Y.y, C = X.x * Y.y, D = X.y * Y.x;
+                const double wr0 = A - B, wi0 = C + D;                   // E_x(h) E_y(k)
+                const double wr1 = A + B, wi1 = D - C;                   // E_x(h) E_y(-k)
+                const double2 *zr = ez + ai * row + l0;
+#pragma unroll
+                for (int j = 0; j < SF_LB; ++j) {
+                    const double2 Z = zr[j];
+                    acc[0][j][0] = fma(wr0, Z.x, acc[0][j][0]); acc[0][j][1] = fma(wi0, Z.x, acc[0][j][1]);
+                    acc[0][j][2] = fma(wr0, Z.y, acc[0][j][2]); acc[0][j][3] = fma(wi0, Z.y, acc[0][j][3]);
+                    acc[1][j][0] = fma(wr1, Z.x, acc[1][j][0]); acc[1][j][1] = fma(wi1, Z.x, acc[1][j][1]);
+                    acc[1][j][2] = fma(wr1, Z.y, acc[1][j][2]); acc[1][j][3] = fma(wi1, Z.y, acc[1][j][3]);
+                }
+            }
+        }
+        if (have) {
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                if (g == 1 && !(h > 0 && k > 0)) continue;               // (h, -k, l): not for k = 0; for h = 0 it mirrors (0, k, -l)
+#pragma unroll
+                for (int j = 0; j < SF_LB; ++j) {
+                    const int l = l0 + j, n2 = h * h + k * k + l * l;
+                    if (n2 < 1 || n2 > q2) continue;
+                    const double pr = acc[g][j][0], pi = acc[g][j][1], qr = acc[g][j][2], qi = acc[g][j][3];
+                    double re = pr + qi, im = pi - qr;                   // rho(+l) = P - i Q
+                    sf_add(shi, slo, smx, n2, (re * re + im * im) / dn);
+                    if (l > 0 && (h | k)) {                              // rho(-l) = P + i Q; (0, 0, -l) mirrors (0, 0, l)
+                        re = pr - qi; im = pi + qr;
+                        sf_add(shi, slo, smx, n2, (re * re + im * im) / dn);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int n2 = tid; n2 < nsh; n2 += SF_BLOCK) {                       // S(-q) = S(q): the full shell's sum is twice the half's
+        if (sf_sum) sf_sum[(size_t)s * nsh + n2] = 2.0 * ((double)shi[n2] * 0x1p-28 + (double)slo[n2] * 0x1p-80);
+        if (sf_max) sf_max[(size_t)s * nsh + n2] = __longlong_as_double((long long)smx[n2]);
+    }
 }
 
 } // namespace nm

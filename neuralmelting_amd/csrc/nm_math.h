@@ -52,4 +52,20 @@ NM_HD void sincos_2pi(double t, double &sn, double &cs)
     if ((n + 1) & 2) cs = -cs;
 }
 
+// sin(2 pi x) and cos(2 pi x) for a phase in turns, |x| <= 1/2 (the structure factor's reduced phases, nm_distr.h).  The quadrant
+// is taken off in turns, where it is exact (x and q/4 are multiples of ulp(x) and the difference is no larger than x), so only
+// f * 2 pi rounds (|f| <= 1/8: at most 1.1 * 2^-53 absolute, the constant's own error included) before the evaluation above,
+// whose second reduction then finds nothing to subtract.
+NM_HD void sincos_turn(double x, double &sn, double &cs)
+{
+    const double q = rint(4.0 * x);                 // -2 .. 2
+    const double f = fma(-0.25, q, x);
+    double s, c;
+    sincos_2pi(f * 6.28318530717958647692e+00, s, c); // |t| <= pi/4 (+ an ulp): the evaluation holds for negative t as well
+    const int n = (int)q & 3;
+    sn = (n & 1) ? c : s; cs = (n & 1) ? s : c;
+    if (n & 2) sn = -sn;
+    if ((n + 1) & 2) cs = -cs;
+}
+
 } // namespace nm

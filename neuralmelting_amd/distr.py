@@ -5,10 +5,13 @@ lammps_parse.py, computes the per-sample radial distribution over the 27 periodi
 and the 3-D histogram of pair displacement vectors (calculate_cdf, distr:161-171) — here one kernel launch over all
 samples (include/nm_distr.h) instead of a Dask/joblib map of numpy calls — and writes the same .dni/.r/.rdf/.dn/.rv/.cdf
 files with the same shapes and dtypes.  With -ad it also writes the angular (bond-angle) distribution the reference names
-.a.npy / .adf.npy but leaves switched off (definition: include/nm_distr.h, nm_distr_angles).
+.a.npy / .adf.npy but leaves switched off (definition: include/nm_distr.h, nm_distr_angles).  With -sf it also writes the
+static structure factor on the reciprocal lattice of each sample's box, averaged and maximised over the shells |q| = const
+(.q.npy / .sf.npy / .sfm.npy; definition: include/nm_distr.h, nm_distr_sfactor), and the number densities (.nrho.npy).
 
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -sf -sq 16
 """
 import argparse
 import ctypes as C
@@ -48,9 +51,16 @@ def parse_args(argv=None):
                    help='outer radius of the neighbour shell of -ad as a fraction of the smallest box edge, in (0, 0.5]; '
                         'default 0.5 (the last radial edge).  The first shell of an fcc crystal of SZ cells per edge ends at '
                         'about 0.85/SZ')
+    p.add_argument('-sf', '--structure_factor', action='store_true',
+                   help='also write <PREFIX>.q.npy, .sf.npy, .sfm.npy and .nrho.npy: the static structure factor S(q) on the '
+                        'reciprocal lattice of each sample\'s box, as the mean and the maximum over each shell of equal |q|')
+    p.add_argument('-sq', '--q_max', type=int, default=16,
+                   help='-sf takes every q = 2 pi (h, k, l) / box with 1 <= h^2 + k^2 + l^2 <= q_max^2; 1..32, default 16')
     a = p.parse_args(argv)
     if not 0.0 < a.angular_cutoff <= 0.5:
         p.error('-ac/--angular_cutoff must lie in (0, 0.5]')
+    if not 1 <= a.q_max <= 32:
+        p.error('-sq/--q_max must lie in 1..32')
     return a
 
 
@@ -119,6 +129,39 @@ def angles(natoms, box, pos, a, r_lo, r_hi, device=0):
     return (adf.astype(np.float64) / na[:, None]).astype(np.float32)
 
 
+def sfactor_shells(qmax):
+    """the shells of nm_distr_sfactor by enumeration: the n2 = h^2 + k^2 + l^2 in 1..qmax^2 that some integer triple reaches
+    (increasing, int64) and the number of triples of each"""
+    qmax = int(qmax)
+    if not 1 <= qmax <= 32:
+        raise ValueError('qmax must lie in 1..32')
+    g = np.arange(-qmax, qmax + 1, dtype=np.int64) ** 2
+    n2 = (g[:, None, None] + g[None, :, None] + g[None, None, :]).reshape(-1)
+    mult = np.bincount(n2[n2 <= qmax * qmax], minlength=qmax * qmax + 1)
+    mult[0] = 0
+    shells = np.flatnonzero(mult)
+    return shells.astype(np.int64), mult[shells].astype(np.int64)
+
+
+def sfactor(natoms, box, pos, qmax, device=0):
+    """static structure factor of all samples on the shells of sfactor_shells(qmax): the shell mean (nm_distr_sfactor's shell
+    sum divided by the number of vectors of the shell) and the shell maximum, both float64 [ns][nshell].  natoms is accepted
+    for symmetry with histograms() and angles(); the atom count is pos.shape[1]."""
+    L = B.load()
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    box = np.ascontiguousarray(box, dtype=np.float32)
+    ns, n = pos.shape[0], pos.shape[1]
+    shells, mult = sfactor_shells(qmax)
+    nsh = int(qmax) * int(qmax) + 1
+    ssum = np.zeros((ns, nsh), dtype=np.float64)
+    smax = np.zeros((ns, nsh), dtype=np.float64)
+    rc = L.nm_distr_sfactor(device, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), int(qmax),
+                            ssum.ctypes.data_as(B.c_double_p), smax.ctypes.data_as(B.c_double_p))
+    if rc != 0:
+        raise RuntimeError('nm_distr_sfactor failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    return ssum[:, shells] / mult[None, :], smax[:, shells]
+
+
 def main(argv=None):
     a = parse_args(argv)
     prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, a.element.lower(), LAT[a.element])
@@ -148,6 +191,13 @@ def main(argv=None):
         adf = angles(natoms, box, pos, ang, 1e-16 * l, a.angular_cutoff * l, device=int(os.environ.get('LOCAL_RANK', '0')))
         np.save(prefix + '.a.npy', ang)
         np.save(prefix + '.adf.npy', adf.reshape(pn, tn, rns, ang.size))
+    if a.structure_factor:
+        shells, _ = sfactor_shells(a.q_max)
+        sf, sfm = sfactor(natoms, box, pos, a.q_max, device=int(os.environ.get('LOCAL_RANK', '0')))
+        np.save(prefix + '.q.npy', 2 * np.pi * np.sqrt(shells.astype(np.float64)))   # |q| of a sample = this / its box
+        np.save(prefix + '.sf.npy', sf.astype(np.float32).reshape(pn, tn, rns, shells.size))
+        np.save(prefix + '.sfm.npy', sfm.astype(np.float32).reshape(pn, tn, rns, shells.size))
+        np.save(prefix + '.nrho.npy', nrho.reshape(pn, tn, rns))
     if a.verbose:
         print('all properties pickled')
 

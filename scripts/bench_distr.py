@@ -2,11 +2,16 @@
 
     python scripts/bench_distr.py [ns=4096] [natoms=256]
     python scripts/bench_distr.py --angles [ns=4096] [cells=4] [cutoff=0.5] [repeats=5]
+    python scripts/bench_distr.py --sfactor [ns=4096] [natoms=256] [qmax=16] [repeats=5]
 
 --angles: nm_distr_angles on displaced fcc frames of 4 cells^3 atoms (shell up to cutoff * l; the first shell is about
 0.85 / cells): the time of the whole call (copies + kernel, host clock around the synchronous call, median of the repeats
 after a warm-up), triplets/s, and the numpy restatement (tests/adf_ref.py) on one host core over a few centres.  The
-kernel's own time comes from `rocprofv3 --kernel-trace --stats -- python scripts/bench_distr.py --angles ...` (nm_adf_kernel)."""
+kernel's own time comes from `rocprofv3 --kernel-trace --stats -- python scripts/bench_distr.py --angles ...` (nm_adf_kernel).
+
+--sfactor: nm_distr_sfactor on random liquids: the time of the whole call as above and the rate in the definition's terms, one
+complex multiply-add (8 flop) per atom and vector of the half space; the kernel's own time from the same rocprofv3 line
+(nm_sfac_kernel)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,6 +65,41 @@ def bench_angles(argv):
     dt = time.perf_counter() - t
     print('numpy restatement, one core, %d centres of sample 0: %.4f s, %.4f G triplets/s, %.2f centres/s' % (kc, dt, nt / dt / 1e9, kc / dt))
 
+
+def bench_sfactor(argv):
+    from neuralmelting_amd import _lib as B
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    n = int(argv[1]) if len(argv) > 1 else 256
+    qmax = int(argv[2]) if len(argv) > 2 else 16
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    rng = np.random.default_rng(3)
+    box = (6.0 + 0.3 * rng.random(ns)).astype(np.float32)
+    pos = (rng.random((ns, n, 3)) * box[:, None, None]).astype(np.float32)
+    nvec = int(distr.sfactor_shells(qmax)[1].sum()) // 2
+    L = B.load()
+    ssum = np.zeros((ns, qmax * qmax + 1))
+    smax = np.zeros((ns, qmax * qmax + 1))
+
+    def run(m):
+        rc = L.nm_distr_sfactor(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), qmax,
+                                ssum.ctypes.data_as(B.c_double_p), smax.ctypes.data_as(B.c_double_p))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+    run(min(ns, 8))
+    run(ns)                                                                   # warm-up at the timed shape
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter(); run(ns); ts.append(time.perf_counter() - t)
+    dt = float(np.median(ts))
+    cma = float(ns) * n * nvec
+    print('sfactor: %d samples x %d atoms, qmax %d: %d half-space vectors, %.3e complex multiply-adds; call (H2D + kernel + D2H) '
+          'median of %d: %.4f s (min %.4f, max %.4f) = %.2f T flop/s at 8 flop each; mean S %.4f'
+          % (ns, n, qmax, nvec, cma, reps, dt, min(ts), max(ts), 8 * cma / dt / 1e12, ssum.sum() / (2.0 * nvec * ns)))
+
+
+if '--sfactor' in sys.argv:
+    bench_sfactor([x for x in sys.argv[1:] if x != '--sfactor'])
+    sys.exit(0)
 
 if '--angles' in sys.argv:
     bench_angles([x for x in sys.argv[1:] if x != '--angles'])
