@@ -76,6 +76,34 @@ int nm_distr_angles(int device, int ns, int natoms, const float *pos, const floa
  * ns == 0 is NM_OK. */
 int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const float *box, int qmax, double *sf_sum, double *sf_max);
 
+/* Steinhardt bond-orientational order parameters: per atom q_l, its neighbour-averaged form (Lechner and Dellago) and the
+ * global Q_l of a frame, all returned as SQUARES.  Definition (the build's own), for sample s and centre atom c:
+ *   entries     exactly the neighbours of nm_distr_angles: (j, a) over the 27 image shifts br[j] (lammps_distr.py:99-102) and all
+ *               atoms a, with v = pos[a] - (pos[c] + box*br[j]) in float32, d = float32 sqrt of the sequential float32 sum of the
+ *               three squares, and r_lo < (double)d <= r_hi.  r_lo >= 0 excludes the atom itself and coincident atoms; an atom
+ *               that qualifies in two images counts as two entries.  Nb(c) is the number of entries;
+ *   directions  n = v / |v| in float64 from the float32 components;
+ *   moments     q_lm(c) = (1 / Nb(c)) sum over the entries of Y_lm(n), m = -l..l, with the orthonormal spherical harmonics in the
+ *               Condon-Shortley phase (Y_l,-m = (-1)^m conj(Y_lm)); q_lm(c) = 0 if Nb(c) = 0;
+ *   q2[s][c][i]    = 4 pi / (2l+1) sum_m |q_lm(c)|^2 for l = ls[i]: the square of Steinhardt's q_l, in [0, 1].  Squares, because
+ *               where q_l vanishes (l = 2 on any cubic lattice) a 1e-16 error of the square is 1e-8 in the root;
+ *   qbar2[s][c][i] the same invariant of qbar_lm(c) = (q_lm(c) + sum over the entries (j, a) of c of q_lm(a)) / (Nb(c) + 1);
+ *   Q2[s][i]       the same invariant of (sum_c sum over the entries of c of Y_lm(n)) / (sum_c Nb(c)); 0 if the frame has no bond;
+ *   nnb[s][c]      = Nb(c).
+ * Error bound, u = 2^-53, M the largest Nb of the call (derivation: csrc/nm_distr.h): per bond the vector (Y_lm)_m is off by at
+ * most e(l) = (3 l^2 + 7 l + 8) u of its norm; e_q = e(l) + M u, e_qbar = e_q + (M + 1) u, e_Q = e(l) + (M + 12 + ceil(natoms/32)) u,
+ * and each returned square x is off by at most 2 e sqrt(x) + e^2.
+ * The result is the same bit for bit on every call: float64 sums in a fixed order, no floating-point atomics.
+ * ls[nl]: 1 to 6 strictly increasing values in 1..12.  pos[ns][natoms][3], box[ns] float32; q2, qbar2 [ns][natoms][nl] and
+ * Q2[ns][nl] float64, nnb[ns][natoms] int32.  Any output may be NULL (it is then not written), but not all four.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_bondorder:".  NM_ERR_ARG,
+ * checked before the device is looked for and with the outputs left untouched, for: ns < 0, natoms outside 1..4095, nl outside
+ * 1..6, ls not strictly increasing within 1..12, not 0 <= r_lo < r_hi, r_hi > min(box)/2 over the batch, a box that is not finite
+ * and positive, a null pos, box or ls, all outputs null, a bad device ordinal.  ns == 0 is NM_OK where a device is found (the
+ * device is looked for first, as in nm_distr_sfactor: NM_ERR_HIP without one). */
+int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
+                       const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb);
+
 #ifdef __cplusplus
 }
 #endif

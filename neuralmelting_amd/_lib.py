@@ -10,6 +10,7 @@ c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 c_uint64_p = C.POINTER(C.c_uint64)
+c_int32_p = C.POINTER(C.c_int32)
 
 NM_OK, NM_ERR_ARG, NM_ERR_HIP, NM_ERR_STATE, NM_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 NM_EL_LJ, NM_EL_AL, NM_EL_NI, NM_EL_CU = 0, 1, 2, 3
@@ -25,7 +26,7 @@ SYMBOLS = ('nm_create', 'nm_destroy', 'nm_last_error', 'nm_create_note', 'nm_nsl
 
 
 # include/nm_distr.h
-DISTR_SYMBOLS = ('nm_distr_histograms', 'nm_distr_angles', 'nm_distr_sfactor', 'nm_distr_last_error')
+DISTR_SYMBOLS = ('nm_distr_histograms', 'nm_distr_angles', 'nm_distr_sfactor', 'nm_distr_bondorder', 'nm_distr_last_error')
 # include/nm_parse.h
 PARSE_SYMBOLS = ('nm_parse_thrm', 'nm_parse_traj', 'nm_parse_last_error')
 
@@ -109,6 +110,9 @@ def load():
                                   c_uint64_p]
     L.nm_distr_sfactor.restype = C.c_int
     L.nm_distr_sfactor.argtypes = [C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, c_double_p, c_double_p]
+    L.nm_distr_bondorder.restype = C.c_int
+    L.nm_distr_bondorder.argtypes = [C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_double, C.c_double, C.c_int, c_int_p,
+                                     c_double_p, c_double_p, c_double_p, c_int32_p]
     L.nm_distr_last_error.restype = C.c_char_p
     c_long_p = C.POINTER(C.c_long)
     L.nm_parse_thrm.restype = C.c_int

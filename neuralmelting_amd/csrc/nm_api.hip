@@ -1771,6 +1771,112 @@ int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const flo
     return NM_OK;
 }
 
+int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
+                       const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb)
+{
+    if (ns < 0 || !pos || !box || !ls) return dfail(NM_ERR_ARG, "nm_distr_bondorder: bad argument");
+    if (!q2 && !qbar2 && !Q2 && !nnb) return dfail(NM_ERR_ARG, "nm_distr_bondorder: all four outputs are null");
+    if (natoms < 1 || natoms > 4095) return dfail(NM_ERR_ARG, "nm_distr_bondorder: natoms must lie in 1..4095");
+    if (nl < 1 || nl > BO_MAXL) return dfail(NM_ERR_ARG, "nm_distr_bondorder: nl must lie in 1..6");
+    for (int i = 0; i < nl; ++i)
+        if (ls[i] < 1 || ls[i] > BO_LMAX || (i > 0 && ls[i] <= ls[i - 1]))
+            return dfail(NM_ERR_ARG, "nm_distr_bondorder: ls must increase strictly within 1..12");
+    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return dfail(NM_ERR_ARG, "nm_distr_bondorder: the shell needs 0 <= r_lo < r_hi");
+    for (int s = 0; s < ns; ++s)
+        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return dfail(NM_ERR_ARG, "nm_distr_bondorder: a box is not finite and positive");
+    // beyond half the smallest box an atom could neighbour its own image
+    for (int s = 0; s < ns; ++s)
+        if (!(r_hi <= 0.5 * (double)box[s])) return dfail(NM_ERR_ARG, "nm_distr_bondorder: r_hi exceeds half the smallest box");
+    if (device < 0) return dfail(NM_ERR_ARG, "nm_distr_bondorder: device ordinal out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_bondorder: no HIP device available");
+    if (device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_bondorder: device ordinal out of range");
+    if (ns == 0) return NM_OK;
+    // the requested l and the recurrence's constants (nm_distr.h): long double, rounded once
+    BoSet set = {nl, 0, ls[nl - 1], 0u, 0ull, 0u};
+    for (int i = 0; i < nl; ++i) {
+        const int l = ls[i];
+        set.lmask |= 1u << l;
+        if (l <= 8) set.off_lo |= (unsigned long long)set.nc << (8 * (l - 1));
+        else set.off_hi |= (unsigned int)set.nc << (8 * (l - 9));
+        set.nc += l + 1;
+    }
+    const int nc2 = 2 * set.nc, W = BO_LMAX + 1;
+    std::vector<double> tab((size_t)BO_TAB, 0.0);
+    {
+        long double c = sqrtl(1.0L / (4.0L * 3.14159265358979323846264338327950288L));
+        for (int m = 0; m <= BO_LMAX; ++m) {
+            if (m > 0) c = -c * sqrtl((long double)(2 * m + 1) / (long double)(2 * m));
+            tab[m] = (double)c;
+            for (int l = m + 1; l <= BO_LMAX; ++l) {
+                tab[W + l * W + m] = (double)sqrtl((long double)(4 * l * l - 1) / (long double)(l * l - m * m));
+                tab[W + W * W + l * W + m] = (double)sqrtl((long double)((l - 1) * (l - 1) - m * m) / (long double)(4 * (l - 1) * (l - 1) - 1));
+            }
+        }
+    }
+    const float cube = r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY); // as nm_distr_angles
+    const int groups = (natoms + BO_CPB - 1) / BO_CPB;
+    // samples per launch: at most 4096 as the other entry points, fewer where the moments' scratch would pass 256 MiB
+    const size_t per = (size_t)natoms * nc2 * sizeof(double);
+    size_t fit = ((size_t)256 << 20) / per;
+    if (fit < 1) fit = 1;
+    int cs = ns < 4096 ? ns : 4096;
+    if ((size_t)cs > fit) cs = (int)fit;
+    float *d_pos = nullptr, *d_box = nullptr;
+    double *d_tab = nullptr, *d_qlm = nullptr, *d_part = nullptr, *d_q2 = nullptr, *d_qb = nullptr, *d_Q = nullptr;
+    int *d_cnt = nullptr, *d_nnb = nullptr;
+    auto release = [&]() {
+        hipFree(d_pos); hipFree(d_box); hipFree(d_tab); hipFree(d_qlm); hipFree(d_part); hipFree(d_q2); hipFree(d_qb); hipFree(d_Q);
+        hipFree(d_cnt); hipFree(d_nnb);
+    };
+#define BCHK(call)                                                                                     \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) { release(); return dfail(NM_ERR_HIP, std::string("nm_distr_bondorder: ") + #call + ": " + hipGetErrorString(e_)); } \
+    } while (0)
+    BCHK(hipSetDevice(device));
+    const size_t lds1 = bo_lds_bytes(natoms, set.nc, true), lds2 = bo_lds_bytes(natoms, set.nc, false); // at most 98,932 B (4095 atoms, six l from 7 to 12)
+    BCHK(hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    BCHK(hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    BCHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
+    BCHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
+    BCHK(hipMalloc((void **)&d_tab, tab.size() * sizeof(double)));
+    BCHK(hipMalloc((void **)&d_qlm, (size_t)cs * per));
+    BCHK(hipMalloc((void **)&d_part, (size_t)cs * groups * nc2 * sizeof(double)));
+    BCHK(hipMalloc((void **)&d_cnt, (size_t)cs * groups * sizeof(int)));
+    if (q2) BCHK(hipMalloc((void **)&d_q2, (size_t)cs * natoms * nl * sizeof(double)));
+    if (qbar2) BCHK(hipMalloc((void **)&d_qb, (size_t)cs * natoms * nl * sizeof(double)));
+    if (Q2) BCHK(hipMalloc((void **)&d_Q, (size_t)cs * nl * sizeof(double)));
+    if (nnb) BCHK(hipMalloc((void **)&d_nnb, (size_t)cs * natoms * sizeof(int)));
+    BCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    for (int s0 = 0; s0 < ns; s0 += cs) {
+        const int n = (ns - s0) < cs ? (ns - s0) : cs;
+        BCHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
+        BCHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(BO_BLOCK), lds1, 0, natoms, d_pos, d_box, r_lo, r_hi, cube, set,
+                           d_tab, d_qlm, d_q2, d_nnb, d_part, d_cnt);
+        BCHK(hipGetLastError());
+        if (qbar2) {
+            hipLaunchKernelGGL(nm_bo_average_kernel, dim3(n * groups), dim3(BO_BLOCK), lds2, 0, natoms, d_pos, d_box, r_lo, r_hi, cube,
+                               set, d_qlm, d_qb);
+            BCHK(hipGetLastError());
+        }
+        if (Q2) {
+            hipLaunchKernelGGL(nm_bo_global_kernel, dim3(n), dim3(128), 0, 0, groups, set, d_part, d_cnt, d_Q);
+            BCHK(hipGetLastError());
+        }
+        BCHK(hipDeviceSynchronize());
+        const size_t pa = (size_t)natoms * nl;
+        if (q2) BCHK(hipMemcpy(q2 + (size_t)s0 * pa, d_q2, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
+        if (qbar2) BCHK(hipMemcpy(qbar2 + (size_t)s0 * pa, d_qb, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
+        if (Q2) BCHK(hipMemcpy(Q2 + (size_t)s0 * nl, d_Q, (size_t)n * nl * sizeof(double), hipMemcpyDeviceToHost));
+        if (nnb) BCHK(hipMemcpy(nnb + (size_t)s0 * natoms, d_nnb, (size_t)n * natoms * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    release();
+#undef BCHK
+    return NM_OK;
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -517,4 +517,373 @@ nm_sfac_kernel(int natoms, const float *__restrict__ pos, const float *__restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Steinhardt bond-order parameters (include/nm_distr.h, nm_distr_bondorder): per centre c the moments
+// q_lm(c) = (1/Nb) sum over the neighbour entries of Y_lm(n), n = v/|v| in float64 from the float32 displacement, the
+// neighbour entries being exactly those of nm_adf_kernel; from them q2 (per atom), qbar2 (the moments averaged over the centre
+// and its entries) and Q2 (the moments of all bonds of the frame).
+//
+// Harmonics without an azimuth and without a division by sin(theta): Y_lm(n) = N_l^m(n_z) (n_x + i n_y)^m for m >= 0, where
+// N_l^m = (normalisation) P_l^m / sin^m(theta) is a polynomial in n_z that obeys the three-term recurrence of the normalised
+// functions at fixed m,
+//   N_m^m = c_m = (-1)^m sqrt((2m+1)!! / (4 pi (2m)!!)),   N_l^m = A_lm (n_z N_(l-1)^m - B_lm N_(l-2)^m),   N_(m-1)^m = 0,
+//   A_lm = sqrt((4 l^2 - 1) / (l^2 - m^2)),   B_lm = sqrt(((l-1)^2 - m^2) / (4 (l-1)^2 - 1)),
+// so a bond along the z axis is no special case.  The host computes c, A and B for l <= 12 (long double, rounded once) into the
+// table the kernels read with wave-uniform indices.  Y_l,-m = (-1)^m conj(Y_lm): only m >= 0 is formed, and the invariant
+// 4 pi / (2l+1) sum_m |q_lm|^2 counts m > 0 twice.
+//
+// Pass 1 (nm_bo_moments_kernel): a workgroup takes BO_CPB consecutive centres of one sample, positions and bounding box staged
+// as nm_adf_kernel does; each wave works through its centres alone.  bo_scan is adf_fill's scan (same float32 arithmetic, same
+// image skip, same ballot compaction) that also records the atom index and hands the wave's list on in batches of 64 entries as
+// it fills, so any number of neighbours is handled with one scan.  For a batch, lane = bond: the lane runs the recurrence (m
+// outer, l inner) and puts the Y_lm of the requested l into the wave's LDS staging rows [component][bond]; when the rows are
+// full, lane = component: each lane adds its row's bonds in list order to the centre's accumulator in LDS.  No accumulator is
+// indexed at run time in registers, so nothing goes to scratch memory.  At the centre's end the wave writes q_lm(c) to the global
+// scratch [sample][atom][component], q2 and nnb, and keeps the unnormalised sums for Q2; the workgroup's partial sums and bond
+// count go to [sample][group].
+// Pass 2 (nm_bo_average_kernel, only if qbar2 is asked for): the same scan, indices only; lane = component gathers q_lm(a) of
+// the batch's entries in list order (one coalesced read of the atom's moments per entry, the reads of up to eight entries in
+// flight), then qbar_lm and its invariant.
+// nm_bo_global_kernel adds the partials of a sample's groups in order and forms Q2.
+// Every sum runs in a fixed order (entries in scan order, centres in order per wave, waves in order, groups in order): the
+// result is the same bits on every call, without a floating-point atomic.
+//
+// Error bound (u = 2^-53), per bond, of the computed vector y = (Y_lm)_m against the exact one, relative to |y| = sqrt((2l+1)/4 pi):
+//   direction   each component of n = v * (1 / sqrt(|v|^2)) carries at most 3 u relative (sum of squares 1.5 u, halved by the
+//               root, the root, the reciprocal, the product), so n is off by at most 3 u in length and 3 u in direction.  y
+//               transforms under the (2l+1)-dimensional unitary representation, whose generators have norm l: a rotation by
+//               3 u moves y by at most 3 l u |y|.  The length error scales (n_x + i n_y)^m by (1 + 3u)^m and moves n_z in a
+//               polynomial of degree l - m whose derivative is at most (l - m)^2 times its maximum (Markov): together at
+//               most 3 (m + (l-m)^2) u <= 3 l^2 u for l >= 1, taken against the same norm.
+//   recurrence  l - m steps of three roundings each on the dominant solution of the recurrence (forward in l at fixed m is
+//               the stable direction), m complex products for the power (at most 3 u each), the table's roundings (one per
+//               step), the final product: at most (4 (l - m) + 3 m + 2) u <= (4 l + 2) u on each component, against its own
+//               envelope sqrt((2l+1)/4 pi).
+//   together    e(l) = (3 l^2 + 7 l + 8) u, the 6 u left over for the invariant's own sum and the division by Nb: 524 u =
+//               5.8e-14 at l = 12.
+// Sums: a fixed-order float64 sum of n terms of norm <= |y| adds at most (n - 1) u |y|.  So with M = the largest Nb:
+//   q      e_q = e(l) + M u;             qbar    e_q + (M + 1) u;             Q    e(l) + (M + 12 + ceil(natoms / 32)) u
+// (Q: the entries of a centre, then a wave's 8 centres, the 4 waves and the groups of 32 centres), and for each invariant
+// x = |.|^2, |dx| <= 2 e sqrt(x) + e^2.  tests/bondorder_ref.py holds the same expressions; the tests allow twice that.
+constexpr int BO_BLOCK = 256;
+constexpr int BO_WAVES = BO_BLOCK / 64;
+constexpr int BO_CPB = 32;      // centres per workgroup
+constexpr int BO_LIST = 128;    // list entries per wave: a batch of 64 and what one scan step can add to 63
+constexpr int BO_SC = 16;       // staging rows (real components) per wave
+constexpr int BO_ROW = 65;      // doubles per staging row: 64 bonds, padded so that lane = component reads spread over the banks
+constexpr int BO_LMAX = 12;
+constexpr int BO_MAXL = 6;      // most l values per call
+constexpr int BO_TAB = (BO_LMAX + 1) * (2 * (BO_LMAX + 1) + 1); // c[m], A[l][m], B[l][m]
+
+// what the kernels need to know of the requested l: bit l of lmask, the component offset of l (sum of l' + 1 over the
+// requested l' < l) in 8 bits each (l = 1..8 in off_lo, 9..12 in off_hi), nc = sum of l + 1: scalar arithmetic only
+struct BoSet { int nl, nc, lmax; unsigned int lmask; unsigned long long off_lo; unsigned int off_hi; };
+
+__host__ __device__ __forceinline__ int bo_off(const BoSet &b, int l)
+{
+    return l <= 8 ? (int)((b.off_lo >> (8 * (l - 1))) & 255ull) : (int)((b.off_hi >> (8 * (l - 9))) & 255u);
+}
+
+__host__ __device__ inline size_t bo_lds_bytes(int natoms, int nc, bool moments)
+{
+    const size_t wave = (size_t)((moments ? BO_SC * BO_ROW + 4 * nc : 2 * nc)) * sizeof(double) // staging, acc and frame sums | qbar
+                      + (size_t)(moments ? 4 : 1) * BO_LIST * 4 + (size_t)(BO_SC / 2 + 2) * 4; // list (vectors, index), row map, count
+    return (size_t)BO_WAVES * wave + ((size_t)3 * natoms + BO_WAVES * 6) * sizeof(float);
+}
+
+// the l of the i-th requested value
+__device__ __forceinline__ int bo_l_of(const BoSet &b, int i)
+{
+    int l = 0, k = -1;
+    while (k < i && l < BO_LMAX) { ++l; if ((b.lmask >> l) & 1u) ++k; }
+    return l;
+}
+
+// 4 pi / (2l+1) sum_{m=-l..l} |q_lm|^2 from the m >= 0 components q[2m], q[2m+1]
+__device__ __forceinline__ double bo_invariant(const double *q, int l)
+{
+    double t = 0.0;
+    for (int m = 1; m <= l; ++m) t += q[2 * m] * q[2 * m] + q[2 * m + 1] * q[2 * m + 1];
+    return (4.0 * 3.14159265358979323846 / (double)(2 * l + 1)) * (q[0] * q[0] + q[1] * q[1] + 2.0 * t);
+}
+
+// stage the sample's positions and their bounding box (as nm_adf_kernel); ends with a workgroup barrier
+__device__ __forceinline__ void bo_stage(const float *ps, int natoms, float *px, float *py, float *pz, float *part, float *bb)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    for (int a = tid; a < natoms; a += BO_BLOCK) {
+        const float x = ps[3 * a], y = ps[3 * a + 1], z = ps[3 * a + 2];
+        px[a] = x; py[a] = y; pz[a] = z;
+        lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
+        lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
+        lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
+    }
+    for (int d = 0; d < 3; ++d) {
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[d] = fminf(lo[d], __shfl_xor(lo[d], o));
+            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o));
+        }
+        if (lane == 0) { part[wave * 6 + 2 * d] = lo[d]; part[wave * 6 + 2 * d + 1] = hi[d]; }
+    }
+    __syncthreads();
+    for (int d = 0; d < 3; ++d) {
+        float l = part[2 * d], u = part[2 * d + 1];
+        for (int w = 1; w < BO_WAVES; ++w) { l = fminf(l, part[w * 6 + 2 * d]); u = fmaxf(u, part[w * 6 + 2 * d + 1]); }
+        bb[2 * d] = l; bb[2 * d + 1] = u;
+    }
+}
+
+// adf_fill's scan with the atom index recorded: the neighbour entries of centre (cx, cy, cz) in scan order go to the wave's
+// list (VEC: with their float32 components), and batch(n) is called with the list's first n entries whenever 64 are there, and
+// with the rest at the end; entries beyond 64 move to the front.  Returns the number of entries.
+template <bool VEC, class F>
+__device__ __forceinline__ int bo_scan(const float *px, const float *py, const float *pz, int natoms, float cx, float cy, float cz,
+                                       float L, float cube, const float *bb, double r_lo, double r_hi, float *lx, float *ly,
+                                       float *lz, int *li, int lane, F &&batch)
+{
+#pragma clang fp contract(off)
+    int cnt = 0, total = 0;
+    for (int img = 0; img < 27; ++img) {
+        // br[j] = (b[i], b[j], b[k]) for i, j, k in range(3), b = [-1, 0, 1]  (lammps_distr.py:99-102)
+        const float bx = (float)(img / 9 - 1), by = (float)((img / 3) % 3 - 1), bz = (float)(img % 3 - 1);
+        const float qx = cx + L * bx, qy = cy + L * by, qz = cz + L * bz; // pos[c] + box*br[j]
+        if (bb[0] - qx > cube || bb[1] - qx < -cube || bb[2] - qy > cube || bb[3] - qy < -cube || bb[4] - qz > cube || bb[5] - qz < -cube)
+            continue; // see adf_fill
+        for (int a0 = 0; a0 < natoms; a0 += 64) {
+            const int a = a0 + lane;
+            bool in = false;
+            float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+            if (a < natoms) {
+                vx = px[a] - qx; vy = py[a] - qy; vz = pz[a] - qz;
+                float d2 = vx * vx;      // sequential float32 sum of three terms, as the rdf path
+                d2 = d2 + vy * vy;
+                d2 = d2 + vz * vz;
+                const double d = (double)sqrtf(d2); // correctly rounded (see nm_distr_kernel)
+                in = r_lo < d && d <= r_hi;
+            }
+            const unsigned long long m = __ballot(in);
+            if (in) {
+                const int o = cnt + __popcll(m & ((1ull << lane) - 1ull)); // cnt <= 63 here: o <= 126 < BO_LIST
+                if (VEC) { lx[o] = vx; ly[o] = vy; lz[o] = vz; }
+                li[o] = a;
+            }
+            cnt += __popcll(m);
+            total += __popcll(m);
+            if (cnt >= 64) {
+                adf_wave_sync();
+                batch(64);
+                adf_wave_sync();
+                const int rest = cnt - 64;
+                float tx = 0.0f, ty = 0.0f, tz = 0.0f;
+                if (VEC) { tx = lx[64 + lane]; ty = ly[64 + lane]; tz = lz[64 + lane]; }
+                const int ti = li[64 + lane];
+                adf_wave_sync();
+                if (lane < rest) {
+                    if (VEC) { lx[lane] = tx; ly[lane] = ty; lz[lane] = tz; }
+                    li[lane] = ti;
+                }
+                adf_wave_sync();
+                cnt = rest;
+            }
+        }
+    }
+    if (cnt > 0) {
+        adf_wave_sync();
+        batch(cnt);
+        adf_wave_sync();
+    }
+    return total;
+}
+
+__global__ void __launch_bounds__(BO_BLOCK)
+nm_bo_moments_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+                     BoSet set, const double *__restrict__ tab, double *__restrict__ qlm, double *__restrict__ q2,
+                     int *__restrict__ nnb, double *__restrict__ partial, int *__restrict__ pcount)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + BO_CPB - 1) / BO_CPB;
+    const int s = blockIdx.x / groups, grp = blockIdx.x % groups, c0 = grp * BO_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nc2 = 2 * set.nc;
+    double *stage_all = (double *)smem, *acc_all = stage_all + BO_WAVES * BO_SC * BO_ROW, *gacc_all = acc_all + BO_WAVES * nc2;
+    float *lv_all = (float *)(gacc_all + BO_WAVES * nc2);
+    int *li_all = (int *)(lv_all + BO_WAVES * 3 * BO_LIST), *rowc_all = li_all + BO_WAVES * BO_LIST;
+    int *wcount = rowc_all + BO_WAVES * (BO_SC / 2);
+    float *px = (float *)(wcount + BO_WAVES * 2), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    bo_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part, bb);
+    double *stage = stage_all + wave * BO_SC * BO_ROW, *acc = acc_all + wave * nc2, *gacc = gacc_all + wave * nc2;
+    float *lx = lv_all + wave * 3 * BO_LIST, *ly = lx + BO_LIST, *lz = ly + BO_LIST;
+    int *li = li_all + wave * BO_LIST, *rowc = rowc_all + wave * (BO_SC / 2);
+    const double *tc = tab, *tA = tab + (BO_LMAX + 1), *tB = tA + (BO_LMAX + 1) * (BO_LMAX + 1);
+    for (int j = lane; j < nc2; j += 64) gacc[j] = 0.0;
+    int gcount = 0;
+    const int cend = c0 + BO_CPB < natoms ? c0 + BO_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += BO_WAVES) {
+        for (int j = lane; j < nc2; j += 64) acc[j] = 0.0;
+        adf_wave_sync();
+        const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px[c])));
+        const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py[c])));
+        const float cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pz[c])));
+        const int nb = bo_scan<true>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, lx, ly, lz, li, lane, [&](int mb) {
+            // lane = bond: the unit vector in float64 from the float32 components
+            const bool act = lane < mb;
+            const double X = act ? (double)lx[lane] : 0.0, Y = act ? (double)ly[lane] : 0.0, Z = act ? (double)lz[lane] : 1.0;
+            const double rinv = 1.0 / sqrt(fma(Z, Z, fma(Y, Y, X * X)));
+            const double nx = X * rinv, ny = Y * rinv, nz = Z * rinv;
+            int nst = 0;
+            // lane = component: add the staged rows' bonds in list order to the centre's accumulators
+            auto flush = [&]() {
+                adf_wave_sync();
+                if (lane < nst) {
+                    const double *r = stage + lane * BO_ROW;
+                    double t = 0.0;
+                    for (int b = 0; b < mb; ++b) t += r[b];
+                    acc[2 * rowc[lane >> 1] + (lane & 1)] += t;
+                }
+                adf_wave_sync();
+                nst = 0;
+            };
+            double pr = 1.0, pi = 0.0; // (n_x + i n_y)^m
+            for (int m = 0; m <= set.lmax; ++m) {
+                if (m > 0) { const double t = pr * nx - pi * ny; pi = pr * ny + pi * nx; pr = t; }
+                double p0 = tc[m], p1 = 0.0; // N_l^m, N_(l-1)^m
+                for (int l = m; l <= set.lmax; ++l) {
+                    if (l > m) {
+                        const double p = tA[l * (BO_LMAX + 1) + m] * (nz * p0 - tB[l * (BO_LMAX + 1) + m] * p1);
+                        p1 = p0; p0 = p;
+                    }
+                    if ((set.lmask >> l) & 1u) {
+                        if (nst + 2 > BO_SC) flush();
+                        stage[nst * BO_ROW + lane] = p0 * pr;
+                        stage[(nst + 1) * BO_ROW + lane] = p0 * pi;
+                        if (lane == 0) rowc[nst >> 1] = bo_off(set, l) + m;
+                        nst += 2;
+                    }
+                }
+            }
+            flush();
+        });
+        // q_lm(c), the frame's sums, q2 and nnb
+        const size_t at = (size_t)s * natoms + c;
+        for (int j = lane; j < nc2; j += 64) {
+            const double a = acc[j];
+            gacc[j] += a;
+            const double q = nb > 0 ? a / (double)nb : 0.0;
+            acc[j] = q;
+            qlm[at * nc2 + j] = q;
+        }
+        gcount += nb;
+        adf_wave_sync();
+        if (q2 && lane < set.nl) {
+            const int l = bo_l_of(set, lane);
+            q2[at * set.nl + lane] = bo_invariant(acc + 2 * bo_off(set, l), l);
+        }
+        if (nnb && lane == 0) nnb[at] = nb;
+        adf_wave_sync();
+    }
+    if (lane == 0) wcount[wave] = gcount;
+    __syncthreads();
+    if (tid < nc2) {
+        double t = gacc_all[tid];
+        for (int w = 1; w < BO_WAVES; ++w) t += gacc_all[w * nc2 + tid];
+        partial[((size_t)s * groups + grp) * nc2 + tid] = t;
+    }
+    if (tid == 0) {
+        int t = 0;
+        for (int w = 0; w < BO_WAVES; ++w) t += wcount[w];
+        pcount[(size_t)s * groups + grp] = t;
+    }
+}
+
+// pass 2's gather: the components lane and lane + 64 of the moments of K list entries, all reads issued before the first sum,
+// added in list order
+template <int K>
+__device__ __forceinline__ void bo_gather(const double *__restrict__ qs, const int *li, int nc2, int lane, bool own0, bool own1,
+                                          double &a0, double &a1)
+{
+    double v0[K], v1[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double *r = qs + (size_t)li[k] * nc2;
+        v0[k] = own0 ? r[lane] : 0.0;
+        v1[k] = own1 ? r[lane + 64] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (own0) a0 += v0[k];
+        if (own1) a1 += v1[k];
+    }
+}
+
+__global__ void __launch_bounds__(BO_BLOCK)
+nm_bo_average_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+                     BoSet set, const double *__restrict__ qlm, double *__restrict__ qbar2)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + BO_CPB - 1) / BO_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * BO_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nc2 = 2 * set.nc; // at most 126: a lane owns the components lane and lane + 64
+    double *acc_all = (double *)smem;
+    int *li_all = (int *)(acc_all + BO_WAVES * nc2);
+    float *px = (float *)(li_all + BO_WAVES * BO_LIST + BO_WAVES * (BO_SC / 2 + 2)), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    bo_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part, bb);
+    double *acc = acc_all + wave * nc2;
+    int *li = li_all + wave * BO_LIST;
+    const double *qs = qlm + (size_t)s * natoms * nc2;
+    const bool own0 = lane < nc2, own1 = lane + 64 < nc2;
+    const int cend = c0 + BO_CPB < natoms ? c0 + BO_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += BO_WAVES) {
+        const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px[c])));
+        const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py[c])));
+        const float cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pz[c])));
+        double a0 = 0.0, a1 = 0.0;
+        const int nb = bo_scan<false>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, nullptr, nullptr, nullptr, li, lane, [&](int mb) {
+            // up to eight entries' reads in flight at a time (one entry's reads after the other leave the wave waiting for L2 four
+            // fifths of its cycles at 126 neighbours); the sums keep the list order
+            int b = 0;
+            for (; b + 8 <= mb; b += 8) bo_gather<8>(qs, li + b, nc2, lane, own0, own1, a0, a1);
+            if (b + 4 <= mb) { bo_gather<4>(qs, li + b, nc2, lane, own0, own1, a0, a1); b += 4; }
+            for (; b < mb; ++b) bo_gather<1>(qs, li + b, nc2, lane, own0, own1, a0, a1);
+        });
+        const double *rc = qs + (size_t)c * nc2;
+        const double den = (double)(nb + 1);
+        if (own0) acc[lane] = (rc[lane] + a0) / den;
+        if (own1) acc[lane + 64] = (rc[lane + 64] + a1) / den;
+        adf_wave_sync();
+        if (lane < set.nl) {
+            const int l = bo_l_of(set, lane);
+            qbar2[((size_t)s * natoms + c) * set.nl + lane] = bo_invariant(acc + 2 * bo_off(set, l), l);
+        }
+        adf_wave_sync();
+    }
+}
+
+// one workgroup of 128 threads per sample: the groups' partial sums in order, the moments of all bonds, Q2
+__global__ void __launch_bounds__(128)
+nm_bo_global_kernel(int groups, BoSet set, const double *__restrict__ partial, const int *__restrict__ pcount, double *__restrict__ Q2)
+{
+    __shared__ double q[2 * BO_MAXL * (BO_LMAX + 1)];
+    const int s = blockIdx.x, tid = threadIdx.x, nc2 = 2 * set.nc;
+    if (tid < nc2) {
+        double t = 0.0;
+        long long n = 0;
+        for (int g = 0; g < groups; ++g) {
+            t += partial[((size_t)s * groups + g) * nc2 + tid];
+            n += pcount[(size_t)s * groups + g];
+        }
+        q[tid] = n > 0 ? t / (double)n : 0.0;
+    }
+    __syncthreads();
+    if (tid < set.nl) {
+        const int l = bo_l_of(set, tid);
+        Q2[(size_t)s * set.nl + tid] = bo_invariant(q + 2 * bo_off(set, l), l);
+    }
+}
+
 } // namespace nm

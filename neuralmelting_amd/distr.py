@@ -8,10 +8,13 @@ files with the same shapes and dtypes.  With -ad it also writes the angular (bon
 .a.npy / .adf.npy but leaves switched off (definition: include/nm_distr.h, nm_distr_angles).  With -sf it also writes the
 static structure factor on the reciprocal lattice of each sample's box, averaged and maximised over the shells |q| = const
 (.q.npy / .sf.npy / .sfm.npy; definition: include/nm_distr.h, nm_distr_sfactor), and the number densities (.nrho.npy).
+With -bo it also writes the Steinhardt bond-order parameters q_l, their neighbour average and the global Q_l (.bo*.npy;
+definition: include/nm_distr.h, nm_distr_bondorder).
 
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -sf -sq 16
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -bo -bl 4 6
 """
 import argparse
 import ctypes as C
@@ -24,8 +27,7 @@ from . import _lib as B
 LAT = {'Ti': 'bcc', 'Al': 'fcc', 'Ni': 'fcc', 'Cu': 'fcc', 'LJ': 'fcc'}
 
 
-def parse_args(argv=None):
-    """lammps_distr.py's flags (distr:15-53); the cluster flags are accepted and ignored"""
+def _parser():
     p = argparse.ArgumentParser()
     p.add_argument('-v', '--verbose', action='store_true')
     p.add_argument('-p', '--parallel', action='store_true')
@@ -56,7 +58,43 @@ def parse_args(argv=None):
                         'reciprocal lattice of each sample\'s box, as the mean and the maximum over each shell of equal |q|')
     p.add_argument('-sq', '--q_max', type=int, default=16,
                    help='-sf takes every q = 2 pi (h, k, l) / box with 1 <= h^2 + k^2 + l^2 <= q_max^2; 1..32, default 16')
+    p.add_argument('-bo', '--bond_order', action='store_true',
+                   help='also write the Steinhardt bond-order parameters: <PREFIX>.bol.npy (the l values), .boq.npy (mean over the '
+                        'atoms of q_l), .bob.npy (mean of the neighbour-averaged q_l), .bog.npy (the global Q_l) and .bon.npy (mean '
+                        'number of neighbours)')
+    p.add_argument('-bl', '--bond_l', type=int, nargs='+', default=[4, 6],
+                   help='the l of -bo: 1 to 6 distinct values in 1..12, default 4 6')
+    p.add_argument('-bc', '--bond_cutoff', type=float, default=0.0,
+                   help='outer radius of the neighbour shell of -bo as a fraction of the smallest box edge, in (0, 0.5]; the '
+                        'default 0 means the first fcc shell, 0.853553 / SZ for natoms = 4 SZ^3 (midway between the first and '
+                        'second neighbour distances of the perfect crystal)')
+    p.add_argument('-ba', '--bond_atoms', action='store_true',
+                   help='with -bo also write the per-atom values: <PREFIX>.boqa.npy, .boba.npy and .bona.npy; 8 nl + 4 bytes per atom '
+                        'and sample for nl values of l, about 10 GB for a grid of 2^20 samples of 500 atoms at two l')
+    return p
+
+
+def bond_cutoff(value, natoms):
+    """the outer radius of -bo as a fraction of the smallest box edge: value, or for value 0 the first fcc shell
+    0.853553 / round(cbrt(natoms / 4)); ValueError outside (0, 0.5]"""
+    cut = float(value)
+    if cut == 0.0:
+        cut = 0.853553 / max(1, int(round((int(natoms) / 4.0) ** (1.0 / 3.0))))
+    if not 0.0 < cut <= 0.5:
+        raise ValueError('-bc/--bond_cutoff must lie in (0, 0.5]; got %g%s' % (cut, '' if float(value) else
+                         ' as the first fcc shell of %d atoms: pass -bc' % int(natoms)))
+    return cut
+
+
+def parse_args(argv=None):
+    """lammps_distr.py's flags (distr:15-53); the cluster flags are accepted and ignored"""
+    p = _parser()
     a = p.parse_args(argv)
+    if not 0.0 <= a.bond_cutoff <= 0.5:
+        p.error('-bc/--bond_cutoff must lie in (0, 0.5], or be 0 for the first fcc shell')
+    a.bond_l = sorted(a.bond_l)
+    if not 1 <= len(a.bond_l) <= 6 or len(set(a.bond_l)) != len(a.bond_l) or a.bond_l[0] < 1 or a.bond_l[-1] > 12:
+        p.error('-bl/--bond_l takes 1 to 6 distinct values in 1..12')
     if not 0.0 < a.angular_cutoff <= 0.5:
         p.error('-ac/--angular_cutoff must lie in (0, 0.5]')
     if not 1 <= a.q_max <= 32:
@@ -162,6 +200,31 @@ def sfactor(natoms, box, pos, qmax, device=0):
     return ssum[:, shells] / mult[None, :], smax[:, shells]
 
 
+def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
+    """Steinhardt bond-order parameters of all samples for the l values ls (strictly increasing, 1..12, at most six), neighbour
+    shell r_lo < d <= r_hi: q and qbar float64 [ns][natoms][nl] (per atom, qbar averaged over the atom and its neighbours), Q float64
+    [ns][nl] (all bonds of the frame) and nb int32 [ns][natoms] (neighbours per atom).  nm_distr_bondorder returns the squares; the
+    roots sqrt(max(x, 0)) are taken here in float64.  natoms is accepted for symmetry with histograms(); the atom count is
+    pos.shape[1]."""
+    L = B.load()
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    box = np.ascontiguousarray(box, dtype=np.float32)
+    ns, n = pos.shape[0], pos.shape[1]
+    ls = np.ascontiguousarray(ls, dtype=np.int32).reshape(-1)
+    nl = len(ls)
+    q2 = np.zeros((ns, n, nl), dtype=np.float64)
+    b2 = np.zeros((ns, n, nl), dtype=np.float64)
+    g2 = np.zeros((ns, nl), dtype=np.float64)
+    nb = np.zeros((ns, n), dtype=np.int32)
+    rc = L.nm_distr_bondorder(device, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), float(r_lo), float(r_hi),
+                              nl, ls.ctypes.data_as(B.c_int_p), q2.ctypes.data_as(B.c_double_p), b2.ctypes.data_as(B.c_double_p),
+                              g2.ctypes.data_as(B.c_double_p), nb.ctypes.data_as(B.c_int32_p))
+    if rc != 0:
+        raise RuntimeError('nm_distr_bondorder failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    root = lambda x: np.sqrt(np.maximum(x, 0.0))
+    return root(q2), root(b2), root(g2), nb
+
+
 def main(argv=None):
     a = parse_args(argv)
     prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, a.element.lower(), LAT[a.element])
@@ -172,6 +235,11 @@ def main(argv=None):
     box = np.load(prefix + '.box.npy').reshape(-1)
     pos = np.load(prefix + '.pos.npy').reshape(-1, natoms[0], 3)
     ns = natoms.size
+    if a.bond_order:
+        try:
+            bcut = bond_cutoff(a.bond_cutoff, natoms[0])
+        except ValueError as e:                                               # the automatic value needs natoms: refused before any file is written
+            raise SystemExit('distr: error: %s' % e)
     nrho, dni, r, dn, rv = calculate_spatial(natoms, box, a.spherical_bins, a.cartesian_bins)
     rns = np.int32(ns / (pn * tn))
     if a.verbose:
@@ -198,6 +266,19 @@ def main(argv=None):
         np.save(prefix + '.sf.npy', sf.astype(np.float32).reshape(pn, tn, rns, shells.size))
         np.save(prefix + '.sfm.npy', sfm.astype(np.float32).reshape(pn, tn, rns, shells.size))
         np.save(prefix + '.nrho.npy', nrho.reshape(pn, tn, rns))
+    if a.bond_order:
+        l = float(np.min(box))
+        n, nl = int(natoms[0]), len(a.bond_l)
+        q, qb, qg, nb = bond_order(natoms, box, pos, a.bond_l, 1e-16 * l, bcut * l, device=int(os.environ.get('LOCAL_RANK', '0')))
+        np.save(prefix + '.bol.npy', np.array(a.bond_l, dtype=np.int64))
+        np.save(prefix + '.boq.npy', q.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
+        np.save(prefix + '.bob.npy', qb.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
+        np.save(prefix + '.bog.npy', qg.astype(np.float32).reshape(pn, tn, rns, nl))
+        np.save(prefix + '.bon.npy', nb.mean(axis=1).astype(np.float32).reshape(pn, tn, rns))
+        if a.bond_atoms:
+            np.save(prefix + '.boqa.npy', q.astype(np.float32).reshape(pn, tn, rns, n, nl))
+            np.save(prefix + '.boba.npy', qb.astype(np.float32).reshape(pn, tn, rns, n, nl))
+            np.save(prefix + '.bona.npy', nb.reshape(pn, tn, rns, n))
     if a.verbose:
         print('all properties pickled')
 

@@ -3,6 +3,7 @@
     python scripts/bench_distr.py [ns=4096] [natoms=256]
     python scripts/bench_distr.py --angles [ns=4096] [cells=4] [cutoff=0.5] [repeats=5]
     python scripts/bench_distr.py --sfactor [ns=4096] [natoms=256] [qmax=16] [repeats=5]
+    python scripts/bench_distr.py --bondorder [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l ...=4 6]
 
 --angles: nm_distr_angles on displaced fcc frames of 4 cells^3 atoms (shell up to cutoff * l; the first shell is about
 0.85 / cells): the time of the whole call (copies + kernel, host clock around the synchronous call, median of the repeats
@@ -11,7 +12,14 @@ kernel's own time comes from `rocprofv3 --kernel-trace --stats -- python scripts
 
 --sfactor: nm_distr_sfactor on random liquids: the time of the whole call as above and the rate in the definition's terms, one
 complex multiply-add (8 flop) per atom and vector of the half space; the kernel's own time from the same rocprofv3 line
-(nm_sfac_kernel)."""
+(nm_sfac_kernel).
+
+--bondorder: nm_distr_bondorder on the frames and shapes of --angles (cutoff 0 = the first fcc shell, 0.853553 / cells), all four
+outputs: the time of the whole call as above, bonds/s, the same call of nm_distr_angles on the same frames and shell next to it
+(the yardstick: it pays for one scan of the candidates, the bond-order path for two plus the harmonics), and the numpy
+restatement on one host core over one sample (imported from tests/bondorder_ref.py, as --angles imports tests/adf_ref.py: the
+script needs the tests directory next to it).  The kernels' own times come from the same rocprofv3 line
+(nm_bo_moments_kernel, nm_bo_average_kernel, nm_bo_global_kernel, nm_adf_kernel)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -96,6 +104,70 @@ def bench_sfactor(argv):
           'median of %d: %.4f s (min %.4f, max %.4f) = %.2f T flop/s at 8 flop each; mean S %.4f'
           % (ns, n, qmax, nvec, cma, reps, dt, min(ts), max(ts), 8 * cma / dt / 1e12, ssum.sum() / (2.0 * nvec * ns)))
 
+
+def bench_bondorder(argv):
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import bondorder_ref as R
+    from neuralmelting_amd import _lib as B, lattice
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    cells = int(argv[1]) if len(argv) > 1 else 4
+    cut = float(argv[2]) if len(argv) > 2 else 0.0
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    ls = np.array([int(x) for x in argv[4:]] or [4, 6], dtype=np.int32)
+    rng = np.random.default_rng(3)                                            # the frames of bench_angles
+    n = 4 * cells ** 3
+    cut = distr.bond_cutoff(cut, n)
+    a0 = lattice.lattice_constant('LJ')
+    box = (cells * a0 * (1.0 + 0.05 * rng.random(ns))).astype(np.float32)
+    frac = lattice.fcc_fractional(cells)
+    pos = ((frac[None] + 0.08 / cells * rng.normal(size=(ns, n, 3))) % 1.0 * box[:, None, None]).astype(np.float32)
+    pos = np.minimum(pos, np.nextafter(box, np.float32(0))[:, None, None])
+    l = float(box.min())
+    L = B.load()
+    nl = len(ls)
+    q2, b2, g2 = np.zeros((ns, n, nl)), np.zeros((ns, n, nl)), np.zeros((ns, nl))
+    nb = np.zeros((ns, n), dtype=np.int32)
+    ce = np.ascontiguousarray(np.cos(np.linspace(1e-16, np.pi, 64)))
+    adf = np.zeros((ns, 64), dtype=np.uint64)
+
+    def run(m):
+        rc = L.nm_distr_bondorder(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, nl,
+                                  ls.ctypes.data_as(B.c_int_p), q2.ctypes.data_as(B.c_double_p), b2.ctypes.data_as(B.c_double_p),
+                                  g2.ctypes.data_as(B.c_double_p), nb.ctypes.data_as(B.c_int32_p))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+
+    def run_angles(m):
+        rc = L.nm_distr_angles(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, 64,
+                               ce.ctypes.data_as(B.c_double_p), adf.ctypes.data_as(B.c_uint64_p))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+    med = {}
+    for name, f in (('bondorder', run), ('angles', run_angles)):
+        f(min(ns, 8))
+        f(ns)                                                                 # warm-up at the timed shape
+        ts = []
+        for _ in range(reps):
+            t = time.perf_counter(); f(ns); ts.append(time.perf_counter() - t)
+        med[name] = (float(np.median(ts)), min(ts), max(ts))
+    bonds = int(nb.sum())
+    dt = med['bondorder'][0]
+    print('bondorder: %d samples x %d atoms, cutoff %.4f l, l = %s: %d bonds (%.1f neighbours per centre, %d at most); call (H2D + kernels '
+          '+ D2H) median of %d: %.4f s (min %.4f, max %.4f) = %.2f G bonds/s, %.1f M centres/s; mean q %s, qbar %s, Q %s'
+          % (ns, n, cut, ls.tolist(), bonds, bonds / (ns * n), nb.max(), reps, dt, med['bondorder'][1], med['bondorder'][2],
+             bonds / dt / 1e9, ns * n / dt / 1e6, np.sqrt(q2).mean(axis=(0, 1)).round(4), np.sqrt(b2).mean(axis=(0, 1)).round(4),
+             np.sqrt(g2).mean(axis=0).round(4)))
+    print('angles on the same frames and shell, 64 edges: call median of %d: %.4f s (min %.4f, max %.4f); bondorder / angles = %.2f'
+          % (reps, med['angles'][0], med['angles'][1], med['angles'][2], dt / med['angles'][0]))
+    t = time.perf_counter()
+    R.bond_order2(pos[:1], box[:1], ls.tolist(), 1e-16 * l, cut * l)
+    dt = time.perf_counter() - t
+    print('numpy restatement, one core, sample 0: %.3f s = %.2f samples/s, %.1f centres/s' % (dt, 1 / dt, n / dt))
+
+
+if '--bondorder' in sys.argv:
+    bench_bondorder([x for x in sys.argv[1:] if x != '--bondorder'])
+    sys.exit(0)
 
 if '--sfactor' in sys.argv:
     bench_sfactor([x for x in sys.argv[1:] if x != '--sfactor'])
