@@ -76,6 +76,7 @@ struct KParams {
     // tagged rec_tag0 + c once the slot's block of that cycle has completed
     double *rec;
     uint32_t rec_tag0;
+    int start_handover;            // NM_START_HANDOVER=1: every trajectory starts with the hand-over of the first step's positions (A/B, tests)
 };
 
 // one slot's record of a recorded cycle: the 17 thermo columns (remcmc:208), box, tag, then x[3N]

@@ -42,10 +42,16 @@ constexpr int NVMAX = 16; // widest block reduction (the 16 raw moments of hmc_v
 #else
 #define RTL(k) do { } while (0)
 #endif
+#if defined(NM_TL_START) && !defined(NM_TL_REBUILD) // a third one: the start of a trajectory (advance_and_share modes 1, 4, 5) stamps its entry into
+#define TLINE_START() TLINE_PREV(5)                 // slot 5 of the energy evaluation it follows (scripts/probe_timeline.py, NM_TL_START=1)
+#else
+#define TLINE_START() do { } while (0)
+#endif
 #else
 #define TLINE(k) do { } while (0)
 #define TLINE_PREV(k) do { } while (0)
 #define RTL(k) do { } while (0)
+#define TLINE_START() do { } while (0)
 #endif
 #ifdef NM_PROF
 #define NM_PROF_SLOTS 16
@@ -194,8 +200,16 @@ struct Cfg {
     static constexpr int LOG2PW = sizeof(IdxT) == 1 ? 3 : 2;
     static_assert(!LIST_LDS || ((sizeof(IdxT) == 1 || sizeof(IdxT) == 2) && MAXNB % (PW * TPA) == 0), "LDS lists: MAXNB a multiple of PW*TPA");
     static constexpr int QMAX = 8;                                               // most workgroups per replica
-    static constexpr size_t XBUF_GRANULES = (size_t)4 * NMAX + 4 * QMAX;         // forces by component, EAM densities, per-workgroup partials
+    // LOCAL_START: a trajectory starts without a hand-over where every workgroup can compute the first kick and drift of ALL atoms itself (the
+    // 4^3 cluster configurations — own rows only, NLIST < NMAX — whose saved forces of all atoms fit in LDS): the exchange buffers get a board
+    // of 3 NMAX granules for the forces that an energy evaluation publishes with its partial sums (Replica::exchange_sums, gaussian_fill,
+    // advance_and_share modes 4 and 5).
+    static constexpr bool LOCAL_START = SAVEF_LDS && NLIST_ < NMAX_;
+    // rarely-touched uniform scalars (Replica::ust) that gaussian_fill reads and writes as 64-bit words
+    static constexpr int UST_BOARD = 24, UST_BOARD_MAGIC = 25, UST_BOARD_OWN = 26, UST_BOARD_LATE = 28;
+    static constexpr size_t XBUF_GRANULES = (size_t)(LOCAL_START ? 7 : 4) * NMAX + 4 * QMAX; // positions by component, EAM densities, per-workgroup partials, board
     static constexpr size_t XG_PART = (size_t)3 * NMAX, XG_RHO = (size_t)3 * NMAX + 4 * QMAX; // granule indices
+    static constexpr size_t XG_BOARD = (size_t)4 * NMAX + 4 * QMAX;              // start forces by component (LOCAL_START)
     static constexpr size_t XBUF_DOUBLES = 2 * XBUF_GRANULES;                    // one exchange buffer (there are two per slot)
 };
 
@@ -217,6 +231,35 @@ __device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int
     double *const gx = (double *)(nm_lds + C::OFF_VEL), *const gy = gx + C::NMAX, *const gz = gy + C::NMAX;
     const double twopi = 6.283185307179586476925286766559;
     const double fac = 1.0 / sqrt(mass);
+    // LOCAL_START, and the caller armed it (Replica::hmc_velocities: ust slot UST_BOARD holds the board of the exchange just made): the peers'
+    // forces that the coming trajectory starts from are asked for here — one atom per thread, three granules as six 8-byte loads past L1 — and
+    // taken into sf[] behind the gaussians, whose arithmetic covers the round trip that advance_and_share mode 4 would wait for.  The granules
+    // were stored before their publishers completed the exchange this workgroup has already left, so they arrive whatever the peers do next; a
+    // granule that has not landed yet (or is torn: the two words of a granule are loaded separately here) fails its tag and is asked for again.
+    [[maybe_unused]] unsigned long long bw[6] = { 0, 0, 0, 0, 0, 0 }, bmg = 0;
+    [[maybe_unused]] const unsigned long long *bg = nullptr;
+    [[maybe_unused]] unsigned long long *us = nullptr;
+    [[maybe_unused]] int bi = -1;
+    if constexpr (C::LOCAL_START) {
+        static_assert(C::NMAX <= C::BLOCK, "one atom per thread");
+        us = (unsigned long long *)(nm_lds + C::OFF_UST) + (tid >> 6) * C::UST_PER_WAVE;
+        const unsigned long long b = us[C::UST_BOARD];
+        bg = (const unsigned long long *)(uintptr_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
+                                                     (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+        if (bg) {
+            bmg = us[C::UST_BOARD_MAGIC];
+            const int a0 = (int)(us[C::UST_BOARD_OWN] & 0xffffu), a1 = (int)(us[C::UST_BOARD_OWN] >> 16), nown = a1 - a0;
+            if (tid < N - nown) {
+                bi = tid < a0 ? tid : tid + nown;
+                bg += 2 * (size_t)bi;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    bw[2 * c] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    bw[2 * c + 1] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
     for (int w = tid; w < 2 * N; w += BLOCK) {
         const int part = w >= N ? 1 : 0, i = w - part * N;
         uint32_t o[4];
@@ -228,6 +271,31 @@ __device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int
         if (part) gz[i] = r * cs * fac;
         else { gx[i] = r * cs * fac; gy[i] = r * sn * fac; }
     }
+    if constexpr (C::LOCAL_START)
+        if (bg) {
+            int late = 0;
+            if (bi >= 0) {
+                unsigned long long t0 = 0;
+                int spins = 0;
+                while (((bw[0] ^ bw[1]) != bmg) | ((bw[2] ^ bw[3]) != bmg) | ((bw[4] ^ bw[5]) != bmg)) {
+                    __builtin_amdgcn_s_sleep(1);
+                    if ((++spins & 63) == 0) { // bounded like every poll of a granule: 2 s of the 100 MHz clock
+                        const unsigned long long now = wall_clock64();
+                        if (t0 == 0) t0 = now | 1ull;
+                        else if (now - t0 > 200000000ull) { late = 1; break; }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        bw[2 * c] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        bw[2 * c + 1] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                double *const sf = (double *)(nm_lds + C::OFF_SAVF);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) sf[(size_t)c * C::NMAX + bi] = __longlong_as_double((long long)bw[2 * c]);
+            }
+            if (__ballot(late) != 0) us[C::UST_BOARD_LATE] = 1; // the start that follows reports it (ST_SYNC_TIMEOUT)
+        }
 }
 
 template <class C>
@@ -360,11 +428,16 @@ struct Replica {
                                              // own atoms when the evaluation made the last half kick of a trajectory
     // slot k of this wave's copy of the rarely-touched uniform scalars (every lane of the wave reads / writes the same value)
     __device__ __forceinline__ double &ust(int k) const { return ((double *)(nm_lds + C::OFF_UST))[(tid >> 6) * C::UST_PER_WAVE + k]; }
+    __device__ __forceinline__ unsigned long long &ustu(int k) const { return ((unsigned long long *)(nm_lds + C::OFF_UST))[(tid >> 6) * C::UST_PER_WAVE + k]; }
     // block-uniform flags in ONE scalar register (three separate bools cost lane masks and spilled scalars in the hot loops)
-    enum : int { F_LIST_OK = 1, F_FRESH = 2, F_SAVED_FRESH = 4, F_LIST_SAVED = 8, F_REBUILT = 16 };
+    // LOCAL_START only — F_BOARD: the peers' forces that belong to f[] of the own atoms stand on the board of the exchange just made (generation
+    // gen - 1): set by finish_sums, gone with the forces (set_fresh(false): a restore, a move, a hand-over — whatever takes the next generation
+    // also goes through there).  F_SF_ALL: sf[] of the OTHER atoms holds the peers' forces of the saved configuration (written by the local start
+    // of a trajectory; any accepted move clears it, restore() keeps it, save() never writes those entries).
+    enum : int { F_LIST_OK = 1, F_FRESH = 2, F_SAVED_FRESH = 4, F_LIST_SAVED = 8, F_REBUILT = 16, F_BOARD = 32, F_SF_ALL = 64 };
     int flags = 0;
     __device__ __forceinline__ bool fresh() const { return (flags & F_FRESH) != 0; }
-    __device__ __forceinline__ void set_fresh(bool b) { flags = b ? (flags | F_FRESH) : (flags & ~F_FRESH); }
+    __device__ __forceinline__ void set_fresh(bool b) { flags = b ? (flags | F_FRESH) : (flags & ~(C::LOCAL_START ? F_FRESH | F_BOARD : F_FRESH)); }
     int status = 0;
     // LIST2: the other list of the slot, and what belongs to the list a move started from
     typename ArrSel<C::LDS_LIST2, double, C::OFF_X0S>::type x0s; typename ArrSel<C::LDS_LIST2, double, C::OFF_X0S + A1>::type y0s;
@@ -519,6 +592,14 @@ struct Replica {
         if (with_v && Q > 1) {
             // (mapping) a Hamiltonian move: the first kick and drift that follow overwrite x, v of the own atoms on thread i - a0, so
             // that thread saves them, and the caller's barrier after wrap() has made them current for it; the other atoms as usual
+            // (LOCAL_START: the others on the thread that takes them in advance_and_share, which may advance them at once — modes 4 and 5)
+            if constexpr (C::LOCAL_START) {
+                const int nown = a1 - a0, shift = ((nown + 63) & ~63) % BLOCK;
+                for (int o = (tid + BLOCK - shift) % BLOCK; o < N - nown; o += BLOCK) {
+                    const int i = o < a0 ? o : o + nown;
+                    sx[i] = px[i]; sy[i] = py[i]; sz[i] = pz[i]; svx[i] = vx[i]; svy[i] = vy[i]; svz[i] = vz[i];
+                }
+            } else
             for (int i = tid; i < N; i += BLOCK)
                 if (i < a0 || i >= a1) { sx[i] = px[i]; sy[i] = py[i]; sz[i] = pz[i]; svx[i] = vx[i]; svy[i] = vy[i]; svz[i] = vz[i]; }
             NM_FOR_OWN(i) { sx[i] = px[i]; sy[i] = py[i]; sz[i] = pz[i]; svx[i] = vx[i]; svy[i] = vy[i]; svz[i] = vz[i]; }
@@ -1469,14 +1550,24 @@ struct Replica {
     // alternate; a workgroup can only run one exchange ahead of the slowest one (it needs everybody's data of generation g
     // to finish g), so buffer g&1 is never overwritten while someone still reads it.  Spins are bounded: a cluster that is
     // not co-resident reports ST_SYNC_TIMEOUT instead of hanging.
+    // The force board (Cfg::LOCAL_START) is the one region that is read AFTER its exchange: the energy evaluation's exchange of generation g
+    // leaves the own atoms' forces in buffer g&1 under magic(g), and the trajectory start reads the peers' when this workgroup has completed
+    // g and stands at generation g + 1 (gaussian_fill, advance_and_share mode 4).  It publishes nothing of g + 1 before it has them: a local
+    // start takes no generation, and whatever comes next (the first position hand-over, or the partial sums of a one-step trajectory) is
+    // issued behind the start's closing barrier.  A peer needs that publication to complete g + 1, and only then can it store generation
+    // g + 2 into buffer g&1, the board of g + 2 included — so the board of g is never overwritten before every workgroup has read it.  The
+    // board is used for the exchange just made and no older one (F_BOARD dies with the forces it belongs to), which is what keeps this short.
+    // Between blocks of one launch the region is as safe as the rest of the buffer: a block's last move publishes no board, and its first
+    // board (generation >= 1) lies behind an exchange of generation 0 that needs every peer in the new block.
     typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     // a workgroup whose own list overflowed publishes under magic ^ POISON: the peers accept the granule and learn the status
     // from it (the only status bit that is not identical in all workgroups of a cluster), so no status words are exchanged
     static constexpr unsigned long long POISON = 0x5555555555555554ull;
-    __device__ __forceinline__ unsigned long long magic() const
+    __device__ __forceinline__ unsigned long long magic_at(int g) const
     {
-        return ((unsigned long long)p.launch_id << 32 | (unsigned long long)(uint32_t)(gen + 1)) * 0x9E3779B97F4A7C15ull | 1ull;
+        return ((unsigned long long)p.launch_id << 32 | (unsigned long long)(uint32_t)(g + 1)) * 0x9E3779B97F4A7C15ull | 1ull;
     }
+    __device__ __forceinline__ unsigned long long magic() const { return magic_at(gen); }
     __device__ __forceinline__ void put_granule(double *g, double v, unsigned long long mg)
     {
         u64x2 w;
@@ -1540,7 +1631,9 @@ struct Replica {
 
     // What crosses the cluster (Q > 1): every workgroup holds all positions but computes forces for, and integrates, only its
     // own atoms a0..a1.  So an HMC step exchanges the NEW POSITIONS of the own atoms (advance_and_share), an energy evaluation
-    // exchanges per-workgroup partial sums (exchange_sums), the EAM adds its densities (pair_loop_sc); forces never travel.
+    // exchanges per-workgroup partial sums (exchange_sums), the EAM adds its densities (pair_loop_sc).  Forces travel in one place: the 4^3
+    // cluster configurations (Cfg::LOCAL_START) publish the own atoms' forces with the partial sums of an energy evaluation, and the trajectory
+    // that starts from them computes the first step of ALL atoms in every workgroup instead of handing its positions over.
     // Every exchange is all-to-all and takes the next generation number; a workgroup whose list overflowed marks whatever it
     // publishes next with POISON, and whoever reads it takes over the status bit, so the cluster leaves the block together.
     __device__ __forceinline__ unsigned long long my_magic() const { return magic() ^ ((status & ST_LIST_OVERFLOW) ? POISON : 0ull); }
@@ -1548,8 +1641,10 @@ struct Replica {
     // cluster-wide sums of K per-workgroup partial sums (identical in all threads of the workgroup on entry): lane r of every
     // wave fetches workgroup r's K granules in one round trip, then the lanes are added in workgroup order, so every thread
     // of every workgroup ends with the identical bits.  Ends with a barrier.
+    // board (LOCAL_START, the exchange of an energy evaluation a trajectory can follow): the own atoms' threads also publish the forces of their
+    // atoms, behind the partial sums the peers are waiting for; nobody waits for them here (advance_and_share mode 4 reads them).
     template <int K>
-    __device__ void exchange_sums(double (&s)[K])
+    __device__ void exchange_sums(double (&s)[K], bool board = false)
     {
         static_assert(K == 4, "one instantiation: callers pad with zeros");
         if (Q == 1) return;
@@ -1561,6 +1656,15 @@ struct Replica {
             for (int k = 1; k < K; ++k) mine = (tid == k) ? s[k] : mine;
             put_granule(xg + 2 * (size_t)(C::XG_PART + 4 * q + tid), mine, my_magic());
         }
+        if constexpr (C::LOCAL_START)
+            if (board) {
+                const unsigned long long mgp = my_magic();
+                NM_FOR_OWN(i) {
+                    put_granule(xg + 2 * (C::XG_BOARD + (size_t)i), fx[i], mgp);
+                    put_granule(xg + 2 * (C::XG_BOARD + (size_t)(NMAX + i)), fy[i], mgp);
+                    put_granule(xg + 2 * (C::XG_BOARD + (size_t)(2 * NMAX + i)), fz[i], mgp);
+                }
+            }
         int timeout = 0, poisoned = 0;
         const int lane = tid & 63;
         double v[K];
@@ -1642,11 +1746,21 @@ struct Replica {
     // mode 1: one half kick + drift; 3: the pair loop did it already (eval_force): f[] holds the new positions of the own atoms
     // and they are published; 2 (HALF configurations, whose forces are complete only behind the pair loop's barrier): the two half kicks
     // around the evaluation that just ended — final_integrate of its step, initial_integrate of the next — and the drift.
+    // 4 and 5 (LOCAL_START, Q > 1): mode 1 without the hand-over.  Every workgroup holds x and the freshly created v of ALL atoms and lacks only
+    // the peers' forces: mode 4 fetches them from the board of the energy evaluation just exchanged (generation gen - 1: long landed, one round
+    // trip, the same bounded poll) and keeps them in sf[]; mode 5 finds them there (F_SF_ALL: the start configuration is the saved one).  The
+    // thread then makes the peer's own first kick and drift, fma(h, fma(dtfm, f, v), x): the bits the peer would have published.  Nothing is
+    // published and no generation is taken.  The peers' atoms go on the threads that fetch them in the other modes, which are the threads
+    // that have just saved them (save(true)); velocity_create and wrap wrote them in front of the caller's barrier.  Their velocities are
+    // not advanced (they are stale during a trajectory anyway).  The board is usually taken into sf[] while the velocities are drawn
+    // (gaussian_fill), so mode 4 is left with the starts whose evaluation comes behind the velocities.
     __device__ bool advance_and_share(int mode, double dtfm, double h)
     {
         int timeout = 0, poisoned = 0;
         double *xg = xb ? xb + (size_t)(gen & 1) * C::XBUF_DOUBLES : nullptr;
         const unsigned long long mg = magic(), mgp = my_magic();
+        const bool local = C::LOCAL_START && mode >= 4;
+        if (mode == 1 || local) TLINE_START();
         // the own atoms first and nothing in their way: the peers are waiting for these granules
         NM_FOR_OWN(i) {
             const double gx = fx[i], gy = fy[i], gz = fz[i];
@@ -1656,7 +1770,7 @@ struct Replica {
             vx[i] = ux; vy[i] = uy; vz[i] = uz;
             const double nx = __builtin_fma(h, ux, px[i]), ny = __builtin_fma(h, uy, py[i]), nz = __builtin_fma(h, uz, pz[i]);
             px[i] = nx; py[i] = ny; pz[i] = nz;
-            if (Q > 1) {
+            if (Q > 1 && !local) {
                 put_granule(xg + 2 * (size_t)i, nx, mgp);
                 put_granule(xg + 2 * (size_t)(NMAX + i), ny, mgp);
                 put_granule(xg + 2 * (size_t)(2 * NMAX + i), nz, mgp);
@@ -1668,18 +1782,35 @@ struct Replica {
         if (Q > 1) {
             const int nown = a1 - a0, nother = N - nown;
             const int shift = ((nown + 63) & ~63) % BLOCK; // the fetching starts on the waves after the ones that integrate
+            // (ONE loop and one get_granules for all modes; `local` is a compile-time false outside LOCAL_START)
+            double *const gr = local ? xb + (size_t)((gen - 1) & 1) * C::XBUF_DOUBLES + 2 * C::XG_BOARD : xg;
+            const unsigned long long mgr = local ? magic_at(gen - 1) : mg;
+            if constexpr (C::LOCAL_START)
+                if (local && ustu(C::UST_BOARD_LATE) != 0) timeout = 1; // (gaussian_fill gave up on a granule of the board)
             for (int o = (tid + BLOCK - shift) % BLOCK; o < nother; o += BLOCK) {
                 const int i = o < a0 ? o : o + nown;
-                double *const g3[3] = { xg + 2 * (size_t)i, xg + 2 * (size_t)(NMAX + i), xg + 2 * (size_t)(2 * NMAX + i) };
+                double *const g3[3] = { gr + 2 * (size_t)i, gr + 2 * (size_t)(NMAX + i), gr + 2 * (size_t)(2 * NMAX + i) };
                 double x3[3];
                 const double rx = x0[i], ry = y0[i], rz = z0[i]; // (read before the poll: at 8^3 they come from the global spill, a memory latency that
                 // now lies under the granules' round trip instead of behind it)
-                if (get_granules<3>(g3, mg, x3, timeout, poisoned)) {
+                bool got = true;
+                if constexpr (C::LOCAL_START) {
+                    if (mode == 5) { x3[0] = sfx[i]; x3[1] = sfy[i]; x3[2] = sfz[i]; }
+                    else got = get_granules<3>(g3, mgr, x3, timeout, poisoned);
+                    if (local && got) {
+                        if (mode == 4) { sfx[i] = x3[0]; sfy[i] = x3[1]; sfz[i] = x3[2]; }
+                        x3[0] = __builtin_fma(h, __builtin_fma(dtfm, x3[0], vx[i]), px[i]);
+                        x3[1] = __builtin_fma(h, __builtin_fma(dtfm, x3[1], vy[i]), py[i]);
+                        x3[2] = __builtin_fma(h, __builtin_fma(dtfm, x3[2], vz[i]), pz[i]);
+                    }
+                } else got = get_granules<3>(g3, mg, x3, timeout, poisoned);
+                if (got) {
                     px[i] = x3[0]; py[i] = x3[1]; pz[i] = x3[2];
                     check_atom(c, x3[0], x3[1], x3[2], rx, ry, rz);
                 }
             }
-            ++gen;
+            if (local) flags |= F_SF_ALL;
+            else ++gen;
         }
         set_fresh(false);
         TLINE_PREV(6);
@@ -1796,12 +1927,15 @@ struct Replica {
     // (Initialised to -1 and to nothing else: with 0 the eleven kernels move again.)
     int layout_pad = -1;
     // completes an energy evaluation; `extra` is one more per-workgroup partial sum that rides along.
-    __device__ double finish_sums(double extra)
+    // board: a trajectory can start from this evaluation's forces, so they go on the board (exchange_sums).
+    __device__ double finish_sums(double extra, bool board = false)
     {
         double s[4] = { psum[0], psum[1], psum[2], extra };
-        exchange_sums<4>(s);
+        exchange_sums<4>(s, board);
         psum[0] = s[0]; psum[1] = s[1]; psum[2] = s[2];
         take_sums();
+        if constexpr (C::LOCAL_START)
+            if (board && Q > 1) flags |= F_BOARD;
         return s[3];
     }
 
@@ -1823,7 +1957,18 @@ struct Replica {
     {
         short *img = nullptr;
         if constexpr (!C::SAVE_LDS) img = im.g;
+        // LOCAL_START: the forces on the board are those the trajectory starts from (F_BOARD implies F_FRESH: nothing is evaluated in
+        // between): gaussian_fill takes them into sf[] under its arithmetic, and the start finds them there (mode 5)
+        [[maybe_unused]] bool pre = false;
+        if constexpr (C::LOCAL_START) {
+            pre = Q > 1 && (flags & F_BOARD);
+            ustu(C::UST_BOARD) = pre ? (unsigned long long)(uintptr_t)(xb + (size_t)((gen - 1) & 1) * C::XBUF_DOUBLES + 2 * C::XG_BOARD) : 0ull;
+            ustu(C::UST_BOARD_MAGIC) = magic_at(gen - 1);
+            ustu(C::UST_BOARD_OWN) = (unsigned long long)a0 | (unsigned long long)a1 << 16;
+        }
         const double mv2 = velocity_create<C>(t, tag, L, N, gslot, parity, p.mass, p.mvv2e, p.kB, p.seed, p.step, img);
+        if constexpr (C::LOCAL_START)
+            if (pre) flags = (flags & ~F_BOARD) | F_SF_ALL;
         parity ^= 1;
         return uniform(mv2); // (the caller's barrier after wrap() orders these velocities for the threads that take the own atoms next)
     }
@@ -2566,6 +2711,10 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     U0 = 0.0; W0 = 0.0; c_pe = 0.0; c_vol = 0.0; c_volnew = 0.0; c_boxl = 0.0;
     double &nth_entry = R.ust(22); // (stats column 7)
     nth_entry = nth;
+    if constexpr (C::LOCAL_START) {
+        R.ust(23) = 0.0; // trajectory starts without a hand-over (stats column 10)
+        R.ustu(C::UST_BOARD_LATE) = 0;
+    }
     // (ST_FORCE_RANGE is set here only by nm_run_md: a plain NVE run has no move to reject, so it stops)
     const int fatal = ST_BOX_TOO_SMALL | ST_LIST_OVERFLOW | ST_SYNC_TIMEOUT | ST_FORCE_RANGE;
 
@@ -2586,7 +2735,13 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             R.eval(have_need, pre_need, phase == PH_HMC_STEP, c_dtfm);
             // cluster-wide U, W of an energy evaluation — ONE exchange site; the kinetic energy rides along.
             if (!(st_before & fatal) && !(R.status & (ST_BOX_TOO_SMALL | ST_SYNC_TIMEOUT)))
-                mv2new = R.finish_sums(phase == PH_HMC_STEP ? R.psum[3] : 0.0);
+            {
+                // LOCAL_START: the forces go on the board where a trajectory can start from them, i.e. unless this was the block's last move
+                bool board = false;
+                if constexpr (C::LOCAL_START)
+                    board = !p.start_handover && !p.eval_only && ((phase == PH_INIT || phase == PH_HMC_START) ? m : m + 1) < p.mod;
+                mv2new = R.finish_sums(phase == PH_HMC_STEP ? R.psum[3] : 0.0, board);
+            }
         }
         skip_eval = false;
         have_need = false;
@@ -2648,7 +2803,15 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             // positions over.  The NSTPS-th evaluation also wants the energy: it is the generic one at the top of this loop.
             const double dtfm_ = uniform(c_dtfm), h_ = uniform(c_h);
             PROF_BEGIN();
-            pre_need = R.advance_and_share(1, dtfm_, h_);
+            // LOCAL_START: no hand-over where the peers' forces of this configuration are at hand — on the board of the evaluation just made, or
+            // in sf[] after a rejection.  flags is replica-uniform state, so all workgroups of the cluster take the same branch.
+            int smode = 1;
+            if constexpr (C::LOCAL_START)
+                if (R.Q > 1 && !p.start_handover && (R.flags & (R.F_BOARD | R.F_SF_ALL))) {
+                    smode = (R.flags & R.F_BOARD) ? 4 : 5;
+                    R.ust(23) += 1.0;
+                }
+            pre_need = R.advance_and_share(smode, dtfm_, h_);
             PROF_END(9);
             const int nfo = p.nstps - 1;
             for (int s = 0; s < nfo; ++s) {
@@ -2681,6 +2844,8 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             branch = 2.0; move_done = true;
         }
         if (move_done) {
+            if constexpr (C::LOCAL_START)
+                if (acc) R.flags &= ~R.F_SF_ALL; // the saved configuration is no longer the one to come back to
             if constexpr (!PLAIN)
                 if (p.trace && writer) {
                     double *tr = p.trace + ((size_t)slot * p.mod + m) * 4;
@@ -2717,6 +2882,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 if constexpr (!PLAIN) { // (not instantiated for the production form)
                     double c2 = 0.0;
                     const int na = R.iter_pmc((uint32_t)m, et, dx, ntp, nap, c2);
+                    if constexpr (C::LOCAL_START) R.flags &= ~R.F_SF_ALL;
                     if (__builtin_amdgcn_readfirstlane(R.status) & fatal) break; // (its exchange of energy differences failed)
                     if constexpr (C::EAM) { // close the move with a full evaluation (c_vol, c_volnew are free during a position move)
                         c_vol = (double)na; c_volnew = c2;
@@ -2821,6 +2987,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         const unsigned long long ticks = wall_clock64() - t_entry;
         if (p.last_ticks) p.last_ticks[slot] = ticks;
         st[4] += (double)ticks; st[5] += R.same_xcd ? 1.0 : 0.0; st[6] += 1.0; st[7] += nth - nth_entry; st[9] = (double)C::MAXNB;
+        if constexpr (C::LOCAL_START) st[10] += R.ust(23);
 #ifdef NM_PROF
         if (p.prof) for (int q = 0; q < NM_PROF_SLOTS; ++q) p.prof[(size_t)slot * NM_PROF_SLOTS + q] += R.prof_acc[q];
 #endif

@@ -243,7 +243,8 @@ class Engine:
 
     def stats(self, reset=False):
         """per-slot (evaluations, list rebuilds, energy evaluations, interacting pairs summed over those, block time in 100 MHz ticks,
-        blocks handed over inside one XCD, blocks, HMC moves, longest list row built, list slots per atom) since the last reset"""
+        blocks handed over inside one XCD, blocks, HMC moves, longest list row built, list slots per atom, HMC moves whose trajectory
+        started without a hand-over inside the cluster) since the last reset"""
         s = np.empty((self.nslots, B.NM_STATS_COLS))
         self._settled(self.lib.nm_stats_get(self.h, _dp(s), int(reset)))
         return s

@@ -29,6 +29,8 @@ L = _lib.load()
 L.nm_tline_get.argtypes = [C.c_void_p, C.c_void_p]
 buf = np.zeros((8, 8, 512, 8), dtype=np.uint64)   # [q][wave][eval][point]
 L.nm_tline_get(e.h, buf.ctypes.data)
+if os.environ.get('NM_TL_DUMP'):   # the raw stamps, for a look of one's own
+    np.save(os.environ['NM_TL_DUMP'], buf)
 Q = e.cus_per_replica
 t = buf[:Q].astype(np.int64)
 n = int((t[0, 0, :, 0] > 0).sum())
@@ -60,6 +62,15 @@ print('  hand-over: last pair done -> granules in (per wave) median %7.0f max %7
     np.median(np.array([np.max(t[:, :, k, 7]) - np.max(t[:, :, k, 3]) for k in ev]) * 10.0)))
 print('  barrier after the pair loop: last pair done -> last wave past it %7.0f' % np.median(np.array([np.max(t[:, :, k, 4]) - np.max(t[:, :, k, 3]) for k in ev]) * 10.0))
 print('  hand-over barrier -> next entry %7.0f' % np.median(np.array([np.min(t[:, :, k + 1, 0]) - np.max(t[:, :, k, 7]) for k in ev]) * 10.0))
+if os.environ.get('NM_TL_START'):   # the expst build (make expst): slot 5 of an energy evaluation holds the entry of the trajectory start behind it, i.e.
+    # the end of save(true); 6 and 7 the two sides of the barrier that closes it.  Evaluations no trajectory started behind keep slot 5 < slot 4.
+    ks = [k for k in range(20, min(n - 1, 400)) if t[0, 0, k, 5] > t[0, 0, k, 4] and t[0, 0, k, 7] > t[0, 0, k, 5]]
+    per_wg = np.array([[np.max(t[q, :, k, 7]) - np.min(t[q, :, k, 5]) for q in range(Q)] for k in ks]) * 10.0
+    whole = np.array([np.max(t[:, :, k, 7]) - np.min(t[:, :, k, 5]) for k in ks]) * 10.0
+    gran = np.array([[np.max(t[q, :, k, 6]) - np.min(t[q, :, k, 5]) for q in range(Q)] for k in ks]) * 10.0
+    print('  trajectory start, end of save(true) -> past the closing barrier (ns), %d starts: per workgroup median %.0f mean %.0f p10 %.0f p90 %.0f ; '
+          'cluster (first entry -> last exit) median %.0f ; entry -> last wave at the barrier, per workgroup median %.0f' % (
+              len(ks), np.median(per_wg), per_wg.mean(), np.percentile(per_wg, 10), np.percentile(per_wg, 90), np.median(whole), np.median(gran)))
 wg_done = np.array([[np.max(t[q, :, k, 3]) for q in range(Q)] for k in ev])
 print('  skew between workgroups at pair-loop end (max-min) %7.0f' % np.median((wg_done.max(1) - wg_done.min(1)) * 10.0))
 flat = buf.reshape(-1)
