@@ -1595,6 +1595,86 @@ int nm_get_exchange_crit(nm_ctx *c, double *crit, int n)
 namespace {
 thread_local std::string g_distr_error;
 int dfail(int code, const std::string &m) { g_distr_error = m; return code; }
+int refuse(const char *fn, const char *why) { return dfail(NM_ERR_ARG, std::string(fn) + ": " + why); }
+
+// a failed HIP call ends the entry point `fn` with NM_ERR_HIP; what it allocated is freed by the buffers' destructors
+#define DISTR_CHK(fn, call)                                                                            \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) return dfail(NM_ERR_HIP, std::string(fn) + ": " + #call + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// device memory that is freed on every way out of the scope that holds it
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { hipFree(p); }
+    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
+    operator T *() const { return p; }
+};
+
+// makes `device` the calling thread's device.  A negative ordinal is refused before a device is looked for: it is the
+// last of an entry point's NM_ERR_ARG that needs none
+int distr_device(const char *fn, int device)
+{
+    if (device < 0) return refuse(fn, "device ordinal out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, std::string(fn) + ": no HIP device available");
+    if (device >= ndev) return refuse(fn, "device ordinal out of range");
+    DISTR_CHK(fn, hipSetDevice(device));
+    return NM_OK;
+}
+
+constexpr int DISTR_CHUNK = 4096; // most samples per launch: bounds device memory (pos 12 N B + results) for long trajectories
+
+// The chunk loop of an entry point: the device copies of `cs` samples' positions and boxes, filled for one chunk after the
+// other; body(s0, n) computes the samples s0 .. s0 + n - 1 from them (launch, synchronise, copy back) and returns NM_OK or
+// what it failed with.
+struct DistrChunks {
+    DevBuf<float> pos, box;
+    template <class Body>
+    int run(const char *fn, int ns, int cs, int natoms, const float *h_pos, const float *h_box, Body &&body)
+    {
+        DISTR_CHK(fn, pos.alloc((size_t)cs * natoms * 3));
+        DISTR_CHK(fn, box.alloc((size_t)cs));
+        for (int s0 = 0; s0 < ns; s0 += cs) {
+            const int n = (ns - s0) < cs ? (ns - s0) : cs;
+            DISTR_CHK(fn, hipMemcpy(pos, h_pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
+            DISTR_CHK(fn, hipMemcpy(box, h_box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+            const int rc = body(s0, n);
+            if (rc != NM_OK) return rc;
+        }
+        return NM_OK;
+    }
+};
+
+int distr_boxes_check(const char *fn, int ns, const float *box)
+{
+    for (int s = 0; s < ns; ++s)
+        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return refuse(fn, "a box is not finite and positive");
+    return NM_OK;
+}
+
+// the neighbour shell of nm_distr_angles and nm_distr_bondorder
+int shell_check(const char *fn, double r_lo, double r_hi)
+{
+    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return refuse(fn, "the shell needs 0 <= r_lo < r_hi");
+    return NM_OK;
+}
+
+// beyond half the smallest box an atom could neighbour its own image (a zero angle that is no bond angle)
+int half_box_check(const char *fn, int ns, const float *box, double r_hi)
+{
+    for (int s = 0; s < ns; ++s)
+        if (!(r_hi <= 0.5 * (double)box[s])) return refuse(fn, "r_hi exceeds half the smallest box");
+    return NM_OK;
+}
+
+// the image pre-test of the scan compares float components with a float at or above r_hi; it is switched off for shells
+// so small that the squares of such components could underflow
+float shell_cube(double r_hi) { return r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY); }
 } // namespace
 
 extern "C" {
@@ -1604,133 +1684,95 @@ const char *nm_distr_last_error(void) { return g_distr_error.c_str(); }
 int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const float *box, int sbins, const double *r_edges,
                         int cbins, const double *rv_edges, float *rdf, float *cdf)
 {
-#define DCHK(call)                                                                                     \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) return dfail(NM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    if (ns < 0 || natoms < 1 || !pos || !box) return dfail(NM_ERR_ARG, "nm_distr_histograms: bad argument");
-    if (rdf && (!r_edges || sbins < 2 || sbins > DISTR_MAXS)) return dfail(NM_ERR_ARG, "nm_distr_histograms: bad spherical bins");
-    if (cdf && (!rv_edges || cbins < 1 || cbins > DISTR_MAXC)) return dfail(NM_ERR_ARG, "nm_distr_histograms: bad cartesian bins");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_histograms: no HIP device available");
-    if (device < 0 || device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_histograms: device ordinal out of range");
+    static const char *const fn = "nm_distr_histograms";
+    if (ns < 0 || natoms < 1 || !pos || !box) return refuse(fn, "bad argument");
+    if (rdf && (!r_edges || sbins < 2 || sbins > DISTR_MAXS)) return refuse(fn, "bad spherical bins");
+    if (cdf && (!rv_edges || cbins < 1 || cbins > DISTR_MAXC)) return refuse(fn, "bad cartesian bins");
+    if (const int rc = distr_device(fn, device)) return rc;
     if (ns == 0) return NM_OK;
-    DCHK(hipSetDevice(device));
     const int sb = rdf ? sbins : 0, cb = cdf ? cbins : 0;
     const size_t nc = (size_t)cb * cb * cb;
-    const int npad = (natoms + 63) & ~63;
-    const size_t lds = (((size_t)3 * (natoms + npad) * sizeof(float) + 7) & ~(size_t)7) + (size_t)(sb + cb + 1) * sizeof(double)
-                     + ((size_t)sb + nc) * sizeof(unsigned int);
-    if (lds > 160 * 1024) return dfail(NM_ERR_ARG, "nm_distr_histograms: working set exceeds LDS");
+    const size_t lds = distr_lds_bytes(natoms, sb, cb);
+    if (lds > 160 * 1024) return refuse(fn, "working set exceeds LDS");
     // one image block's count of a bin is at most natoms^2, exact as a float below 2^24; the sum of the 27 blocks can exceed
     // natoms^2 (a displacement on +-l/2 lies in the closed cube in two images per axis) and is checked after the copy-back
-    if (natoms >= 4096) return dfail(NM_ERR_ARG, "nm_distr_histograms: natoms^2 must stay below 2^24 (float32 counts of one periodic image)");
-    DCHK(hipFuncSetAttribute((const void *)nm_distr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int chunk = 4096; // samples per launch: bounds device memory (pos 12 N B + counts) for long trajectories
-    float *d_pos = nullptr, *d_box = nullptr;
-    double *d_re = nullptr, *d_ve = nullptr;
-    float *d_r = nullptr, *d_c = nullptr;
-    const int cs = ns < chunk ? ns : chunk;
-    DCHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
-    DCHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
-    if (rdf) { DCHK(hipMalloc((void **)&d_re, sbins * sizeof(double))); DCHK(hipMalloc((void **)&d_r, (size_t)cs * sbins * sizeof(float)));
-               DCHK(hipMemcpy(d_re, r_edges, sbins * sizeof(double), hipMemcpyHostToDevice)); }
-    if (cdf) { DCHK(hipMalloc((void **)&d_ve, (cbins + 1) * sizeof(double))); DCHK(hipMalloc((void **)&d_c, (size_t)cs * nc * sizeof(float)));
-               DCHK(hipMemcpy(d_ve, rv_edges, (cbins + 1) * sizeof(double), hipMemcpyHostToDevice)); }
-    for (int s0 = 0; s0 < ns; s0 += cs) {
-        const int n = (ns - s0) < cs ? (ns - s0) : cs;
-        DCHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
-        DCHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        if (rdf) DCHK(hipMemset(d_r, 0, (size_t)n * sbins * sizeof(float)));
-        if (cdf) DCHK(hipMemset(d_c, 0, (size_t)n * nc * sizeof(float)));
-        hipLaunchKernelGGL(nm_distr_kernel, dim3(n * 27), dim3(DISTR_BLOCK), lds, 0, natoms, d_pos, d_box, sb, d_re, cb, d_ve, d_r, d_c);
-        DCHK(hipGetLastError());
-        DCHK(hipDeviceSynchronize());
-        if (rdf) DCHK(hipMemcpy(rdf + (size_t)s0 * sbins, d_r, (size_t)n * sbins * sizeof(float), hipMemcpyDeviceToHost));
-        if (cdf) DCHK(hipMemcpy(cdf + (size_t)s0 * nc, d_c, (size_t)n * nc * sizeof(float), hipMemcpyDeviceToHost));
+    if (natoms >= 4096) return refuse(fn, "natoms^2 must stay below 2^24 (float32 counts of one periodic image)");
+    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_distr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    DevBuf<double> d_re, d_ve;
+    DevBuf<float> d_r, d_c;
+    if (rdf) {
+        DISTR_CHK(fn, d_re.alloc(sbins));
+        DISTR_CHK(fn, d_r.alloc((size_t)cs * sbins));
+        DISTR_CHK(fn, hipMemcpy(d_re, r_edges, sbins * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (cdf) {
+        DISTR_CHK(fn, d_ve.alloc(cbins + 1));
+        DISTR_CHK(fn, d_c.alloc((size_t)cs * nc));
+        DISTR_CHK(fn, hipMemcpy(d_ve, rv_edges, (cbins + 1) * sizeof(double), hipMemcpyHostToDevice));
+    }
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        if (rdf) DISTR_CHK(fn, hipMemset(d_r, 0, (size_t)n * sbins * sizeof(float)));
+        if (cdf) DISTR_CHK(fn, hipMemset(d_c, 0, (size_t)n * nc * sizeof(float)));
+        hipLaunchKernelGGL(nm_distr_kernel, dim3(n * 27), dim3(DISTR_BLOCK), lds, 0, natoms, ch.pos, ch.box, sb, d_re, cb, d_ve, d_r, d_c);
+        DISTR_CHK(fn, hipGetLastError());
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        if (rdf) DISTR_CHK(fn, hipMemcpy(rdf + (size_t)s0 * sbins, d_r, (size_t)n * sbins * sizeof(float), hipMemcpyDeviceToHost));
+        if (cdf) DISTR_CHK(fn, hipMemcpy(cdf + (size_t)s0 * nc, d_c, (size_t)n * nc * sizeof(float), hipMemcpyDeviceToHost));
         // every partial sum below 2^24 is exact, so a total reaches 2^24 exactly when the returned float does; from there on
         // the float atomics round in the order they land, and the counts are no longer the reference's
         bool big = false;
         if (rdf) for (size_t i = 0; i < (size_t)n * sbins; ++i) big |= rdf[(size_t)s0 * sbins + i] >= 16777216.0f;
         if (cdf) for (size_t i = 0; i < (size_t)n * nc; ++i) big |= cdf[(size_t)s0 * nc + i] >= 16777216.0f;
-        if (big) {
-            hipFree(d_pos); hipFree(d_box); hipFree(d_re); hipFree(d_ve); hipFree(d_r); hipFree(d_c);
-            return dfail(NM_ERR_ARG, "nm_distr_histograms: a bin holds 2^24 counts or more, beyond what float32 counts hold exactly");
-        }
-    }
-    hipFree(d_pos); hipFree(d_box); hipFree(d_re); hipFree(d_ve); hipFree(d_r); hipFree(d_c);
-#undef DCHK
-    return NM_OK;
+        if (big) return refuse(fn, "a bin holds 2^24 counts or more, beyond what float32 counts hold exactly");
+        return NM_OK;
+    });
 }
 
 int nm_distr_angles(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int abins,
                     const double *cos_edges, uint64_t *adf)
 {
-    if (ns < 0 || !pos || !box || !cos_edges || !adf) return dfail(NM_ERR_ARG, "nm_distr_angles: bad argument");
-    if (natoms < 1 || natoms > 4095) return dfail(NM_ERR_ARG, "nm_distr_angles: natoms must lie in 1..4095");
-    if (abins < 2 || abins > ADF_MAXB) return dfail(NM_ERR_ARG, "nm_distr_angles: abins must lie in 2..256");
+    static const char *const fn = "nm_distr_angles";
+    if (ns < 0 || !pos || !box || !cos_edges || !adf) return refuse(fn, "bad argument");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (abins < 2 || abins > ADF_MAXB) return refuse(fn, "abins must lie in 2..256");
     for (int k = 0; k + 1 < abins; ++k)
-        if (!(cos_edges[k] > cos_edges[k + 1])) return dfail(NM_ERR_ARG, "nm_distr_angles: cos_edges must decrease strictly");
-    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return dfail(NM_ERR_ARG, "nm_distr_angles: the shell needs 0 <= r_lo < r_hi");
-    // beyond half the smallest box an atom could neighbour its own image (a zero angle that is no bond angle)
-    for (int s = 0; s < ns; ++s)
-        if (!(r_hi <= 0.5 * (double)box[s])) return dfail(NM_ERR_ARG, "nm_distr_angles: r_hi exceeds half the smallest box");
-    if (device < 0) return dfail(NM_ERR_ARG, "nm_distr_angles: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_angles: no HIP device available");
-    if (device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_angles: device ordinal out of range");
+        if (!(cos_edges[k] > cos_edges[k + 1])) return refuse(fn, "cos_edges must decrease strictly");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = distr_device(fn, device)) return rc;
     if (ns == 0) return NM_OK;
-    // the image pre-test of the scan compares float components with a float at or above r_hi; it is switched off for shells
-    // so small that the squares of such components could underflow
-    const float cube = r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY);
-    const int chunk = 4096; // samples per launch, as nm_distr_histograms
-    const int cs = ns < chunk ? ns : chunk;
-    const int groups = (natoms + ADF_CPB - 1) / ADF_CPB;
-    float *d_pos = nullptr, *d_box = nullptr;
-    double *d_e = nullptr;
-    unsigned long long *d_a = nullptr;
-    auto release = [&]() { hipFree(d_pos); hipFree(d_box); hipFree(d_e); hipFree(d_a); };
-#define ACHK(call)                                                                                     \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) { release(); return dfail(NM_ERR_HIP, std::string("nm_distr_angles: ") + #call + ": " + hipGetErrorString(e_)); } \
-    } while (0)
-    ACHK(hipSetDevice(device));
+    const float cube = shell_cube(r_hi);
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
     const size_t lds = adf_lds_bytes(natoms, abins); // at most 109,652 B (natoms 4095, abins 256)
-    ACHK(hipFuncSetAttribute((const void *)nm_adf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ACHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
-    ACHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
-    ACHK(hipMalloc((void **)&d_e, (size_t)abins * sizeof(double)));
-    ACHK(hipMalloc((void **)&d_a, (size_t)cs * abins * sizeof(unsigned long long)));
-    ACHK(hipMemcpy(d_e, cos_edges, (size_t)abins * sizeof(double), hipMemcpyHostToDevice));
-    for (int s0 = 0; s0 < ns; s0 += cs) {
-        const int n = (ns - s0) < cs ? (ns - s0) : cs;
-        ACHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
-        ACHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        ACHK(hipMemset(d_a, 0, (size_t)n * abins * sizeof(unsigned long long)));
-        hipLaunchKernelGGL(nm_adf_kernel, dim3(n * groups), dim3(ADF_BLOCK), lds, 0, natoms, d_pos, d_box, r_lo, r_hi, cube, abins, d_e, d_a);
-        ACHK(hipGetLastError());
-        ACHK(hipDeviceSynchronize());
-        ACHK(hipMemcpy(adf + (size_t)s0 * abins, d_a, (size_t)n * abins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    }
-    release();
-#undef ACHK
-    return NM_OK;
+    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_adf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DevBuf<double> d_e;
+    DevBuf<unsigned long long> d_a;
+    DISTR_CHK(fn, d_e.alloc(abins));
+    DISTR_CHK(fn, d_a.alloc((size_t)cs * abins));
+    DISTR_CHK(fn, hipMemcpy(d_e, cos_edges, (size_t)abins * sizeof(double), hipMemcpyHostToDevice));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        DISTR_CHK(fn, hipMemset(d_a, 0, (size_t)n * abins * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(nm_adf_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, abins, d_e, d_a);
+        DISTR_CHK(fn, hipGetLastError());
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        DISTR_CHK(fn, hipMemcpy(adf + (size_t)s0 * abins, d_a, (size_t)n * abins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
 }
 
 int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const float *box, int qmax, double *sf_sum, double *sf_max)
 {
-    if (ns < 0 || !pos || !box) return dfail(NM_ERR_ARG, "nm_distr_sfactor: bad argument");
-    if (!sf_sum && !sf_max) return dfail(NM_ERR_ARG, "nm_distr_sfactor: sf_sum and sf_max are both null");
-    if (natoms < 1 || natoms > 4095) return dfail(NM_ERR_ARG, "nm_distr_sfactor: natoms must lie in 1..4095");
-    if (qmax < 1 || qmax > SF_QMAX) return dfail(NM_ERR_ARG, "nm_distr_sfactor: qmax must lie in 1..32");
-    for (int s = 0; s < ns; ++s)
-        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return dfail(NM_ERR_ARG, "nm_distr_sfactor: a box is not finite and positive");
-    if (device < 0) return dfail(NM_ERR_ARG, "nm_distr_sfactor: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_sfactor: no HIP device available");
-    if (device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_sfactor: device ordinal out of range");
+    static const char *const fn = "nm_distr_sfactor";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!sf_sum && !sf_max) return refuse(fn, "sf_sum and sf_max are both null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (qmax < 1 || qmax > SF_QMAX) return refuse(fn, "qmax must lie in 1..32");
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = distr_device(fn, device)) return rc;
     if (ns == 0) return NM_OK;
     // the work items (nm_distr.h): every (h >= 0, k >= 0, l0) whose chunk l0 .. l0 + SF_LB - 1 reaches into the sphere, l0 slowest
     std::vector<unsigned int> items;
@@ -1740,60 +1782,40 @@ int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const flo
                 if (h * h + k * k + l0 * l0 <= qmax * qmax) items.push_back(sf_item(h, k, l0));
     const int nitems = (int)items.size();
     const size_t nsh = (size_t)qmax * qmax + 1;
-    const int chunk = 4096; // samples per launch, as nm_distr_histograms
-    const int cs = ns < chunk ? ns : chunk;
-    float *d_pos = nullptr, *d_box = nullptr;
-    unsigned int *d_it = nullptr;
-    double *d_sum = nullptr, *d_max = nullptr;
-    auto release = [&]() { hipFree(d_pos); hipFree(d_box); hipFree(d_it); hipFree(d_sum); hipFree(d_max); };
-#define SCHK(call)                                                                                     \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) { release(); return dfail(NM_ERR_HIP, std::string("nm_distr_sfactor: ") + #call + ": " + hipGetErrorString(e_)); } \
-    } while (0)
-    SCHK(hipSetDevice(device));
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
     const size_t lds = sf_lds_bytes(qmax); // below the 64 KiB a kernel gets without asking
-    SCHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
-    SCHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
-    SCHK(hipMalloc((void **)&d_it, (size_t)nitems * sizeof(unsigned int)));
-    if (sf_sum) SCHK(hipMalloc((void **)&d_sum, (size_t)cs * nsh * sizeof(double)));
-    if (sf_max) SCHK(hipMalloc((void **)&d_max, (size_t)cs * nsh * sizeof(double)));
-    SCHK(hipMemcpy(d_it, items.data(), (size_t)nitems * sizeof(unsigned int), hipMemcpyHostToDevice));
-    for (int s0 = 0; s0 < ns; s0 += cs) {
-        const int n = (ns - s0) < cs ? (ns - s0) : cs;
-        SCHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
-        SCHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nm_sfac_kernel, dim3(n), dim3(SF_BLOCK), lds, 0, natoms, d_pos, d_box, qmax, nitems, d_it, d_sum, d_max);
-        SCHK(hipGetLastError());
-        SCHK(hipDeviceSynchronize());
-        if (sf_sum) SCHK(hipMemcpy(sf_sum + (size_t)s0 * nsh, d_sum, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
-        if (sf_max) SCHK(hipMemcpy(sf_max + (size_t)s0 * nsh, d_max, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    release();
-#undef SCHK
-    return NM_OK;
+    DevBuf<unsigned int> d_it;
+    DevBuf<double> d_sum, d_max;
+    DISTR_CHK(fn, d_it.alloc(nitems));
+    if (sf_sum) DISTR_CHK(fn, d_sum.alloc((size_t)cs * nsh));
+    if (sf_max) DISTR_CHK(fn, d_max.alloc((size_t)cs * nsh));
+    DISTR_CHK(fn, hipMemcpy(d_it, items.data(), (size_t)nitems * sizeof(unsigned int), hipMemcpyHostToDevice));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        hipLaunchKernelGGL(nm_sfac_kernel, dim3(n), dim3(SF_BLOCK), lds, 0, natoms, ch.pos, ch.box, qmax, nitems, d_it, d_sum, d_max);
+        DISTR_CHK(fn, hipGetLastError());
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        if (sf_sum) DISTR_CHK(fn, hipMemcpy(sf_sum + (size_t)s0 * nsh, d_sum, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
+        if (sf_max) DISTR_CHK(fn, hipMemcpy(sf_max + (size_t)s0 * nsh, d_max, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
 }
 
 int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
                        const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb)
 {
-    if (ns < 0 || !pos || !box || !ls) return dfail(NM_ERR_ARG, "nm_distr_bondorder: bad argument");
-    if (!q2 && !qbar2 && !Q2 && !nnb) return dfail(NM_ERR_ARG, "nm_distr_bondorder: all four outputs are null");
-    if (natoms < 1 || natoms > 4095) return dfail(NM_ERR_ARG, "nm_distr_bondorder: natoms must lie in 1..4095");
-    if (nl < 1 || nl > BO_MAXL) return dfail(NM_ERR_ARG, "nm_distr_bondorder: nl must lie in 1..6");
+    static const char *const fn = "nm_distr_bondorder";
+    if (ns < 0 || !pos || !box || !ls) return refuse(fn, "bad argument");
+    if (!q2 && !qbar2 && !Q2 && !nnb) return refuse(fn, "all four outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (nl < 1 || nl > BO_MAXL) return refuse(fn, "nl must lie in 1..6");
     for (int i = 0; i < nl; ++i)
         if (ls[i] < 1 || ls[i] > BO_LMAX || (i > 0 && ls[i] <= ls[i - 1]))
-            return dfail(NM_ERR_ARG, "nm_distr_bondorder: ls must increase strictly within 1..12");
-    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return dfail(NM_ERR_ARG, "nm_distr_bondorder: the shell needs 0 <= r_lo < r_hi");
-    for (int s = 0; s < ns; ++s)
-        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return dfail(NM_ERR_ARG, "nm_distr_bondorder: a box is not finite and positive");
-    // beyond half the smallest box an atom could neighbour its own image
-    for (int s = 0; s < ns; ++s)
-        if (!(r_hi <= 0.5 * (double)box[s])) return dfail(NM_ERR_ARG, "nm_distr_bondorder: r_hi exceeds half the smallest box");
-    if (device < 0) return dfail(NM_ERR_ARG, "nm_distr_bondorder: device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, "nm_distr_bondorder: no HIP device available");
-    if (device >= ndev) return dfail(NM_ERR_ARG, "nm_distr_bondorder: device ordinal out of range");
+            return refuse(fn, "ls must increase strictly within 1..12");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = distr_device(fn, device)) return rc;
     if (ns == 0) return NM_OK;
     // the requested l and the recurrence's constants (nm_distr.h): long double, rounded once
     BoSet set = {nl, 0, ls[nl - 1], 0u, 0ull, 0u};
@@ -1817,68 +1839,52 @@ int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const f
             }
         }
     }
-    const float cube = r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY); // as nm_distr_angles
-    const int groups = (natoms + BO_CPB - 1) / BO_CPB;
-    // samples per launch: at most 4096 as the other entry points, fewer where the moments' scratch would pass 256 MiB
+    const float cube = shell_cube(r_hi);
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    // samples per launch: at most DISTR_CHUNK as the other entry points, fewer where the moments' scratch would pass 256 MiB
     const size_t per = (size_t)natoms * nc2 * sizeof(double);
     size_t fit = ((size_t)256 << 20) / per;
     if (fit < 1) fit = 1;
-    int cs = ns < 4096 ? ns : 4096;
+    int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
     if ((size_t)cs > fit) cs = (int)fit;
-    float *d_pos = nullptr, *d_box = nullptr;
-    double *d_tab = nullptr, *d_qlm = nullptr, *d_part = nullptr, *d_q2 = nullptr, *d_qb = nullptr, *d_Q = nullptr;
-    int *d_cnt = nullptr, *d_nnb = nullptr;
-    auto release = [&]() {
-        hipFree(d_pos); hipFree(d_box); hipFree(d_tab); hipFree(d_qlm); hipFree(d_part); hipFree(d_q2); hipFree(d_qb); hipFree(d_Q);
-        hipFree(d_cnt); hipFree(d_nnb);
-    };
-#define BCHK(call)                                                                                     \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) { release(); return dfail(NM_ERR_HIP, std::string("nm_distr_bondorder: ") + #call + ": " + hipGetErrorString(e_)); } \
-    } while (0)
-    BCHK(hipSetDevice(device));
     const size_t lds1 = bo_lds_bytes(natoms, set.nc, true), lds2 = bo_lds_bytes(natoms, set.nc, false); // at most 98,932 B (4095 atoms, six l from 7 to 12)
-    BCHK(hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    BCHK(hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    BCHK(hipMalloc((void **)&d_pos, (size_t)cs * natoms * 3 * sizeof(float)));
-    BCHK(hipMalloc((void **)&d_box, (size_t)cs * sizeof(float)));
-    BCHK(hipMalloc((void **)&d_tab, tab.size() * sizeof(double)));
-    BCHK(hipMalloc((void **)&d_qlm, (size_t)cs * per));
-    BCHK(hipMalloc((void **)&d_part, (size_t)cs * groups * nc2 * sizeof(double)));
-    BCHK(hipMalloc((void **)&d_cnt, (size_t)cs * groups * sizeof(int)));
-    if (q2) BCHK(hipMalloc((void **)&d_q2, (size_t)cs * natoms * nl * sizeof(double)));
-    if (qbar2) BCHK(hipMalloc((void **)&d_qb, (size_t)cs * natoms * nl * sizeof(double)));
-    if (Q2) BCHK(hipMalloc((void **)&d_Q, (size_t)cs * nl * sizeof(double)));
-    if (nnb) BCHK(hipMalloc((void **)&d_nnb, (size_t)cs * natoms * sizeof(int)));
-    BCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    for (int s0 = 0; s0 < ns; s0 += cs) {
-        const int n = (ns - s0) < cs ? (ns - s0) : cs;
-        BCHK(hipMemcpy(d_pos, pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
-        BCHK(hipMemcpy(d_box, box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(BO_BLOCK), lds1, 0, natoms, d_pos, d_box, r_lo, r_hi, cube, set,
+    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    const size_t pa = (size_t)natoms * nl;
+    DevBuf<double> d_tab, d_qlm, d_part, d_q2, d_qb, d_Q;
+    DevBuf<int> d_cnt, d_nnb;
+    DISTR_CHK(fn, d_tab.alloc(tab.size()));
+    DISTR_CHK(fn, d_qlm.alloc((size_t)cs * natoms * nc2));
+    DISTR_CHK(fn, d_part.alloc((size_t)cs * groups * nc2));
+    DISTR_CHK(fn, d_cnt.alloc((size_t)cs * groups));
+    if (q2) DISTR_CHK(fn, d_q2.alloc((size_t)cs * pa));
+    if (qbar2) DISTR_CHK(fn, d_qb.alloc((size_t)cs * pa));
+    if (Q2) DISTR_CHK(fn, d_Q.alloc((size_t)cs * nl));
+    if (nnb) DISTR_CHK(fn, d_nnb.alloc((size_t)cs * natoms));
+    DISTR_CHK(fn, hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, set,
                            d_tab, d_qlm, d_q2, d_nnb, d_part, d_cnt);
-        BCHK(hipGetLastError());
+        DISTR_CHK(fn, hipGetLastError());
         if (qbar2) {
-            hipLaunchKernelGGL(nm_bo_average_kernel, dim3(n * groups), dim3(BO_BLOCK), lds2, 0, natoms, d_pos, d_box, r_lo, r_hi, cube,
+            hipLaunchKernelGGL(nm_bo_average_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube,
                                set, d_qlm, d_qb);
-            BCHK(hipGetLastError());
+            DISTR_CHK(fn, hipGetLastError());
         }
         if (Q2) {
             hipLaunchKernelGGL(nm_bo_global_kernel, dim3(n), dim3(128), 0, 0, groups, set, d_part, d_cnt, d_Q);
-            BCHK(hipGetLastError());
+            DISTR_CHK(fn, hipGetLastError());
         }
-        BCHK(hipDeviceSynchronize());
-        const size_t pa = (size_t)natoms * nl;
-        if (q2) BCHK(hipMemcpy(q2 + (size_t)s0 * pa, d_q2, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
-        if (qbar2) BCHK(hipMemcpy(qbar2 + (size_t)s0 * pa, d_qb, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
-        if (Q2) BCHK(hipMemcpy(Q2 + (size_t)s0 * nl, d_Q, (size_t)n * nl * sizeof(double), hipMemcpyDeviceToHost));
-        if (nnb) BCHK(hipMemcpy(nnb + (size_t)s0 * natoms, d_nnb, (size_t)n * natoms * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    release();
-#undef BCHK
-    return NM_OK;
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        if (q2) DISTR_CHK(fn, hipMemcpy(q2 + (size_t)s0 * pa, d_q2, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
+        if (qbar2) DISTR_CHK(fn, hipMemcpy(qbar2 + (size_t)s0 * pa, d_qb, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
+        if (Q2) DISTR_CHK(fn, hipMemcpy(Q2 + (size_t)s0 * nl, d_Q, (size_t)n * nl * sizeof(double), hipMemcpyDeviceToHost));
+        if (nnb) DISTR_CHK(fn, hipMemcpy(nnb + (size_t)s0 * natoms, d_nnb, (size_t)n * natoms * sizeof(int), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
 }
+#undef DISTR_CHK
 
 } // extern "C"
 

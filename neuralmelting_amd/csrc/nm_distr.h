@@ -13,6 +13,19 @@ constexpr int DISTR_BLOCK = 256;
 constexpr int DISTR_MAXS = 256;  // most spherical bin edges
 constexpr int DISTR_MAXC = 32;   // most cartesian bins per axis
 
+// nm_distr_kernel's LDS: the positions and their shifted, padded copy (distr_pos_bytes, rounded up for the float64 edges behind
+// them), the edges of both histograms, the counts
+__host__ __device__ inline size_t distr_pos_bytes(int natoms)
+{
+    return ((size_t)3 * (natoms + ((natoms + 63) & ~63)) * sizeof(float) + 7) & ~(size_t)7;
+}
+
+__host__ __device__ inline size_t distr_lds_bytes(int natoms, int sbins, int cbins)
+{
+    return distr_pos_bytes(natoms) + (size_t)(sbins + cbins + 1) * sizeof(double)
+         + ((size_t)sbins + (size_t)cbins * cbins * cbins) * sizeof(unsigned int);
+}
+
 // np.histogram with explicit edges: bin k holds e[k] <= d < e[k+1], the last bin also d == e[n-1]; -1 = outside
 __device__ __forceinline__ int bin_of(const double *e, int n, double d)
 {
@@ -57,7 +70,7 @@ nm_distr_kernel(int natoms, const float *__restrict__ pos, const float *__restri
     const int npad = (natoms + 63) & ~63;
     float *px = (float *)smem, *py = px + natoms, *pz = py + natoms;
     float *qx = pz + natoms, *qy = qx + npad, *qz = qy + npad; // pos[b] + box*br, padded with far-away entries
-    double *re = (double *)(smem + (((size_t)3 * (natoms + npad) * sizeof(float) + 7) & ~(size_t)7));
+    double *re = (double *)(smem + distr_pos_bytes(natoms));
     double *ve = re + sbins;
     unsigned int *hr = (unsigned int *)(ve + (cbins + 1));
     unsigned int *hc = hr + sbins;
@@ -131,28 +144,114 @@ nm_distr_kernel(int natoms, const float *__restrict__ pos, const float *__restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// What the kernels over a neighbour shell share (nm_adf_kernel, nm_bo_moments_kernel, nm_bo_average_kernel).  A workgroup of
+// SHELL_BLOCK threads takes SHELL_CPB consecutive centres of one sample and stages the sample's positions and their bounding box
+// in LDS once (shell_stage, shell_bounds); each wave then works through its centres on its own and finds a centre's neighbours
+// with shell_scan.  That scan is the one place where a neighbour is decided, so the entries of the bond order are those of the
+// angular distribution by construction (include/nm_distr.h).
+constexpr int SHELL_BLOCK = 256;
+constexpr int SHELL_WAVES = SHELL_BLOCK / 64;
+constexpr int SHELL_CPB = 32;   // centres per workgroup
+
+// A wave's lanes exchange the neighbour tiles through LDS without a workgroup barrier: a wave's LDS operations complete in
+// program order, and this keeps the compiler from moving them across the hand-over.
+__device__ __forceinline__ void adf_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a wave-uniform value in a scalar register
+__device__ __forceinline__ float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+// Staging, first part: the sample's positions go to LDS, and every wave writes the bounding box of the atoms it copied to
+// part[wave][lo x, hi x, lo y, hi y, lo z, hi z].  A workgroup barrier belongs between this and shell_bounds.
+__device__ __forceinline__ void shell_stage(const float *ps, int natoms, float *px, float *py, float *pz, float *part)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    for (int a = tid; a < natoms; a += SHELL_BLOCK) {
+        const float x = ps[3 * a], y = ps[3 * a + 1], z = ps[3 * a + 2];
+        px[a] = x; py[a] = y; pz[a] = z;
+        lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
+        lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
+        lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
+    }
+    for (int d = 0; d < 3; ++d) {
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[d] = fminf(lo[d], __shfl_xor(lo[d], o));
+            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o));
+        }
+        if (lane == 0) { part[wave * 6 + 2 * d] = lo[d]; part[wave * 6 + 2 * d + 1] = hi[d]; }
+    }
+}
+
+// Staging, second part: the sample's bounding box from the waves' partials, in every thread's registers
+__device__ __forceinline__ void shell_bounds(const float *part, float *bb)
+{
+    for (int d = 0; d < 3; ++d) {
+        float l = part[2 * d], u = part[2 * d + 1];
+        for (int w = 1; w < SHELL_WAVES; ++w) { l = fminf(l, part[w * 6 + 2 * d]); u = fmaxf(u, part[w * 6 + 2 * d + 1]); }
+        bb[2 * d] = l; bb[2 * d + 1] = u;
+    }
+}
+
+// The neighbour scan: the candidates of centre (cx, cy, cz) are the 27 images x natoms atoms, image-major, walked by a wave 64
+// atoms at a time (lane = atom a0 + lane).  A candidate is a neighbour if its float32 displacement length d, numpy's arithmetic
+// (no contraction, sequential sum, correctly rounded root), has r_lo < (double)d <= r_hi.  An image whose shift puts the whole
+// sample outside the cube |component| <= cube around the centre is skipped.  After each 64 candidates the scan calls
+// sink(a, in, vx, vy, vz, ballot): the lane's atom, whether it is a neighbour, its displacement, and the wave's ballot of `in`,
+// whose set bits below the lane number the neighbours in scan order.  The scan goes on while sink returns true.
+template <class F>
+__device__ __forceinline__ void shell_scan(const float *px, const float *py, const float *pz, int natoms, float cx, float cy, float cz,
+                                           float L, float cube, const float *bb, double r_lo, double r_hi, int lane, F &&sink)
+{
+#pragma clang fp contract(off)
+    for (int img = 0; img < 27; ++img) {
+        // br[j] = (b[i], b[j], b[k]) for i, j, k in range(3), b = [-1, 0, 1]  (lammps_distr.py:99-102)
+        const float bx = (float)(img / 9 - 1), by = (float)((img / 3) % 3 - 1), bz = (float)(img % 3 - 1);
+        const float qx = cx + L * bx, qy = cy + L * by, qz = cz + L * bz; // pos[c] + box*br[j]
+        // float subtraction is monotone, so every atom's component lies between those of the bounding box; a component beyond
+        // cube >= r_hi in magnitude gives d >= |component| > r_hi (sqrt(x*x) rounds to |x|, the further terms only add)
+        if (bb[0] - qx > cube || bb[1] - qx < -cube || bb[2] - qy > cube || bb[3] - qy < -cube || bb[4] - qz > cube || bb[5] - qz < -cube)
+            continue;
+        for (int a0 = 0; a0 < natoms; a0 += 64) {
+            const int a = a0 + lane;
+            bool in = false;
+            float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+            if (a < natoms) {
+                vx = px[a] - qx; vy = py[a] - qy; vz = pz[a] - qz;
+                float d2 = vx * vx;      // sequential float32 sum of three terms, as the rdf path
+                d2 = d2 + vy * vy;
+                d2 = d2 + vz * vz;
+                const double d = (double)sqrtf(d2); // correctly rounded (see nm_distr_kernel)
+                in = r_lo < d && d <= r_hi;
+            }
+            if (!sink(a, in, vx, vy, vz, __ballot(in))) return;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Angular distribution (include/nm_distr.h, nm_distr_angles): for every centre atom c the angle between every unordered
 // pair of its neighbours, a neighbour being an (image, atom) whose float32 displacement length lies in (r_lo, r_hi].
 //
-// A workgroup takes ADF_CPB consecutive centres of one sample; the sample's positions are staged in LDS once.  Each wave
+// A workgroup takes SHELL_CPB consecutive centres of one sample; the sample's positions are staged in LDS once.  Each wave
 // works through its centres on its own (no workgroup barrier after the staging):
-//   scan   the 27 images x natoms candidates, 64 at a time, with numpy's float32 arithmetic; survivors are appended to
-//          the wave's LDS neighbour list (ballot + prefix count): the float32 components and 1/|v| in float64.  An image
-//          whose shift puts the whole sample outside the cube |component| <= cube around the centre is skipped first.
+//   scan   shell_scan's neighbours are appended to the wave's LDS neighbour list (ballot + prefix count): the float32
+//          components and 1/|v| in float64.
 //   pairs  every unordered pair of the list, spread evenly over the lanes (the numbering is given at the loop), binned in cosine
 //          space into one of ADF_REP copies of the wave's LDS histogram (crystal frames put nearly all counts into four
 //          bins; the copies cut that contention by ADF_REP).
 //   tiles  a list longer than ADF_TILE is processed in tiles: tile A against itself, then against every later tile B,
 //          which is produced by scanning again.  Any number of neighbours is handled.
 // The LDS histograms are 32-bit; a wave adds them to the 64-bit global counts before they could overflow and at its end.
-constexpr int ADF_BLOCK = 256;
-constexpr int ADF_WAVES = ADF_BLOCK / 64;
 constexpr int ADF_TILE = 256;   // neighbours per LDS tile (two tiles per wave)
-constexpr int ADF_CPB = 32;     // centres per workgroup
 constexpr int ADF_REP = 4;      // copies of a wave's histogram, chosen by lane
 constexpr int ADF_LUT = 4096;   // cells of the bin-guess table over cos(theta) in [-1, 1]
 constexpr int ADF_MAXB = 256;   // most edges (a bin index fits the table's bytes)
-static_assert(ADF_LUT % ADF_BLOCK == 0 && ADF_MAXB <= 256, "each thread fills ADF_LUT / ADF_BLOCK cells with byte-sized bins");
+static_assert(ADF_LUT % SHELL_BLOCK == 0 && ADF_MAXB <= 256, "each thread fills ADF_LUT / SHELL_BLOCK cells with byte-sized bins");
 
 // The estimate est = dot * (r1 * r2), r_i = 1 / sqrt(n_i), against the definition's cth = clip(dot / sqrt(n1 * n2)):
 // with u = 2^-53 and every operation correctly rounded, cth carries a relative error of at most (1/2 + 1 + 1) u = 2.5 u
@@ -166,9 +265,9 @@ constexpr double ADF_MARGIN = 0x1p-48;
 
 __host__ __device__ inline size_t adf_lds_bytes(int natoms, int abins)
 {
-    return (size_t)(abins + 1 + ADF_WAVES * 2 * ADF_TILE) * sizeof(double)                // edges and their sentinel, 1/|v| of the tiles
-         + ((size_t)3 * natoms + (size_t)ADF_WAVES * 2 * 3 * ADF_TILE + ADF_WAVES * 6) * sizeof(float) // positions, tiles, bounding box partials
-         + (size_t)ADF_WAVES * ADF_REP * abins * sizeof(unsigned int) + ADF_LUT;           // histograms, guess table
+    return (size_t)(abins + 1 + SHELL_WAVES * 2 * ADF_TILE) * sizeof(double)                // edges and their sentinel, 1/|v| of the tiles
+         + ((size_t)3 * natoms + (size_t)SHELL_WAVES * 2 * 3 * ADF_TILE + SHELL_WAVES * 6) * sizeof(float) // positions, tiles, bounding box partials
+         + (size_t)SHELL_WAVES * ADF_REP * abins * sizeof(unsigned int) + ADF_LUT;           // histograms, guess table
 }
 
 // bin k (0 <= k <= n-2) holds e[k] >= c > e[k+1] for strictly decreasing e, the last bin also c == e[n-1]; -1 = outside.
@@ -215,109 +314,60 @@ __device__ __forceinline__ int adf_bin(const double *e, int n, const unsigned ch
     return k;
 }
 
-// A wave's lanes exchange the neighbour tiles through LDS without a workgroup barrier: a wave's LDS operations complete in
-// program order, and this keeps the compiler from moving them across the hand-over.
-__device__ __forceinline__ void adf_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// One scan of the candidates of centre (cx, cy, cz): neighbours number t0 .. t0+ADF_TILE-1 (in scan order) go to the tile.
+// One shell_scan of centre (cx, cy, cz): neighbours number t0 .. t0+ADF_TILE-1 (in scan order) go to the tile.
 // Returns the number of neighbours seen; the scan ends early once that reaches `stop`.
 __device__ __forceinline__ int adf_fill(const float *px, const float *py, const float *pz, int natoms, float cx, float cy, float cz,
                                         float L, float cube, const float *bb, double r_lo, double r_hi, int t0, int stop, float *tx,
                                         float *ty, float *tz, double *tr, int lane)
 {
-#pragma clang fp contract(off)
     int base = 0;
-    for (int img = 0; img < 27; ++img) {
-        // br[j] = (b[i], b[j], b[k]) for i, j, k in range(3), b = [-1, 0, 1]  (lammps_distr.py:99-102)
-        const float bx = (float)(img / 9 - 1), by = (float)((img / 3) % 3 - 1), bz = (float)(img % 3 - 1);
-        const float qx = cx + L * bx, qy = cy + L * by, qz = cz + L * bz; // pos[c] + box*br[j]
-        // float subtraction is monotone, so every atom's component lies between those of the bounding box; a component beyond
-        // cube >= r_hi in magnitude gives d >= |component| > r_hi (sqrt(x*x) rounds to |x|, the further terms only add)
-        if (bb[0] - qx > cube || bb[1] - qx < -cube || bb[2] - qy > cube || bb[3] - qy < -cube || bb[4] - qz > cube || bb[5] - qz < -cube)
-            continue;
-        for (int a0 = 0; a0 < natoms; a0 += 64) {
-            const int a = a0 + lane;
-            bool in = false;
-            float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-            if (a < natoms) {
-                vx = px[a] - qx; vy = py[a] - qy; vz = pz[a] - qz;
-                float d2 = vx * vx;      // sequential float32 sum of three terms, as the rdf path
-                d2 = d2 + vy * vy;
-                d2 = d2 + vz * vz;
-                const double d = (double)sqrtf(d2); // correctly rounded (see nm_distr_kernel)
-                in = r_lo < d && d <= r_hi;
+    shell_scan(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, lane,
+               [&](int, bool in, float vx, float vy, float vz, unsigned long long m) {
+        if (in) {
+            const int o = base + __popcll(m & ((1ull << lane) - 1ull)) - t0;
+            if (o >= 0 && o < ADF_TILE) {
+                const double X = vx, Y = vy, Z = vz;
+                tx[o] = vx; ty[o] = vy; tz[o] = vz;
+                tr[o] = 1.0 / sqrt(fma(Z, Z, fma(Y, Y, X * X)));
             }
-            const unsigned long long m = __ballot(in);
-            if (in) {
-                const int o = base + __popcll(m & ((1ull << lane) - 1ull)) - t0;
-                if (o >= 0 && o < ADF_TILE) {
-                    const double X = vx, Y = vy, Z = vz;
-                    tx[o] = vx; ty[o] = vy; tz[o] = vz;
-                    tr[o] = 1.0 / sqrt(fma(Z, Z, fma(Y, Y, X * X)));
-                }
-            }
-            base += __popcll(m);
-            if (base >= stop) return base;
         }
-    }
+        base += __popcll(m);
+        return base < stop;
+    });
     return base;
 }
 
-__global__ void __launch_bounds__(ADF_BLOCK)
+__global__ void __launch_bounds__(SHELL_BLOCK)
 nm_adf_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
               int abins, const double *__restrict__ cos_edges, unsigned long long *__restrict__ adf)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int groups = (natoms + ADF_CPB - 1) / ADF_CPB;
-    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * ADF_CPB;
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * SHELL_CPB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double *e = (double *)smem, *tr_all = e + abins + 1;
-    float *px = (float *)(tr_all + ADF_WAVES * 2 * ADF_TILE), *py = px + natoms, *pz = py + natoms;
-    float *txyz_all = pz + natoms, *part = txyz_all + ADF_WAVES * 2 * 3 * ADF_TILE;
-    unsigned int *h_all = (unsigned int *)(part + ADF_WAVES * 6);
-    unsigned char *lut = (unsigned char *)(h_all + ADF_WAVES * ADF_REP * abins);
+    float *px = (float *)(tr_all + SHELL_WAVES * 2 * ADF_TILE), *py = px + natoms, *pz = py + natoms;
+    float *txyz_all = pz + natoms, *part = txyz_all + SHELL_WAVES * 2 * 3 * ADF_TILE;
+    unsigned int *h_all = (unsigned int *)(part + SHELL_WAVES * 6);
+    unsigned char *lut = (unsigned char *)(h_all + SHELL_WAVES * ADF_REP * abins);
     const float L = box[s];
-    const float *ps = pos + (size_t)s * natoms * 3;
     // stage the positions, their bounding box, the edges, the guess table; clear the histograms
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int a = tid; a < natoms; a += ADF_BLOCK) {
-        const float x = ps[3 * a], y = ps[3 * a + 1], z = ps[3 * a + 2];
-        px[a] = x; py[a] = y; pz[a] = z;
-        lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
-        lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
-        lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
-    }
-    for (int d = 0; d < 3; ++d) {
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[d] = fminf(lo[d], __shfl_xor(lo[d], o));
-            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o));
-        }
-        if (lane == 0) { part[wave * 6 + 2 * d] = lo[d]; part[wave * 6 + 2 * d + 1] = hi[d]; }
-    }
-    for (int k = tid; k <= abins; k += ADF_BLOCK) e[k] = k < abins ? cos_edges[k] : -INFINITY;
-    for (int k = tid; k < ADF_WAVES * ADF_REP * abins; k += ADF_BLOCK) h_all[k] = 0u;
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    for (int k = tid; k <= abins; k += SHELL_BLOCK) e[k] = k < abins ? cos_edges[k] : -INFINITY;
+    for (int k = tid; k < SHELL_WAVES * ADF_REP * abins; k += SHELL_BLOCK) h_all[k] = 0u;
     __syncthreads();
     {
         // the bin of each cell's largest value (cells in decreasing order of cos: the bin never decreases along a thread's
         // consecutive cells); a hint only, adf_bin is exact for any table
         int k = 0;
-        for (int g = tid * (ADF_LUT / ADF_BLOCK); g < (tid + 1) * (ADF_LUT / ADF_BLOCK); ++g) {
+        for (int g = tid * (ADF_LUT / SHELL_BLOCK); g < (tid + 1) * (ADF_LUT / SHELL_BLOCK); ++g) {
             const double top = 1.0 - (double)g * (2.0 / ADF_LUT);
             while (k < abins - 2 && top <= e[k + 1]) ++k;
             lut[g] = (unsigned char)k;
         }
     }
     float bb[6];
-    for (int d = 0; d < 3; ++d) {
-        float l = part[2 * d], u = part[2 * d + 1];
-        for (int w = 1; w < ADF_WAVES; ++w) { l = fminf(l, part[w * 6 + 2 * d]); u = fmaxf(u, part[w * 6 + 2 * d + 1]); }
-        bb[2 * d] = l; bb[2 * d + 1] = u;
-    }
+    shell_bounds(part, bb);
     __syncthreads();
     // this wave's tiles and histogram copies
     float *ax = txyz_all + (size_t)wave * 2 * 3 * ADF_TILE, *ay = ax + ADF_TILE, *az = ay + ADF_TILE;
@@ -335,13 +385,10 @@ nm_adf_kernel(int natoms, const float *__restrict__ pos, const float *__restrict
         }
         held = 0ull;
     };
-    const int cend = c0 + ADF_CPB < natoms ? c0 + ADF_CPB : natoms;
-    for (int c = c0 + wave; c < cend; c += ADF_WAVES) {
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
         adf_wave_sync(); // the previous centre's pair loops are done with the tiles
-        // wave-uniform values in scalar registers
-        const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px[c])));
-        const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py[c])));
-        const float cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pz[c])));
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
         const int M = adf_fill(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, 0, 0x7fffffff, ax, ay, az, ar, lane);
         adf_wave_sync();
         const int nt = (M + ADF_TILE - 1) / ADF_TILE;
@@ -532,15 +579,15 @@ nm_sfac_kernel(int natoms, const float *__restrict__ pos, const float *__restric
 // table the kernels read with wave-uniform indices.  Y_l,-m = (-1)^m conj(Y_lm): only m >= 0 is formed, and the invariant
 // 4 pi / (2l+1) sum_m |q_lm|^2 counts m > 0 twice.
 //
-// Pass 1 (nm_bo_moments_kernel): a workgroup takes BO_CPB consecutive centres of one sample, positions and bounding box staged
-// as nm_adf_kernel does; each wave works through its centres alone.  bo_scan is adf_fill's scan (same float32 arithmetic, same
-// image skip, same ballot compaction) that also records the atom index and hands the wave's list on in batches of 64 entries as
-// it fills, so any number of neighbours is handled with one scan.  For a batch, lane = bond: the lane runs the recurrence (m
-// outer, l inner) and puts the Y_lm of the requested l into the wave's LDS staging rows [component][bond]; when the rows are
-// full, lane = component: each lane adds its row's bonds in list order to the centre's accumulator in LDS.  No accumulator is
-// indexed at run time in registers, so nothing goes to scratch memory.  At the centre's end the wave writes q_lm(c) to the global
-// scratch [sample][atom][component], q2 and nnb, and keeps the unnormalised sums for Q2; the workgroup's partial sums and bond
-// count go to [sample][group].
+// Pass 1 (nm_bo_moments_kernel): a workgroup takes SHELL_CPB consecutive centres of one sample, positions and bounding box
+// staged by shell_stage and shell_bounds; each wave works through its centres alone.  bo_scan is a sink of shell_scan, as
+// adf_fill is: both see the same neighbours in the same order, whatever the scan does to find them.  bo_scan also records the
+// atom index and hands the wave's list on in batches of 64 entries as it fills, so any number of neighbours is handled with one
+// scan.  For a batch, lane = bond: the lane runs the recurrence (m outer, l inner) and puts the Y_lm of the requested l into
+// the wave's LDS staging rows [component][bond]; when the rows are full, lane = component: each lane adds its row's bonds in
+// list order to the centre's accumulator in LDS.  No accumulator is indexed at run time in registers, so nothing goes to
+// scratch memory.  At the centre's end the wave writes q_lm(c) to the global scratch [sample][atom][component], q2 and nnb, and
+// keeps the unnormalised sums for Q2; the workgroup's partial sums and bond count go to [sample][group].
 // Pass 2 (nm_bo_average_kernel, only if qbar2 is asked for): the same scan, indices only; lane = component gathers q_lm(a) of
 // the batch's entries in list order (one coalesced read of the atom's moments per entry, the reads of up to eight entries in
 // flight), then qbar_lm and its invariant.
@@ -565,9 +612,6 @@ nm_sfac_kernel(int natoms, const float *__restrict__ pos, const float *__restric
 //   q      e_q = e(l) + M u;             qbar    e_q + (M + 1) u;             Q    e(l) + (M + 12 + ceil(natoms / 32)) u
 // (Q: the entries of a centre, then a wave's 8 centres, the 4 waves and the groups of 32 centres), and for each invariant
 // x = |.|^2, |dx| <= 2 e sqrt(x) + e^2.  tests/bondorder_ref.py holds the same expressions; the tests allow twice that.
-constexpr int BO_BLOCK = 256;
-constexpr int BO_WAVES = BO_BLOCK / 64;
-constexpr int BO_CPB = 32;      // centres per workgroup
 constexpr int BO_LIST = 128;    // list entries per wave: a batch of 64 and what one scan step can add to 63
 constexpr int BO_SC = 16;       // staging rows (real components) per wave
 constexpr int BO_ROW = 65;      // doubles per staging row: 64 bonds, padded so that lane = component reads spread over the banks
@@ -588,7 +632,7 @@ __host__ __device__ inline size_t bo_lds_bytes(int natoms, int nc, bool moments)
 {
     const size_t wave = (size_t)((moments ? BO_SC * BO_ROW + 4 * nc : 2 * nc)) * sizeof(double) // staging, acc and frame sums | qbar
                       + (size_t)(moments ? 4 : 1) * BO_LIST * 4 + (size_t)(BO_SC / 2 + 2) * 4; // list (vectors, index), row map, count
-    return (size_t)BO_WAVES * wave + ((size_t)3 * natoms + BO_WAVES * 6) * sizeof(float);
+    return (size_t)SHELL_WAVES * wave + ((size_t)3 * natoms + SHELL_WAVES * 6) * sizeof(float);
 }
 
 // the l of the i-th requested value
@@ -607,34 +651,7 @@ __device__ __forceinline__ double bo_invariant(const double *q, int l)
     return (4.0 * 3.14159265358979323846 / (double)(2 * l + 1)) * (q[0] * q[0] + q[1] * q[1] + 2.0 * t);
 }
 
-// stage the sample's positions and their bounding box (as nm_adf_kernel); ends with a workgroup barrier
-__device__ __forceinline__ void bo_stage(const float *ps, int natoms, float *px, float *py, float *pz, float *part, float *bb)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int a = tid; a < natoms; a += BO_BLOCK) {
-        const float x = ps[3 * a], y = ps[3 * a + 1], z = ps[3 * a + 2];
-        px[a] = x; py[a] = y; pz[a] = z;
-        lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
-        lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
-        lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
-    }
-    for (int d = 0; d < 3; ++d) {
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[d] = fminf(lo[d], __shfl_xor(lo[d], o));
-            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o));
-        }
-        if (lane == 0) { part[wave * 6 + 2 * d] = lo[d]; part[wave * 6 + 2 * d + 1] = hi[d]; }
-    }
-    __syncthreads();
-    for (int d = 0; d < 3; ++d) {
-        float l = part[2 * d], u = part[2 * d + 1];
-        for (int w = 1; w < BO_WAVES; ++w) { l = fminf(l, part[w * 6 + 2 * d]); u = fmaxf(u, part[w * 6 + 2 * d + 1]); }
-        bb[2 * d] = l; bb[2 * d + 1] = u;
-    }
-}
-
-// adf_fill's scan with the atom index recorded: the neighbour entries of centre (cx, cy, cz) in scan order go to the wave's
+// One shell_scan of centre (cx, cy, cz) with the atom index recorded: the neighbour entries in scan order go to the wave's
 // list (VEC: with their float32 components), and batch(n) is called with the list's first n entries whenever 64 are there, and
 // with the rest at the end; entries beyond 64 move to the front.  Returns the number of entries.
 template <bool VEC, class F>
@@ -642,52 +659,34 @@ __device__ __forceinline__ int bo_scan(const float *px, const float *py, const f
                                        float L, float cube, const float *bb, double r_lo, double r_hi, float *lx, float *ly,
                                        float *lz, int *li, int lane, F &&batch)
 {
-#pragma clang fp contract(off)
     int cnt = 0, total = 0;
-    for (int img = 0; img < 27; ++img) {
-        // br[j] = (b[i], b[j], b[k]) for i, j, k in range(3), b = [-1, 0, 1]  (lammps_distr.py:99-102)
-        const float bx = (float)(img / 9 - 1), by = (float)((img / 3) % 3 - 1), bz = (float)(img % 3 - 1);
-        const float qx = cx + L * bx, qy = cy + L * by, qz = cz + L * bz; // pos[c] + box*br[j]
-        if (bb[0] - qx > cube || bb[1] - qx < -cube || bb[2] - qy > cube || bb[3] - qy < -cube || bb[4] - qz > cube || bb[5] - qz < -cube)
-            continue; // see adf_fill
-        for (int a0 = 0; a0 < natoms; a0 += 64) {
-            const int a = a0 + lane;
-            bool in = false;
-            float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-            if (a < natoms) {
-                vx = px[a] - qx; vy = py[a] - qy; vz = pz[a] - qz;
-                float d2 = vx * vx;      // sequential float32 sum of three terms, as the rdf path
-                d2 = d2 + vy * vy;
-                d2 = d2 + vz * vz;
-                const double d = (double)sqrtf(d2); // correctly rounded (see nm_distr_kernel)
-                in = r_lo < d && d <= r_hi;
-            }
-            const unsigned long long m = __ballot(in);
-            if (in) {
-                const int o = cnt + __popcll(m & ((1ull << lane) - 1ull)); // cnt <= 63 here: o <= 126 < BO_LIST
-                if (VEC) { lx[o] = vx; ly[o] = vy; lz[o] = vz; }
-                li[o] = a;
-            }
-            cnt += __popcll(m);
-            total += __popcll(m);
-            if (cnt >= 64) {
-                adf_wave_sync();
-                batch(64);
-                adf_wave_sync();
-                const int rest = cnt - 64;
-                float tx = 0.0f, ty = 0.0f, tz = 0.0f;
-                if (VEC) { tx = lx[64 + lane]; ty = ly[64 + lane]; tz = lz[64 + lane]; }
-                const int ti = li[64 + lane];
-                adf_wave_sync();
-                if (lane < rest) {
-                    if (VEC) { lx[lane] = tx; ly[lane] = ty; lz[lane] = tz; }
-                    li[lane] = ti;
-                }
-                adf_wave_sync();
-                cnt = rest;
-            }
+    shell_scan(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, lane,
+               [&](int a, bool in, float vx, float vy, float vz, unsigned long long m) {
+        if (in) {
+            const int o = cnt + __popcll(m & ((1ull << lane) - 1ull)); // cnt <= 63 here: o <= 126 < BO_LIST
+            if (VEC) { lx[o] = vx; ly[o] = vy; lz[o] = vz; }
+            li[o] = a;
         }
-    }
+        cnt += __popcll(m);
+        total += __popcll(m);
+        if (cnt >= 64) {
+            adf_wave_sync();
+            batch(64);
+            adf_wave_sync();
+            const int rest = cnt - 64;
+            float tx = 0.0f, ty = 0.0f, tz = 0.0f;
+            if (VEC) { tx = lx[64 + lane]; ty = ly[64 + lane]; tz = lz[64 + lane]; }
+            const int ti = li[64 + lane];
+            adf_wave_sync();
+            if (lane < rest) {
+                if (VEC) { lx[lane] = tx; ly[lane] = ty; lz[lane] = tz; }
+                li[lane] = ti;
+            }
+            adf_wave_sync();
+            cnt = rest;
+        }
+        return true;
+    });
     if (cnt > 0) {
         adf_wave_sync();
         batch(cnt);
@@ -696,37 +695,37 @@ __device__ __forceinline__ int bo_scan(const float *px, const float *py, const f
     return total;
 }
 
-__global__ void __launch_bounds__(BO_BLOCK)
+__global__ void __launch_bounds__(SHELL_BLOCK)
 nm_bo_moments_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
                      BoSet set, const double *__restrict__ tab, double *__restrict__ qlm, double *__restrict__ q2,
                      int *__restrict__ nnb, double *__restrict__ partial, int *__restrict__ pcount)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int groups = (natoms + BO_CPB - 1) / BO_CPB;
-    const int s = blockIdx.x / groups, grp = blockIdx.x % groups, c0 = grp * BO_CPB;
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, grp = blockIdx.x % groups, c0 = grp * SHELL_CPB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nc2 = 2 * set.nc;
-    double *stage_all = (double *)smem, *acc_all = stage_all + BO_WAVES * BO_SC * BO_ROW, *gacc_all = acc_all + BO_WAVES * nc2;
-    float *lv_all = (float *)(gacc_all + BO_WAVES * nc2);
-    int *li_all = (int *)(lv_all + BO_WAVES * 3 * BO_LIST), *rowc_all = li_all + BO_WAVES * BO_LIST;
-    int *wcount = rowc_all + BO_WAVES * (BO_SC / 2);
-    float *px = (float *)(wcount + BO_WAVES * 2), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    double *stage_all = (double *)smem, *acc_all = stage_all + SHELL_WAVES * BO_SC * BO_ROW, *gacc_all = acc_all + SHELL_WAVES * nc2;
+    float *lv_all = (float *)(gacc_all + SHELL_WAVES * nc2);
+    int *li_all = (int *)(lv_all + SHELL_WAVES * 3 * BO_LIST), *rowc_all = li_all + SHELL_WAVES * BO_LIST;
+    int *wcount = rowc_all + SHELL_WAVES * (BO_SC / 2);
+    float *px = (float *)(wcount + SHELL_WAVES * 2), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
     const float L = box[s];
     float bb[6];
-    bo_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part, bb);
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    __syncthreads();
+    shell_bounds(part, bb);
     double *stage = stage_all + wave * BO_SC * BO_ROW, *acc = acc_all + wave * nc2, *gacc = gacc_all + wave * nc2;
     float *lx = lv_all + wave * 3 * BO_LIST, *ly = lx + BO_LIST, *lz = ly + BO_LIST;
     int *li = li_all + wave * BO_LIST, *rowc = rowc_all + wave * (BO_SC / 2);
     const double *tc = tab, *tA = tab + (BO_LMAX + 1), *tB = tA + (BO_LMAX + 1) * (BO_LMAX + 1);
     for (int j = lane; j < nc2; j += 64) gacc[j] = 0.0;
     int gcount = 0;
-    const int cend = c0 + BO_CPB < natoms ? c0 + BO_CPB : natoms;
-    for (int c = c0 + wave; c < cend; c += BO_WAVES) {
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
         for (int j = lane; j < nc2; j += 64) acc[j] = 0.0;
         adf_wave_sync();
-        const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px[c])));
-        const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py[c])));
-        const float cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pz[c])));
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
         const int nb = bo_scan<true>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, lx, ly, lz, li, lane, [&](int mb) {
             // lane = bond: the unit vector in float64 from the float32 components
             const bool act = lane < mb;
@@ -788,12 +787,12 @@ nm_bo_moments_kernel(int natoms, const float *__restrict__ pos, const float *__r
     __syncthreads();
     if (tid < nc2) {
         double t = gacc_all[tid];
-        for (int w = 1; w < BO_WAVES; ++w) t += gacc_all[w * nc2 + tid];
+        for (int w = 1; w < SHELL_WAVES; ++w) t += gacc_all[w * nc2 + tid];
         partial[((size_t)s * groups + grp) * nc2 + tid] = t;
     }
     if (tid == 0) {
         int t = 0;
-        for (int w = 0; w < BO_WAVES; ++w) t += wcount[w];
+        for (int w = 0; w < SHELL_WAVES; ++w) t += wcount[w];
         pcount[(size_t)s * groups + grp] = t;
     }
 }
@@ -818,30 +817,30 @@ __device__ __forceinline__ void bo_gather(const double *__restrict__ qs, const i
     }
 }
 
-__global__ void __launch_bounds__(BO_BLOCK)
+__global__ void __launch_bounds__(SHELL_BLOCK)
 nm_bo_average_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
                      BoSet set, const double *__restrict__ qlm, double *__restrict__ qbar2)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int groups = (natoms + BO_CPB - 1) / BO_CPB;
-    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * BO_CPB;
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * SHELL_CPB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nc2 = 2 * set.nc; // at most 126: a lane owns the components lane and lane + 64
     double *acc_all = (double *)smem;
-    int *li_all = (int *)(acc_all + BO_WAVES * nc2);
-    float *px = (float *)(li_all + BO_WAVES * BO_LIST + BO_WAVES * (BO_SC / 2 + 2)), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    int *li_all = (int *)(acc_all + SHELL_WAVES * nc2);
+    float *px = (float *)(li_all + SHELL_WAVES * BO_LIST + SHELL_WAVES * (BO_SC / 2 + 2)), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
     const float L = box[s];
     float bb[6];
-    bo_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part, bb);
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    __syncthreads();
+    shell_bounds(part, bb);
     double *acc = acc_all + wave * nc2;
     int *li = li_all + wave * BO_LIST;
     const double *qs = qlm + (size_t)s * natoms * nc2;
     const bool own0 = lane < nc2, own1 = lane + 64 < nc2;
-    const int cend = c0 + BO_CPB < natoms ? c0 + BO_CPB : natoms;
-    for (int c = c0 + wave; c < cend; c += BO_WAVES) {
-        const float cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px[c])));
-        const float cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py[c])));
-        const float cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pz[c])));
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
         double a0 = 0.0, a1 = 0.0;
         const int nb = bo_scan<false>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, nullptr, nullptr, nullptr, li, lane, [&](int mb) {
             // up to eight entries' reads in flight at a time (one entry's reads after the other leave the wave waiting for L2 four

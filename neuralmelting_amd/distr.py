@@ -121,12 +121,28 @@ def calculate_spatial(natoms, box, sbins, cbins):
     return nrho, dni, r, dn, rv
 
 
+def _frames(pos, box):
+    """pos and box as the entry points of include/nm_distr.h take them: contiguous float32, and their pointers"""
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    box = np.ascontiguousarray(box, dtype=np.float32)
+    return pos, box, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p)
+
+
+def _check(L, name, rc):
+    if rc != 0:
+        raise RuntimeError('%s failed (%d): %s' % (name, rc, L.nm_distr_last_error().decode()))
+
+
+def _device():
+    """the device of a command-line run: the launcher's LOCAL_RANK, else 0"""
+    return int(os.environ.get('LOCAL_RANK', '0'))
+
+
 def histograms(natoms, box, pos, r, rv, device=0, want_rdf=True, want_cdf=True):
     """raw counts of calculate_rdf / calculate_cdf for all samples, divided by natoms as the reference does:
     rdf[ns][sbins] float32, cdf[ns][cb][cb][cb] float32"""
     L = B.load()
-    pos = np.ascontiguousarray(pos, dtype=np.float32)
-    box = np.ascontiguousarray(box, dtype=np.float32)
+    pos, box, ppos, pbox = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     r = np.ascontiguousarray(r, dtype=np.float64)
     ve = np.ascontiguousarray(rv[0], dtype=np.float64)
@@ -136,10 +152,8 @@ def histograms(natoms, box, pos, r, rv, device=0, want_rdf=True, want_cdf=True):
     rdf = np.zeros((ns, sb), dtype=np.float32) if want_rdf else None
     cdf = np.zeros((ns, cb, cb, cb), dtype=np.float32) if want_cdf else None
     fp = lambda a: None if a is None else a.ctypes.data_as(B.c_float_p)
-    rc = L.nm_distr_histograms(device, ns, n, fp(pos), fp(box), sb, r.ctypes.data_as(B.c_double_p), cb,
-                               ve.ctypes.data_as(B.c_double_p), fp(rdf), fp(cdf))
-    if rc != 0:
-        raise RuntimeError('nm_distr_histograms failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    _check(L, 'nm_distr_histograms', L.nm_distr_histograms(device, ns, n, ppos, pbox, sb, r.ctypes.data_as(B.c_double_p), cb,
+                                                           ve.ctypes.data_as(B.c_double_p), fp(rdf), fp(cdf)))
     na = np.asarray(natoms).reshape(-1)
     if want_rdf:
         rdf = rdf / na[:, None]                           # rd/natoms (distr:135): float32 / uint16 -> float32
@@ -154,15 +168,12 @@ def angles(natoms, box, pos, a, r_lo, r_hi, device=0):
     adf[:, 0] = 0) divided by natoms in float64 and cast to float32 [ns][sbins], the dtype of the other histogram files.  The
     exact integers are available through the C-ABI."""
     L = B.load()
-    pos = np.ascontiguousarray(pos, dtype=np.float32)
-    box = np.ascontiguousarray(box, dtype=np.float32)
+    pos, box, ppos, pbox = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     ce = np.ascontiguousarray(np.cos(np.asarray(a, dtype=np.float64)))   # bins are compared in cosine space
     adf = np.zeros((ns, len(ce)), dtype=np.uint64)
-    rc = L.nm_distr_angles(device, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), float(r_lo), float(r_hi),
-                           len(ce), ce.ctypes.data_as(B.c_double_p), adf.ctypes.data_as(B.c_uint64_p))
-    if rc != 0:
-        raise RuntimeError('nm_distr_angles failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    _check(L, 'nm_distr_angles', L.nm_distr_angles(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), len(ce),
+                                                   ce.ctypes.data_as(B.c_double_p), adf.ctypes.data_as(B.c_uint64_p)))
     na = np.asarray(natoms).reshape(-1).astype(np.float64)
     return (adf.astype(np.float64) / na[:, None]).astype(np.float32)
 
@@ -186,17 +197,14 @@ def sfactor(natoms, box, pos, qmax, device=0):
     sum divided by the number of vectors of the shell) and the shell maximum, both float64 [ns][nshell].  natoms is accepted
     for symmetry with histograms() and angles(); the atom count is pos.shape[1]."""
     L = B.load()
-    pos = np.ascontiguousarray(pos, dtype=np.float32)
-    box = np.ascontiguousarray(box, dtype=np.float32)
+    pos, box, ppos, pbox = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     shells, mult = sfactor_shells(qmax)
     nsh = int(qmax) * int(qmax) + 1
     ssum = np.zeros((ns, nsh), dtype=np.float64)
     smax = np.zeros((ns, nsh), dtype=np.float64)
-    rc = L.nm_distr_sfactor(device, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), int(qmax),
-                            ssum.ctypes.data_as(B.c_double_p), smax.ctypes.data_as(B.c_double_p))
-    if rc != 0:
-        raise RuntimeError('nm_distr_sfactor failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    _check(L, 'nm_distr_sfactor', L.nm_distr_sfactor(device, ns, n, ppos, pbox, int(qmax), ssum.ctypes.data_as(B.c_double_p),
+                                                     smax.ctypes.data_as(B.c_double_p)))
     return ssum[:, shells] / mult[None, :], smax[:, shells]
 
 
@@ -207,8 +215,7 @@ def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
     roots sqrt(max(x, 0)) are taken here in float64.  natoms is accepted for symmetry with histograms(); the atom count is
     pos.shape[1]."""
     L = B.load()
-    pos = np.ascontiguousarray(pos, dtype=np.float32)
-    box = np.ascontiguousarray(box, dtype=np.float32)
+    pos, box, ppos, pbox = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     ls = np.ascontiguousarray(ls, dtype=np.int32).reshape(-1)
     nl = len(ls)
@@ -216,17 +223,16 @@ def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
     b2 = np.zeros((ns, n, nl), dtype=np.float64)
     g2 = np.zeros((ns, nl), dtype=np.float64)
     nb = np.zeros((ns, n), dtype=np.int32)
-    rc = L.nm_distr_bondorder(device, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), float(r_lo), float(r_hi),
-                              nl, ls.ctypes.data_as(B.c_int_p), q2.ctypes.data_as(B.c_double_p), b2.ctypes.data_as(B.c_double_p),
-                              g2.ctypes.data_as(B.c_double_p), nb.ctypes.data_as(B.c_int32_p))
-    if rc != 0:
-        raise RuntimeError('nm_distr_bondorder failed (%d): %s' % (rc, L.nm_distr_last_error().decode()))
+    _check(L, 'nm_distr_bondorder', L.nm_distr_bondorder(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), nl, ls.ctypes.data_as(B.c_int_p),
+                                                         q2.ctypes.data_as(B.c_double_p), b2.ctypes.data_as(B.c_double_p),
+                                                         g2.ctypes.data_as(B.c_double_p), nb.ctypes.data_as(B.c_int32_p)))
     root = lambda x: np.sqrt(np.maximum(x, 0.0))
     return root(q2), root(b2), root(g2), nb
 
 
 def main(argv=None):
     a = parse_args(argv)
+    dev = _device()
     prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, a.element.lower(), LAT[a.element])
     P = np.load(prefix + '.virial.trgt.npy')
     T = np.load(prefix + '.temp.trgt.npy')
@@ -244,7 +250,7 @@ def main(argv=None):
     rns = np.int32(ns / (pn * tn))
     if a.verbose:
         print('computing %s %s samples' % (ns, a.element.lower()))
-    rdf, cdf = histograms(natoms, box, pos, r, rv, device=int(os.environ.get('LOCAL_RANK', '0')))
+    rdf, cdf = histograms(natoms, box, pos, r, rv, device=dev)
     g = np.divide(np.array(rdf, dtype=np.float32), dni)                        # distr:305-311
     np.save(prefix + '.dni.npy', dni.reshape(pn, tn, rns, r.size))
     np.save(prefix + '.r.npy', r)
@@ -256,12 +262,12 @@ def main(argv=None):
     if a.angular:
         l = float(np.min(box))
         ang = np.linspace(1e-16, np.pi, a.spherical_bins)                     # distr:88
-        adf = angles(natoms, box, pos, ang, 1e-16 * l, a.angular_cutoff * l, device=int(os.environ.get('LOCAL_RANK', '0')))
+        adf = angles(natoms, box, pos, ang, 1e-16 * l, a.angular_cutoff * l, device=dev)
         np.save(prefix + '.a.npy', ang)
         np.save(prefix + '.adf.npy', adf.reshape(pn, tn, rns, ang.size))
     if a.structure_factor:
         shells, _ = sfactor_shells(a.q_max)
-        sf, sfm = sfactor(natoms, box, pos, a.q_max, device=int(os.environ.get('LOCAL_RANK', '0')))
+        sf, sfm = sfactor(natoms, box, pos, a.q_max, device=dev)
         np.save(prefix + '.q.npy', 2 * np.pi * np.sqrt(shells.astype(np.float64)))   # |q| of a sample = this / its box
         np.save(prefix + '.sf.npy', sf.astype(np.float32).reshape(pn, tn, rns, shells.size))
         np.save(prefix + '.sfm.npy', sfm.astype(np.float32).reshape(pn, tn, rns, shells.size))
@@ -269,7 +275,7 @@ def main(argv=None):
     if a.bond_order:
         l = float(np.min(box))
         n, nl = int(natoms[0]), len(a.bond_l)
-        q, qb, qg, nb = bond_order(natoms, box, pos, a.bond_l, 1e-16 * l, bcut * l, device=int(os.environ.get('LOCAL_RANK', '0')))
+        q, qb, qg, nb = bond_order(natoms, box, pos, a.bond_l, 1e-16 * l, bcut * l, device=dev)
         np.save(prefix + '.bol.npy', np.array(a.bond_l, dtype=np.int64))
         np.save(prefix + '.boq.npy', q.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
         np.save(prefix + '.bob.npy', qb.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))

@@ -5,10 +5,11 @@ which stays below 1e-12 for every l <= 12.
 
 Covered: random liquids on both sides of the block of centres (32), of the wave (64) and of 256 atoms at a first-shell cutoff and
 at half the box (more than 64 neighbours from about 130 atoms up: several batches of the wave's list); a cluster with 529
-neighbours per centre; 2048 atoms; a sparse frame with empty and single-neighbour shells; the l sets (4, 6), (1,), (12,) and
-(2, .., 12); lattices on integer coordinates (fcc, simple cubic with bonds on the poles, a cutoff exactly on the second-neighbour
+neighbours per centre; 2048 atoms; a sparse frame with empty and single-neighbour shells; the l sets (4, 6), (1,), (12,) and (2,
+.., 12); lattices on integer coordinates (fcc, simple cubic with bonds on the poles, a cutoff exactly on the second-neighbour
 distance, every neighbour in two images); boxes that differ inside a batch, an unwrapped frame, a metal-unit box, coincident atoms,
-two launch chunks; NULL outputs; a permutation, an exact translation, determinism; crystal against ideal gas; the command line."""
+two launch chunks, a batch that the scratch cap splits; the entries against nm_distr_angles' neighbours; NULL outputs; a
+permutation, an exact translation, determinism; crystal against ideal gas; the command line."""
 import os
 
 import numpy as np
@@ -225,6 +226,62 @@ def test_more_samples_than_one_launch_chunk():
     out, ref = check(pos, box, (4, 6), 1e-16, 0.5 * float(box.min()))
     for s in (0, 4095, 4096):
         assert out['nnb'][s].sum() > 0
+
+
+def test_scratch_cap_splits_the_batch():
+    """4096 samples of 66 atoms with l = 7 .. 12: nc2 = 2 * (8 + 9 + 10 + 11 + 12 + 13) = 126 doubles per atom, so a sample's moments
+    take 66 * 126 * 8 = 66,528 B of the scratch, and 2^28 // 66,528 = 4034 of them fit under the cap of 256 MiB (4034 * 66,528 =
+    268,373,952 <= 268,435,456 < 4035 * 66,528): launch chunks of 4034 and 62 samples where the sample cap alone would give one.
+    The samples on both sides of the seam and the last one equal, bit for bit, a call of their own (the entry point is
+    reproducible bit for bit), and four of them pass the restatement.  This checks the results across the seam, not that the
+    batch is split: one launch of 4096 samples would give the same bits, and the split cannot be seen through the entry point"""
+    ls = (7, 8, 9, 10, 11, 12)
+    rng = np.random.default_rng(7950)
+    pos, box = liquid(rng, 4096, 66)
+    assert float(box.min()) > 3.0
+    big = run(pos, box, ls, 1e-16, 1.5)
+    for sl in (slice(4030, 4040), slice(4095, 4096)):
+        part = run(pos[sl], box[sl], ls, 1e-16, 1.5)
+        for k in NAMES:
+            assert big[k][sl].tobytes() == part[k].tobytes(), (k, sl)
+    pick = [0, 4033, 4034, 4095]
+    out, ref = check(pos[pick], box[pick], ls, 1e-16, 1.5)
+    for k in NAMES:
+        assert big[k][pick].tobytes() == out[k].tobytes(), k
+    assert out['nnb'].sum() > 0
+
+
+# ---- the entries are the neighbours of nm_distr_angles
+def test_entries_are_the_neighbours_of_the_angular_distribution():
+    """nm_distr_angles with the edges cos = (1, 0, -1) counts every unordered pair of a centre's neighbours in one of its two bins
+    (the clipped cosine lies in [-1, 1]); with Nb(c) entries per centre that is sum_c Nb(c) (Nb(c) - 1) / 2, in integers.  Liquids of
+    65 and 257 atoms at half the box and the ball of test_more_than_256_neighbours (529 neighbours: three tiles of the angular
+    kernel, nine batches of the list)"""
+    L = B.load()
+    frames = []
+    for n in (65, 257):
+        pos, box = liquid(np.random.default_rng(7000 + n), 2, n)
+        frames.append((pos, box, 1e-16 * float(box.min()), 0.5 * float(box.min())))
+    rng = np.random.default_rng(7100)
+    u = rng.normal(size=(530, 3))
+    u *= (2.4 * rng.random(530) ** (1 / 3) / np.linalg.norm(u, axis=1))[:, None]
+    frames.append(((u + 5.0).astype(np.float32)[None], np.full(1, 10.0, dtype=np.float32), 1e-15, 5.0))
+    ce = np.array([1.0, 0.0, -1.0])
+    for pos, box, r_lo, r_hi in frames:
+        pos = np.ascontiguousarray(pos, dtype=np.float32)
+        rc, msg, out = call(pos, box, (4,), r_lo, r_hi, want=('nnb',))
+        assert rc == 0, msg
+        adf = np.full((pos.shape[0], 3), 2 ** 64 - 1, dtype=np.uint64)
+        rc = L.nm_distr_angles(0, pos.shape[0], pos.shape[1], pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p),
+                               float(r_lo), float(r_hi), 3, ce.ctypes.data_as(B.c_double_p), adf.ctypes.data_as(B.c_uint64_p))
+        assert rc == 0, L.nm_distr_last_error().decode()
+        for s in range(pos.shape[0]):
+            nb = [int(x) for x in out['nnb'][s]]
+            assert min(nb) >= 0 and max(nb) > 1
+            assert int(adf[s, 0]) == 0
+            assert int(adf[s, 1]) + int(adf[s, 2]) == sum(m * (m - 1) // 2 for m in nb), (pos.shape[1], s)
+        if pos.shape[1] == 530:
+            assert (out['nnb'] == 529).all()
 
 
 # ---- NULL outputs, invariance, determinism
