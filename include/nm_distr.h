@@ -104,6 +104,38 @@ int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const flo
 int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
                        const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb);
 
+/* Solid-like atoms and crystal clusters: ten Wolde, Ruiz-Montero and Frenkel's criterion on the normalised dot products of the
+ * q_lm vectors of neighbouring atoms, and the connected components of the solid-like atoms.  Definition (the build's own), for
+ * sample s, one l and centre atom c:
+ *   entries     exactly those of nm_distr_bondorder: (j, a) over the 27 image shifts br[j] and all atoms a, the float32
+ *               displacement and its float32 length d, r_lo < (double)d <= r_hi; an atom that qualifies in two images is two
+ *               entries;
+ *   moments     q_lm(c) exactly those of nm_distr_bondorder: float64, m >= 0 stored, 0 if c has no entry;
+ *   norm        |q(c)|^2 = |q_l0|^2 + 2 sum_{m>0} |q_lm|^2;
+ *   bond value  for the entry (j, a) of c: s(c, a) = (Re q_l0(c) conj q_l0(a) + 2 sum_{m>0} Re q_lm(c) conj q_lm(a)) / (|q(c)| |q(a)|)
+ *               in float64, the sums with m ascending; s = 0 where the product of the norms is exactly 0;
+ *   connection  the entry is connected iff s(c, a) > s_min;
+ *   nconn[s][c] the number of connected entries of c;
+ *   solid-like  nconn[s][c] >= n_min;
+ *   clusters    the connected components of the undirected graph on the solid-like atoms that has the edge {c, a} whenever a is an
+ *               entry of c or c is an entry of a.  The edge does not ask for a connection (the usual convention).  The float32 test
+ *               is not guaranteed to be symmetric on the cutoff itself, hence the "or";
+ *   label[s][c] the smallest atom index in c's cluster, -1 for an atom that is not solid-like: canonical, independent of the
+ *               order of execution;
+ *   nsolid[s]   the number of solid-like atoms, nclus[s] the number of clusters, largest[s] the size of the largest cluster (0 if
+ *               there is none).
+ * The bond value carries the error of the moments (nm_distr_bondorder: e_q per vector, relative to the harmonics' norm), so an
+ * entry whose value lies within about 4 (e_q / |q(c)| + e_q / |q(a)|) + 16 u of s_min can fall on either side; everything else is
+ * integer and exact.  The result is the same bit for bit on every call: fixed summation orders, integer atomics only.
+ * pos[ns][natoms][3], box[ns] float32; nconn, label [ns][natoms] and nsolid, nclus, largest [ns] int32.  Any output may be NULL (it
+ * is then not written), but not all five.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_solid:".  NM_ERR_ARG, checked
+ * before the device is looked for and with the outputs left untouched, for: ns < 0, natoms outside 1..4095, l outside 1..12, s_min
+ * not within [-1, 1), n_min < 1, not 0 <= r_lo < r_hi, r_hi > min(box)/2 over the batch, a box that is not finite and positive, a
+ * null pos or box, all outputs null, a bad device ordinal.  ns == 0 as in nm_distr_bondorder. */
+int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int l, double s_min,
+                   int n_min, int32_t *nconn, int32_t *label, int32_t *nsolid, int32_t *nclus, int32_t *largest);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1675,6 +1675,48 @@ int half_box_check(const char *fn, int ns, const float *box, double r_hi)
 // the image pre-test of the scan compares float components with a float at or above r_hi; it is switched off for shells
 // so small that the squares of such components could underflow
 float shell_cube(double r_hi) { return r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY); }
+
+// what the bond-order kernels need to know of the requested l (nm_distr.h, BoSet); ls increases strictly within 1..12
+BoSet bo_set(int nl, const int *ls)
+{
+    BoSet set = {nl, 0, ls[nl - 1], 0u, 0ull, 0u};
+    for (int i = 0; i < nl; ++i) {
+        const int l = ls[i];
+        set.lmask |= 1u << l;
+        if (l <= 8) set.off_lo |= (unsigned long long)set.nc << (8 * (l - 1));
+        else set.off_hi |= (unsigned int)set.nc << (8 * (l - 9));
+        set.nc += l + 1;
+    }
+    return set;
+}
+
+// the constants of the harmonics' recurrence (nm_distr.h): long double, rounded once
+std::vector<double> bo_table()
+{
+    const int W = BO_LMAX + 1;
+    std::vector<double> tab((size_t)BO_TAB, 0.0);
+    long double c = sqrtl(1.0L / (4.0L * 3.14159265358979323846264338327950288L));
+    for (int m = 0; m <= BO_LMAX; ++m) {
+        if (m > 0) c = -c * sqrtl((long double)(2 * m + 1) / (long double)(2 * m));
+        tab[m] = (double)c;
+        for (int l = m + 1; l <= BO_LMAX; ++l) {
+            tab[W + l * W + m] = (double)sqrtl((long double)(4 * l * l - 1) / (long double)(l * l - m * m));
+            tab[W + W * W + l * W + m] = (double)sqrtl((long double)((l - 1) * (l - 1) - m * m) / (long double)(4 * (l - 1) * (l - 1) - 1));
+        }
+    }
+    return tab;
+}
+
+// samples per launch of the entry points that keep the moments q_lm in a device scratch of `per` bytes per sample: at most
+// DISTR_CHUNK as the other entry points, fewer where the scratch would pass 256 MiB
+int bo_chunk(int ns, size_t per)
+{
+    size_t fit = ((size_t)256 << 20) / per;
+    if (fit < 1) fit = 1;
+    int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    if ((size_t)cs > fit) cs = (int)fit;
+    return cs;
+}
 } // namespace
 
 extern "C" {
@@ -1817,36 +1859,12 @@ int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const f
     if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
     if (const int rc = distr_device(fn, device)) return rc;
     if (ns == 0) return NM_OK;
-    // the requested l and the recurrence's constants (nm_distr.h): long double, rounded once
-    BoSet set = {nl, 0, ls[nl - 1], 0u, 0ull, 0u};
-    for (int i = 0; i < nl; ++i) {
-        const int l = ls[i];
-        set.lmask |= 1u << l;
-        if (l <= 8) set.off_lo |= (unsigned long long)set.nc << (8 * (l - 1));
-        else set.off_hi |= (unsigned int)set.nc << (8 * (l - 9));
-        set.nc += l + 1;
-    }
-    const int nc2 = 2 * set.nc, W = BO_LMAX + 1;
-    std::vector<double> tab((size_t)BO_TAB, 0.0);
-    {
-        long double c = sqrtl(1.0L / (4.0L * 3.14159265358979323846264338327950288L));
-        for (int m = 0; m <= BO_LMAX; ++m) {
-            if (m > 0) c = -c * sqrtl((long double)(2 * m + 1) / (long double)(2 * m));
-            tab[m] = (double)c;
-            for (int l = m + 1; l <= BO_LMAX; ++l) {
-                tab[W + l * W + m] = (double)sqrtl((long double)(4 * l * l - 1) / (long double)(l * l - m * m));
-                tab[W + W * W + l * W + m] = (double)sqrtl((long double)((l - 1) * (l - 1) - m * m) / (long double)(4 * (l - 1) * (l - 1) - 1));
-            }
-        }
-    }
+    const BoSet set = bo_set(nl, ls);
+    const int nc2 = 2 * set.nc;
+    const std::vector<double> tab = bo_table();
     const float cube = shell_cube(r_hi);
     const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
-    // samples per launch: at most DISTR_CHUNK as the other entry points, fewer where the moments' scratch would pass 256 MiB
-    const size_t per = (size_t)natoms * nc2 * sizeof(double);
-    size_t fit = ((size_t)256 << 20) / per;
-    if (fit < 1) fit = 1;
-    int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
-    if ((size_t)cs > fit) cs = (int)fit;
+    const int cs = bo_chunk(ns, (size_t)natoms * nc2 * sizeof(double));
     const size_t lds1 = bo_lds_bytes(natoms, set.nc, true), lds2 = bo_lds_bytes(natoms, set.nc, false); // at most 98,932 B (4095 atoms, six l from 7 to 12)
     DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
     DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
@@ -1881,6 +1899,67 @@ int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const f
         if (qbar2) DISTR_CHK(fn, hipMemcpy(qbar2 + (size_t)s0 * pa, d_qb, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
         if (Q2) DISTR_CHK(fn, hipMemcpy(Q2 + (size_t)s0 * nl, d_Q, (size_t)n * nl * sizeof(double), hipMemcpyDeviceToHost));
         if (nnb) DISTR_CHK(fn, hipMemcpy(nnb + (size_t)s0 * natoms, d_nnb, (size_t)n * natoms * sizeof(int), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
+}
+
+int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int l, double s_min,
+                   int n_min, int32_t *nconn, int32_t *label, int32_t *nsolid, int32_t *nclus, int32_t *largest)
+{
+    static const char *const fn = "nm_distr_solid";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!nconn && !label && !nsolid && !nclus && !largest) return refuse(fn, "all five outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (l < 1 || l > BO_LMAX) return refuse(fn, "l must lie in 1..12");
+    if (!(s_min >= -1.0) || !(s_min < 1.0)) return refuse(fn, "s_min must lie in [-1, 1)");
+    if (n_min < 1) return refuse(fn, "n_min must be at least 1");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = distr_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const BoSet set = bo_set(1, &l);
+    const int nc2 = 2 * set.nc;
+    const std::vector<double> tab = bo_table();
+    const float cube = shell_cube(r_hi);
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int cs = bo_chunk(ns, (size_t)natoms * nc2 * sizeof(double));
+    const size_t lds1 = bo_lds_bytes(natoms, set.nc, true), lds2 = solid_lds_bytes(natoms); // at most 92,532 B and 51,284 B (4095 atoms, l = 12)
+    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    DevBuf<double> d_tab, d_qlm, d_part;
+    DevBuf<int> d_cnt, d_conn, d_par, d_lab, d_ns, d_nc, d_big;
+    DISTR_CHK(fn, d_tab.alloc(tab.size()));
+    DISTR_CHK(fn, d_qlm.alloc((size_t)cs * natoms * nc2));
+    DISTR_CHK(fn, d_part.alloc((size_t)cs * groups * nc2));
+    DISTR_CHK(fn, d_cnt.alloc((size_t)cs * groups));
+    DISTR_CHK(fn, d_conn.alloc((size_t)cs * natoms));
+    DISTR_CHK(fn, d_par.alloc((size_t)cs * natoms));
+    DISTR_CHK(fn, d_lab.alloc((size_t)cs * natoms));
+    DISTR_CHK(fn, d_ns.alloc((size_t)cs));
+    DISTR_CHK(fn, d_nc.alloc((size_t)cs));
+    DISTR_CHK(fn, d_big.alloc((size_t)cs));
+    DISTR_CHK(fn, hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        // each kernel reads what the one before it wrote for the whole chunk: the launches of one stream run in order
+        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, set,
+                           d_tab, d_qlm, (double *)nullptr, (int *)nullptr, d_part, d_cnt);
+        DISTR_CHK(fn, hipGetLastError());
+        hipLaunchKernelGGL(nm_solid_connect_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, l,
+                           s_min, d_qlm, d_conn, d_par);
+        DISTR_CHK(fn, hipGetLastError());
+        hipLaunchKernelGGL(nm_solid_union_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, n_min,
+                           d_conn, d_par);
+        DISTR_CHK(fn, hipGetLastError());
+        hipLaunchKernelGGL(nm_solid_label_kernel, dim3(n), dim3(SOLID_BLOCK), 0, 0, natoms, n_min, d_conn, d_par, d_lab, d_ns, d_nc, d_big);
+        DISTR_CHK(fn, hipGetLastError());
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        const size_t pa = (size_t)natoms * sizeof(int);
+        if (nconn) DISTR_CHK(fn, hipMemcpy(nconn + (size_t)s0 * natoms, d_conn, (size_t)n * pa, hipMemcpyDeviceToHost));
+        if (label) DISTR_CHK(fn, hipMemcpy(label + (size_t)s0 * natoms, d_lab, (size_t)n * pa, hipMemcpyDeviceToHost));
+        if (nsolid) DISTR_CHK(fn, hipMemcpy(nsolid + s0, d_ns, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        if (nclus) DISTR_CHK(fn, hipMemcpy(nclus + s0, d_nc, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        if (largest) DISTR_CHK(fn, hipMemcpy(largest + s0, d_big, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
         return NM_OK;
     });
 }

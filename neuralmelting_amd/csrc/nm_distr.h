@@ -885,4 +885,195 @@ nm_bo_global_kernel(int groups, BoSet set, const double *__restrict__ partial, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Solid-like atoms and crystal clusters (include/nm_distr.h, nm_distr_solid): ten Wolde, Ruiz-Montero and Frenkel's criterion on
+// the normalised dot products of the q_lm vectors of neighbouring atoms, then the connected components of the solid-like atoms.
+// The moments come from nm_bo_moments_kernel, launched for the single l and unchanged; three kernels follow, each a kernel
+// boundary behind what it reads:
+//   connect  (nm_solid_connect_kernel) the grid and staging of the average pass, bo_scan<false>.  For a batch, lane = entry: the
+//            lane walks the moments' rows of the centre (the same address in every lane) and of its entry's atom (l + 1 reads of
+//            16 B from a row of at most 208 B that L2 holds) and forms the dot product and both norms with m ascending, a fixed
+//            order: the same bits on every call.  The connections are counted by ballot and popcount.  The wave writes nconn[c]
+//            (an atom is solid-like where nconn >= n_min: the later kernels read the flag off that array) and parent[c] = c.
+//   union    (nm_solid_union_kernel) the same grid; a centre that is not solid-like is skipped, a solid-like one is scanned
+//            again, indices only, and every entry whose atom is solid-like is united with the centre in the sample's parent
+//            array.  An edge that only one of its two ends sees as an entry (the float32 test on the cutoff itself) is united
+//            from that end: both ends are scanned, being solid-like.
+//   label    (nm_solid_label_kernel) one workgroup per sample: label = root or -1, the cluster sizes by LDS integer atomics on
+//            the root, then nsolid, nclus, largest.
+// The union-find is lock-free and no thread ever waits for another: no spin loop, no polled flag, no cooperative launch.
+// Invariants of parent[] (one int per atom, indices within the sample):
+//   (1) parent[x] <= x always: it starts as x, and every write stores a smaller value;
+//   (2) every write lowers a value: a hook is atomicCAS(parent[r], r, smaller root), a compression is atomicMin(parent[x],
+//       grandparent); so a value read earlier is still an ancestor, and a root (parent[r] == r) is never written by a compression;
+//   (3) the atomicCAS of a hook fails only if r is no longer a root, which only another hook's success can cause: a sample sees at
+//       most natoms - 1 successful hooks, so all threads together retry at most that often per root they aimed at;
+//   (4) a find terminates: along parent[] the indices decrease strictly until a root, at most natoms - 1 steps.
+// The smaller root always wins, so the root of a finished cluster is its smallest index: the label is canonical, whatever the
+// order of execution.  Reads of parent[] that race with other workgroups are relaxed atomic loads at agent scope (they pass the
+// caches that are not coherent across the device); the label kernel runs behind a kernel boundary and reads plainly.
+// Integer atomics only.
+constexpr int SOLID_BLOCK = 256;    // threads of the label kernel
+constexpr int SOLID_MAXN = 4096;    // its LDS counters: natoms <= 4095
+
+__host__ __device__ inline size_t solid_lds_bytes(int natoms) // 51,284 B at 4095 atoms
+{
+    return (size_t)SHELL_WAVES * BO_LIST * sizeof(int) + ((size_t)3 * natoms + SHELL_WAVES * 6) * sizeof(float);
+}
+
+__global__ void __launch_bounds__(SHELL_BLOCK)
+nm_solid_connect_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+                        int l, double s_min, const double *__restrict__ qlm, int *__restrict__ nconn, int *__restrict__ parent)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * SHELL_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int *li_all = (int *)smem;
+    float *px = (float *)(li_all + SHELL_WAVES * BO_LIST), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    __syncthreads();
+    shell_bounds(part, bb);
+    int *li = li_all + wave * BO_LIST;
+    const int nc2 = 2 * (l + 1); // a row is 16 (l + 1) bytes: every (Re, Im) pair is one aligned 16-byte read
+    const double *qs = qlm + (size_t)s * natoms * nc2;
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
+        const double2 *rc = (const double2 *)(qs + (size_t)c * nc2);
+        int conn = 0;
+        bo_scan<false>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, nullptr, nullptr, nullptr, li, lane, [&](int mb) {
+            const bool act = lane < mb;
+            const double2 *ra = (const double2 *)(qs + (size_t)(act ? li[lane] : c) * nc2);
+            const double2 C0 = rc[0], A0 = ra[0];
+            double dm = 0.0, cm = 0.0, am = 0.0; // the sums over m > 0, m ascending
+            for (int m = 1; m <= l; ++m) {
+                const double2 C = rc[m], A = ra[m];
+                dm = fma(C.y, A.y, fma(C.x, A.x, dm));
+                cm = fma(C.y, C.y, fma(C.x, C.x, cm));
+                am = fma(A.y, A.y, fma(A.x, A.x, am));
+            }
+            const double dot = fma(C0.y, A0.y, C0.x * A0.x) + 2.0 * dm;
+            const double n2c = fma(C0.y, C0.y, C0.x * C0.x) + 2.0 * cm, n2a = fma(A0.y, A0.y, A0.x * A0.x) + 2.0 * am;
+            const double den = sqrt(n2c) * sqrt(n2a);
+            const double sv = den > 0.0 ? dot / den : 0.0;
+            conn += __popcll(__ballot(act && sv > s_min));
+        });
+        if (lane == 0) {
+            nconn[(size_t)s * natoms + c] = conn;
+            parent[(size_t)s * natoms + c] = c;
+        }
+    }
+}
+
+__device__ __forceinline__ int solid_peek(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x, halving the path on the way: x's parent is lowered to its grandparent (invariant 2), then the walk goes on from
+// the grandparent.  Every step lowers x or ends the walk (invariant 4).
+__device__ __forceinline__ int solid_find(int *parent, int x)
+{
+    for (;;) {
+        const int p = solid_peek(parent + x);
+        if (p == x) return x;
+        const int g = solid_peek(parent + p);
+        if (g < p) atomicMin(parent + x, g);
+        x = g;
+    }
+}
+
+// unites the clusters of x and y: the larger of the two roots is hooked under the smaller with one atomicCAS.  A failure means
+// that the larger one has been hooked by someone else in the meantime (invariant 3): find again from where we are, nothing to
+// wait for.
+__device__ __forceinline__ void solid_union(int *parent, int x, int y)
+{
+    for (;;) {
+        x = solid_find(parent, x);
+        y = solid_find(parent, y);
+        if (x == y) return;
+        const int hi = x > y ? x : y, lo = x > y ? y : x;
+        if (atomicCAS(parent + hi, hi, lo) == hi) return;
+        x = hi; y = lo;
+    }
+}
+
+__global__ void __launch_bounds__(SHELL_BLOCK)
+nm_solid_union_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+                      int n_min, const int *__restrict__ nconn, int *parent)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * SHELL_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int *nc = nconn + (size_t)s * natoms;
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    {
+        // a workgroup without a solid-like centre has nothing to unite (the same answer in every thread: no barrier is skipped
+        // by a part of the workgroup)
+        bool any = false;
+        for (int c = c0; c < cend; ++c) any = any || nc[c] >= n_min;
+        if (!any) return;
+    }
+    int *li_all = (int *)smem;
+    float *px = (float *)(li_all + SHELL_WAVES * BO_LIST), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    __syncthreads();
+    shell_bounds(part, bb);
+    int *li = li_all + wave * BO_LIST;
+    int *par = parent + (size_t)s * natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
+        if (nc[c] < n_min) continue; // wave-uniform
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
+        bo_scan<false>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, nullptr, nullptr, nullptr, li, lane, [&](int mb) {
+            if (lane < mb) {
+                const int a = li[lane];
+                if (a != c && nc[a] >= n_min) solid_union(par, c, a);
+            }
+        });
+    }
+}
+
+__global__ void __launch_bounds__(SOLID_BLOCK)
+nm_solid_label_kernel(int natoms, int n_min, const int *__restrict__ nconn, const int *__restrict__ parent, int *__restrict__ label,
+                      int *__restrict__ nsolid, int *__restrict__ nclus, int *__restrict__ largest)
+{
+    __shared__ int size[SOLID_MAXN];
+    __shared__ int red[SOLID_BLOCK / 64][3];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int *nc = nconn + (size_t)s * natoms, *par = parent + (size_t)s * natoms;
+    for (int c = tid; c < natoms; c += SOLID_BLOCK) size[c] = 0;
+    __syncthreads();
+    for (int c = tid; c < natoms; c += SOLID_BLOCK) {
+        int r = -1;
+        if (nc[c] >= n_min) {
+            r = c;
+            for (int p = par[r]; p != r; p = par[r]) r = p; // invariant 4
+            atomicAdd(&size[r], 1);
+        }
+        label[(size_t)s * natoms + c] = r;
+    }
+    __syncthreads();
+    int ns = 0, ncl = 0, big = 0;
+    for (int c = tid; c < natoms; c += SOLID_BLOCK) {
+        const int v = size[c];
+        ns += v; ncl += v > 0 ? 1 : 0; big = v > big ? v : big;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        ns += __shfl_xor(ns, o); ncl += __shfl_xor(ncl, o);
+        const int t = __shfl_xor(big, o);
+        big = t > big ? t : big;
+    }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = ns; red[tid >> 6][1] = ncl; red[tid >> 6][2] = big; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < SOLID_BLOCK / 64; ++w) {
+            ns += red[w][0]; ncl += red[w][1]; big = red[w][2] > big ? red[w][2] : big;
+        }
+        nsolid[s] = ns; nclus[s] = ncl; largest[s] = big;
+    }
+}
+
 } // namespace nm

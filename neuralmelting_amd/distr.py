@@ -9,12 +9,15 @@ files with the same shapes and dtypes.  With -ad it also writes the angular (bon
 static structure factor on the reciprocal lattice of each sample's box, averaged and maximised over the shells |q| = const
 (.q.npy / .sf.npy / .sfm.npy; definition: include/nm_distr.h, nm_distr_sfactor), and the number densities (.nrho.npy).
 With -bo it also writes the Steinhardt bond-order parameters q_l, their neighbour average and the global Q_l (.bo*.npy;
-definition: include/nm_distr.h, nm_distr_bondorder).
+definition: include/nm_distr.h, nm_distr_bondorder).  With -so it also writes the solid-like atoms and crystal clusters of each
+sample: the solid fraction, the largest cluster's share, the number of clusters and the mean number of connections (.so*.npy;
+definition: include/nm_distr.h, nm_distr_solid).
 
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -sf -sq 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -bo -bl 4 6
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -so -sl 6 -st 0.5 -sx 8
 """
 import argparse
 import ctypes as C
@@ -71,6 +74,21 @@ def _parser():
     p.add_argument('-ba', '--bond_atoms', action='store_true',
                    help='with -bo also write the per-atom values: <PREFIX>.boqa.npy, .boba.npy and .bona.npy; 8 nl + 4 bytes per atom '
                         'and sample for nl values of l, about 10 GB for a grid of 2^20 samples of 500 atoms at two l')
+    p.add_argument('-so', '--solid', action='store_true',
+                   help='also write the solid-like atoms and crystal clusters (ten Wolde, Ruiz-Montero and Frenkel): <PREFIX>.sof.npy '
+                        '(solid-like atoms / natoms), .sol.npy (largest cluster / natoms), .soc.npy (number of clusters) and .son.npy '
+                        '(mean number of connections per atom).  The neighbour shell is that of -bc')
+    p.add_argument('-sl', '--solid_l', type=int, default=6, help='the l of -so: 1..12, default 6')
+    p.add_argument('-st', '--solid_threshold', type=float, default=0.5,
+                   help='a neighbour entry is a connection of -so if the normalised dot product of the two q_lm vectors exceeds this '
+                        'value, in [-1, 1); default 0.5, a common choice whose suitability for the LJ and Sutton-Chen grids of this '
+                        'package has not been measured')
+    p.add_argument('-sx', '--solid_connections', type=int, default=8,
+                   help='an atom is solid-like for -so if it has at least this many connections, >= 1; default 8, a common choice '
+                        'whose suitability for the LJ and Sutton-Chen grids of this package has not been measured')
+    p.add_argument('-sa', '--solid_atoms', action='store_true',
+                   help='with -so also write the per-atom values: <PREFIX>.sona.npy (connections) and .sola.npy (cluster label: the '
+                        'smallest atom index of the cluster, -1 for an atom that is not solid-like); 8 bytes per atom and sample')
     return p
 
 
@@ -99,6 +117,12 @@ def parse_args(argv=None):
         p.error('-ac/--angular_cutoff must lie in (0, 0.5]')
     if not 1 <= a.q_max <= 32:
         p.error('-sq/--q_max must lie in 1..32')
+    if not 1 <= a.solid_l <= 12:
+        p.error('-sl/--solid_l must lie in 1..12')
+    if not -1.0 <= a.solid_threshold < 1.0:
+        p.error('-st/--solid_threshold must lie in [-1, 1)')
+    if a.solid_connections < 1:
+        p.error('-sx/--solid_connections must be at least 1')
     return a
 
 
@@ -230,6 +254,26 @@ def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
     return root(q2), root(b2), root(g2), nb
 
 
+def solid(natoms, box, pos, l, r_lo, r_hi, s_min, n_min, device=0):
+    """solid-like atoms and crystal clusters of all samples (include/nm_distr.h, nm_distr_solid) for one l in 1..12, neighbour shell
+    r_lo < d <= r_hi, connection threshold s_min in [-1, 1) and n_min >= 1 connections for a solid-like atom: nconn int32 [ns][natoms]
+    (connections per atom), label int32 [ns][natoms] (the smallest atom index of the atom's cluster, -1 if the atom is not solid-like),
+    nsolid, nclus and largest int32 [ns] (solid-like atoms, clusters, size of the largest cluster).  natoms is accepted for symmetry
+    with histograms(); the atom count is pos.shape[1]."""
+    L = B.load()
+    pos, box, ppos, pbox = _frames(pos, box)
+    ns, n = pos.shape[0], pos.shape[1]
+    nconn = np.zeros((ns, n), dtype=np.int32)
+    label = np.zeros((ns, n), dtype=np.int32)
+    nsolid = np.zeros(ns, dtype=np.int32)
+    nclus = np.zeros(ns, dtype=np.int32)
+    largest = np.zeros(ns, dtype=np.int32)
+    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
+    _check(L, 'nm_distr_solid', L.nm_distr_solid(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), int(l), float(s_min), int(n_min),
+                                                 ip(nconn), ip(label), ip(nsolid), ip(nclus), ip(largest)))
+    return nconn, label, nsolid, nclus, largest
+
+
 def main(argv=None):
     a = parse_args(argv)
     dev = _device()
@@ -241,7 +285,7 @@ def main(argv=None):
     box = np.load(prefix + '.box.npy').reshape(-1)
     pos = np.load(prefix + '.pos.npy').reshape(-1, natoms[0], 3)
     ns = natoms.size
-    if a.bond_order:
+    if a.bond_order or a.solid:
         try:
             bcut = bond_cutoff(a.bond_cutoff, natoms[0])
         except ValueError as e:                                               # the automatic value needs natoms: refused before any file is written
@@ -285,6 +329,18 @@ def main(argv=None):
             np.save(prefix + '.boqa.npy', q.astype(np.float32).reshape(pn, tn, rns, n, nl))
             np.save(prefix + '.boba.npy', qb.astype(np.float32).reshape(pn, tn, rns, n, nl))
             np.save(prefix + '.bona.npy', nb.reshape(pn, tn, rns, n))
+    if a.solid:
+        l = float(np.min(box))
+        n = int(natoms[0])
+        nconn, label, nsolid, nclus, largest = solid(natoms, box, pos, a.solid_l, 1e-16 * l, bcut * l, a.solid_threshold,
+                                                     a.solid_connections, device=dev)
+        np.save(prefix + '.sof.npy', (nsolid / np.float64(n)).astype(np.float32).reshape(pn, tn, rns))
+        np.save(prefix + '.sol.npy', (largest / np.float64(n)).astype(np.float32).reshape(pn, tn, rns))
+        np.save(prefix + '.soc.npy', nclus.reshape(pn, tn, rns))
+        np.save(prefix + '.son.npy', nconn.mean(axis=1).astype(np.float32).reshape(pn, tn, rns))
+        if a.solid_atoms:
+            np.save(prefix + '.sona.npy', nconn.reshape(pn, tn, rns, n))
+            np.save(prefix + '.sola.npy', label.reshape(pn, tn, rns, n))
     if a.verbose:
         print('all properties pickled')
 

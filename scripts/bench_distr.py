@@ -4,6 +4,7 @@
     python scripts/bench_distr.py --angles [ns=4096] [cells=4] [cutoff=0.5] [repeats=5]
     python scripts/bench_distr.py --sfactor [ns=4096] [natoms=256] [qmax=16] [repeats=5]
     python scripts/bench_distr.py --bondorder [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l ...=4 6]
+    python scripts/bench_distr.py --solid [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l=6] [s_min=0.5] [n_min=8]
 
 --angles: nm_distr_angles on displaced fcc frames of 4 cells^3 atoms (shell up to cutoff * l; the first shell is about
 0.85 / cells): the time of the whole call (copies + kernel, host clock around the synchronous call, median of the repeats
@@ -19,7 +20,12 @@ outputs: the time of the whole call as above, bonds/s, the same call of nm_distr
 (the yardstick: it pays for one scan of the candidates, the bond-order path for two plus the harmonics), and the numpy
 restatement on one host core over one sample (imported from tests/bondorder_ref.py, as --angles imports tests/adf_ref.py: the
 script needs the tests directory next to it).  The kernels' own times come from the same rocprofv3 line
-(nm_bo_moments_kernel, nm_bo_average_kernel, nm_bo_global_kernel, nm_adf_kernel)."""
+(nm_bo_moments_kernel, nm_bo_average_kernel, nm_bo_global_kernel, nm_adf_kernel).
+
+--solid: nm_distr_solid on the frames and shapes of --bondorder, all five outputs: the time of the whole call as above, entries/s,
+and next to it nm_distr_bondorder with qbar2 alone for the same single l on the same frames and shell (the yardstick: two scans
+of the candidates; the solid path does three and the gather of the bond values).  The kernels' own times come from the same
+rocprofv3 line (nm_bo_moments_kernel, nm_solid_connect_kernel, nm_solid_union_kernel, nm_solid_label_kernel)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -164,6 +170,67 @@ def bench_bondorder(argv):
     dt = time.perf_counter() - t
     print('numpy restatement, one core, sample 0: %.3f s = %.2f samples/s, %.1f centres/s' % (dt, 1 / dt, n / dt))
 
+
+def bench_solid(argv):
+    from neuralmelting_amd import _lib as B, lattice
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    cells = int(argv[1]) if len(argv) > 1 else 4
+    cut = float(argv[2]) if len(argv) > 2 else 0.0
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    lv = int(argv[4]) if len(argv) > 4 else 6
+    s_min = float(argv[5]) if len(argv) > 5 else 0.5
+    n_min = int(argv[6]) if len(argv) > 6 else 8
+    rng = np.random.default_rng(3)                                            # the frames of bench_angles
+    n = 4 * cells ** 3
+    cut = distr.bond_cutoff(cut, n)
+    a0 = lattice.lattice_constant('LJ')
+    box = (cells * a0 * (1.0 + 0.05 * rng.random(ns))).astype(np.float32)
+    frac = lattice.fcc_fractional(cells)
+    pos = ((frac[None] + 0.08 / cells * rng.normal(size=(ns, n, 3))) % 1.0 * box[:, None, None]).astype(np.float32)
+    pos = np.minimum(pos, np.nextafter(box, np.float32(0))[:, None, None])
+    l = float(box.min())
+    L = B.load()
+    ls = np.array([lv], dtype=np.int32)
+    b2 = np.zeros((ns, n, 1))
+    nb = np.zeros((ns, n), dtype=np.int32)
+    nconn, label = np.zeros((ns, n), dtype=np.int32), np.zeros((ns, n), dtype=np.int32)
+    nsolid, nclus, largest = np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32)
+    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
+
+    def run(m):
+        rc = L.nm_distr_solid(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, lv, s_min, n_min,
+                              ip(nconn), ip(label), ip(nsolid), ip(nclus), ip(largest))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+
+    def run_qbar(m, nnb=None):
+        rc = L.nm_distr_bondorder(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, 1,
+                                  ls.ctypes.data_as(B.c_int_p), None, b2.ctypes.data_as(B.c_double_p), None, nnb)
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+    med = {}
+    for name, f in (('solid', run), ('qbar', run_qbar)):
+        f(min(ns, 8))
+        f(ns)                                                                 # warm-up at the timed shape
+        ts = []
+        for _ in range(reps):
+            t = time.perf_counter(); f(ns); ts.append(time.perf_counter() - t)
+        med[name] = (float(np.median(ts)), min(ts), max(ts))
+    run_qbar(ns, ip(nb))                                                      # the entries, outside the timing
+    ent = int(nb.sum())
+    dt = med['solid'][0]
+    print('solid: %d samples x %d atoms, cutoff %.4f l, l = %d, s_min %g, n_min %d: %d entries (%.1f per centre, %d at most), %.2f connections '
+          'per atom; solid fraction %.4f, %.2f clusters per sample, largest / natoms %.4f; call (H2D + kernels + D2H) median of %d: %.4f s '
+          '(min %.4f, max %.4f) = %.2f G entries/s, %.1f M centres/s'
+          % (ns, n, cut, lv, s_min, n_min, ent, ent / (ns * n), nb.max(), nconn.mean(), nsolid.mean() / n, nclus.mean(), largest.mean() / n,
+             reps, dt, med['solid'][1], med['solid'][2], ent / dt / 1e9, ns * n / dt / 1e6))
+    print('bondorder with qbar2 alone, l = %d, on the same frames and shell: call median of %d: %.4f s (min %.4f, max %.4f); solid / bondorder = %.2f'
+          % (lv, reps, med['qbar'][0], med['qbar'][1], med['qbar'][2], dt / med['qbar'][0]))
+
+
+if '--solid' in sys.argv:
+    bench_solid([x for x in sys.argv[1:] if x != '--solid'])
+    sys.exit(0)
 
 if '--bondorder' in sys.argv:
     bench_bondorder([x for x in sys.argv[1:] if x != '--bondorder'])
