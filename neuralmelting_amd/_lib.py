@@ -11,6 +11,7 @@ c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 c_uint64_p = C.POINTER(C.c_uint64)
 c_int32_p = C.POINTER(C.c_int32)
+c_int64_p = C.POINTER(C.c_int64)
 
 NM_OK, NM_ERR_ARG, NM_ERR_HIP, NM_ERR_STATE, NM_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 NM_EL_LJ, NM_EL_AL, NM_EL_NI, NM_EL_CU = 0, 1, 2, 3
@@ -29,6 +30,8 @@ SYMBOLS = ('nm_create', 'nm_destroy', 'nm_last_error', 'nm_create_note', 'nm_nsl
 DISTR_SYMBOLS = ('nm_distr_histograms', 'nm_distr_angles', 'nm_distr_sfactor', 'nm_distr_bondorder', 'nm_distr_solid', 'nm_distr_last_error')
 # include/nm_parse.h
 PARSE_SYMBOLS = ('nm_parse_thrm', 'nm_parse_traj', 'nm_parse_last_error')
+# include/nm_reweight.h
+REWEIGHT_SYMBOLS = ('nm_reweight_solve', 'nm_reweight_expect', 'nm_reweight_last_error')
 
 
 class NMConfig(C.Structure):
@@ -124,5 +127,13 @@ def load():
     L.nm_parse_traj.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), c_float_p, c_float_p, C.c_long, C.c_long, c_long_p, c_long_p,
                                 C.c_int]
     L.nm_parse_last_error.restype = C.c_char_p
+    L.nm_reweight_solve.restype = C.c_int
+    L.nm_reweight_solve.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, C.c_int64, c_double_p, c_double_p, C.c_double,
+                                    C.c_int, c_double_p, c_double_p, c_int_p, c_double_p]
+    L.nm_reweight_expect.restype = C.c_int
+    L.nm_reweight_expect.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, c_double_p, C.c_int64, c_double_p, c_double_p,
+                                     C.c_int, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                     c_double_p]
+    L.nm_reweight_last_error.restype = C.c_char_p
     _lib = L
     return L

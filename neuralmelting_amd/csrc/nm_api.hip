@@ -7,8 +7,10 @@
 #include "nm_format.h"
 #include "nm_parse.h"
 #include "nm_lattice.h"
+#include "nm_reweight.h"
 #include "../../include/nm_distr.h"
 #include "../../include/nm_parse.h"
+#include "../../include/nm_reweight.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2041,3 +2043,277 @@ int nm_parse_traj(const char *path, uint16_t *natoms, float *box, float *pos, lo
     } catch (const std::exception &e) { g_parse_error = e.what(); return NM_ERR_ARG; }
 }
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// multistate reweighting of the replica grid (include/nm_reweight.h; kernels: nm_reweight.h)
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+thread_local std::string g_rw_error;
+int rwfail(int code, const std::string &m) { g_rw_error = m; return code; }
+int rwrefuse(const char *fn, const char *why) { return rwfail(NM_ERR_ARG, std::string(fn) + ": " + why); }
+
+#define RW_CHK(fn, call)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess) return rwfail(NM_ERR_HIP, std::string(fn) + ": " + #call + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+bool rw_finite(const double *x, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(x[i])) return false;
+    return true;
+}
+
+// what both entry points ask of the states and the samples
+int rw_check(const char *fn, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
+             const double *e, const double *v)
+{
+    if (nstates < 1 || nstates > RW_MAXSTATES) return rwrefuse(fn, "nstates must lie in 1..4096");
+    if (nsamples < 1) return rwrefuse(fn, "nsamples must be at least 1");
+    if (!b || !c || !count || !f || !e || !v) return rwrefuse(fn, "a needed pointer is null");
+    int64_t sum = 0;
+    for (int k = 0; k < nstates; ++k) {
+        if (count[k] < 0) return rwrefuse(fn, "a count is negative");
+        if (count[k] > nsamples - sum) return rwrefuse(fn, "the counts do not sum to nsamples");
+        sum += count[k];
+    }
+    if (sum != nsamples) return rwrefuse(fn, "the counts do not sum to nsamples");
+    if (!rw_finite(b, nstates) || !rw_finite(c, nstates)) return rwrefuse(fn, "a state's b or c is not finite");
+    if (!rw_finite(f, nstates)) return rwrefuse(fn, "an f is not finite");
+    if (!rw_finite(e, nsamples) || !rw_finite(v, nsamples)) return rwrefuse(fn, "a sample's e or v is not finite");
+    return NM_OK;
+}
+
+int rw_device(const char *fn, int device)
+{
+    if (device < 0) return rwrefuse(fn, "device ordinal out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rwfail(NM_ERR_HIP, std::string(fn) + ": no HIP device available");
+    if (device >= ndev) return rwrefuse(fn, "device ordinal out of range");
+    RW_CHK(fn, hipSetDevice(device));
+    return NM_OK;
+}
+
+// s = b e0 + c v0 as an unevaluated sum: the two rounded products and what their roundings lost (exactly, by fma).  With e0 or v0
+// at 1e6 a long double product is good to 1e-13 only, and the weights would carry that; the differences below cancel the large
+// parts first (sums of doubles of one magnitude are exact in a long double) and add the small parts last.
+struct RwOffset {
+    double p1 = 0.0, p2 = 0.0, lo = 0.0;
+    RwOffset() = default;
+    RwOffset(double b, double c, double e0, double v0)
+    {
+#pragma clang fp contract(off)
+        p1 = b * e0;
+        p2 = c * v0;
+        lo = std::fma(b, e0, -p1) + std::fma(c, v0, -p2);
+    }
+    // x + (this - o)
+    long double add_to(long double x, const RwOffset &o) const { return ((((x + p1) + p2) - o.p1) - o.p2) + ((long double)lo - o.lo); }
+    // (x - y) - (this - o): x and y first, then the large parts pair by pair, so that every partial sum is exact
+    long double take_from(double x, double y, const RwOffset &o) const
+    {
+        return ((((((long double)x - y) - p1) + o.p1) - p2) + o.p2) - ((long double)lo - o.lo);
+    }
+    long double value() const { return ((long double)p1 + p2) + lo; }
+};
+
+// The problem as the device sees it: samples centred on their means, the sampled states as a list, f in the centred gauge
+// (f_centred[k] = (f[k] - f[0]) - (s_k - s_0), s_k = b[k] e0 + c[k] v0: of the size of the centred u whatever f[0], e0 and v0
+// are), and the scratch of the moments kernels.  With logd' and F' what the kernels make of it: logd = logd' + f[0] - s_0 and
+// F[i] = F'[i] + (s_i - s_0) + f[0].
+struct RwProblem {
+    int K = 0, ka = 0;
+    int64_t N = 0, nchunks = 0;
+    double e0 = 0.0, v0 = 0.0;
+    std::vector<RwOffset> s; // s_k
+    RwOffset s0;
+    double f0 = 0.0; // f[0] as it came in
+    DevBuf<double> e, v, logd, b, c, f, ab, ac, alc, part, F;
+    DevBuf<int> aidx;
+    DevBuf<RwStatus> st;
+    int64_t part_doubles = 0;
+
+    // x + (s_t - s_0) + f[0] for a target
+    double shifted(double x, double tb, double tc) const { return (double)(RwOffset(tb, tc, e0, v0).add_to(x, s0) + f0); }
+
+    int setup(const char *fn, int nstates, const double *hb, const double *hc, const int64_t *count, const double *hf, int64_t nsamples,
+              const double *he, const double *hv)
+    {
+        K = nstates;
+        N = nsamples;
+        nchunks = (N + RW_CH - 1) / RW_CH;
+        long double se = 0.0L, sv = 0.0L;
+        for (int64_t i = 0; i < N; ++i) { se += he[i]; sv += hv[i]; }
+        e0 = (double)(se / N);
+        v0 = (double)(sv / N);
+        if (!std::isfinite(e0) || !std::isfinite(v0)) return rwrefuse(fn, "the mean of e or v is not finite");
+        std::vector<double> ce((size_t)N), cv((size_t)N);
+        for (int64_t i = 0; i < N; ++i) { ce[i] = he[i] - e0; cv[i] = hv[i] - v0; }
+        s0 = RwOffset(hb[0], hc[0], e0, v0);
+        f0 = hf[0];
+        s.resize(K);
+        std::vector<double> cf(K), hab, hac, halc;
+        std::vector<int> hidx;
+        for (int k = 0; k < K; ++k) {
+            s[k] = RwOffset(hb[k], hc[k], e0, v0);
+            cf[k] = (double)s[k].take_from(hf[k], hf[0], s0);
+            if (count[k] > 0) {
+                hab.push_back(hb[k]);
+                hac.push_back(hc[k]);
+                halc.push_back(std::log((double)count[k]));
+                hidx.push_back(k);
+            }
+        }
+        ka = (int)hidx.size(); // >= 1: the counts sum to N >= 1
+        const size_t nb = (size_t)N * sizeof(double);
+        RW_CHK(fn, e.alloc(N));
+        RW_CHK(fn, v.alloc(N));
+        RW_CHK(fn, logd.alloc(N));
+        RW_CHK(fn, b.alloc(K));
+        RW_CHK(fn, c.alloc(K));
+        RW_CHK(fn, f.alloc(K));
+        RW_CHK(fn, F.alloc(K));
+        RW_CHK(fn, ab.alloc(ka));
+        RW_CHK(fn, ac.alloc(ka));
+        RW_CHK(fn, alc.alloc(ka));
+        RW_CHK(fn, aidx.alloc(ka));
+        RW_CHK(fn, st.alloc(1));
+        RW_CHK(fn, hipMemcpy(e, ce.data(), nb, hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(v, cv.data(), nb, hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(b, hb, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(c, hc, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(f, cf.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(ab, hab.data(), (size_t)ka * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(ac, hac.data(), (size_t)ka * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(alc, halc.data(), (size_t)ka * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(aidx, hidx.data(), (size_t)ka * sizeof(int), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemset(st, 0, sizeof(RwStatus)));
+        return NM_OK;
+    }
+
+    // how many targets a launch of the moments kernel takes: its partials stay within 128 MiB (but TB targets at least)
+    int batch(int nf, int tb, int most) const
+    {
+        int64_t n = ((int64_t)1 << 24) / (nchunks * nf);
+        n = n / tb * tb;
+        if (n < tb) n = tb;
+        return n < most ? (int)n : most;
+    }
+
+    int scratch(const char *fn, int nf, int nbatch)
+    {
+        part_doubles = (int64_t)nbatch * nchunks * nf;
+        RW_CHK(fn, part.alloc((size_t)part_doubles));
+        return NM_OK;
+    }
+
+    void denominators()
+    {
+        hipLaunchKernelGGL(nm_rw_denom_kernel, dim3((unsigned)((N + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, st, N, e, v, ka, ab, ac, alc,
+                           aidx, f, logd);
+    }
+
+    // the targets t0 .. t0 + nb - 1 of (tb, tc): partials, then F[t] (and sums[t][RW_NF] with MOM); nb is at most the batch
+    template <int TB, bool MOM>
+    void moments(int t0, int nb, const double *tb, const double *tc, int nobs, const double *obs, double *Fout, double *sums)
+    {
+        hipLaunchKernelGGL((nm_rw_moments_kernel<TB, MOM>), dim3((unsigned)nchunks, (unsigned)((nb + TB - 1) / TB)), dim3(RW_BLOCK), 0, 0, st, N, e, v,
+                           logd, t0, t0 + nb, tb, tc, nobs, obs, part);
+        hipLaunchKernelGGL((nm_rw_combine_kernel<MOM>), dim3((unsigned)((nb + RW_WAVES - 1) / RW_WAVES)), dim3(RW_BLOCK), 0, 0, st, nb, nchunks, nobs,
+                           part, Fout + t0, MOM ? sums + (size_t)t0 * RW_NF : nullptr);
+    }
+};
+} // namespace
+
+extern "C" {
+const char *nm_reweight_last_error(void) { return g_rw_error.c_str(); }
+
+int nm_reweight_solve(int device, int nstates, const double *b, const double *c, const int64_t *count, int64_t nsamples, const double *e,
+                      const double *v, double tol, int max_iter, double *f, double *logd, int *iters, double *delta)
+{
+    static const char *const fn = "nm_reweight_solve";
+    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    if (!iters || !delta) return rwrefuse(fn, "a needed pointer is null");
+    if (!(tol >= 0.0)) return rwrefuse(fn, "tol must not be negative");
+    if (max_iter < 1) return rwrefuse(fn, "max_iter must be at least 1");
+    if (const int rc = rw_device(fn, device)) return rc;
+    RwProblem p;
+    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    const int nbatch = p.batch(2, RW_TB, (nstates + RW_TB - 1) / RW_TB * RW_TB);
+    if (const int rc = p.scratch(fn, 2, nbatch)) return rc;
+    RwStatus st = {0, 0, 0.0};
+    for (int it = 0; it < max_iter && !st.done; ++it) {
+        p.denominators();
+        for (int t0 = 0; t0 < nstates; t0 += nbatch)
+            p.moments<RW_TB, false>(t0, (nstates - t0) < nbatch ? (nstates - t0) : nbatch, p.b, p.c, 0, nullptr, p.F, nullptr);
+        hipLaunchKernelGGL(nm_rw_update_kernel, dim3(1), dim3(RW_BLOCK), 0, 0, p.st, nstates, p.F, p.f, it == 0 ? p.f0 : 0.0, tol);
+        RW_CHK(fn, hipGetLastError());
+        if ((it + 1) % RW_POLL == 0 || it + 1 == max_iter) RW_CHK(fn, hipMemcpy(&st, p.st, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    RW_CHK(fn, hipDeviceSynchronize());
+    std::vector<double> cf(nstates);
+    RW_CHK(fn, hipMemcpy(cf.data(), p.f, (size_t)nstates * sizeof(double), hipMemcpyDeviceToHost));
+    if (logd) {
+        std::vector<double> cl((size_t)nsamples);
+        RW_CHK(fn, hipMemcpy(cl.data(), p.logd, (size_t)nsamples * sizeof(double), hipMemcpyDeviceToHost));
+        const long double g = (st.iters == 1 ? (long double)p.f0 : 0.0L) - p.s0.value(); // behind the first application f[0] = 0
+        for (int64_t i = 0; i < nsamples; ++i) logd[i] = (double)((long double)cl[i] + g);
+    }
+    for (int k = 0; k < nstates; ++k) f[k] = (double)p.s[k].add_to(cf[k], p.s0);
+    *iters = st.iters;
+    *delta = st.delta;
+    return NM_OK;
+}
+
+int nm_reweight_expect(int device, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
+                       const double *e, const double *v, int ntargets, const double *tb, const double *tc, int nobs, const double *obs,
+                       double *tf, double *ess, double *mean, double *cov, double *omean)
+{
+    static const char *const fn = "nm_reweight_expect";
+    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    if (ntargets < 1 || ntargets > 65536) return rwrefuse(fn, "ntargets must lie in 1..65536");
+    if (nobs < 0 || nobs > RW_MAXOBS) return rwrefuse(fn, "nobs must lie in 0..8");
+    if (!tb || !tc || !tf || !ess || !mean || !cov || (nobs > 0 && (!obs || !omean))) return rwrefuse(fn, "a needed pointer is null");
+    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return rwrefuse(fn, "a target's tb or tc is not finite");
+    if (const int rc = rw_device(fn, device)) return rc;
+    RwProblem p;
+    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    const int nbatch = p.batch(RW_NF, 1, RW_TGB);
+    if (const int rc = p.scratch(fn, RW_NF, nbatch)) return rc;
+    DevBuf<double> d_tb, d_tc, d_obs, d_F, d_sums;
+    RW_CHK(fn, d_tb.alloc(ntargets));
+    RW_CHK(fn, d_tc.alloc(ntargets));
+    RW_CHK(fn, d_F.alloc(ntargets));
+    RW_CHK(fn, d_sums.alloc((size_t)ntargets * RW_NF));
+    RW_CHK(fn, hipMemcpy(d_tb, tb, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
+    RW_CHK(fn, hipMemcpy(d_tc, tc, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
+    if (nobs > 0) {
+        RW_CHK(fn, d_obs.alloc((size_t)nobs * nsamples));
+        RW_CHK(fn, hipMemcpy(d_obs, obs, (size_t)nobs * nsamples * sizeof(double), hipMemcpyHostToDevice));
+    }
+    p.denominators();
+    for (int t0 = 0; t0 < ntargets; t0 += nbatch)
+        p.moments<1, true>(t0, (ntargets - t0) < nbatch ? (ntargets - t0) : nbatch, d_tb, d_tc, nobs, d_obs, d_F, d_sums);
+    RW_CHK(fn, hipGetLastError());
+    RW_CHK(fn, hipDeviceSynchronize());
+    std::vector<double> hF(ntargets), hs((size_t)ntargets * RW_NF);
+    RW_CHK(fn, hipMemcpy(hF.data(), d_F, (size_t)ntargets * sizeof(double), hipMemcpyDeviceToHost));
+    RW_CHK(fn, hipMemcpy(hs.data(), d_sums, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int t = 0; t < ntargets; ++t) {
+        const double *q = hs.data() + (size_t)t * RW_NF; // max, sum w, sum w^2, sums of w e, w v, w ee, w ev, w vv, w obs (centred e, v)
+        const long double s0 = q[1];
+        const long double me = q[3] / s0, mv = q[4] / s0;
+        tf[t] = p.shifted(hF[t], tb[t], tc[t]);
+        const long double n_eff = s0 * s0 / q[2];
+        ess[t] = (double)(n_eff < 1.0L ? 1.0L : (n_eff > (long double)nsamples ? (long double)nsamples : n_eff));
+        mean[2 * t] = (double)((long double)p.e0 + me);
+        mean[2 * t + 1] = (double)((long double)p.v0 + mv);
+        cov[3 * t] = (double)(q[5] / s0 - me * me);
+        cov[3 * t + 1] = (double)(q[6] / s0 - me * mv);
+        cov[3 * t + 2] = (double)(q[7] / s0 - mv * mv);
+        for (int j = 0; j < nobs; ++j) omean[(size_t)t * nobs + j] = (double)(q[8 + j] / s0);
+    }
+    return NM_OK;
+}
+} // extern "C"

@@ -1,0 +1,196 @@
+"""Multistate reweighting of the replica grid (include/nm_reweight.h): free energies of the P x T
+states, and enthalpy, volume and heat capacity as continuous curves in T at every pressure, from what `parse` wrote.
+
+A replica-exchange run over a P x T grid is the input of MBAR (Shirts and Chodera 2008): every sample of every replica
+contributes to every state.  The reference locates the transition with a VAE on the histograms instead (lammps_vae.py);
+this stage is the build's own.  The arithmetic runs in the HIP library (nm_reweight_solve, nm_reweight_expect), there is no
+host fallback.
+
+What makes the grid's samples the samples of its states: the sampler's exchange moves configurations between slots, never
+temperatures or pressures between configurations (remcmc.py, Run.replica_exchange / exchange.sweep: the energies, volumes
+and the slot-to-buffer map are swapped, et and pf stay with the slot), the record of a cycle is taken behind the cycle's
+block of moves and in front of its exchange (Run.main), and slot k = p * TN + t writes the files of grid index (p, t)
+(Run.file_prefix).  So row (p, t) of `.pe.npy` / `.vol.npy` holds samples generated at the target (P_p, T_t).  The reduced
+potential uses the potential energy: the kinetic energy of a record is that of the HMC move's fresh momenta, Gaussian at the
+state's temperature whatever the configuration, and integrates out of every configurational average.
+
+    python -m neuralmelting_amd.reweight -v -n remcmc_run_5 -e LJ -sk 128 -ob sof sol
+"""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from . import _lib as B
+from .parse import LAT
+from .remcmc import init_constant
+
+MAX_OBS = 8
+MAX_TARGETS = 65536     # include/nm_reweight.h: ntargets of one call
+SUFFIXES = ('rwf', 'rwi', 'rwt', 'rwg', 'rwh', 'rwv', 'rwc', 'rwn', 'rwo', 'rwm')
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(
+        description='MBAR reweighting of the (P, T) grid: .rwf (PN, TN) the states\' reduced free energies f (f[0, 0] = 0); .rwi '
+        '(iterations, delta, tol); .rwt (TG,) the fine temperatures; and on (PN, TG): .rwg reduced free energy, .rwh enthalpy per '
+        'atom, .rwv volume per atom, .rwc configurational Cp / (natoms kB) - the kinetic 3/2 is NOT included -, .rwn the Kish '
+        'effective sample size, .rwo (PN, TG, nobs) the observables of -ob; .rwm (PN,) the temperature of the largest Cp on the '
+        'fine grid.  A peak on an end of the range means that the transition is not bracketed: the value is written as it is.')
+    p.add_argument('-v', '--verbose', action='store_true')
+    p.add_argument('-n', '--name', type=str, default='remcmc_init')
+    p.add_argument('-e', '--element', type=str, default='LJ')
+    p.add_argument('-sk', '--skip', type=int, default=0, help='samples dropped at the start of every grid point')
+    p.add_argument('-sd', '--stride', type=int, default=1, help='keep every STRIDE-th sample')
+    p.add_argument('-tg', '--temperature_grid', type=int, default=256,
+                   help='fine temperatures per pressure, linspace(T[0], T[-1], TG).  The defaults of -tg, -rt and -ri are conveniences: '
+                   'whether they suit the LJ and Sutton-Chen grids has not been measured')
+    p.add_argument('-rt', '--tolerance', type=float, default=1e-9, help='the iteration stops at max |f_new - f_old| <= this')
+    p.add_argument('-ri', '--max_iterations', type=int, default=20000,
+                   help='most applications of the map; if delta > tol then, the files are still written and the exit status is 1')
+    p.add_argument('-ob', '--observables', type=str, nargs='+', default=[],
+                   help='up to 8 names: <PREFIX>.NAME.npy of shape (PN, TN, SN) is averaged with the weights (e.g. distr\'s sof, sol)')
+    p.add_argument('-dv', '--device', type=int, default=0)
+    a = p.parse_args(argv)
+    if a.skip < 0 or a.stride < 1 or not 1 <= a.temperature_grid <= MAX_TARGETS or a.max_iterations < 1 or not a.tolerance >= 0 or len(a.observables) > MAX_OBS:
+        p.error('need -sk >= 0, -sd >= 1, -tg in 1..65536 (PN x TG <= 65536), -ri >= 1, -rt >= 0 and at most 8 names behind -ob')
+    return a
+
+
+def _f64(x):
+    return np.ascontiguousarray(x, dtype=np.float64)
+
+
+def _dp(a):
+    return a.ctypes.data_as(B.c_double_p)
+
+
+def _fail(fn, rc):
+    raise RuntimeError('%s failed (%d): %s' % (fn, rc, B.load().nm_reweight_last_error().decode()))
+
+
+def states(P, T, el):
+    """(b, c) of the K = PN x TN states, k = p * TN + t: 1/et and pf of remcmc.init_constant"""
+    et, pf = np.array([init_constant(P, T, el, i, j) for i in range(len(P)) for j in range(len(T))], dtype=np.float64).T
+    return 1.0 / et, np.ascontiguousarray(pf)
+
+
+def solve(b, c, count, e, v, f0=None, tol=1e-9, max_iter=20000, device=0, want_logd=False):
+    """nm_reweight_solve: (f, iterations, delta[, logd]); f0 = None starts from zeros"""
+    b, c, e, v = _f64(b), _f64(c), _f64(e).reshape(-1), _f64(v).reshape(-1)
+    count = np.ascontiguousarray(count, dtype=np.int64)
+    f = np.zeros(b.size) if f0 is None else _f64(f0).copy()
+    if not (b.size == c.size == count.size == f.size and e.size == v.size):
+        raise ValueError('b, c, count, f0 want one length and e, v another')
+    logd = np.empty(e.size) if want_logd else None
+    iters, delta = C.c_int(0), C.c_double(0.0)
+    rc = B.load().nm_reweight_solve(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), e.size, _dp(e), _dp(v), tol,
+                                    max_iter, _dp(f), _dp(logd) if want_logd else None, C.byref(iters), C.byref(delta))
+    if rc != B.NM_OK:
+        _fail('nm_reweight_solve', rc)
+    return (f, iters.value, delta.value, logd) if want_logd else (f, iters.value, delta.value)
+
+
+def expect(b, c, count, f, e, v, tb, tc, obs=None, device=0):
+    """nm_reweight_expect: dict of tf, ess (T,), mean (T, 2), cov (T, 3), omean (T, nobs); obs (nobs, N) or None"""
+    b, c, f, e, v = _f64(b), _f64(c), _f64(f), _f64(e).reshape(-1), _f64(v).reshape(-1)
+    tb, tc = _f64(tb).reshape(-1), _f64(tc).reshape(-1)
+    count = np.ascontiguousarray(count, dtype=np.int64)
+    obs = None if obs is None or len(obs) == 0 else _f64(obs).reshape(len(obs), -1)
+    nobs = 0 if obs is None else obs.shape[0]
+    if not (b.size == c.size == count.size == f.size and e.size == v.size and tb.size == tc.size) or (nobs and obs.shape[1] != e.size):
+        raise ValueError('b, c, count, f want one length, e, v and every observable another, tb, tc a third')
+    nt = tb.size
+    out = dict(tf=np.empty(nt), ess=np.empty(nt), mean=np.empty((nt, 2)), cov=np.empty((nt, 3)), omean=np.empty((nt, nobs)))
+    rc = B.load().nm_reweight_expect(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), _dp(f), e.size, _dp(e), _dp(v),
+                                     nt, _dp(tb), _dp(tc), nobs, _dp(obs) if nobs else None, _dp(out['tf']), _dp(out['ess']),
+                                     _dp(out['mean']), _dp(out['cov']), _dp(out['omean']) if nobs else None)
+    if rc != B.NM_OK:
+        _fail('nm_reweight_expect', rc)
+    return out
+
+
+def fine_targets(P, T, el, tg):
+    """the fine temperatures (TG,) and the targets (tb, tc), each (PN, TG), with init_constant's constants"""
+    tf = np.linspace(float(T[0]), float(T[-1]), tg)
+    tb, tc = states(np.asarray(P, dtype=np.float64), tf, el)
+    return tf, tb.reshape(len(P), tg), tc.reshape(len(P), tg)
+
+
+def curves(f, iters, delta, tol, tfine, tb, tc, ex, natoms):
+    """the ten arrays, keyed by suffix, from the solution (f (PN, TN), iters, delta, tol), the fine temperatures (TG,), the
+    targets tb, tc (PN, TG) and nm_reweight_expect's results for them in that order; host arithmetic only.
+    H = <e> + (c/b) <v>: c/b is the pressure in energy per volume.  Cp here is d<H>/dT at constant P per atom and kB,
+    (b^2 var_e + 2 b c cov_ev + c^2 var_v) / natoms = var(u) / natoms, without the kinetic 3/2."""
+    pn, tg = tb.shape
+    mean, cov = ex['mean'].reshape(pn, tg, 2), ex['cov'].reshape(pn, tg, 3)
+    n = float(natoms)
+    cp = (tb * tb * cov[..., 0] + 2.0 * tb * tc * cov[..., 1] + tc * tc * cov[..., 2]) / n
+    return dict(rwf=_f64(f), rwi=np.array([float(iters), float(delta), float(tol)]), rwt=_f64(tfine),
+                rwg=ex['tf'].reshape(pn, tg), rwh=(mean[..., 0] + tc / tb * mean[..., 1]) / n, rwv=mean[..., 1] / n, rwc=cp,
+                rwn=ex['ess'].reshape(pn, tg), rwo=ex['omean'].reshape(pn, tg, -1), rwm=_f64(tfine)[np.argmax(cp, axis=1)])
+
+
+def load_observables(prefix, names, shape):
+    """the (PN, TN, SN) arrays of -ob, or ValueError naming the file that is missing or misshapen"""
+    out = []
+    for name in names:
+        path = prefix + '.%s.npy' % name
+        if not os.path.isfile(path):
+            raise ValueError('-ob %s: %s is missing' % (name, path))
+        a = np.load(path)
+        if a.shape != tuple(shape):
+            raise ValueError('-ob %s: %s has shape %s, not %s' % (name, path, a.shape, tuple(shape)))
+        out.append(a)
+    return out
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    el = a.element
+    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, el.lower(), LAT[el])
+    P = np.load(prefix + '.virial.trgt.npy')
+    T = np.load(prefix + '.temp.trgt.npy')
+    pe = np.load(prefix + '.pe.npy')
+    vol = np.load(prefix + '.vol.npy')
+    natoms = int(np.load(prefix + '.natoms.npy').reshape(-1)[0])
+    pn, tn = P.size, T.size
+    if pn * a.temperature_grid > MAX_TARGETS:
+        raise SystemExit('reweight: -tg %d at %d pressures is more than the %d targets of one nm_reweight_expect call' % (a.temperature_grid, pn, MAX_TARGETS))
+    if pe.shape != vol.shape or pe.shape[:2] != (pn, tn):
+        raise SystemExit('reweight: .pe.npy %s and .vol.npy %s do not fit the %d x %d grid' % (pe.shape, vol.shape, pn, tn))
+    try:
+        obs = load_observables(prefix, a.observables, pe.shape)         # refused before anything is written
+    except ValueError as err:
+        raise SystemExit('reweight: %s' % err)
+    keep = slice(a.skip, None, a.stride)
+    e = _f64(pe[:, :, keep]).reshape(pn * tn, -1)
+    v = _f64(vol[:, :, keep]).reshape(pn * tn, -1)
+    sn = e.shape[1]
+    if sn < 1:
+        raise SystemExit('reweight: -sk %d leaves no sample' % a.skip)
+    obs = [_f64(o[:, :, keep]).reshape(-1) for o in obs]
+    b, c = states(P, T, el)
+    count = np.full(pn * tn, sn, dtype=np.int64)
+    f0 = b * e.mean(axis=1) + c * v.mean(axis=1)                        # the mean of u_k over state k's own samples
+    if a.verbose:
+        print('reweighting %d states x %d samples of %d atoms' % (pn * tn, pn * tn * sn, natoms))
+    f, iters, delta = solve(b, c, count, e, v, f0, a.tolerance, a.max_iterations, a.device)
+    tfine, tb, tc = fine_targets(P, T, el, a.temperature_grid)
+    ex = expect(b, c, count, f, e, v, tb, tc, obs, a.device)
+    out = curves(f.reshape(pn, tn), iters, delta, a.tolerance, tfine, tb, tc, ex, natoms)
+    for key in SUFFIXES:
+        if key != 'rwo' or obs:
+            np.save(prefix + '.%s.npy' % key, out[key])
+    if a.verbose:
+        print('%d iterations, delta %.3g; largest Cp at T = %s' % (iters, delta, np.array2string(out['rwm'], precision=4)))
+    if not delta <= a.tolerance:
+        print('reweight: not converged: delta = %.6g > %g after %d iterations' % (delta, a.tolerance, iters), file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

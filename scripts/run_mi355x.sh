@@ -5,6 +5,8 @@
 # Anything after the fourth argument goes to the distr stage: -ad adds the angular distribution (.a.npy / .adf.npy), -ac its
 # neighbour shell as a fraction of the smallest box edge (first fcc shell: about 0.85 / supercell); -sf adds the static structure
 # factor on the box's reciprocal lattice (.q.npy / .sf.npy / .sfm.npy, and .nrho.npy), -sq its largest index (1..32, default 16).
+# REWEIGHT=1 in the environment adds a fifth stage: the multistate reweighting of the grid (.rw*.npy: free energies, H(T), V(T), Cp(T)
+# and the temperature of its peak at every pressure); REWEIGHT_ARGS goes to it (e.g. "-sk 128 -ob sof sol" behind a distr stage with -so).
 # For several GPUs start the first two stages under  python -m torch.distributed.run --nproc-per-node N -m neuralmelting_amd.remcmc ...
 set -euo pipefail
 s=${1:-5}; pn=${2:-32}; tn=${3:-32}; sn=${4:-1024}
@@ -21,3 +23,7 @@ python -m neuralmelting_amd.remcmc -v -r -rn remcmc_init_$s -rs $sn -n remcmc_ru
 python -m neuralmelting_amd.parse -v -n remcmc_run_$s
 # radial and cartesian pair histograms (and, with -ad, the angular distribution; with -sf, the structure factor)
 python -m neuralmelting_amd.distr -v -n remcmc_run_$s -cb 11 "$@"
+# optional: free energies and H(T), V(T), Cp(T) between the sampled temperatures (exit status 1 if the iteration did not converge)
+if [ "${REWEIGHT:-0}" = 1 ]; then
+  python -m neuralmelting_amd.reweight -v -n remcmc_run_$s ${REWEIGHT_ARGS:-}
+fi
