@@ -136,6 +136,53 @@ int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const f
 int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int l, double s_min,
                    int n_min, int32_t *nconn, int32_t *label, int32_t *nsolid, int32_t *nclus, int32_t *largest);
 
+/* Common neighbour analysis (Honeycutt and Andersen; Faken and Jonsson; the adaptive form of Stukowski, Modelling Simul. Mater. Sci.
+ * Eng. 20 (2012) 045021): the structure type of every atom (fcc, hcp, bcc, icosahedral, other) from the bonds among its own
+ * neighbours, in integers.  Definition (the build's own), for sample s and centre atom c:
+ *   entries     exactly those of nm_distr_bondorder: (j, a) over the 27 image shifts br[j] and all atoms a, the float32 displacement v
+ *               and its float32 length d (sequential sum, correctly rounded root, no contraction), r_lo < (double)d <= r_hi; an atom
+ *               that qualifies in two images is two entries.  Scan order: image-major, then atom index;
+ *   graph       on a set of entries (the vertices) with a local cutoff rc: the entries k and m are bonded iff the float32 difference
+ *               w = v_m - v_k (componentwise) has a float32 length dw (the arithmetic of d) with r_lo < (double)dw <= rc.  The graph
+ *               is local to the centre, bonds among the centre's own neighbour vectors (as OVITO defines them), not a lookup in the
+ *               other atoms' entries: it needs no image bookkeeping, and an atom present in two images is two vertices;
+ *   signature   of the entry k, the triple (ncn, nb, nlc): ncn the number of vertices bonded to k (the common neighbours of c and k),
+ *               nb the number of bonds among those, nlc the largest number of bonds that one connected component of those bonds
+ *               holds.  That is OVITO's definition.  It equals the "longest chain" of bonds of the original method wherever the
+ *               largest component is a path or a ring, which it is for every signature of the columns below as the fcc, hcp, bcc and
+ *               icosahedral environments produce them; no longest path is searched, and a star of three bonds has nlc = 3;
+ *   columns     8, in this order: (4,2,1) (4,2,2) (4,4,4) (6,6,6) (5,5,5) (5,4,4) (4,3,3) and `other`;
+ *   types       0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico.  From the column counts n of a graph of Nv vertices:
+ *               fcc if Nv = 12 and n421 = 12; hcp if Nv = 12, n421 = 6 and n422 = 6; ico if Nv = 12 and n555 = 12;
+ *               bcc if Nv = 14, n444 = 6 and n666 = 8; else other;
+ *   mode NM_CNA_FIXED     the vertices are all Nb entries of c and rc = r_hi: the conventional analysis, whose column sums are the
+ *               Honeycutt-Andersen pair statistics of a liquid.  sig[s][c] = the column counts (they add up to Nb) and the type as
+ *               above with Nv = Nb.  If Nb > 32: type other, and all Nb entries are counted in the column `other`;
+ *   mode NM_CNA_ADAPTIVE  r_hi is only the search radius.  The entries are sorted by (d as float32, scan order).  With fewer than 12
+ *               entries: type other, sig[s][c] all zero.  Otherwise the first 12 are the vertices, with
+ *                 rc12 = 1.2071067811865475 * (d_0 + ... + d_11) / 12.0          ((1 + sqrt 2) / 2 times the mean)
+ *               in float64: the d converted from float32 and added in sorted order, then the product, then the quotient, one rounding
+ *               per operation, no contraction; fcc, hcp or ico as above.  If none of them holds and there are at least 14 entries,
+ *               the first 14 are the vertices, with
+ *                 rc14 = 1.2071067811865475 * S / 14.0,   S = sum_{k<8} (d_k * 1.1547005383792517) + sum_{8<=k<14} d_k
+ *               (2 / sqrt 3 scales the first bcc shell onto the second; each product rounded, all terms added in that order); bcc
+ *               if n444 = 6 and n666 = 8.  sig[s][c] = the column counts of the graph that decided the type, for type other those
+ *               of the 12-vertex graph;
+ *   per sample  ntype[s][t] the number of atoms of type t, nsig[s][k] the sum of sig[s][c][k] over the atoms (below 2^31 for every
+ *               accepted call).
+ * Everything returned is an integer, and every comparison is the stated float32 or float64 one: the result is the same bit for bit
+ * on every call (integer atomics only) and equals a restatement of the text above exactly.
+ * pos[ns][natoms][3], box[ns] float32; type[ns][natoms], sig[ns][natoms][8], ntype[ns][5], nsig[ns][8] int32.  Any output may be NULL
+ * (it is then not written), but not all four.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_cna:".  NM_ERR_ARG, checked before
+ * the device is looked for and with the outputs left untouched, for: ns < 0, natoms outside 1..4095, mode neither of the two, not
+ * 0 <= r_lo < r_hi, r_hi > min(box)/2 over the batch, a box that is not finite and positive, a null pos or box, all outputs null, a
+ * working set beyond the LDS, a bad device ordinal.  ns == 0 as in nm_distr_bondorder. */
+#define NM_CNA_FIXED 0
+#define NM_CNA_ADAPTIVE 1
+int nm_distr_cna(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int mode,
+                 int32_t *type, int32_t *sig, int32_t *ntype, int32_t *nsig);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1965,6 +1965,47 @@ int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float
         return NM_OK;
     });
 }
+
+int nm_distr_cna(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int mode,
+                 int32_t *type, int32_t *sig, int32_t *ntype, int32_t *nsig)
+{
+    static const char *const fn = "nm_distr_cna";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!type && !sig && !ntype && !nsig) return refuse(fn, "all four outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (mode != NM_CNA_FIXED && mode != NM_CNA_ADAPTIVE) return refuse(fn, "mode must be NM_CNA_FIXED or NM_CNA_ADAPTIVE");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    const size_t lds = cna_lds_bytes(natoms); // at most 51,604 B (4095 atoms)
+    if (lds > 160 * 1024) return refuse(fn, "working set exceeds LDS");
+    if (const int rc = distr_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const float cube = shell_cube(r_hi);
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const size_t pa = (size_t)natoms, ps = pa * CNA_NSIG;
+    const int cs = bo_chunk(ns, ps * sizeof(int)); // the per-atom columns are the largest device array
+    DevBuf<int> d_type, d_sig, d_ntype, d_nsig;
+    if (type) DISTR_CHK(fn, d_type.alloc((size_t)cs * pa));
+    if (sig) DISTR_CHK(fn, d_sig.alloc((size_t)cs * ps));
+    if (ntype) DISTR_CHK(fn, d_ntype.alloc((size_t)cs * CNA_NTYPE));
+    if (nsig) DISTR_CHK(fn, d_nsig.alloc((size_t)cs * CNA_NSIG));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        // the per-sample sums are added to by every workgroup of the sample
+        if (ntype) DISTR_CHK(fn, hipMemset(d_ntype, 0, (size_t)n * CNA_NTYPE * sizeof(int)));
+        if (nsig) DISTR_CHK(fn, hipMemset(d_nsig, 0, (size_t)n * CNA_NSIG * sizeof(int)));
+        hipLaunchKernelGGL(nm_cna_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube,
+                           mode == NM_CNA_ADAPTIVE, d_type, d_sig, d_ntype, d_nsig);
+        DISTR_CHK(fn, hipGetLastError());
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        if (type) DISTR_CHK(fn, hipMemcpy(type + (size_t)s0 * pa, d_type, (size_t)n * pa * sizeof(int), hipMemcpyDeviceToHost));
+        if (sig) DISTR_CHK(fn, hipMemcpy(sig + (size_t)s0 * ps, d_sig, (size_t)n * ps * sizeof(int), hipMemcpyDeviceToHost));
+        if (ntype) DISTR_CHK(fn, hipMemcpy(ntype + (size_t)s0 * CNA_NTYPE, d_ntype, (size_t)n * CNA_NTYPE * sizeof(int), hipMemcpyDeviceToHost));
+        if (nsig) DISTR_CHK(fn, hipMemcpy(nsig + (size_t)s0 * CNA_NSIG, d_nsig, (size_t)n * CNA_NSIG * sizeof(int), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
+}
 #undef DISTR_CHK
 
 } // extern "C"

@@ -1076,4 +1076,237 @@ nm_solid_label_kernel(int natoms, int n_min, const int *__restrict__ nconn, cons
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Common neighbour analysis (include/nm_distr.h, nm_distr_cna): per centre the graph of bonds among its own neighbour vectors, per
+// neighbour the signature (common neighbours, bonds among them, bonds of their largest component), from the signatures' counts the
+// structure type.  The grid and staging of the other shell kernels; each wave works through its centres alone:
+//   scan       shell_scan, one pass.  FIXED: the entries are counted and the first CNA_MAXV vectors go to the wave's LDS list in scan
+//              order.  ADAPTIVE: the wave keeps the CNA_KEEP smallest entries by (d, scan order) sorted in its lanes' registers (lane
+//              k holds entry k).  A scan step's candidates are the lanes whose d lies below the list's last (a tie loses: the list's
+//              entries come earlier in the scan); where there is none, which is nearly every step once the list is full, the step
+//              costs one ballot.  Otherwise the step is merged in: every held entry and every candidate counts the keys before its
+//              own (the candidates' d arrive by one cross-lane read per candidate, the held d by one per held entry), which is its
+//              rank in the union, a total order; the ranks below CNA_KEEP are scattered to LDS slots, each written once, and read
+//              back by the lanes.  Any number of entries is handled; the list is never longer than CNA_KEEP.
+//   cutoffs    ADAPTIVE: rc12 and rc14 in float64 from the sorted d, every lane the same sum in the stated order (cna_rc), no
+//              contraction.
+//   adjacency  the nv <= 32 vertices' nv (nv - 1) / 2 pairs spread over the lanes (adf's numbering), at most 8 steps; a bond sets the
+//              two bits of the vertices' 32-bit masks in the wave's LDS (integer OR: the order does not matter).
+//   signature  lane k = vertex k, integer registers: cn = adj[k]; the bonds among cn are half the sum of popcount(adj[m] & cn) over
+//              the m in cn; the components of cn by a flood fill over the masks, the bonds of each counted the same way.
+//   counts     the column counts of a centre by eight ballots (wave-uniform: the type follows without a further exchange); lane
+//              k < 8 keeps the wave's sum of column k, lane 8 + t the wave's number of atoms of type t; at the end LDS integer
+//              atomics per workgroup, then one global integer atomic per column and type.
+// Integer atomics only: the same bits on every call.
+constexpr int CNA_MAXV = 32;    // most vertices of a graph: one mask word per vertex
+constexpr int CNA_KEEP = 14;    // entries the adaptive mode keeps: the bcc test's
+constexpr int CNA_NSIG = 8;     // signature columns: 421 422 444 666 555 544 433 other
+constexpr int CNA_NTYPE = 5;    // other fcc hcp bcc ico
+constexpr int CNA_WAVE = 4 * CNA_MAXV + 16;                 // a wave's LDS words: list vectors, masks, merge slots' d
+constexpr int CNA_TOT = 16;                                 // the workgroup's sums: CNA_NSIG columns, CNA_NTYPE types, padding
+static_assert(CNA_NSIG + CNA_NTYPE <= CNA_TOT && CNA_KEEP <= 16 && CNA_KEEP <= CNA_MAXV, "the sums and merge slots fit their arrays");
+
+__host__ __device__ inline size_t cna_lds_bytes(int natoms) // 51,604 B at 4095 atoms
+{
+    return (size_t)(SHELL_WAVES * CNA_WAVE + CNA_TOT) * 4 + ((size_t)3 * natoms + SHELL_WAVES * 6) * sizeof(float);
+}
+
+// the float32 length of the definition: sequential sum, correctly rounded root (see nm_distr_kernel), no contraction
+__device__ __forceinline__ float cna_len(float x, float y, float z)
+{
+#pragma clang fp contract(off)
+    float d2 = x * x;
+    d2 = d2 + y * y;
+    d2 = d2 + z * z;
+    return sqrtf(d2);
+}
+
+// the adaptive cutoff over the first nv = 12 or 14 sorted entries (lane k holds d_k): float64, added in order, one rounding per
+// operation; at 14 the first 8 are scaled by 2 / sqrt 3 (the bcc shells' ratio)
+__device__ __forceinline__ double cna_rc(float hd, int nv)
+{
+#pragma clang fp contract(off)
+    double sum = 0.0;
+    for (int k = 0; k < nv; ++k) {
+        const double dk = (double)__shfl(hd, k);
+        const double term = (nv == 14 && k < 8) ? dk * 1.1547005383792517 : dk;
+        sum = sum + term;
+    }
+    const double scaled = 1.2071067811865475 * sum;
+    return scaled / (double)nv;
+}
+
+__device__ __forceinline__ int cna_column(int ncn, int nb, int nlc)
+{
+    if (ncn == 4 && nb == 2 && nlc == 1) return 0;
+    if (ncn == 4 && nb == 2 && nlc == 2) return 1;
+    if (ncn == 4 && nb == 4 && nlc == 4) return 2;
+    if (ncn == 6 && nb == 6 && nlc == 6) return 3;
+    if (ncn == 5 && nb == 5 && nlc == 5) return 4;
+    if (ncn == 5 && nb == 4 && nlc == 4) return 5;
+    if (ncn == 4 && nb == 3 && nlc == 3) return 6;
+    return 7;
+}
+
+// fcc, hcp or ico from the column counts of 12 vertices, else other
+__device__ __forceinline__ int cna_close_packed(const int (&n)[CNA_NSIG])
+{
+    return n[0] == 12 ? 1 : (n[0] == 6 && n[1] == 6) ? 2 : n[4] == 12 ? 4 : 0;
+}
+
+// The graph on the first nv <= CNA_MAXV vectors of the wave's list with the cutoff rc, and every vertex's signature column: n[] are
+// the column counts, the same in every lane.
+__device__ __forceinline__ void cna_columns(const float *lx, const float *ly, const float *lz, unsigned int *adj, int nv, double r_lo,
+                                            double rc, int lane, int (&n)[CNA_NSIG])
+{
+    if (lane < CNA_MAXV) adj[lane] = 0u;
+    adf_wave_sync(); // the list and the cleared masks are in place
+    if (nv >= 2) {
+        // pair number q = (dd - 1) * nv + i is (i, (i + dd) mod nv) for the offsets dd = 1 .. nv/2 (for even nv the last offset only
+        // with i < nv/2): nv (nv - 1) / 2 pairs, each once
+        const int Q = nv * (nv - 1) / 2;
+        int dd = 1 + lane / nv, i = lane % nv;
+        for (int q = lane; q < Q; q += 64) {
+            const int j = i + dd < nv ? i + dd : i + dd - nv;
+            const double dw = (double)cna_len(lx[j] - lx[i], ly[j] - ly[i], lz[j] - lz[i]);
+            if (r_lo < dw && dw <= rc) {
+                atomicOr(&adj[i], 1u << j);
+                atomicOr(&adj[j], 1u << i);
+            }
+            i += 64;
+            while (i >= nv) { i -= nv; ++dd; }
+        }
+    }
+    adf_wave_sync();
+    int col = -1;
+    if (lane < nv) {
+        const unsigned int cn = adj[lane];
+        int nb2 = 0, nlc = 0;
+        for (unsigned int t = cn; t; t &= t - 1u) nb2 += __popc(adj[__ffs((int)t) - 1] & cn);
+        for (unsigned int rem = cn; rem;) {
+            unsigned int comp = rem & (0u - rem), front = comp; // the component of the lowest vertex left
+            while (front) {
+                unsigned int grow = 0u;
+                for (unsigned int t = front; t; t &= t - 1u) grow |= adj[__ffs((int)t) - 1] & cn;
+                front = grow & ~comp;
+                comp |= front;
+            }
+            int b2 = 0;
+            for (unsigned int t = comp; t; t &= t - 1u) b2 += __popc(adj[__ffs((int)t) - 1] & comp);
+            nlc = b2 >> 1 > nlc ? b2 >> 1 : nlc;
+            rem &= ~comp;
+        }
+        col = cna_column(__popc(cn), nb2 >> 1, nlc);
+    }
+#pragma unroll
+    for (int k = 0; k < CNA_NSIG; ++k) n[k] = __popcll(__ballot(col == k));
+}
+
+__global__ void __launch_bounds__(SHELL_BLOCK)
+nm_cna_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+              bool adaptive, int *__restrict__ type, int *__restrict__ sig, int *__restrict__ ntype, int *__restrict__ nsig)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, c0 = (blockIdx.x % groups) * SHELL_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float *wave_all = (float *)smem;
+    int *tot = (int *)(wave_all + SHELL_WAVES * CNA_WAVE);
+    float *px = (float *)(tot + CNA_TOT), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    if (tid < CNA_TOT) tot[tid] = 0;
+    __syncthreads();
+    shell_bounds(part, bb);
+    float *lx = wave_all + wave * CNA_WAVE, *ly = lx + CNA_MAXV, *lz = ly + CNA_MAXV;
+    unsigned int *adj = (unsigned int *)(lz + CNA_MAXV);
+    float *sd = (float *)(adj + CNA_MAXV);
+    int wsum = 0; // lane k < 8: column k over this wave's centres; lane 8 + t: its atoms of type t
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
+        adf_wave_sync(); // the previous centre is done with the list
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
+        int n[CNA_NSIG] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int typ = 0;
+        if (!adaptive) {
+            int cnt = 0;
+            shell_scan(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, lane,
+                       [&](int, bool in, float vx, float vy, float vz, unsigned long long m) {
+                if (in) {
+                    const int o = cnt + __popcll(m & ((1ull << lane) - 1ull));
+                    if (o < CNA_MAXV) { lx[o] = vx; ly[o] = vy; lz[o] = vz; }
+                }
+                cnt += __popcll(m);
+                return true;
+            });
+            if (cnt > CNA_MAXV) n[CNA_NSIG - 1] = cnt;
+            else {
+                cna_columns(lx, ly, lz, adj, cnt, r_lo, r_hi, lane, n);
+                if (cnt == 12) typ = cna_close_packed(n);
+                else if (cnt == 14 && n[2] == 6 && n[3] == 8) typ = 3;
+            }
+        } else {
+            float hd = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f; // lane k < nh: the k-th smallest entry so far
+            float thr = INFINITY;                              // the last one's d once CNA_KEEP are held
+            int nh = 0;
+            shell_scan(px, py, pz, natoms, cx, cy, cz, L, cube, bb, r_lo, r_hi, lane,
+                       [&](int, bool in, float vx, float vy, float vz, unsigned long long) {
+                const float d = cna_len(vx, vy, vz); // the scan's own d
+                const bool cand = in && d < thr;
+                const unsigned long long cm = __ballot(cand);
+                if (cm == 0ull) return true;
+                // the entries before this lane's held one (rh) and before its candidate (rk) in the order (d, scan order): held
+                // entries precede every candidate of this step in the scan, the candidates follow the lanes
+                int rh = lane, rk = 0;
+                for (unsigned long long t = cm; t; t &= t - 1ull) {
+                    const int b = __ffsll((long long)t) - 1;
+                    const float db = __shfl(d, b);
+                    rh += db < hd ? 1 : 0;
+                    rk += (db < d || (db == d && b < lane)) ? 1 : 0;
+                }
+                for (int k = 0; k < nh; ++k) rk += __shfl(hd, k) <= d ? 1 : 0;
+                if (lane < nh && rh < CNA_KEEP) { sd[rh] = hd; lx[rh] = hx; ly[rh] = hy; lz[rh] = hz; }
+                if (cand && rk < CNA_KEEP) { sd[rk] = d; lx[rk] = vx; ly[rk] = vy; lz[rk] = vz; }
+                adf_wave_sync();
+                nh += __popcll(cm);
+                nh = nh < CNA_KEEP ? nh : CNA_KEEP;
+                if (lane < nh) { hd = sd[lane]; hx = lx[lane]; hy = ly[lane]; hz = lz[lane]; }
+                adf_wave_sync();
+                if (nh == CNA_KEEP) thr = __shfl(hd, CNA_KEEP - 1);
+                return true;
+            });
+            // the list's slots 0 .. nh - 1 hold the sorted entries: the last merge left them there
+            if (nh >= 12) {
+                cna_columns(lx, ly, lz, adj, 12, r_lo, cna_rc(hd, 12), lane, n);
+                typ = cna_close_packed(n);
+                if (typ == 0 && nh >= 14) {
+                    int n14[CNA_NSIG];
+                    cna_columns(lx, ly, lz, adj, 14, r_lo, cna_rc(hd, 14), lane, n14);
+                    if (n14[2] == 6 && n14[3] == 8) {
+                        typ = 3;
+#pragma unroll
+                        for (int k = 0; k < CNA_NSIG; ++k) n[k] = n14[k];
+                    }
+                }
+            }
+        }
+        int mine = 0;
+#pragma unroll
+        for (int k = 0; k < CNA_NSIG; ++k) mine = lane == k ? n[k] : mine;
+        mine = lane == CNA_NSIG + typ ? 1 : mine;
+        const size_t at = (size_t)s * natoms + c;
+        if (sig && lane < CNA_NSIG) sig[at * CNA_NSIG + lane] = mine;
+        if (type && lane == 0) type[at] = typ;
+        wsum += mine;
+    }
+    if (lane < CNA_NSIG + CNA_NTYPE && wsum) atomicAdd(&tot[lane], wsum);
+    __syncthreads();
+    if (tid < CNA_NSIG) {
+        if (nsig && tot[tid]) atomicAdd(&nsig[(size_t)s * CNA_NSIG + tid], tot[tid]);
+    } else if (tid < CNA_NSIG + CNA_NTYPE) {
+        if (ntype && tot[tid]) atomicAdd(&ntype[(size_t)s * CNA_NTYPE + tid - CNA_NSIG], tot[tid]);
+    }
+}
+
 } // namespace nm

@@ -11,13 +11,15 @@ static structure factor on the reciprocal lattice of each sample's box, averaged
 With -bo it also writes the Steinhardt bond-order parameters q_l, their neighbour average and the global Q_l (.bo*.npy;
 definition: include/nm_distr.h, nm_distr_bondorder).  With -so it also writes the solid-like atoms and crystal clusters of each
 sample: the solid fraction, the largest cluster's share, the number of clusters and the mean number of connections (.so*.npy;
-definition: include/nm_distr.h, nm_distr_solid).
+definition: include/nm_distr.h, nm_distr_solid).  With -cn it also writes the common neighbour analysis of each sample: the shares
+of fcc, hcp, bcc and icosahedral atoms and of the eight signature columns (.cn*.npy; definition: include/nm_distr.h, nm_distr_cna).
 
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -sf -sq 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -bo -bl 4 6
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -so -sl 6 -st 0.5 -sx 8
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -cn -cm adaptive
 """
 import argparse
 import ctypes as C
@@ -28,6 +30,7 @@ import numpy as np
 from . import _lib as B
 
 LAT = {'Ti': 'bcc', 'Al': 'fcc', 'Ni': 'fcc', 'Cu': 'fcc', 'LJ': 'fcc'}
+CNA_MODES = {'fixed': 0, 'adaptive': 1}                     # NM_CNA_FIXED, NM_CNA_ADAPTIVE (include/nm_distr.h)
 
 
 def _parser():
@@ -89,7 +92,39 @@ def _parser():
     p.add_argument('-sa', '--solid_atoms', action='store_true',
                    help='with -so also write the per-atom values: <PREFIX>.sona.npy (connections) and .sola.npy (cluster label: the '
                         'smallest atom index of the cluster, -1 for an atom that is not solid-like); 8 bytes per atom and sample')
+    p.add_argument('-cn', '--common_neighbours', action='store_true',
+                   help='also write the common neighbour analysis: <PREFIX>.cnf.npy, .cnh.npy, .cnb.npy and .cni.npy (fcc, hcp, bcc and '
+                        'icosahedral atoms / natoms) and .cns.npy (the share of each of the eight signature columns 421 422 444 666 '
+                        '555 544 433 other among the counted neighbour entries)')
+    p.add_argument('-cm', '--cna_mode', type=str, choices=sorted(CNA_MODES), default='adaptive',
+                   help='adaptive (default): a cutoff per atom from its own 12 and 14 nearest neighbours, no parameter; fixed: the '
+                        'one cutoff of -cr for every atom')
+    p.add_argument('-cr', '--cna_radius', type=float, default=0.0,
+                   help='the search radius (adaptive) or the cutoff (fixed) of -cn as a fraction of the smallest box edge, in (0, 0.5]; '
+                        'the default 0 means the first fcc shell of -bc for fixed and min(0.5, 1.3 / SZ) for adaptive, natoms = 4 SZ^3: '
+                        'a sphere that holds the 14 nearest neighbours of a crystal with room to spare, whose suitability for the LJ '
+                        'and Sutton-Chen grids of this package has not yet been measured')
+    p.add_argument('-ca', '--cna_atoms', action='store_true',
+                   help='with -cn also write the per-atom type: <PREFIX>.cnta.npy (0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico), one byte per '
+                        'atom and sample')
     return p
+
+
+def _cells(natoms):
+    """SZ, the cells per edge of an fcc crystal of natoms = 4 SZ^3 atoms, at least 1"""
+    return max(1, int(round((int(natoms) / 4.0) ** (1.0 / 3.0))))
+
+
+def cna_radius(value, natoms, mode):
+    """the radius of -cn as a fraction of the smallest box edge: value, or for value 0 bond_cutoff's first fcc shell (fixed) or
+    min(0.5, 1.3 / SZ) (adaptive); ValueError outside (0, 0.5]"""
+    cut = float(value)
+    if cut == 0.0:
+        cut = 0.853553 / _cells(natoms) if mode == 'fixed' else min(0.5, 1.3 / _cells(natoms))
+    if not 0.0 < cut <= 0.5:
+        raise ValueError('-cr/--cna_radius must lie in (0, 0.5]; got %g%s' % (cut, '' if float(value) else
+                         ' as the first fcc shell of %d atoms: pass -cr' % int(natoms)))
+    return cut
 
 
 def bond_cutoff(value, natoms):
@@ -97,7 +132,7 @@ def bond_cutoff(value, natoms):
     0.853553 / round(cbrt(natoms / 4)); ValueError outside (0, 0.5]"""
     cut = float(value)
     if cut == 0.0:
-        cut = 0.853553 / max(1, int(round((int(natoms) / 4.0) ** (1.0 / 3.0))))
+        cut = 0.853553 / _cells(natoms)
     if not 0.0 < cut <= 0.5:
         raise ValueError('-bc/--bond_cutoff must lie in (0, 0.5]; got %g%s' % (cut, '' if float(value) else
                          ' as the first fcc shell of %d atoms: pass -bc' % int(natoms)))
@@ -123,6 +158,8 @@ def parse_args(argv=None):
         p.error('-st/--solid_threshold must lie in [-1, 1)')
     if a.solid_connections < 1:
         p.error('-sx/--solid_connections must be at least 1')
+    if not 0.0 <= a.cna_radius <= 0.5:
+        p.error('-cr/--cna_radius must lie in (0, 0.5], or be 0 for the automatic value')
     return a
 
 
@@ -274,6 +311,25 @@ def solid(natoms, box, pos, l, r_lo, r_hi, s_min, n_min, device=0):
     return nconn, label, nsolid, nclus, largest
 
 
+def cna(natoms, box, pos, r_lo, r_hi, mode, device=0):
+    """common neighbour analysis of all samples (include/nm_distr.h, nm_distr_cna), mode 'adaptive' or 'fixed' (or NM_CNA_ADAPTIVE = 1,
+    NM_CNA_FIXED = 0), neighbour shell r_lo < d <= r_hi (adaptive: the search radius): type int32 [ns][natoms] (0 other, 1 fcc, 2 hcp,
+    3 bcc, 4 ico), sig int32 [ns][natoms][8] (the atom's entries per signature column 421 422 444 666 555 544 433 other), ntype int32
+    [ns][5] and nsig int32 [ns][8] (their sums over the atoms).  natoms is accepted for symmetry with histograms(); the atom count is
+    pos.shape[1]."""
+    L = B.load()
+    pos, box, ppos, pbox = _frames(pos, box)
+    ns, n = pos.shape[0], pos.shape[1]
+    typ = np.zeros((ns, n), dtype=np.int32)
+    sig = np.zeros((ns, n, 8), dtype=np.int32)
+    ntype = np.zeros((ns, 5), dtype=np.int32)
+    nsig = np.zeros((ns, 8), dtype=np.int32)
+    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
+    _check(L, 'nm_distr_cna', L.nm_distr_cna(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), int(CNA_MODES.get(mode, mode)),
+                                             ip(typ), ip(sig), ip(ntype), ip(nsig)))
+    return typ, sig, ntype, nsig
+
+
 def main(argv=None):
     a = parse_args(argv)
     dev = _device()
@@ -289,6 +345,11 @@ def main(argv=None):
         try:
             bcut = bond_cutoff(a.bond_cutoff, natoms[0])
         except ValueError as e:                                               # the automatic value needs natoms: refused before any file is written
+            raise SystemExit('distr: error: %s' % e)
+    if a.common_neighbours:
+        try:
+            ccut = cna_radius(a.cna_radius, natoms[0], a.cna_mode)
+        except ValueError as e:
             raise SystemExit('distr: error: %s' % e)
     nrho, dni, r, dn, rv = calculate_spatial(natoms, box, a.spherical_bins, a.cartesian_bins)
     rns = np.int32(ns / (pn * tn))
@@ -341,6 +402,17 @@ def main(argv=None):
         if a.solid_atoms:
             np.save(prefix + '.sona.npy', nconn.reshape(pn, tn, rns, n))
             np.save(prefix + '.sola.npy', label.reshape(pn, tn, rns, n))
+    if a.common_neighbours:
+        l = float(np.min(box))
+        n = int(natoms[0])
+        typ, _, ntype, nsig = cna(natoms, box, pos, 1e-16 * l, ccut * l, a.cna_mode, device=dev)
+        for name, t in (('cnf', 1), ('cnh', 2), ('cnb', 3), ('cni', 4)):
+            np.save(prefix + '.%s.npy' % name, (ntype[:, t] / np.float64(n)).astype(np.float32).reshape(pn, tn, rns))
+        counted = nsig.sum(axis=1, dtype=np.int64)[:, None]
+        share = np.divide(nsig, counted, out=np.zeros(nsig.shape, dtype=np.float64), where=counted > 0)
+        np.save(prefix + '.cns.npy', share.astype(np.float32).reshape(pn, tn, rns, 8))
+        if a.cna_atoms:
+            np.save(prefix + '.cnta.npy', typ.astype(np.int8).reshape(pn, tn, rns, n))
     if a.verbose:
         print('all properties pickled')
 

@@ -5,6 +5,7 @@
     python scripts/bench_distr.py --sfactor [ns=4096] [natoms=256] [qmax=16] [repeats=5]
     python scripts/bench_distr.py --bondorder [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l ...=4 6]
     python scripts/bench_distr.py --solid [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l=6] [s_min=0.5] [n_min=8]
+    python scripts/bench_distr.py --cna [ns=4096] [cells=4] [cutoff=0] [repeats=5] [mode=adaptive]
 
 --angles: nm_distr_angles on displaced fcc frames of 4 cells^3 atoms (shell up to cutoff * l; the first shell is about
 0.85 / cells): the time of the whole call (copies + kernel, host clock around the synchronous call, median of the repeats
@@ -25,7 +26,13 @@ script needs the tests directory next to it).  The kernels' own times come from 
 --solid: nm_distr_solid on the frames and shapes of --bondorder, all five outputs: the time of the whole call as above, entries/s,
 and next to it nm_distr_bondorder with qbar2 alone for the same single l on the same frames and shell (the yardstick: two scans
 of the candidates; the solid path does three and the gather of the bond values).  The kernels' own times come from the same
-rocprofv3 line (nm_bo_moments_kernel, nm_solid_connect_kernel, nm_solid_union_kernel, nm_solid_label_kernel)."""
+rocprofv3 line (nm_bo_moments_kernel, nm_solid_connect_kernel, nm_solid_union_kernel, nm_solid_label_kernel).
+
+--cna: nm_distr_cna (mode adaptive or fixed) on the frames of --bondorder, all four outputs (cutoff 0 = distr.cna_radius's automatic
+value for the mode): the time of the whole call as above, centres/s and entries/s, the types and columns found, and next to it
+nm_distr_solid (l = 6, the defaults) on the same frames and the same shell, the nearest scan-bound sibling (three scans of the
+candidates and the moments against this path's one scan and the graphs).  The kernel's own time comes from the same rocprofv3 line
+(nm_cna_kernel against nm_bo_moments_kernel + nm_solid_connect_kernel + nm_solid_union_kernel + nm_solid_label_kernel)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,6 +234,70 @@ def bench_solid(argv):
     print('bondorder with qbar2 alone, l = %d, on the same frames and shell: call median of %d: %.4f s (min %.4f, max %.4f); solid / bondorder = %.2f'
           % (lv, reps, med['qbar'][0], med['qbar'][1], med['qbar'][2], dt / med['qbar'][0]))
 
+
+def bench_cna(argv):
+    from neuralmelting_amd import _lib as B, lattice
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    cells = int(argv[1]) if len(argv) > 1 else 4
+    cut = float(argv[2]) if len(argv) > 2 else 0.0
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    mode = argv[4] if len(argv) > 4 else 'adaptive'
+    rng = np.random.default_rng(3)                                            # the frames of bench_angles
+    n = 4 * cells ** 3
+    cut = distr.cna_radius(cut, n, mode)
+    a0 = lattice.lattice_constant('LJ')
+    box = (cells * a0 * (1.0 + 0.05 * rng.random(ns))).astype(np.float32)
+    frac = lattice.fcc_fractional(cells)
+    pos = ((frac[None] + 0.08 / cells * rng.normal(size=(ns, n, 3))) % 1.0 * box[:, None, None]).astype(np.float32)
+    pos = np.minimum(pos, np.nextafter(box, np.float32(0))[:, None, None])
+    l = float(box.min())
+    L = B.load()
+    typ, sig = np.zeros((ns, n), dtype=np.int32), np.zeros((ns, n, 8), dtype=np.int32)
+    ntype, nsig = np.zeros((ns, 5), dtype=np.int32), np.zeros((ns, 8), dtype=np.int32)
+    nconn, label = np.zeros((ns, n), dtype=np.int32), np.zeros((ns, n), dtype=np.int32)
+    nsolid, nclus, largest = np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32)
+    nb = np.zeros((ns, n), dtype=np.int32)
+    ls = np.array([6], dtype=np.int32)
+    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
+
+    def run(m):
+        rc = L.nm_distr_cna(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l,
+                            distr.CNA_MODES[mode], ip(typ), ip(sig), ip(ntype), ip(nsig))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+
+    def run_solid(m):
+        rc = L.nm_distr_solid(0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, 6, 0.5, 8,
+                              ip(nconn), ip(label), ip(nsolid), ip(nclus), ip(largest))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+    med = {}
+    for name, f in (('cna', run), ('solid', run_solid)):
+        f(min(ns, 8))
+        f(ns)                                                                 # warm-up at the timed shape
+        ts = []
+        for _ in range(reps):
+            t = time.perf_counter(); f(ns); ts.append(time.perf_counter() - t)
+        med[name] = (float(np.median(ts)), min(ts), max(ts))
+    rc = L.nm_distr_bondorder(0, ns, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, 1,
+                              ls.ctypes.data_as(B.c_int_p), None, None, None, ip(nb))   # the entries, outside the timing
+    if rc != 0:
+        raise RuntimeError(L.nm_distr_last_error().decode())
+    ent = int(nb.sum())
+    dt = med['cna'][0]
+    print('cna %s: %d samples x %d atoms, radius %.4f l: %d entries (%.1f per centre, %d at most); types other fcc hcp bcc ico %s, '
+          'columns 421 422 444 666 555 544 433 other %s; call (H2D + kernel + D2H) median of %d: %.4f s (min %.4f, max %.4f) = '
+          '%.2f G entries/s, %.1f M centres/s'
+          % (mode, ns, n, cut, ent, ent / (ns * n), nb.max(), (ntype.sum(axis=0) / (ns * n)).round(4).tolist(),
+             (nsig.sum(axis=0) / max(1, int(nsig.sum()))).round(4).tolist(), reps, dt, med['cna'][1], med['cna'][2], ent / dt / 1e9,
+             ns * n / dt / 1e6))
+    print('solid (l = 6, s_min 0.5, n_min 8) on the same frames and shell: call median of %d: %.4f s (min %.4f, max %.4f); cna / solid = %.2f'
+          % (reps, med['solid'][0], med['solid'][1], med['solid'][2], dt / med['solid'][0]))
+
+
+if '--cna' in sys.argv:
+    bench_cna([x for x in sys.argv[1:] if x != '--cna'])
+    sys.exit(0)
 
 if '--solid' in sys.argv:
     bench_solid([x for x in sys.argv[1:] if x != '--solid'])
