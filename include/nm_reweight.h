@@ -28,6 +28,9 @@
  * Determinism.  The same bits on every call: every sum runs in a fixed order, no floating-point atomics.
  * No K x N array exists at any time: device memory is 3 N doubles, the observables, and a partial per (state, 4096 samples).
  *
+ * Reweighted histograms of any per-sample quantity with the same weights (the probability distribution p(x | P, T), not only
+ * its mean): nm_reweight_hist.h, included below; its function is part of this interface and follows the same rules.
+ *
  * Both functions return 0 or a negative NM_ERR_* code (include/nm.h); message via nm_reweight_last_error(), starting with the
  * function's name.  NM_ERR_ARG, checked before the device is looked for and with every output left untouched, for: nstates
  * outside 1..4096, nsamples < 1, a count that is negative or counts that do not sum to nsamples, a non-finite value in b, c,
@@ -66,4 +69,5 @@ const char *nm_reweight_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+#include "nm_reweight_hist.h"
 #endif

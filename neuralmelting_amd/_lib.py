@@ -33,6 +33,8 @@ DISTR_SYMBOLS = ('nm_distr_histograms', 'nm_distr_angles', 'nm_distr_sfactor', '
 PARSE_SYMBOLS = ('nm_parse_thrm', 'nm_parse_traj', 'nm_parse_last_error')
 # include/nm_reweight.h
 REWEIGHT_SYMBOLS = ('nm_reweight_solve', 'nm_reweight_expect', 'nm_reweight_last_error')
+# include/nm_reweight_hist.h, which nm_reweight.h includes
+REWEIGHT_HIST_SYMBOLS = ('nm_reweight_histogram',)
 
 
 class NMConfig(C.Structure):
@@ -138,6 +140,9 @@ def load():
     L.nm_reweight_expect.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, c_double_p, C.c_int64, c_double_p, c_double_p,
                                      C.c_int, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                      c_double_p]
+    L.nm_reweight_histogram.restype = C.c_int
+    L.nm_reweight_histogram.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, c_double_p, C.c_int64, c_double_p, c_double_p,
+                                        C.c_int, c_double_p, c_double_p, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p]
     L.nm_reweight_last_error.restype = C.c_char_p
     _lib = L
     return L

@@ -2357,4 +2357,95 @@ int nm_reweight_expect(int device, int nstates, const double *b, const double *c
     }
     return NM_OK;
 }
+
+int nm_reweight_histogram(int device, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
+                          const double *e, const double *v, int ntargets, const double *tb, const double *tc, int nq, const double *x,
+                          int nbins, const double *edges, double *hist, double *outside)
+{
+    static const char *const fn = "nm_reweight_histogram";
+    if (nsamples > RW_HIST_MAXN) return rwrefuse(fn, "nsamples must not exceed 2^28");
+    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    if (ntargets < 1 || ntargets > 65536) return rwrefuse(fn, "ntargets must lie in 1..65536");
+    if (nq < 1 || nq > RW_MAXQ) return rwrefuse(fn, "nq must lie in 1..8");
+    if (nbins < 1 || nbins > RW_MAXBINS) return rwrefuse(fn, "nbins must lie in 1..1024");
+    if (!tb || !tc || !x || !edges || !hist) return rwrefuse(fn, "a needed pointer is null");
+    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return rwrefuse(fn, "a target's tb or tc is not finite");
+    if (!rw_finite(edges, (int64_t)nq * (nbins + 1))) return rwrefuse(fn, "an edge is not finite");
+    for (int q = 0; q < nq; ++q)
+        for (int j = 0; j < nbins; ++j)
+            if (!(edges[(size_t)q * (nbins + 1) + j] < edges[(size_t)q * (nbins + 1) + j + 1])) return rwrefuse(fn, "the edges are not strictly increasing");
+    if (!rw_finite(x, (int64_t)nq * nsamples)) return rwrefuse(fn, "an x is not finite");
+    if (const int rc = rw_device(fn, device)) return rc;
+    RwProblem p;
+    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    const int nbatch = p.batch(2, RW_TB, (ntargets + RW_TB - 1) / RW_TB * RW_TB);
+    if (const int rc = p.scratch(fn, 2, nbatch)) return rc;
+    const int nb2 = nbins + 2, per = nq * nb2;                    // a target's counters: per quantity the bins, below, above
+    const int nlaunch = ntargets < RW_TGB ? ntargets : RW_TGB;
+    const size_t ncount = (size_t)nlaunch * per;
+    DevBuf<double> d_tb, d_tc, d_F, d_edges, d_out;
+    DevBuf<uint16_t> d_code;
+    DevBuf<unsigned long long> d_hi, d_lo;
+    RW_CHK(fn, d_tb.alloc(ntargets));
+    RW_CHK(fn, d_tc.alloc(ntargets));
+    RW_CHK(fn, d_F.alloc(ntargets));
+    RW_CHK(fn, d_edges.alloc((size_t)nq * (nbins + 1)));
+    RW_CHK(fn, d_code.alloc((size_t)nq * nsamples));
+    RW_CHK(fn, d_hi.alloc(ncount));
+    RW_CHK(fn, d_lo.alloc(ncount));
+    RW_CHK(fn, d_out.alloc(ncount));
+    RW_CHK(fn, hipMemcpy(d_tb, tb, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
+    RW_CHK(fn, hipMemcpy(d_tc, tc, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
+    RW_CHK(fn, hipMemcpy(d_edges, edges, (size_t)nq * (nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
+    RW_CHK(fn, hipMemset(d_hi, 0, ncount * sizeof(unsigned long long)));
+    RW_CHK(fn, hipMemset(d_lo, 0, ncount * sizeof(unsigned long long)));
+    {   // the bin codes, a quantity at a time: the quantities themselves do not stay on the device
+        DevBuf<double> d_x;
+        RW_CHK(fn, d_x.alloc((size_t)nsamples));
+        for (int q = 0; q < nq; ++q) {
+            RW_CHK(fn, hipMemcpy(d_x, x + (size_t)q * nsamples, (size_t)nsamples * sizeof(double), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(nm_rw_bins_kernel, dim3((unsigned)((nsamples + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, nsamples, d_x, nbins,
+                               d_edges + (size_t)q * (nbins + 1), d_code + (size_t)q * nsamples);
+        }
+        RW_CHK(fn, hipGetLastError());
+        RW_CHK(fn, hipDeviceSynchronize());
+    }
+    p.denominators();
+    for (int t0 = 0; t0 < ntargets; t0 += nbatch)
+        p.moments<RW_TB, false>(t0, (ntargets - t0) < nbatch ? (ntargets - t0) : nbatch, d_tb, d_tc, 0, nullptr, d_F, nullptr);
+    RW_CHK(fn, hipGetLastError());
+    // the tile of targets: four where their counters stay within RW_HIST_LDS, else two, else one (131,328 B at nq = 8, nbins = 1024)
+    const size_t one = (size_t)per * 2 * sizeof(unsigned long long);
+    const int tt = 4 * one <= (size_t)RW_HIST_LDS ? 4 : 2 * one <= (size_t)RW_HIST_LDS ? 2 : 1;
+    const size_t lds = tt * one;
+    const void *kern = tt == 4 ? (const void *)nm_rw_hist_kernel<4> : tt == 2 ? (const void *)nm_rw_hist_kernel<2> : (const void *)nm_rw_hist_kernel<1>;
+    RW_CHK(fn, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned gx = (unsigned)((p.nchunks + RW_HG - 1) / RW_HG);
+    std::vector<double> out(ncount);
+    for (int t0 = 0; t0 < ntargets; t0 += RW_TGB) {
+        const int nb = (ntargets - t0) < RW_TGB ? (ntargets - t0) : RW_TGB;
+        const dim3 grid(gx, (unsigned)((nb + tt - 1) / tt));
+#define RW_HIST_LAUNCH(TT)                                                                                                                   \
+        hipLaunchKernelGGL(nm_rw_hist_kernel<TT>, grid, dim3(RW_BLOCK), lds, 0, p.N, p.e, p.v, p.logd, t0, t0 + nb, d_tb, d_tc, d_F, nq, nb2, d_code, \
+                           d_hi, d_lo)
+        if (tt == 4) RW_HIST_LAUNCH(4);
+        else if (tt == 2) RW_HIST_LAUNCH(2);
+        else RW_HIST_LAUNCH(1);
+#undef RW_HIST_LAUNCH
+        const int64_t cnt = (int64_t)nb * per;
+        hipLaunchKernelGGL(nm_rw_hist_out_kernel, dim3((unsigned)((cnt + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, cnt, d_hi, d_lo, d_out);
+        RW_CHK(fn, hipGetLastError());
+        RW_CHK(fn, hipMemcpy(out.data(), d_out, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
+        for (int t = 0; t < nb; ++t)
+            for (int q = 0; q < nq; ++q) {
+                const double *src = out.data() + ((size_t)t * nq + q) * nb2;
+                std::copy(src, src + nbins, hist + ((size_t)(t0 + t) * nq + q) * nbins);
+                if (outside) {
+                    outside[((size_t)(t0 + t) * nq + q) * 2] = src[nbins];
+                    outside[((size_t)(t0 + t) * nq + q) * 2 + 1] = src[nbins + 1];
+                }
+            }
+    }
+    return NM_OK;
+}
 } // extern "C"

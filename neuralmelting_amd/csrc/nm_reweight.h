@@ -283,4 +283,139 @@ nm_rw_update_kernel(RwStatus *__restrict__ st, int k, const double *__restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Reweighted histograms (include/nm_reweight_hist.h, nm_reweight_histogram): hist[t][q][j] = the sum of the weights w_n =
+// exp(-u_t(n) - logd[n] + tf) over the samples whose x[q][n] lies in bin j, and the weight below and above the edges.
+//
+//   nm_rw_bins_kernel      once per call and quantity: one thread per sample, the quantity's edges in LDS, a bisection that
+//                          compares x with the edges themselves.  It writes a 16-bit code per sample: the bin 0 .. nbins - 1,
+//                          nbins for "below", nbins + 1 for "above" - the index of the sample's counter, so that the histogram
+//                          kernel does not branch on it.
+//   tf                     nm_rw_denom_kernel, nm_rw_moments_kernel<RW_TB, false>, nm_rw_combine_kernel<false> as they are.
+//   nm_rw_hist_kernel<TT>  one workgroup per (TT targets, RW_HG chunks of RW_CH samples).  A thread reads a sample and its nq
+//                          codes once, forms the TT exponentials, and adds each weight to the nq counters it belongs to.
+//   nm_rw_hist_out_kernel  the launch's integer counters to float64 with ordinary stores; it leaves the counters at zero.
+//
+// Fixed point.  A weight lies in [0, 1 + 1e-9]: tf = -(M + log S) with S >= 1 the sum of exp(t_n - M), so exp(t_n + tf) <= 1 up to
+// the roundings of tf and of the exponential.  w 2^RW_HS = hi + fr with hi the integer part (hi <= 2^48 + 2^19, exact as a double,
+// and x - hi is exact); lo = the integer part of fr 2^RW_LS < 2^48: a power of two times a double is exact, so the only loss is
+// what lies below 2^-(RW_HS + RW_LS) = 2^-96 of the weight, less than 2^-96 per term, N 2^-96 per counter.  hi and lo go to two
+// 64-bit LDS counters by integer atomics: integer addition is associative, so a counter holds the same bits in whatever order
+// the lanes arrive.
+// Overflow.  Low word in LDS: between two normalisations it takes at most RW_CH = 2^12 terms below 2^48 on top of a rest below
+//   2^48: < 2^61.  A normalisation moves lo >> 48 into the high word and keeps lo < 2^48.
+//   High word in LDS: a workgroup adds at most RW_HG RW_CH = 2^14 terms of at most 2^48 (1 + 1e-9) and RW_HG carries of at most
+//   2^12: < 2^63, whatever the weights sum to.
+//   Global low word: every workgroup adds a normalised rest below 2^48, one per RW_HG chunks: with nsamples <= 2^28 =
+//   RW_HIST_MAXN at most 2^14 of them, < 2^62.  (2^16 single chunks would still fit: the limit does not depend on RW_HG.)
+//   Global high word: with the last carry it is the integer part of 2^48 times a sum of weights of one target, and all weights of
+//   a target sum to 1 up to the error bound of tf (< 1e-9 for every admitted problem): < 2^49.
+//   nm_rw_hist_out_kernel normalises once more: hi < 2^49 and lo < 2^48 convert exactly, hi 2^-48 + lo 2^-96 rounds once.
+// LDS.  2 words of 8 B per (target of the tile, quantity, nbins + 2 counters).  The host takes TT = 4 targets where that stays
+// within RW_HIST_LDS = 40 KiB (four workgroups per CU), else 2, else 1; one target at nq = 8, nbins = 1024 is 131,328 B of the
+// CU's 163,840 B, one workgroup per CU.
+constexpr int RW_MAXQ = 8;
+constexpr int RW_MAXBINS = 1024;
+constexpr int RW_HS = 48, RW_LS = 48;           // the weight's fixed-point split: truncation unit 2^-(RW_HS + RW_LS)
+constexpr int RW_HG = 4;                        // chunks per workgroup of the histogram kernel: a quarter of the global atomics
+constexpr int RW_HIST_LDS = 40 * 1024;          // what a tile of more than one target may take
+constexpr int64_t RW_HIST_MAXN = (int64_t)1 << 28;
+constexpr unsigned long long RW_LMASK = (1ull << RW_LS) - 1ull;
+static_assert(RW_LS + 12 + 1 <= 64 && (1 << 12) == RW_CH, "the LDS low word takes a chunk of terms on top of a rest");
+static_assert(RW_HS + 14 + 1 <= 63 && RW_HG * RW_CH == (1 << 14), "the LDS high word takes a workgroup's terms and carries");
+
+__global__ void __launch_bounds__(RW_BLOCK)
+nm_rw_bins_kernel(int64_t n, const double *__restrict__ x, int nbins, const double *__restrict__ edges, uint16_t *__restrict__ code)
+{
+    __shared__ double se[RW_MAXBINS + 1];
+    for (int k = threadIdx.x; k <= nbins; k += RW_BLOCK) se[k] = edges[k];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * RW_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double xi = x[i];
+    int lo = 0, hi = nbins; // se[lo] <= xi, and xi < se[hi] or hi = nbins: the last bin is closed on the right
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (se[mid] <= xi) lo = mid;
+        else hi = mid;
+    }
+    code[i] = (uint16_t)(xi < se[0] ? nbins : xi > se[nbins] ? nbins + 1 : lo);
+}
+
+// ghi, glo [(target - t0)][nq][nb2 = nbins + 2] += the fixed-point weights of the targets t0 + blockIdx.y * TT + (0..TT-1) below
+// nt over the chunks blockIdx.x * RW_HG + (0..RW_HG-1); F [nt] is tf in the centred gauge, code [nq][n].  Dynamic LDS: 16 TT nq nb2 B.
+template <int TT>
+__global__ void __launch_bounds__(RW_BLOCK)
+nm_rw_hist_kernel(int64_t n, const double *__restrict__ e, const double *__restrict__ v, const double *__restrict__ logd, int t0, int nt,
+                  const double *__restrict__ tb, const double *__restrict__ tc, const double *__restrict__ F, int nq, int nb2,
+                  const uint16_t *__restrict__ code, unsigned long long *__restrict__ ghi, unsigned long long *__restrict__ glo)
+{
+    extern __shared__ __align__(16) unsigned char rw_smem[];
+    const int tid = threadIdx.x;
+    const int per = nq * nb2, nc = TT * per;
+    unsigned long long *shi = (unsigned long long *)rw_smem, *slo = shi + nc;
+    for (int k = tid; k < 2 * nc; k += RW_BLOCK) shi[k] = 0ull;
+    const int tfirst = t0 + (int)blockIdx.y * TT;
+    double b[TT], c[TT], f[TT];
+#pragma unroll
+    for (int j = 0; j < TT; ++j) {
+        const int t = (tfirst + j) < nt ? (tfirst + j) : nt - 1; // a tile past the end repeats the last target and does not write it
+        b[j] = tb[t];
+        c[j] = tc[t];
+        f[j] = F[t];
+    }
+    __syncthreads();
+    for (int g = 0; g < RW_HG; ++g) {
+        const int64_t c0 = ((int64_t)blockIdx.x * RW_HG + g) * RW_CH;
+        if (c0 >= n) break; // uniform
+        const int64_t c1 = (n - c0) < RW_CH ? n : c0 + RW_CH;
+        for (int64_t i = c0 + tid; i < c1; i += RW_BLOCK) {
+            const double ei = e[i], vi = v[i], li = logd[i];
+            int cd[RW_MAXQ];
+#pragma unroll
+            for (int q = 0; q < RW_MAXQ; ++q) cd[q] = q < nq ? (int)code[(int64_t)q * n + i] : 0;
+#pragma unroll
+            for (int j = 0; j < TT; ++j) {
+                const double x = exp(f[j] - fma(b[j], ei, fma(c[j], vi, li))) * 0x1p48;
+                const unsigned long long hi = (unsigned long long)x;
+                const unsigned long long lo = (unsigned long long)((x - (double)hi) * 0x1p48); // x - hi is exact
+#pragma unroll
+                for (int q = 0; q < RW_MAXQ; ++q) {
+                    if (q < nq) { // uniform
+                        const int k = j * per + q * nb2 + cd[q];
+                        if (hi) atomicAdd(&shi[k], hi);
+                        if (lo) atomicAdd(&slo[k], lo);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int k = tid; k < nc; k += RW_BLOCK) { // the carries of this chunk
+            const unsigned long long l = slo[k];
+            shi[k] += l >> RW_LS;
+            slo[k] = l & RW_LMASK;
+        }
+        __syncthreads();
+    }
+    for (int k = tid; k < nc; k += RW_BLOCK) {
+        const int j = k / per;
+        if (tfirst + j >= nt) break; // j does not decrease with k
+        const size_t dst = (size_t)(tfirst - t0) * per + k;
+        if (shi[k]) atomicAdd(&ghi[dst], shi[k]);
+        if (slo[k]) atomicAdd(&glo[dst], slo[k]);
+    }
+}
+
+// out[k] = the counter k as a float64, k < count; the counters are left at zero for the next launch
+__global__ void __launch_bounds__(RW_BLOCK)
+nm_rw_hist_out_kernel(int64_t count, unsigned long long *__restrict__ ghi, unsigned long long *__restrict__ glo, double *__restrict__ out)
+{
+    const int64_t k = (int64_t)blockIdx.x * RW_BLOCK + threadIdx.x;
+    if (k >= count) return;
+    const unsigned long long l = glo[k], h = ghi[k] + (l >> RW_LS);
+    out[k] = (double)h * 0x1p-48 + (double)(l & RW_LMASK) * 0x1p-96;
+    ghi[k] = 0ull;
+    glo[k] = 0ull;
+}
+
 } // namespace nm

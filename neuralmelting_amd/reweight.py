@@ -3,8 +3,8 @@ states, and enthalpy, volume and heat capacity as continuous curves in T at ever
 
 A replica-exchange run over a P x T grid is the input of MBAR (Shirts and Chodera 2008): every sample of every replica
 contributes to every state.  The reference locates the transition with a VAE on the histograms instead (lammps_vae.py);
-this stage is the build's own.  The arithmetic runs in the HIP library (nm_reweight_solve, nm_reweight_expect), there is no
-host fallback.
+this stage is the build's own.  The arithmetic runs in the HIP library (nm_reweight_solve, nm_reweight_expect,
+nm_reweight_histogram), there is no host fallback.
 
 What makes the grid's samples the samples of its states: the sampler's exchange moves configurations between slots, never
 temperatures or pressures between configurations (remcmc.py, Run.replica_exchange / exchange.sweep: the energies, volumes
@@ -15,6 +15,7 @@ potential uses the potential energy: the kinetic energy of a record is that of t
 state's temperature whatever the configuration, and integrates out of every configurational average.
 
     python -m neuralmelting_amd.reweight -v -n remcmc_run_5 -e LJ -sk 128 -ob sof sol
+    python -m neuralmelting_amd.reweight -v -n remcmc_run_5 -e LJ -sk 128 -hq sof pe vol -hx 0.5     # p(x | P, T) and the equal-weight T
 """
 import argparse
 import ctypes as C
@@ -29,7 +30,9 @@ from .remcmc import init_constant
 
 MAX_OBS = 8
 MAX_TARGETS = 65536     # include/nm_reweight.h: ntargets of one call
+MAX_HIST, MAX_BINS = 8, 1024    # include/nm_reweight_hist.h: nq and nbins
 SUFFIXES = ('rwf', 'rwi', 'rwt', 'rwg', 'rwh', 'rwv', 'rwc', 'rwn', 'rwo', 'rwm')
+HIST_SUFFIXES = ('rwx', 'rwp', 'rwa', 'rwe')    # written with -hq only (rwa, rwe with -hx only)
 
 
 def parse_args(argv=None):
@@ -38,7 +41,9 @@ def parse_args(argv=None):
         '(iterations, delta, tol); .rwt (TG,) the fine temperatures; and on (PN, TG): .rwg reduced free energy, .rwh enthalpy per '
         'atom, .rwv volume per atom, .rwc configurational Cp / (natoms kB) - the kinetic 3/2 is NOT included -, .rwn the Kish '
         'effective sample size, .rwo (PN, TG, nobs) the observables of -ob; .rwm (PN,) the temperature of the largest Cp on the '
-        'fine grid.  A peak on an end of the range means that the transition is not bracketed: the value is written as it is.')
+        'fine grid.  A peak on an end of the range means that the transition is not bracketed: the value is written as it is.  With '
+        '-hq: .rwx (nq, NBINS + 1) the bin edges and .rwp (PN, TG, nq, NBINS) the reweighted probability of every bin; with -hx: .rwa '
+        '(PN, TG) the weight at or above the cut and .rwe (PN,) the temperature where it first crosses 1/2 (NaN without a crossing).')
     p.add_argument('-v', '--verbose', action='store_true')
     p.add_argument('-n', '--name', type=str, default='remcmc_init')
     p.add_argument('-e', '--element', type=str, default='LJ')
@@ -52,8 +57,18 @@ def parse_args(argv=None):
                    help='most applications of the map; if delta > tol then, the files are still written and the exit status is 1')
     p.add_argument('-ob', '--observables', type=str, nargs='+', default=[],
                    help='up to 8 names: <PREFIX>.NAME.npy of shape (PN, TN, SN) is averaged with the weights (e.g. distr\'s sof, sol)')
+    p.add_argument('-hq', '--histogram', type=str, nargs='+', default=[],
+                   help='up to 8 names to histogram with the weights: pe (potential energy per atom), vol (volume per atom), or a name as '
+                   'behind -ob.  The edges are linspace(min, max, NBINS + 1) of the kept samples (min - 0.5 .. min + 0.5 for a constant)')
+    p.add_argument('-hb', '--histogram_bins', type=int, default=128, help='NBINS of -hq, 1..1024')
+    p.add_argument('-hx', '--histogram_cut', type=float, default=None,
+                   help='a cut on the first name of -hq, moved to the nearest bin edge: the weight at or above it and its crossing of 1/2')
     p.add_argument('-dv', '--device', type=int, default=0)
     a = p.parse_args(argv)
+    if a.histogram_cut is not None and not a.histogram:
+        p.error('-hx needs -hq')
+    if len(a.histogram) > MAX_HIST or not 1 <= a.histogram_bins <= MAX_BINS or (a.histogram_cut is not None and not np.isfinite(a.histogram_cut)):
+        p.error('need at most 8 names behind -hq, -hb in 1..1024 and a finite -hx')
     if a.skip < 0 or a.stride < 1 or not 1 <= a.temperature_grid <= MAX_TARGETS or a.max_iterations < 1 or not a.tolerance >= 0 or len(a.observables) > MAX_OBS:
         p.error('need -sk >= 0, -sd >= 1, -tg in 1..65536 (PN x TG <= 65536), -ri >= 1, -rt >= 0 and at most 8 names behind -ob')
     return a
@@ -112,6 +127,51 @@ def expect(b, c, count, f, e, v, tb, tc, obs=None, device=0):
     return out
 
 
+def histogram(b, c, count, f, e, v, tb, tc, x, edges, device=0):
+    """nm_reweight_histogram: (hist (T, nq, nbins), outside (T, nq, 2)); x (nq, N), edges (nq, nbins + 1)"""
+    b, c, f, e, v = _f64(b), _f64(c), _f64(f), _f64(e).reshape(-1), _f64(v).reshape(-1)
+    tb, tc = _f64(tb).reshape(-1), _f64(tc).reshape(-1)
+    count = np.ascontiguousarray(count, dtype=np.int64)
+    x, edges = _f64(x), _f64(edges)
+    if not (b.size == c.size == count.size == f.size and e.size == v.size and tb.size == tc.size) or x.ndim != 2 or edges.ndim != 2 \
+            or x.shape[1] != e.size or edges.shape[0] != x.shape[0] or edges.shape[1] < 2:
+        raise ValueError('b, c, count, f want one length, e, v another, tb, tc a third; x (nq, N) and edges (nq, nbins + 1)')
+    nt, nq, nbins = tb.size, x.shape[0], edges.shape[1] - 1
+    hist, outside = np.empty((nt, nq, nbins)), np.empty((nt, nq, 2))
+    rc = B.load().nm_reweight_histogram(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), _dp(f), e.size, _dp(e), _dp(v),
+                                        nt, _dp(tb), _dp(tc), nq, _dp(x), nbins, _dp(edges), _dp(hist), _dp(outside))
+    if rc != B.NM_OK:
+        _fail('nm_reweight_histogram', rc)
+    return hist, outside
+
+
+def equal_weight(tfine, above):
+    """per pressure the temperature where `above` (PN, TG), the weight above a cut, first crosses 1/2: the first pair of
+    neighbouring fine temperatures with (a_i - 1/2)(a_i+1 - 1/2) <= 0 and a_i != a_i+1, interpolated linearly in T; NaN where
+    there is none (a flat stretch at 1/2 is no crossing)"""
+    tfine, d = _f64(tfine), np.atleast_2d(_f64(above)) - 0.5
+    out = np.full(d.shape[0], np.nan)
+    for p, row in enumerate(d):
+        hit = np.nonzero((row[:-1] * row[1:] <= 0.0) & (row[:-1] != row[1:]))[0]
+        if hit.size:
+            i = hit[0]
+            out[p] = tfine[i] + (tfine[i + 1] - tfine[i]) * (row[i] / (row[i] - row[i + 1]))
+    return out
+
+
+def linear_edges(x, nbins):
+    """linspace(min, max, nbins + 1) of every row of x (nq, N); min - 0.5 .. min + 0.5 for a constant row"""
+    lo, hi = x.min(axis=1), x.max(axis=1)
+    flat = lo == hi
+    return np.stack([np.linspace(l - 0.5 if s else l, l + 0.5 if s else h, nbins + 1) for l, h, s in zip(lo, hi, flat)])
+
+
+def cut_weight(hist, edges, cut):
+    """(the weight (T,) of the bins of quantity 0 at or above the edge nearest to `cut`, that edge)"""
+    j = int(np.argmin(np.abs(edges[0] - cut)))
+    return hist[:, 0, j:].sum(axis=1), float(edges[0, j])
+
+
 def fine_targets(P, T, el, tg):
     """the fine temperatures (TG,) and the targets (tb, tc), each (PN, TG), with init_constant's constants"""
     tf = np.linspace(float(T[0]), float(T[-1]), tg)
@@ -133,16 +193,16 @@ def curves(f, iters, delta, tol, tfine, tb, tc, ex, natoms):
                 rwn=ex['ess'].reshape(pn, tg), rwo=ex['omean'].reshape(pn, tg, -1), rwm=_f64(tfine)[np.argmax(cp, axis=1)])
 
 
-def load_observables(prefix, names, shape):
-    """the (PN, TN, SN) arrays of -ob, or ValueError naming the file that is missing or misshapen"""
+def load_observables(prefix, names, shape, flag='-ob'):
+    """the (PN, TN, SN) arrays of -ob (or -hq), or ValueError naming the file that is missing or misshapen"""
     out = []
     for name in names:
         path = prefix + '.%s.npy' % name
         if not os.path.isfile(path):
-            raise ValueError('-ob %s: %s is missing' % (name, path))
+            raise ValueError('%s %s: %s is missing' % (flag, name, path))
         a = np.load(path)
         if a.shape != tuple(shape):
-            raise ValueError('-ob %s: %s has shape %s, not %s' % (name, path, a.shape, tuple(shape)))
+            raise ValueError('%s %s: %s has shape %s, not %s' % (flag, name, path, a.shape, tuple(shape)))
         out.append(a)
     return out
 
@@ -163,6 +223,8 @@ def main(argv=None):
         raise SystemExit('reweight: .pe.npy %s and .vol.npy %s do not fit the %d x %d grid' % (pe.shape, vol.shape, pn, tn))
     try:
         obs = load_observables(prefix, a.observables, pe.shape)         # refused before anything is written
+        hq = [_f64(pe) / natoms if name == 'pe' else _f64(vol) / natoms if name == 'vol' else load_observables(prefix, [name], pe.shape, '-hq')[0]
+              for name in a.histogram]
     except ValueError as err:
         raise SystemExit('reweight: %s' % err)
     keep = slice(a.skip, None, a.stride)
@@ -172,6 +234,9 @@ def main(argv=None):
     if sn < 1:
         raise SystemExit('reweight: -sk %d leaves no sample' % a.skip)
     obs = [_f64(o[:, :, keep]).reshape(-1) for o in obs]
+    x = np.stack([_f64(q[:, :, keep]).reshape(-1) for q in hq]) if hq else None
+    if hq and not np.isfinite(x).all():
+        raise SystemExit('reweight: -hq: a kept sample is not finite')
     b, c = states(P, T, el)
     count = np.full(pn * tn, sn, dtype=np.int64)
     f0 = b * e.mean(axis=1) + c * v.mean(axis=1)                        # the mean of u_k over state k's own samples
@@ -186,6 +251,19 @@ def main(argv=None):
             np.save(prefix + '.%s.npy' % key, out[key])
     if a.verbose:
         print('%d iterations, delta %.3g; largest Cp at T = %s' % (iters, delta, np.array2string(out['rwm'], precision=4)))
+    if hq:
+        edges = linear_edges(x, a.histogram_bins)
+        hist, _ = histogram(b, c, count, f, e, v, tb, tc, x, edges, a.device)
+        np.save(prefix + '.rwx.npy', edges)
+        np.save(prefix + '.rwp.npy', hist.reshape(pn, a.temperature_grid, len(hq), a.histogram_bins))
+        if a.histogram_cut is not None:
+            above, at = cut_weight(hist, edges, a.histogram_cut)
+            above = above.reshape(pn, a.temperature_grid)
+            np.save(prefix + '.rwa.npy', above)
+            np.save(prefix + '.rwe.npy', equal_weight(tfine, above))
+            if a.verbose:
+                print('-hx %g on %s: the cut is the edge %.9g; equal weight at T = %s' % (
+                    a.histogram_cut, a.histogram[0], at, np.array2string(equal_weight(tfine, above), precision=4)))
     if not delta <= a.tolerance:
         print('reweight: not converged: delta = %.6g > %g after %d iterations' % (delta, a.tolerance, iters), file=sys.stderr)
         return 1

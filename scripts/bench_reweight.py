@@ -5,6 +5,8 @@ iterations to a tolerance, the expectation call, and the same map as blocked flo
     python scripts/bench_reweight.py                      # K = 32 x 32 states, N = 2^20 samples of Gamma data
     python scripts/bench_reweight.py --numpy 16           # adds the host restatement at N / 16, scaled by K N
     rocprofv3 --kernel-trace --stats -d OUT -- python scripts/bench_reweight.py --profile    # per-launch times, a run of its own
+    python scripts/bench_reweight.py --hist 3 128         # only: nm_reweight_histogram (3 quantities, 128 bins) against nm_reweight_expect
+                                                          # with 3 observables, whole calls alternated in one process; with --profile one call of each
 """
 import argparse
 import json
@@ -71,6 +73,8 @@ def main():
     ap.add_argument('--numpy', type=int, default=0, help='time the host restatement on N / this many samples (0: skip)')
     ap.add_argument('--threads', type=int, default=16)
     ap.add_argument('--profile', action='store_true', help='only 20 iterations and one expectation call, for a kernel trace')
+    ap.add_argument('--hist', type=int, nargs=2, metavar=('NQ', 'NBINS'), default=None,
+                    help='only the histogram leg: NQ quantities (e, v, then noise) in NBINS bins over their range at the --targets grid')
     a = ap.parse_args()
     b, c, count, e, v = gamma_grid(a.side, a.per_state)
     f0 = b * e.reshape(b.size, -1).mean(axis=1) + c * v.reshape(b.size, -1).mean(axis=1)
@@ -78,6 +82,28 @@ def main():
     tc = np.tile(c[:a.side], a.targets)
     res = dict(states=int(b.size), samples=int(e.size))
     reweight.solve(b, c, count, e, v, f0, 0.0, 2)                                            # warm-up: code objects, allocator
+    if a.hist:
+        nq, nbins = a.hist
+        rng = np.random.default_rng(2)
+        x = np.stack([e, v] + [rng.normal(size=e.size) for _ in range(nq - 2)])[:nq]
+        edges = reweight.linear_edges(x, nbins)
+        f, iters, delta = reweight.solve(b, c, count, e, v, f0, a.tol, 20000)
+        both = (lambda: reweight.expect(b, c, count, f, e, v, tb, tc, x), lambda: reweight.histogram(b, c, count, f, e, v, tb, tc, x, edges))
+        for fn in both:                                                                      # warm-up: code objects, allocator
+            fn()
+        if a.profile:
+            return
+        times = ([], [])
+        for _ in range(a.repeats):                                                           # alternated: the box is shared
+            for fn, out in zip(both, times):
+                out.append(timed(fn, 1)[0])
+        hist, outside = both[1]()
+        res.update(targets=int(tb.size), nq=nq, nbins=nbins, iterations=iters, delta=delta, expect_s=float(np.median(times[0])),
+                   histogram_s=float(np.median(times[1])), expect_all_s=times[0], histogram_all_s=times[1],
+                   largest_sum_error=float(np.abs(hist.sum(axis=2) + outside.sum(axis=2) - 1).max()))
+        res['histogram_over_expect'] = res['histogram_s'] / res['expect_s']
+        print(json.dumps(res))
+        return
     if a.profile:
         f, _, _ = reweight.solve(b, c, count, e, v, f0, 0.0, 20)
         reweight.expect(b, c, count, f, e, v, tb, tc)
