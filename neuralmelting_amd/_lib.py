@@ -35,6 +35,8 @@ PARSE_SYMBOLS = ('nm_parse_thrm', 'nm_parse_traj', 'nm_parse_last_error')
 REWEIGHT_SYMBOLS = ('nm_reweight_solve', 'nm_reweight_expect', 'nm_reweight_last_error')
 # include/nm_reweight_hist.h, which nm_reweight.h includes
 REWEIGHT_HIST_SYMBOLS = ('nm_reweight_histogram',)
+# include/nm_reweight_boot.h
+REWEIGHT_BOOT_SYMBOLS = ('nm_reweight_boot_solve', 'nm_reweight_boot_expect')
 
 
 class NMConfig(C.Structure):
@@ -143,6 +145,13 @@ def load():
     L.nm_reweight_histogram.restype = C.c_int
     L.nm_reweight_histogram.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, c_double_p, C.c_int64, c_double_p, c_double_p,
                                         C.c_int, c_double_p, c_double_p, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p]
+    L.nm_reweight_boot_solve.restype = C.c_int
+    L.nm_reweight_boot_solve.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                         C.c_int, C.POINTER(C.c_uint16), C.c_double, C.c_int, c_double_p, c_int_p, c_double_p, c_int_p]
+    L.nm_reweight_boot_expect.restype = C.c_int
+    L.nm_reweight_boot_expect.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_int64_p, c_double_p, C.c_int64, c_double_p, c_double_p,
+                                          C.c_int, C.POINTER(C.c_uint16), c_double_p, C.c_int, c_double_p, c_double_p, C.c_int, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.nm_reweight_last_error.restype = C.c_char_p
     _lib = L
     return L

@@ -8,9 +8,11 @@
 #include "nm_parse.h"
 #include "nm_lattice.h"
 #include "nm_reweight.h"
+#include "nm_reweight_boot.h"
 #include "../../include/nm_distr.h"
 #include "../../include/nm_parse.h"
 #include "../../include/nm_reweight.h"
+#include "../../include/nm_reweight_boot.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2445,6 +2447,227 @@ int nm_reweight_histogram(int device, int nstates, const double *b, const double
                     outside[((size_t)(t0 + t) * nq + q) * 2 + 1] = src[nbins + 1];
                 }
             }
+    }
+    return NM_OK;
+}
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// block-bootstrap replicates of the reweighting (include/nm_reweight_boot.h; kernels: nm_reweight_boot.h)
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+// what both entry points ask of the replicates
+int rb_check(const char *fn, int nrep, const uint16_t *mult, int64_t nsamples)
+{
+    if (nrep < 1 || nrep > RB_MAXREP) return rwrefuse(fn, "nrep must lie in 1..1024");
+    if (!mult) return rwrefuse(fn, "a needed pointer is null");
+    for (int r = 0; r < nrep; ++r) {
+        const uint16_t *m = mult + (size_t)r * nsamples;
+        int64_t sum = 0;
+        for (int64_t i = 0; i < nsamples; ++i) sum += m[i];
+        if (sum != nsamples) return rwrefuse(fn, "a replicate's multiplicities do not sum to nsamples");
+    }
+    return NM_OK;
+}
+
+// the replicates on the device: the multiplicities, the perturbations d [nrep][K], the tile's weights g [RB_RT][N], and the
+// words that freeze a finished replicate
+struct RbWork {
+    int nrep = 0;
+    DevBuf<uint16_t> mult;
+    DevBuf<double> d, g;
+    DevBuf<int> done;
+    DevBuf<RbControl> ctl;
+    std::vector<double> cf; // the centred base solution as the device holds it
+
+    int setup(const char *fn, const RwProblem &p, int nrep_, const uint16_t *hmult, const std::vector<double> &hd)
+    {
+        nrep = nrep_;
+        const RbControl hc = {0, nrep};
+        RW_CHK(fn, mult.alloc((size_t)nrep * p.N));
+        RW_CHK(fn, d.alloc((size_t)nrep * p.K));
+        RW_CHK(fn, g.alloc((size_t)RB_RT * p.N));
+        RW_CHK(fn, done.alloc(nrep));
+        RW_CHK(fn, ctl.alloc(1));
+        RW_CHK(fn, hipMemcpy(mult, hmult, (size_t)nrep * p.N * sizeof(uint16_t), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemcpy(d, hd.data(), (size_t)nrep * p.K * sizeof(double), hipMemcpyHostToDevice));
+        RW_CHK(fn, hipMemset(done, 0, (size_t)nrep * sizeof(int)));
+        RW_CHK(fn, hipMemcpy(ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
+        return NM_OK;
+    }
+
+    template <bool INV>
+    void weights(const RwProblem &p, int r0, int rt)
+    {
+        hipLaunchKernelGGL((nm_rb_weights_kernel<INV>), dim3((unsigned)((p.N + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, ctl, done, p.N, p.e,
+                           p.v, p.logd, p.ka, p.ab, p.ac, p.alc, p.aidx, p.f, p.K, d, r0, rt, mult, g);
+    }
+};
+} // namespace
+
+extern "C" {
+int nm_reweight_boot_solve(int device, int nstates, const double *b, const double *c, const int64_t *count, int64_t nsamples,
+                           const double *e, const double *v, const double *f, int nrep, const uint16_t *mult, double tol, int max_iter,
+                           double *fr, int *iters, double *delta, int *status)
+{
+    static const char *const fn = "nm_reweight_boot_solve";
+    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    if (!fr || !iters || !delta || !status) return rwrefuse(fn, "a needed pointer is null");
+    if (!(tol >= 0.0)) return rwrefuse(fn, "tol must not be negative");
+    if (max_iter < 1) return rwrefuse(fn, "max_iter must be at least 1");
+    if (const int rc = rb_check(fn, nrep, mult, nsamples)) return rc;
+    if (const int rc = rw_device(fn, device)) return rc;
+    RwProblem p;
+    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    RbWork w;
+    if (const int rc = w.setup(fn, p, nrep, mult, std::vector<double>((size_t)nrep * nstates, 0.0))) return rc;
+    DevBuf<double> d_S, d_part, d_delta;
+    DevBuf<int> d_iters, d_status;
+    std::vector<int> hstatus(nrep, 1), hiters(nrep, 0);
+    std::vector<double> hdelta(nrep, 0.0);
+    RW_CHK(fn, d_S.alloc((size_t)nrep * nstates));
+    RW_CHK(fn, d_part.alloc((size_t)RB_RT * nstates * p.nchunks));
+    RW_CHK(fn, d_delta.alloc(nrep));
+    RW_CHK(fn, d_iters.alloc(nrep));
+    RW_CHK(fn, d_status.alloc(nrep));
+    RW_CHK(fn, hipMemcpy(d_status, hstatus.data(), (size_t)nrep * sizeof(int), hipMemcpyHostToDevice));
+    RW_CHK(fn, hipMemset(d_iters, 0, (size_t)nrep * sizeof(int)));
+    RW_CHK(fn, hipMemset(d_delta, 0, (size_t)nrep * sizeof(double)));
+    p.denominators(); // of the base solution, once
+    RbControl hc = {0, nrep};
+    const dim3 sgrid((unsigned)(p.nchunks * ((nstates + RB_SB - 1) / RB_SB))); // chunk-major: nm_rb_sums_kernel
+    for (int it = 0; it < max_iter && hc.ndone < nrep; ++it) {
+        for (int r0 = 0; r0 < nrep; r0 += RB_RT) {
+            const int rt = (nrep - r0) < RB_RT ? (nrep - r0) : RB_RT;
+            const int64_t rows = (int64_t)rt * nstates;
+            w.weights<false>(p, r0, rt);
+            hipLaunchKernelGGL(nm_rb_sums_kernel, sgrid, dim3(RW_BLOCK), 0, 0, w.ctl, w.done, p.N, p.e, p.v, p.logd, nstates, p.b, p.c, p.f, r0, rt,
+                               w.g, d_part);
+            hipLaunchKernelGGL(nm_rb_combine_kernel<1>, dim3((unsigned)((rows + RW_WAVES - 1) / RW_WAVES)), dim3(RW_BLOCK), 0, 0, w.ctl, w.done, r0,
+                               rt, rows, p.nchunks, d_part, d_S + (size_t)r0 * nstates);
+        }
+        hipLaunchKernelGGL(nm_rb_update_kernel, dim3((unsigned)nrep), dim3(RW_BLOCK), 0, 0, w.ctl, w.done, nstates, d_S, w.d, it == 0 ? p.f0 : 0.0,
+                           tol, d_iters, d_delta, d_status);
+        RW_CHK(fn, hipGetLastError());
+        if ((it + 1) % RB_POLL == 0 || it + 1 == max_iter) RW_CHK(fn, hipMemcpy(&hc, w.ctl, sizeof(hc), hipMemcpyDeviceToHost));
+    }
+    RW_CHK(fn, hipDeviceSynchronize());
+    std::vector<double> cf(nstates), hd((size_t)nrep * nstates);
+    RW_CHK(fn, hipMemcpy(cf.data(), p.f, (size_t)nstates * sizeof(double), hipMemcpyDeviceToHost));
+    RW_CHK(fn, hipMemcpy(hd.data(), w.d, hd.size() * sizeof(double), hipMemcpyDeviceToHost));
+    RW_CHK(fn, hipMemcpy(hiters.data(), d_iters, (size_t)nrep * sizeof(int), hipMemcpyDeviceToHost));
+    RW_CHK(fn, hipMemcpy(hdelta.data(), d_delta, (size_t)nrep * sizeof(double), hipMemcpyDeviceToHost));
+    RW_CHK(fn, hipMemcpy(hstatus.data(), d_status, (size_t)nrep * sizeof(int), hipMemcpyDeviceToHost));
+    for (int r = 0; r < nrep; ++r) {
+        for (int k = 0; k < nstates; ++k)
+            fr[(size_t)r * nstates + k] =
+                hstatus[r] == 2 ? NAN : (double)p.s[k].add_to((long double)cf[k] + hd[(size_t)r * nstates + k], p.s0);
+        iters[r] = hiters[r];
+        delta[r] = hdelta[r];
+        status[r] = hstatus[r];
+    }
+    return NM_OK;
+}
+
+int nm_reweight_boot_expect(int device, int nstates, const double *b, const double *c, const int64_t *count, const double *f,
+                            int64_t nsamples, const double *e, const double *v, int nrep, const uint16_t *mult, const double *fr,
+                            int ntargets, const double *tb, const double *tc, int nobs, const double *obs, double *tf, double *ess,
+                            double *mean, double *cov, double *omean)
+{
+    static const char *const fn = "nm_reweight_boot_expect";
+    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    if (ntargets < 1 || ntargets > 65536) return rwrefuse(fn, "ntargets must lie in 1..65536");
+    if (nobs < 0 || nobs > RW_MAXOBS) return rwrefuse(fn, "nobs must lie in 0..8");
+    if (!tb || !tc || !tf || !ess || !mean || !cov || !fr || (nobs > 0 && (!obs || !omean))) return rwrefuse(fn, "a needed pointer is null");
+    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return rwrefuse(fn, "a target's tb or tc is not finite");
+    if (const int rc = rb_check(fn, nrep, mult, nsamples)) return rc;
+    std::vector<char> skip(nrep, 0); // a replicate without a solution: NaN in, NaN out
+    for (int r = 0; r < nrep; ++r)
+        for (int k = 0; k < nstates; ++k) {
+            const double x = fr[(size_t)r * nstates + k];
+            if (std::isinf(x)) return rwrefuse(fn, "an fr is neither finite nor NaN");
+            if (std::isnan(x)) skip[r] = 1;
+        }
+    if (const int rc = rw_device(fn, device)) return rc;
+    RwProblem p;
+    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
+    std::vector<double> cf(nstates), hd((size_t)nrep * nstates, 0.0);
+    RW_CHK(fn, hipMemcpy(cf.data(), p.f, (size_t)nstates * sizeof(double), hipMemcpyDeviceToHost));
+    for (int r = 0; r < nrep; ++r) {
+        if (skip[r]) continue;
+        const double *x = fr + (size_t)r * nstates;
+        for (int k = 0; k < nstates; ++k) hd[(size_t)r * nstates + k] = (double)(p.s[k].take_from(x[k], x[0], p.s0) - (long double)cf[k]);
+    }
+    RbWork w;
+    if (const int rc = w.setup(fn, p, nrep, mult, hd)) return rc;
+    DevBuf<double> d_tb, d_tc, d_obs, d_F, d_part, d_sums;
+    RW_CHK(fn, d_tb.alloc(ntargets));
+    RW_CHK(fn, d_tc.alloc(ntargets));
+    RW_CHK(fn, d_F.alloc(ntargets));
+    RW_CHK(fn, hipMemcpy(d_tb, tb, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
+    RW_CHK(fn, hipMemcpy(d_tc, tc, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
+    if (nobs > 0) {
+        RW_CHK(fn, d_obs.alloc((size_t)nobs * nsamples));
+        RW_CHK(fn, hipMemcpy(d_obs, obs, (size_t)nobs * nsamples * sizeof(double), hipMemcpyHostToDevice));
+    }
+    {   // the base tf of every target with the existing kernels: the scale that keeps q_t(n) <= 1
+        const int nb2 = p.batch(2, RW_TB, (ntargets + RW_TB - 1) / RW_TB * RW_TB);
+        if (const int rc = p.scratch(fn, 2, nb2)) return rc;
+        p.denominators();
+        for (int t0 = 0; t0 < ntargets; t0 += nb2)
+            p.moments<RW_TB, false>(t0, (ntargets - t0) < nb2 ? (ntargets - t0) : nb2, d_tb, d_tc, 0, nullptr, d_F, nullptr);
+        RW_CHK(fn, hipGetLastError());
+    }
+    std::vector<double> hF(ntargets);
+    RW_CHK(fn, hipMemcpy(hF.data(), d_F, (size_t)ntargets * sizeof(double), hipMemcpyDeviceToHost));
+    const int64_t nech = (p.N + RB_ECH - 1) / RB_ECH; // the expectation kernel's own chunks
+    int64_t nbatch = ((int64_t)1 << 24) / ((int64_t)RB_RT * nech * RB_NS); // the partials stay within 128 MiB (one target at least)
+    nbatch = nbatch < 1 ? 1 : nbatch > RW_TGB ? RW_TGB : nbatch;
+    RW_CHK(fn, d_part.alloc((size_t)nbatch * RB_RT * nech * RB_NS));
+    RW_CHK(fn, d_sums.alloc((size_t)nbatch * RB_RT * RB_NS));
+    std::vector<double> hs((size_t)nbatch * RB_RT * RB_NS);
+    for (int r0 = 0; r0 < nrep; r0 += RB_RT) {
+        const int rt = (nrep - r0) < RB_RT ? (nrep - r0) : RB_RT;
+        w.weights<true>(p, r0, rt);
+        for (int t0 = 0; t0 < ntargets; t0 += (int)nbatch) {
+            const int nb = (ntargets - t0) < nbatch ? (ntargets - t0) : (int)nbatch;
+            const int64_t rows = (int64_t)nb * rt;
+            const int tt = nobs > 0 ? RB_ETO : RB_ET;
+            const dim3 egrid((unsigned)(nech * ((nb + tt - 1) / tt) * ((rt + RB_RE - 1) / RB_RE)));
+            if (nobs > 0)
+                hipLaunchKernelGGL((nm_rb_expect_kernel<RB_ETO, RB_NS>), egrid, dim3(RW_BLOCK), 0, 0, p.N, p.e, p.v, p.logd, t0, nb, d_tb, d_tc, d_F, nobs,
+                                   d_obs, r0, rt, w.mult, w.g, d_part);
+            else
+                hipLaunchKernelGGL((nm_rb_expect_kernel<RB_ET, 7>), egrid, dim3(RW_BLOCK), 0, 0, p.N, p.e, p.v, p.logd, t0, nb, d_tb, d_tc, d_F, nobs,
+                                   d_obs, r0, rt, w.mult, w.g, d_part);
+            hipLaunchKernelGGL(nm_rb_combine_kernel<RB_NS>, dim3((unsigned)((rows + RW_WAVES - 1) / RW_WAVES)), dim3(RW_BLOCK), 0, 0, w.ctl, nullptr, r0,
+                               rt, rows, nech, d_part, d_sums);
+            RW_CHK(fn, hipGetLastError());
+            RW_CHK(fn, hipMemcpy(hs.data(), d_sums, (size_t)rows * RB_NS * sizeof(double), hipMemcpyDeviceToHost));
+            for (int t = 0; t < nb; ++t) {
+                const RwOffset st(tb[t0 + t], tc[t0 + t], p.e0, p.v0);
+                for (int j = 0; j < rt; ++j) {
+                    const size_t o = (size_t)(r0 + j) * ntargets + t0 + t;
+                    if (skip[r0 + j]) {
+                        tf[o] = ess[o] = mean[2 * o] = mean[2 * o + 1] = cov[3 * o] = cov[3 * o + 1] = cov[3 * o + 2] = NAN;
+                        for (int q = 0; q < nobs; ++q) omean[o * nobs + q] = NAN;
+                        continue;
+                    }
+                    const double *q = hs.data() + ((size_t)t * rt + j) * RB_NS; // sums of x = m w, x w, x e, x v, x ee, x ev, x vv, x obs
+                    const long double s0 = q[0];
+                    const long double me = q[2] / s0, mv = q[3] / s0;
+                    tf[o] = (double)(st.add_to((long double)hF[t0 + t] - logl(s0), p.s0) + fr[(size_t)(r0 + j) * nstates]);
+                    const long double n_eff = s0 * s0 / q[1];
+                    ess[o] = (double)(n_eff < 1.0L ? 1.0L : (n_eff > (long double)nsamples ? (long double)nsamples : n_eff));
+                    mean[2 * o] = (double)((long double)p.e0 + me);
+                    mean[2 * o + 1] = (double)((long double)p.v0 + mv);
+                    cov[3 * o] = (double)(q[4] / s0 - me * me);
+                    cov[3 * o + 1] = (double)(q[5] / s0 - me * mv);
+                    cov[3 * o + 2] = (double)(q[6] / s0 - mv * mv);
+                    for (int k = 0; k < nobs; ++k) omean[o * nobs + k] = (double)(q[7 + k] / s0);
+                }
+            }
+        }
     }
     return NM_OK;
 }

@@ -6,7 +6,8 @@
 # neighbour shell as a fraction of the smallest box edge (first fcc shell: about 0.85 / supercell); -sf adds the static structure
 # factor on the box's reciprocal lattice (.q.npy / .sf.npy / .sfm.npy, and .nrho.npy), -sq its largest index (1..32, default 16).
 # REWEIGHT=1 in the environment adds a fifth stage: the multistate reweighting of the grid (.rw*.npy: free energies, H(T), V(T), Cp(T)
-# and the temperature of its peak at every pressure); REWEIGHT_ARGS goes to it (e.g. "-sk 128 -ob sof sol" behind a distr stage with -so).
+# and the temperature of its peak at every pressure); REWEIGHT_ARGS goes to it (e.g. "-sk 128 -ob sof sol" behind a distr stage with -so;
+# add "-bs 200" for block-bootstrap error bars on every curve and on the transition temperatures: .rw?s.npy, .rwms.npy, .rwes.npy).
 # For several GPUs start the first two stages under  python -m torch.distributed.run --nproc-per-node N -m neuralmelting_amd.remcmc ...
 set -euo pipefail
 s=${1:-5}; pn=${2:-32}; tn=${3:-32}; sn=${4:-1024}
