@@ -183,6 +183,43 @@ int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float
 int nm_distr_cna(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int mode,
                  int32_t *type, int32_t *sig, int32_t *ntype, int32_t *nsig);
 
+/* Pair entropy per atom: Piaggi and Parrinello's local-entropy fingerprint (J. Chem. Phys. 147, 114112 (2017); Phys. Rev. Lett. 119,
+ * 015701 (2017)), the projection of the two-body excess entropy -2 pi rho int (g ln g - g + 1) r^2 dr on each atom, in units of k_B, and
+ * its average over the neighbours.  The papers define the quantity; the discretisation is the build's own.  For sample s and centre c:
+ *   entries     exactly those of nm_distr_bondorder with r_lo = 0 and r_hi = r_m: (j, a) over the 27 image shifts br[j] and all atoms a,
+ *               the float32 displacement and its float32 length d, 0 < (double)d <= r_m; an atom that qualifies in two images is two
+ *               entries.  nnb[s][c] is their number;
+ *   density     rho = natoms / L^3 with L = (double)box[s];
+ *   grid        D = r_m / nbins and r_k = k * D for k = 0..nbins, each the float64 result of that one operation;
+ *   smeared radial density   h_k = (1 / (4 pi rho sigma sqrt(2 pi))) * sum over the entries of exp(-(r_k - d)^2 / (2 sigma^2)), which
+ *               is r_k^2 g_m(r_k) of the papers.  A term whose computed exponent is below -50 is left out;
+ *   integrand   I_0 = 0; for k >= 1, I_k = r_k^2 where h_k == 0, otherwise I_k = h_k ln(h_k / r_k^2) - h_k + r_k^2;
+ *   s[s][c]     = -2 pi rho D (I_0 / 2 + I_1 + ... + I_(nbins-1) + I_nbins / 2), the trapezoid rule.  An atom without entries has
+ *               exactly -2 pi rho D (r_1^2 + ... + r_(nbins-1)^2 + r_nbins^2 / 2) up to the rounding of that sum;
+ *   sbar[s][c]  = (s(c) + sum over the entries (j, a) of c with (double)d <= r_avg of s(a)) / (1 + their number): the plain-cutoff
+ *               neighbour average, the shape of qbar_lm of nm_distr_bondorder.  r_avg is independent of r_m;
+ *   smean[s], sbarmean[s]   the means of s and sbar over the atoms of the sample;
+ *   nlow[s]     the number of atoms with sbar < s_cut (s_cut may be infinite; -infinity counts none).
+ * Error bound, u = 2^-53, E = 50 the largest |exponent| kept, M the largest nnb of the call, M_a the largest number of entries within
+ * r_avg (derivation: csrc/nm_distr.h).  With A(c) = 2 pi rho D sum' (h_k |ln(h_k / r_k^2)| + h_k + r_k^2) >= |s(c)|, sum' the
+ * trapezoid sum over k >= 1:
+ *   |s - exact| <= e_s = (7 E + M + nbins + 30) u A + omitted,
+ *   omitted = 2 pi rho D sum' om (1 + |ln(om / r_k^2)| + |ln(h_k / r_k^2)|), om = M exp(-E) (1 + 1e-12) / (4 pi rho sigma sqrt(2 pi)),
+ *   the last logarithm only where h_k > 0 (the allowance for the terms left out: about 1e-19 A);
+ *   |sbar - exact| <= max e_s + (M_a + 2) u max |s|,   |smean - exact| <= max e_s + (natoms + 1) u max |s|,
+ *   |sbarmean - exact| <= max e_s + (M_a + natoms + 3) u max |s|, the maxima over the atoms of the sample.
+ * For M <= 2200 and nbins <= 1024 that is below 4e-13 A.  nlow is exact unless an sbar lies within its bound of s_cut.
+ * The result is the same bit for bit on every call: float64 sums in a fixed order, no atomics.
+ * pos[ns][natoms][3], box[ns] float32; s, sbar [ns][natoms] and smean, sbarmean [ns] float64; nnb [ns][natoms] and nlow [ns] int32.
+ * Any output may be NULL (it is then not written), but not all six.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_entropy:".  NM_ERR_ARG, checked
+ * before the device is looked for and with the outputs left untouched, for: ns < 0, natoms outside 1..4095, nbins outside 1..1024,
+ * sigma or r_m not positive and finite, r_m or r_avg above min(box)/2 over the batch, r_avg <= 0, s_cut NaN, a box that is not finite
+ * and positive, a null pos or box, all outputs null, a bad device ordinal.  ns == 0 as in nm_distr_bondorder. */
+int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const float *box, double r_m, double sigma, int nbins,
+                     double r_avg, double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean,
+                     int32_t *nlow);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ SYMBOLS = ('nm_create', 'nm_destroy', 'nm_last_error', 'nm_create_note', 'nm_nsl
 
 # include/nm_distr.h
 DISTR_SYMBOLS = ('nm_distr_histograms', 'nm_distr_angles', 'nm_distr_sfactor', 'nm_distr_bondorder', 'nm_distr_solid', 'nm_distr_cna',
-                 'nm_distr_last_error')
+                 'nm_distr_entropy', 'nm_distr_last_error')
 # include/nm_parse.h
 PARSE_SYMBOLS = ('nm_parse_thrm', 'nm_parse_traj', 'nm_parse_last_error')
 # include/nm_reweight.h
@@ -127,6 +127,9 @@ def load():
     L.nm_distr_cna.restype = C.c_int
     L.nm_distr_cna.argtypes = [C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_double, C.c_double, C.c_int, c_int32_p, c_int32_p,
                                c_int32_p, c_int32_p]
+    L.nm_distr_entropy.restype = C.c_int
+    L.nm_distr_entropy.argtypes = [C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                   c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p, c_int32_p]
     L.nm_distr_last_error.restype = C.c_char_p
     c_long_p = C.POINTER(C.c_long)
     L.nm_parse_thrm.restype = C.c_int

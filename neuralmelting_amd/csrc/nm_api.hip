@@ -2008,6 +2008,76 @@ int nm_distr_cna(int device, int ns, int natoms, const float *pos, const float *
         return NM_OK;
     });
 }
+
+int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const float *box, double r_m, double sigma, int nbins, double r_avg,
+                     double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean, int32_t *nlow)
+{
+    static const char *const fn = "nm_distr_entropy";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!s && !sbar && !nnb && !smean && !sbarmean && !nlow) return refuse(fn, "all six outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (nbins < 1 || nbins > ENT_MAXBINS) return refuse(fn, "nbins must lie in 1..1024");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return refuse(fn, "sigma must be positive and finite");
+    if (!(r_m > 0.0) || !std::isfinite(r_m)) return refuse(fn, "r_m must be positive and finite");
+    if (!(r_avg > 0.0)) return refuse(fn, "r_avg must be positive");
+    if (s_cut != s_cut) return refuse(fn, "s_cut is not a number");
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    for (int i = 0; i < ns; ++i)
+        if (!(r_m <= 0.5 * (double)box[i]) || !(r_avg <= 0.5 * (double)box[i])) return refuse(fn, "r_m or r_avg exceeds half the smallest box");
+    if (const int rc = distr_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const bool average = sbar || sbarmean || nlow, means = smean || sbarmean || nlow;
+    const float cube_m = shell_cube(r_m), cube_a = shell_cube(r_avg);
+    const double D = r_m / (double)nbins, inv2s2 = 1.0 / (2.0 * (sigma * sigma));
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    const size_t lds1 = ent_lds_bytes(natoms, false), lds2 = ent_lds_bytes(natoms, true); // at most 49,284 B and 51,332 B (4095 atoms)
+    DevBuf<double> d_s, d_b, d_ps, d_pb, d_sm, d_bm;
+    DevBuf<int> d_nnb, d_pl, d_low;
+    DISTR_CHK(fn, d_s.alloc((size_t)cs * natoms)); // pass 2 reads it, whether or not the caller asks for s
+    DISTR_CHK(fn, d_ps.alloc((size_t)cs * groups));
+    if (nnb) DISTR_CHK(fn, d_nnb.alloc((size_t)cs * natoms));
+    if (sbar) DISTR_CHK(fn, d_b.alloc((size_t)cs * natoms));
+    if (average) {
+        DISTR_CHK(fn, d_pb.alloc((size_t)cs * groups));
+        DISTR_CHK(fn, d_pl.alloc((size_t)cs * groups));
+    }
+    if (smean) DISTR_CHK(fn, d_sm.alloc((size_t)cs));
+    if (sbarmean) DISTR_CHK(fn, d_bm.alloc((size_t)cs));
+    if (nlow) DISTR_CHK(fn, d_low.alloc((size_t)cs));
+    const int points = nbins + 1; // a lane owns ceil(points / 64) grid points: the next instantiation that holds them
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        auto local = [&](auto na) {
+            hipLaunchKernelGGL(nm_ent_local_kernel<decltype(na)::value>, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_m,
+                               cube_m, sigma, inv2s2, nbins, D, d_s, d_nnb, d_ps);
+        };
+        if (points <= 64) local(std::integral_constant<int, 1>());
+        else if (points <= 128) local(std::integral_constant<int, 2>());
+        else if (points <= 256) local(std::integral_constant<int, 4>());
+        else if (points <= 512) local(std::integral_constant<int, 8>());
+        else local(std::integral_constant<int, ENT_MAXACC>());
+        DISTR_CHK(fn, hipGetLastError());
+        if (average) {
+            hipLaunchKernelGGL(nm_ent_average_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_avg, cube_a, s_cut,
+                               d_s, d_b, d_pb, d_pl);
+            DISTR_CHK(fn, hipGetLastError());
+        }
+        if (means) {
+            hipLaunchKernelGGL(nm_ent_mean_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, n, natoms, groups, d_ps, d_pb, d_pl, d_sm, d_bm, d_low);
+            DISTR_CHK(fn, hipGetLastError());
+        }
+        DISTR_CHK(fn, hipDeviceSynchronize());
+        const size_t pa = (size_t)natoms;
+        if (s) DISTR_CHK(fn, hipMemcpy(s + (size_t)s0 * pa, d_s, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
+        if (sbar) DISTR_CHK(fn, hipMemcpy(sbar + (size_t)s0 * pa, d_b, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
+        if (nnb) DISTR_CHK(fn, hipMemcpy(nnb + (size_t)s0 * pa, d_nnb, (size_t)n * pa * sizeof(int), hipMemcpyDeviceToHost));
+        if (smean) DISTR_CHK(fn, hipMemcpy(smean + s0, d_sm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        if (sbarmean) DISTR_CHK(fn, hipMemcpy(sbarmean + s0, d_bm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        if (nlow) DISTR_CHK(fn, hipMemcpy(nlow + s0, d_low, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
+}
 #undef DISTR_CHK
 
 } // extern "C"

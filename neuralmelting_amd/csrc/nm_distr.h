@@ -1309,4 +1309,195 @@ nm_cna_kernel(int natoms, const float *__restrict__ pos, const float *__restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Pair entropy per atom (include/nm_distr.h, nm_distr_entropy): Piaggi and Parrinello's projection of the two-body excess entropy
+// on each atom, s(c) = -2 pi rho integral over (0, r_m] of (g_m ln g_m - g_m + 1) r^2 dr with g_m the Gaussian-smeared radial
+// density around c, on the grid r_k = k D, D = r_m / nbins, by the trapezoid rule; then its neighbour average sbar.
+//
+// Pass 1 (nm_ent_local_kernel<NA>): the grid and staging of the other shell kernels (SHELL_CPB centres per workgroup, shell_stage /
+// shell_bounds, then a wave per centre in turn) and one shell_scan per centre with r_lo = 0, r_hi = r_m.  lane = grid point: a lane
+// owns the points k = lane + 64 j, j < NA = ceil((nbins + 1) / 64), each with a float64 accumulator in a register (NA is a template
+// argument, 1 2 4 8 or 17, so that no accumulator is indexed at run time; a point beyond nbins sits at r = infinity and never gets
+// a term).  The sink sees 64 candidates at a time; it walks the set bits of the step's ballot in ascending order, that is the
+// entries in scan order, takes each entry's float32 d out of its lane with v_readlane (no neighbour list is stored anywhere, so
+// there is no cap on the entries), and every lane adds exp(-(r_k - d)^2 / (2 sigma^2)) to its accumulators.  A term is left out
+// iff its computed exponent is below -ENT_EMAX; a block of 64 grid points that lies more than ENT_REACH sigma from d as a whole is
+// skipped by a wave-uniform branch (every term of it would be left out anyway: ENT_REACH^2 / 2 exceeds ENT_EMAX by 1e-6 of it,
+// the exponent's rounding is 1e-14 of it).  After the scan h_k = pref * acc, the integrand per lane, the lanes' sums over j
+// ascending, then an xor butterfly over the wave (floating-point addition commutes, so all lanes hold the same bits).
+// Pass 2 (nm_ent_average_kernel): the same staging, bo_scan<false> with r_hi = r_avg (indices only); for a batch, lane = entry reads
+// s(a) of its entry from the global array that pass 1 wrote for the whole chunk, a butterfly adds the batch, the batches are added in
+// order.  sbar(c) = (s(c) + sum) / (1 + entries).
+// Both passes leave their workgroup's sum of s / sbar over its centres (a wave's centres in order, then the waves in order), and
+// pass 2 its count of sbar < s_cut, in [sample][group]; nm_ent_mean_kernel adds a sample's groups in order.  No atomic of any
+// kind: the result is the same bits on every call.
+//
+// Error bound (u = 2^-53; E = ENT_EMAX = 50; M the largest number of entries of a centre; the grid r_k = k D is the float64 product
+// and belongs to the definition, so it carries no error).  For one centre let
+//   A = 2 pi rho D sum' (h_k |ln(h_k / r_k^2)| + h_k + r_k^2)        (sum' the trapezoid sum over k >= 1; A >= |s|).
+//   term      t = r_k - d is one rounding (d is a float32, exact in float64); the exponent -(t t) * (1 / (2 sigma^2)) carries the
+//             rounding of t twice, of the square, of the constant (3 roundings) and of the product: at most 7 u relative, so at most
+//             7 E u absolute, which is the relative error of the exponential; the exponential itself at most 2 ulp = 4 u:
+//             (7 E + 4) u per term, all terms positive;
+//   h_k       the fixed-order sum of at most M positive terms adds (M - 1) u; the prefactor 1 / (4 pi rho sigma sqrt(2 pi)) with
+//             rho = natoms / L^3 at most 10 u; the product 1 u: eta = (7 E + M + 14) u relative;
+//   integrand d/dh (h ln(h / r^2) - h + r^2) = ln(h / r^2), so eta moves I_k by eta h_k (|ln(h_k / r_k^2)| + eta); its own evaluation
+//             (quotient, logarithm at 2 ulp, two products, two sums) at most 8 u (h_k |ln| + h_k + r_k^2);
+//   sums      any order of adding the nbins + 1 weighted terms at most (nbins + 1) u sum' |I_k|; -2 pi rho D and its product 6 u;
+//   together  e_s = (7 E + M + nbins + 30) u A + omitted = (M + nbins + 380) u A + omitted;
+//   omitted   every term left out is below exp(-E) (1 + 1e-12), so h_k is short by at most om = M exp(-E) pref (1 + 1e-12), and with
+//             phi(h) = h ln(h / r^2) - h convex, |phi(h + om) - phi(h)| <= om (1 + |ln(om / r_k^2)| + |ln(h_k / r_k^2)|) (the last
+//             term only where h_k > 0): omitted = 2 pi rho D sum' of that, about 1e-19 A for M = 2200.
+//   sbar      the mean of 1 + n <= 1 + M_a values (M_a the largest number of entries within r_avg), each within e_s: the largest e_s of
+//             the sample plus (M_a + 2) u max |s| for the butterflies, the batches and the division;
+//   means     the largest e_s (e_sbar) of the sample plus (natoms + 1) u max |s|.
+// tests/entropy_ref.py holds the same expressions; the tests allow exactly that.
+constexpr int ENT_MAXBINS = 1024;
+constexpr int ENT_MAXACC = (ENT_MAXBINS + 1 + 63) / 64; // 17
+constexpr double ENT_EMAX = 50.0;
+constexpr double ENT_REACH = 10.00001;                 // sqrt(2 ENT_EMAX) and a margin
+
+__host__ __device__ inline size_t ent_lds_bytes(int natoms, bool average) // 51,332 B at 4095 atoms for the average pass
+{
+    return (size_t)SHELL_WAVES * (sizeof(double) + sizeof(int)) + (average ? (size_t)SHELL_WAVES * BO_LIST * sizeof(int) : 0)
+         + ((size_t)3 * natoms + SHELL_WAVES * 6) * sizeof(float);
+}
+
+template <int NA>
+__global__ void __launch_bounds__(SHELL_BLOCK)
+nm_ent_local_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_m, float cube, double sigma,
+                    double inv2s2, int nbins, double D, double *__restrict__ sl, int *__restrict__ nnb, double *__restrict__ psum)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, grp = blockIdx.x % groups, c0 = grp * SHELL_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double *wsum = (double *)smem;
+    float *px = (float *)((int *)(wsum + SHELL_WAVES) + SHELL_WAVES), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    __syncthreads();
+    shell_bounds(part, bb);
+    const double PI = 3.14159265358979323846, Ld = (double)L, rho = (double)natoms / (Ld * Ld * Ld);
+    const double pref = 1.0 / (4.0 * PI * rho * sigma * 2.50662827463100050242); // sqrt(2 pi)
+    const double reach = ENT_REACH * sigma;
+    double rk[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) rk[j] = lane + 64 * j <= nbins ? (double)(lane + 64 * j) * D : INFINITY;
+    double wtot = 0.0;
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
+        double acc[NA];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) acc[j] = 0.0;
+        int nb = 0;
+        shell_scan(px, py, pz, natoms, cx, cy, cz, L, cube, bb, 0.0, r_m, lane,
+                   [&](int, bool, float vx, float vy, float vz, unsigned long long m) {
+            nb += __popcll(m);
+            const int df = __float_as_int(cna_len(vx, vy, vz)); // the scan's own d
+            for (; m; m &= m - 1ull) {
+                const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+                const double d = (double)__int_as_float(__builtin_amdgcn_readlane(df, src));
+#pragma unroll
+                for (int j = 0; j < NA; ++j) {
+                    if (NA > 1 && (d < (double)(64 * j) * D - reach || d > (double)(64 * j + 63) * D + reach)) continue; // wave-uniform
+                    const double t = rk[j] - d, e = -(t * t) * inv2s2;
+                    if (e >= -ENT_EMAX) acc[j] += exp(e);
+                }
+            }
+            return true;
+        });
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int k = lane + 64 * j;
+            if (k >= 1 && k <= nbins) {
+                const double r2 = rk[j] * rk[j], h = pref * acc[j];
+                const double I = h > 0.0 ? h * log(h / r2) - h + r2 : r2;
+                sum += k == nbins ? 0.5 * I : I;
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        const double sv = -(2.0 * PI * rho * D) * sum;
+        const size_t at = (size_t)s * natoms + c;
+        if (lane == 0) {
+            sl[at] = sv;
+            if (nnb) nnb[at] = nb;
+        }
+        wtot += sv;
+    }
+    if (lane == 0) wsum[wave] = wtot;
+    __syncthreads();
+    if (tid == 0) {
+        double t = wsum[0];
+        for (int w = 1; w < SHELL_WAVES; ++w) t += wsum[w];
+        psum[(size_t)s * groups + grp] = t;
+    }
+}
+
+__global__ void __launch_bounds__(SHELL_BLOCK)
+nm_ent_average_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_avg, float cube, double s_cut,
+                      const double *__restrict__ sl, double *__restrict__ sbar, double *__restrict__ psum, int *__restrict__ plow)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int s = blockIdx.x / groups, grp = blockIdx.x % groups, c0 = grp * SHELL_CPB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double *wsum = (double *)smem;
+    int *wlow = (int *)(wsum + SHELL_WAVES), *li_all = wlow + SHELL_WAVES;
+    float *px = (float *)(li_all + SHELL_WAVES * BO_LIST), *py = px + natoms, *pz = py + natoms, *part = pz + natoms;
+    const float L = box[s];
+    float bb[6];
+    shell_stage(pos + (size_t)s * natoms * 3, natoms, px, py, pz, part);
+    __syncthreads();
+    shell_bounds(part, bb);
+    int *li = li_all + wave * BO_LIST;
+    const double *ss = sl + (size_t)s * natoms;
+    double wtot = 0.0;
+    int low = 0;
+    const int cend = c0 + SHELL_CPB < natoms ? c0 + SHELL_CPB : natoms;
+    for (int c = c0 + wave; c < cend; c += SHELL_WAVES) {
+        const float cx = wave_uniform(px[c]), cy = wave_uniform(py[c]), cz = wave_uniform(pz[c]);
+        double a = 0.0;
+        const int nb = bo_scan<false>(px, py, pz, natoms, cx, cy, cz, L, cube, bb, 0.0, r_avg, nullptr, nullptr, nullptr, li, lane, [&](int mb) {
+            double v = lane < mb ? ss[li[lane]] : 0.0; // lane = entry
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            a += v;
+        });
+        const double b = (ss[c] + a) / (double)(nb + 1);
+        if (sbar && lane == 0) sbar[(size_t)s * natoms + c] = b;
+        wtot += b;
+        low += b < s_cut ? 1 : 0;
+    }
+    if (lane == 0) { wsum[wave] = wtot; wlow[wave] = low; }
+    __syncthreads();
+    if (tid == 0) {
+        double t = wsum[0];
+        int n = wlow[0];
+        for (int w = 1; w < SHELL_WAVES; ++w) { t += wsum[w]; n += wlow[w]; }
+        psum[(size_t)s * groups + grp] = t;
+        plow[(size_t)s * groups + grp] = n;
+    }
+}
+
+// one thread per sample: the groups' sums in order, the means over the atoms and the count below the cut
+__global__ void __launch_bounds__(64)
+nm_ent_mean_kernel(int ns, int natoms, int groups, const double *__restrict__ ps, const double *__restrict__ pb, const int *__restrict__ pl,
+                   double *__restrict__ smean, double *__restrict__ sbarmean, int *__restrict__ nlow)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= ns) return;
+    double ts = 0.0, tb = 0.0;
+    int n = 0;
+    for (int g = 0; g < groups; ++g) {
+        ts += ps[(size_t)s * groups + g];
+        if (pb) { tb += pb[(size_t)s * groups + g]; n += pl[(size_t)s * groups + g]; }
+    }
+    if (smean) smean[s] = ts / (double)natoms;
+    if (sbarmean) sbarmean[s] = tb / (double)natoms;
+    if (nlow) nlow[s] = n;
+}
+
 } // namespace nm

@@ -13,6 +13,10 @@ definition: include/nm_distr.h, nm_distr_bondorder).  With -so it also writes th
 sample: the solid fraction, the largest cluster's share, the number of clusters and the mean number of connections (.so*.npy;
 definition: include/nm_distr.h, nm_distr_solid).  With -cn it also writes the common neighbour analysis of each sample: the shares
 of fcc, hcp, bcc and icosahedral atoms and of the eight signature columns (.cn*.npy; definition: include/nm_distr.h, nm_distr_cna).
+With -le it also writes the pair entropy per atom (Piaggi and Parrinello's local-entropy fingerprint) and its neighbour average as
+means over each sample (.le*.npy; definition: include/nm_distr.h, nm_distr_entropy).  With -ef it also writes the entropy functional
+(g ln g - g + 1) r^2 of the rdf that lammps_distr.py names .ef.npy but leaves switched off, and its integral, the two-body excess
+entropy of each sample (.s2.npy).
 
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
@@ -20,6 +24,7 @@ of fcc, hcp, bcc and icosahedral atoms and of the eight signature columns (.cn*.
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -bo -bl 4 6
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -so -sl 6 -st 0.5 -sx 8
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -cn -cm adaptive
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -le -lt -5.0 -ef
 """
 import argparse
 import ctypes as C
@@ -107,6 +112,31 @@ def _parser():
     p.add_argument('-ca', '--cna_atoms', action='store_true',
                    help='with -cn also write the per-atom type: <PREFIX>.cnta.npy (0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico), one byte per '
                         'atom and sample')
+    unmeasured = 'a convenience whose suitability for the LJ and Sutton-Chen grids of this package has not yet been measured'
+    p.add_argument('-le', '--local_entropy', action='store_true',
+                   help='also write the pair entropy per atom (Piaggi and Parrinello) as float64 means over each sample: <PREFIX>.les.npy '
+                        '(mean s), .leb.npy (mean of the neighbour-averaged s) and .len.npy (mean number of entries within the radius '
+                        'of -lr), in units of k_B')
+    p.add_argument('-lr', '--entropy_radius', type=float, default=0.0,
+                   help='the upper limit r_m of the integral of -le as a fraction of the smallest box edge, in (0, 0.5]; the default 0 '
+                        'means min(0.5, 1.4 / SZ) for natoms = 4 SZ^3, ' + unmeasured)
+    p.add_argument('-lw', '--entropy_width', type=float, default=0.0,
+                   help='the width sigma of the Gaussians of -le as a fraction of the smallest box edge, positive; the default 0 means '
+                        '0.05 / SZ, ' + unmeasured)
+    p.add_argument('-lg', '--entropy_grid', type=int, default=0,
+                   help='the number of intervals of the radial grid of -le, 1..1024; the default 0 means min(1024, ceil(2 r_m / sigma)), '
+                        + unmeasured)
+    p.add_argument('-lv', '--entropy_average', type=float, default=0.0,
+                   help='the radius of the neighbour average of -le as a fraction of the smallest box edge, in (0, 0.5]; the default 0 '
+                        'means the first fcc shell of -bc, ' + unmeasured)
+    p.add_argument('-lt', '--entropy_threshold', type=float, default=None,
+                   help='with -le also write <PREFIX>.lef.npy: the atoms whose neighbour-averaged s lies below this value / natoms; no '
+                        'default')
+    p.add_argument('-la', '--entropy_atoms', action='store_true',
+                   help='with -le also write the per-atom values: <PREFIX>.lesa.npy and .leba.npy, 16 bytes per atom and sample')
+    p.add_argument('-ef', '--entropy_functional', action='store_true',
+                   help='also write <PREFIX>.ef.npy, (g ln g - g + 1) r^2 for every bin of the rdf (r^2 where g = 0), and .s2.npy, the '
+                        'two-body excess entropy -2 pi nrho sum over the bins of that times dr, in units of k_B')
     return p
 
 
@@ -125,6 +155,26 @@ def cna_radius(value, natoms, mode):
         raise ValueError('-cr/--cna_radius must lie in (0, 0.5]; got %g%s' % (cut, '' if float(value) else
                          ' as the first fcc shell of %d atoms: pass -cr' % int(natoms)))
     return cut
+
+
+def entropy_params(a, natoms):
+    """(r_m, sigma, nbins, r_avg) of -le from the parsed flags, the radii as fractions of the smallest box edge: the values given, or
+    for 0 the automatic ones, r_m = min(0.5, 1.4 / SZ), sigma = 0.05 / SZ, nbins = min(1024, ceil(2 r_m / sigma)) and r_avg =
+    bond_cutoff's first fcc shell; ValueError outside their ranges"""
+    sz = _cells(natoms)
+    rm = float(a.entropy_radius) or min(0.5, 1.4 / sz)
+    sigma = float(a.entropy_width) or 0.05 / sz
+    nbins = int(a.entropy_grid) or min(1024, int(np.ceil(2.0 * rm / sigma)))
+    ravg = float(a.entropy_average) or bond_cutoff(a.bond_cutoff, natoms)
+    if not 0.0 < rm <= 0.5:
+        raise ValueError('-lr/--entropy_radius must lie in (0, 0.5]; got %g' % rm)
+    if not (sigma > 0.0 and np.isfinite(sigma)):
+        raise ValueError('-lw/--entropy_width must be positive; got %g' % sigma)
+    if not 1 <= nbins <= 1024:
+        raise ValueError('-lg/--entropy_grid must lie in 1..1024; got %d' % nbins)
+    if not 0.0 < ravg <= 0.5:
+        raise ValueError('-lv/--entropy_average must lie in (0, 0.5]; got %g' % ravg)
+    return rm, sigma, nbins, ravg
 
 
 def bond_cutoff(value, natoms):
@@ -160,6 +210,18 @@ def parse_args(argv=None):
         p.error('-sx/--solid_connections must be at least 1')
     if not 0.0 <= a.cna_radius <= 0.5:
         p.error('-cr/--cna_radius must lie in (0, 0.5], or be 0 for the automatic value')
+    if not 0.0 <= a.entropy_radius <= 0.5:
+        p.error('-lr/--entropy_radius must lie in (0, 0.5], or be 0 for the automatic value')
+    if not (0.0 <= a.entropy_width and np.isfinite(a.entropy_width)):
+        p.error('-lw/--entropy_width must be positive, or 0 for the automatic value')
+    if not 0 <= a.entropy_grid <= 1024:
+        p.error('-lg/--entropy_grid must lie in 1..1024, or be 0 for the automatic value')
+    if not 0.0 <= a.entropy_average <= 0.5:
+        p.error('-lv/--entropy_average must lie in (0, 0.5], or be 0 for the first fcc shell')
+    if a.entropy_threshold is not None and np.isnan(a.entropy_threshold):
+        p.error('-lt/--entropy_threshold must be a number')
+    if (a.entropy_threshold is not None or a.entropy_atoms) and not a.local_entropy:
+        p.error('-lt/--entropy_threshold and -la/--entropy_atoms need -le/--local_entropy')
     return a
 
 
@@ -330,6 +392,42 @@ def cna(natoms, box, pos, r_lo, r_hi, mode, device=0):
     return typ, sig, ntype, nsig
 
 
+def local_entropy(natoms, box, pos, r_m, sigma, nbins, r_avg, s_cut=None, device=0):
+    """pair entropy per atom of all samples (include/nm_distr.h, nm_distr_entropy) on the grid r_k = k r_m / nbins with Gaussians of
+    width sigma, averaged over the entries within r_avg: s and sbar float64 [ns][natoms], nnb int32 [ns][natoms] (entries within r_m),
+    smean and sbarmean float64 [ns] and nlow int32 [ns], the atoms with sbar < s_cut (none for s_cut None).  natoms is accepted for
+    symmetry with histograms(); the atom count is pos.shape[1]."""
+    L = B.load()
+    pos, box, ppos, pbox = _frames(pos, box)
+    ns, n = pos.shape[0], pos.shape[1]
+    s = np.zeros((ns, n), dtype=np.float64)
+    sbar = np.zeros((ns, n), dtype=np.float64)
+    nnb = np.zeros((ns, n), dtype=np.int32)
+    smean = np.zeros(ns, dtype=np.float64)
+    sbarmean = np.zeros(ns, dtype=np.float64)
+    nlow = np.zeros(ns, dtype=np.int32)
+    dp = lambda x: x.ctypes.data_as(B.c_double_p)
+    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
+    _check(L, 'nm_distr_entropy', L.nm_distr_entropy(device, ns, n, ppos, pbox, float(r_m), float(sigma), int(nbins), float(r_avg),
+                                                     -np.inf if s_cut is None else float(s_cut), dp(s), dp(sbar), ip(nnb), dp(smean),
+                                                     dp(sbarmean), ip(nlow)))
+    return s, sbar, nnb, smean, sbarmean, nlow
+
+
+def entropy_functional(g, r, nrho):
+    """the entropy functional of the rdf g [ns][sbins] on the radii r [sbins] and its integral, in float64: ef = (g ln g - g + 1) r^2
+    per bin with g ln g = 0 where g = 0, float64 [ns][sbins], and s2 = -2 pi nrho sum over the bins of ef * dr, float64 [ns], with
+    dr = r[1] - r[0] (the radii are evenly spaced)"""
+    g = np.asarray(g, dtype=np.float64)
+    r = np.asarray(r, dtype=np.float64)
+    glg = np.zeros(g.shape, dtype=np.float64)
+    filled = g > 0.0
+    glg[filled] = g[filled] * np.log(g[filled])
+    ef = (glg - g + 1.0) * (r * r)[None, :]
+    s2 = -2.0 * np.pi * np.asarray(nrho, dtype=np.float64).reshape(-1) * (ef.sum(axis=1) * (r[1] - r[0]))
+    return ef, s2
+
+
 def main(argv=None):
     a = parse_args(argv)
     dev = _device()
@@ -349,6 +447,11 @@ def main(argv=None):
     if a.common_neighbours:
         try:
             ccut = cna_radius(a.cna_radius, natoms[0], a.cna_mode)
+        except ValueError as e:
+            raise SystemExit('distr: error: %s' % e)
+    if a.local_entropy:
+        try:
+            lrm, lsig, lbins, lavg = entropy_params(a, natoms[0])
         except ValueError as e:
             raise SystemExit('distr: error: %s' % e)
     nrho, dni, r, dn, rv = calculate_spatial(natoms, box, a.spherical_bins, a.cartesian_bins)
@@ -413,6 +516,23 @@ def main(argv=None):
         np.save(prefix + '.cns.npy', share.astype(np.float32).reshape(pn, tn, rns, 8))
         if a.cna_atoms:
             np.save(prefix + '.cnta.npy', typ.astype(np.int8).reshape(pn, tn, rns, n))
+    if a.local_entropy:
+        l = float(np.min(box))
+        n = int(natoms[0])
+        s, sbar, nnb, smean, sbarmean, nlow = local_entropy(natoms, box, pos, lrm * l, lsig * l, lbins, lavg * l, a.entropy_threshold,
+                                                            device=dev)
+        np.save(prefix + '.les.npy', smean.reshape(pn, tn, rns))
+        np.save(prefix + '.leb.npy', sbarmean.reshape(pn, tn, rns))
+        np.save(prefix + '.len.npy', nnb.mean(axis=1, dtype=np.float64).reshape(pn, tn, rns))
+        if a.entropy_threshold is not None:
+            np.save(prefix + '.lef.npy', (nlow / np.float64(n)).reshape(pn, tn, rns))
+        if a.entropy_atoms:
+            np.save(prefix + '.lesa.npy', s.reshape(pn, tn, rns, n))
+            np.save(prefix + '.leba.npy', sbar.reshape(pn, tn, rns, n))
+    if a.entropy_functional:
+        ef, s2 = entropy_functional(g, r, nrho)
+        np.save(prefix + '.ef.npy', ef.astype(np.float32).reshape(pn, tn, rns, r.size))
+        np.save(prefix + '.s2.npy', s2.reshape(pn, tn, rns))
     if a.verbose:
         print('all properties pickled')
 

@@ -6,6 +6,7 @@
     python scripts/bench_distr.py --bondorder [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l ...=4 6]
     python scripts/bench_distr.py --solid [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l=6] [s_min=0.5] [n_min=8]
     python scripts/bench_distr.py --cna [ns=4096] [cells=4] [cutoff=0] [repeats=5] [mode=adaptive]
+    python scripts/bench_distr.py --entropy [ns=4096] [cells=4] [repeats=5] [r_m=0] [sigma=0] [nbins=0] [r_avg=0]
 
 --angles: nm_distr_angles on displaced fcc frames of 4 cells^3 atoms (shell up to cutoff * l; the first shell is about
 0.85 / cells): the time of the whole call (copies + kernel, host clock around the synchronous call, median of the repeats
@@ -32,7 +33,11 @@ rocprofv3 line (nm_bo_moments_kernel, nm_solid_connect_kernel, nm_solid_union_ke
 value for the mode): the time of the whole call as above, centres/s and entries/s, the types and columns found, and next to it
 nm_distr_solid (l = 6, the defaults) on the same frames and the same shell, the nearest scan-bound sibling (three scans of the
 candidates and the moments against this path's one scan and the graphs).  The kernel's own time comes from the same rocprofv3 line
-(nm_cna_kernel against nm_bo_moments_kernel + nm_solid_connect_kernel + nm_solid_union_kernel + nm_solid_label_kernel)."""
+(nm_cna_kernel against nm_bo_moments_kernel + nm_solid_connect_kernel + nm_solid_union_kernel + nm_solid_label_kernel).
+
+--entropy: nm_distr_entropy on the frames of --bondorder at distr -le's automatic parameters (or the fractions given), all six outputs:
+the time of the whole call as above, the entries and the Gaussian terms (entries x grid points) per second.  The kernels' own times
+come from the same rocprofv3 line (nm_ent_local_kernel, nm_ent_average_kernel, nm_ent_mean_kernel)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -294,6 +299,43 @@ def bench_cna(argv):
     print('solid (l = 6, s_min 0.5, n_min 8) on the same frames and shell: call median of %d: %.4f s (min %.4f, max %.4f); cna / solid = %.2f'
           % (reps, med['solid'][0], med['solid'][1], med['solid'][2], dt / med['solid'][0]))
 
+
+def bench_entropy(argv):
+    from neuralmelting_amd import lattice
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    cells = int(argv[1]) if len(argv) > 1 else 4
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    flags = ['-le']
+    for f, v in zip(('-lr', '-lw', '-lg', '-lv'), argv[3:7]):
+        flags += [f, v]
+    rng = np.random.default_rng(3)                                            # the frames of bench_angles
+    n = 4 * cells ** 3
+    rm, sigma, nbins, ravg = distr.entropy_params(distr.parse_args(flags), n)
+    a0 = lattice.lattice_constant('LJ')
+    box = (cells * a0 * (1.0 + 0.05 * rng.random(ns))).astype(np.float32)
+    frac = lattice.fcc_fractional(cells)
+    pos = ((frac[None] + 0.08 / cells * rng.normal(size=(ns, n, 3))) % 1.0 * box[:, None, None]).astype(np.float32)
+    pos = np.minimum(pos, np.nextafter(box, np.float32(0))[:, None, None])
+    l = float(box.min())
+    natoms = np.full(ns, n)
+    run = lambda m: distr.local_entropy(natoms[:m], box[:m], pos[:m], rm * l, sigma * l, nbins, ravg * l, -4.0)
+    run(min(ns, 8))
+    run(ns)                                                                   # warm-up at the timed shape
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter(); s, sbar, nnb, smean, sbarmean, nlow = run(ns); ts.append(time.perf_counter() - t)
+    dt = float(np.median(ts))
+    ent = int(nnb.sum())
+    print('entropy: %d samples x %d atoms, r_m %.4f l, sigma %.5f l, %d intervals, r_avg %.4f l: %d entries (%.1f per centre, %d at most), '
+          '%.3e Gaussian terms on the grid; mean s %.4f, mean sbar %.4f, below -4: %.4f; call (H2D + kernels + D2H) median of %d: %.4f s '
+          '(min %.4f, max %.4f) = %.2f G entries/s, %.1f M centres/s'
+          % (ns, n, rm, sigma, nbins, ravg, ent, ent / (ns * n), nnb.max(), float(ent) * (nbins + 1), smean.mean(), sbarmean.mean(),
+             nlow.mean() / n, reps, dt, min(ts), max(ts), ent / dt / 1e9, ns * n / dt / 1e6))
+
+
+if '--entropy' in sys.argv:
+    bench_entropy([x for x in sys.argv[1:] if x != '--entropy'])
+    sys.exit(0)
 
 if '--cna' in sys.argv:
     bench_cna([x for x in sys.argv[1:] if x != '--cna'])
