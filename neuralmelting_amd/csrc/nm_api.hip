@@ -3,16 +3,7 @@
 // HIP device nm_create fails with NM_ERR_HIP.
 #include "../../include/nm.h"
 #include "nm_kernels.h"
-#include "nm_distr.h"
-#include "nm_format.h"
-#include "nm_parse.h"
 #include "nm_lattice.h"
-#include "nm_reweight.h"
-#include "nm_reweight_boot.h"
-#include "../../include/nm_distr.h"
-#include "../../include/nm_parse.h"
-#include "../../include/nm_reweight.h"
-#include "../../include/nm_reweight_boot.h"
 
 #include <algorithm>
 #include <cmath>
@@ -21,11 +12,14 @@
 #include <cstring>
 #include <deque>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
 using namespace nm;
+
+// what nm_last_error(NULL) returns: the message of a call that failed without a context.  nm_io.cpp's nm_lattice_state has none
+// either and writes it too, so it is the one name the two files share
+namespace nm { __attribute__((visibility("hidden"))) thread_local std::string g_create_error; }
 
 namespace {
 
@@ -123,8 +117,6 @@ R with_row(int pot, int kind, int q, R none, F &&f)
 NM_CFG_ROWS(NM_ROW)
 #undef NM_ROW
 static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");
-
-thread_local std::string g_create_error;
 
 struct EvPair { hipEvent_t a, b; bool used; uint32_t launch_id; };
 
@@ -1051,18 +1043,6 @@ int nm_set_state(nm_ctx *c, int k0, int nk, const double *x, const double *v, co
     return NM_OK;
 }
 
-int nm_lattice_state(int element, int sz, int np, int nt, const float *P, uint32_t seed, int gslot, double dx, int interpolate, double *x,
-                     double *box)
-{
-    if ((element != NM_EL_LJ && !lat::sc_element(element)) || sz < 1 || np < 1 || nt < 1 || !P || gslot < 0 || gslot >= np * nt || !x || !box)
-        return fail(nullptr, NM_ERR_ARG, "nm_lattice_state: bad argument");
-    std::vector<double> frac;
-    lat::fcc_fractional(sz, frac);
-    const double b = lat::relax_box(element, sz, (double)P[gslot / nt]);
-    lat::init_state(element, sz, b, seed, gslot, gslot % nt, nt, dx, interpolate, frac, x, box);
-    return NM_OK;
-}
-
 int nm_init_lattice(nm_ctx *c, double dx, double dv, int interpolate)
 {
     if (!c) return NM_ERR_ARG;
@@ -1592,1153 +1572,4 @@ int nm_get_exchange_crit(nm_ctx *c, double *crit, int n)
     return NM_OK;
 }
 
-} // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------
-// structural histograms (include/nm_distr.h; lammps_distr.py:123-171)
-namespace {
-thread_local std::string g_distr_error;
-int dfail(int code, const std::string &m) { g_distr_error = m; return code; }
-int refuse(const char *fn, const char *why) { return dfail(NM_ERR_ARG, std::string(fn) + ": " + why); }
-
-// a failed HIP call ends the entry point `fn` with NM_ERR_HIP; what it allocated is freed by the buffers' destructors
-#define DISTR_CHK(fn, call)                                                                            \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) return dfail(NM_ERR_HIP, std::string(fn) + ": " + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// device memory that is freed on every way out of the scope that holds it
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
-    operator T *() const { return p; }
-};
-
-// makes `device` the calling thread's device.  A negative ordinal is refused before a device is looked for: it is the
-// last of an entry point's NM_ERR_ARG that needs none
-int distr_device(const char *fn, int device)
-{
-    if (device < 0) return refuse(fn, "device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dfail(NM_ERR_HIP, std::string(fn) + ": no HIP device available");
-    if (device >= ndev) return refuse(fn, "device ordinal out of range");
-    DISTR_CHK(fn, hipSetDevice(device));
-    return NM_OK;
-}
-
-constexpr int DISTR_CHUNK = 4096; // most samples per launch: bounds device memory (pos 12 N B + results) for long trajectories
-
-// The chunk loop of an entry point: the device copies of `cs` samples' positions and boxes, filled for one chunk after the
-// other; body(s0, n) computes the samples s0 .. s0 + n - 1 from them (launch, synchronise, copy back) and returns NM_OK or
-// what it failed with.
-struct DistrChunks {
-    DevBuf<float> pos, box;
-    template <class Body>
-    int run(const char *fn, int ns, int cs, int natoms, const float *h_pos, const float *h_box, Body &&body)
-    {
-        DISTR_CHK(fn, pos.alloc((size_t)cs * natoms * 3));
-        DISTR_CHK(fn, box.alloc((size_t)cs));
-        for (int s0 = 0; s0 < ns; s0 += cs) {
-            const int n = (ns - s0) < cs ? (ns - s0) : cs;
-            DISTR_CHK(fn, hipMemcpy(pos, h_pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
-            DISTR_CHK(fn, hipMemcpy(box, h_box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-            const int rc = body(s0, n);
-            if (rc != NM_OK) return rc;
-        }
-        return NM_OK;
-    }
-};
-
-int distr_boxes_check(const char *fn, int ns, const float *box)
-{
-    for (int s = 0; s < ns; ++s)
-        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return refuse(fn, "a box is not finite and positive");
-    return NM_OK;
-}
-
-// the neighbour shell of nm_distr_angles and nm_distr_bondorder
-int shell_check(const char *fn, double r_lo, double r_hi)
-{
-    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return refuse(fn, "the shell needs 0 <= r_lo < r_hi");
-    return NM_OK;
-}
-
-// beyond half the smallest box an atom could neighbour its own image (a zero angle that is no bond angle)
-int half_box_check(const char *fn, int ns, const float *box, double r_hi)
-{
-    for (int s = 0; s < ns; ++s)
-        if (!(r_hi <= 0.5 * (double)box[s])) return refuse(fn, "r_hi exceeds half the smallest box");
-    return NM_OK;
-}
-
-// the image pre-test of the scan compares float components with a float at or above r_hi; it is switched off for shells
-// so small that the squares of such components could underflow
-float shell_cube(double r_hi) { return r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY); }
-
-// what the bond-order kernels need to know of the requested l (nm_distr.h, BoSet); ls increases strictly within 1..12
-BoSet bo_set(int nl, const int *ls)
-{
-    BoSet set = {nl, 0, ls[nl - 1], 0u, 0ull, 0u};
-    for (int i = 0; i < nl; ++i) {
-        const int l = ls[i];
-        set.lmask |= 1u << l;
-        if (l <= 8) set.off_lo |= (unsigned long long)set.nc << (8 * (l - 1));
-        else set.off_hi |= (unsigned int)set.nc << (8 * (l - 9));
-        set.nc += l + 1;
-    }
-    return set;
-}
-
-// the constants of the harmonics' recurrence (nm_distr.h): long double, rounded once
-std::vector<double> bo_table()
-{
-    const int W = BO_LMAX + 1;
-    std::vector<double> tab((size_t)BO_TAB, 0.0);
-    long double c = sqrtl(1.0L / (4.0L * 3.14159265358979323846264338327950288L));
-    for (int m = 0; m <= BO_LMAX; ++m) {
-        if (m > 0) c = -c * sqrtl((long double)(2 * m + 1) / (long double)(2 * m));
-        tab[m] = (double)c;
-        for (int l = m + 1; l <= BO_LMAX; ++l) {
-            tab[W + l * W + m] = (double)sqrtl((long double)(4 * l * l - 1) / (long double)(l * l - m * m));
-            tab[W + W * W + l * W + m] = (double)sqrtl((long double)((l - 1) * (l - 1) - m * m) / (long double)(4 * (l - 1) * (l - 1) - 1));
-        }
-    }
-    return tab;
-}
-
-// samples per launch of the entry points that keep the moments q_lm in a device scratch of `per` bytes per sample: at most
-// DISTR_CHUNK as the other entry points, fewer where the scratch would pass 256 MiB
-int bo_chunk(int ns, size_t per)
-{
-    size_t fit = ((size_t)256 << 20) / per;
-    if (fit < 1) fit = 1;
-    int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
-    if ((size_t)cs > fit) cs = (int)fit;
-    return cs;
-}
-} // namespace
-
-extern "C" {
-
-const char *nm_distr_last_error(void) { return g_distr_error.c_str(); }
-
-int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const float *box, int sbins, const double *r_edges,
-                        int cbins, const double *rv_edges, float *rdf, float *cdf)
-{
-    static const char *const fn = "nm_distr_histograms";
-    if (ns < 0 || natoms < 1 || !pos || !box) return refuse(fn, "bad argument");
-    if (rdf && (!r_edges || sbins < 2 || sbins > DISTR_MAXS)) return refuse(fn, "bad spherical bins");
-    if (cdf && (!rv_edges || cbins < 1 || cbins > DISTR_MAXC)) return refuse(fn, "bad cartesian bins");
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    const int sb = rdf ? sbins : 0, cb = cdf ? cbins : 0;
-    const size_t nc = (size_t)cb * cb * cb;
-    const size_t lds = distr_lds_bytes(natoms, sb, cb);
-    if (lds > 160 * 1024) return refuse(fn, "working set exceeds LDS");
-    // one image block's count of a bin is at most natoms^2, exact as a float below 2^24; the sum of the 27 blocks can exceed
-    // natoms^2 (a displacement on +-l/2 lies in the closed cube in two images per axis) and is checked after the copy-back
-    if (natoms >= 4096) return refuse(fn, "natoms^2 must stay below 2^24 (float32 counts of one periodic image)");
-    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_distr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
-    DevBuf<double> d_re, d_ve;
-    DevBuf<float> d_r, d_c;
-    if (rdf) {
-        DISTR_CHK(fn, d_re.alloc(sbins));
-        DISTR_CHK(fn, d_r.alloc((size_t)cs * sbins));
-        DISTR_CHK(fn, hipMemcpy(d_re, r_edges, sbins * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (cdf) {
-        DISTR_CHK(fn, d_ve.alloc(cbins + 1));
-        DISTR_CHK(fn, d_c.alloc((size_t)cs * nc));
-        DISTR_CHK(fn, hipMemcpy(d_ve, rv_edges, (cbins + 1) * sizeof(double), hipMemcpyHostToDevice));
-    }
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        if (rdf) DISTR_CHK(fn, hipMemset(d_r, 0, (size_t)n * sbins * sizeof(float)));
-        if (cdf) DISTR_CHK(fn, hipMemset(d_c, 0, (size_t)n * nc * sizeof(float)));
-        hipLaunchKernelGGL(nm_distr_kernel, dim3(n * 27), dim3(DISTR_BLOCK), lds, 0, natoms, ch.pos, ch.box, sb, d_re, cb, d_ve, d_r, d_c);
-        DISTR_CHK(fn, hipGetLastError());
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        if (rdf) DISTR_CHK(fn, hipMemcpy(rdf + (size_t)s0 * sbins, d_r, (size_t)n * sbins * sizeof(float), hipMemcpyDeviceToHost));
-        if (cdf) DISTR_CHK(fn, hipMemcpy(cdf + (size_t)s0 * nc, d_c, (size_t)n * nc * sizeof(float), hipMemcpyDeviceToHost));
-        // every partial sum below 2^24 is exact, so a total reaches 2^24 exactly when the returned float does; from there on
-        // the float atomics round in the order they land, and the counts are no longer the reference's
-        bool big = false;
-        if (rdf) for (size_t i = 0; i < (size_t)n * sbins; ++i) big |= rdf[(size_t)s0 * sbins + i] >= 16777216.0f;
-        if (cdf) for (size_t i = 0; i < (size_t)n * nc; ++i) big |= cdf[(size_t)s0 * nc + i] >= 16777216.0f;
-        if (big) return refuse(fn, "a bin holds 2^24 counts or more, beyond what float32 counts hold exactly");
-        return NM_OK;
-    });
-}
-
-int nm_distr_angles(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int abins,
-                    const double *cos_edges, uint64_t *adf)
-{
-    static const char *const fn = "nm_distr_angles";
-    if (ns < 0 || !pos || !box || !cos_edges || !adf) return refuse(fn, "bad argument");
-    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
-    if (abins < 2 || abins > ADF_MAXB) return refuse(fn, "abins must lie in 2..256");
-    for (int k = 0; k + 1 < abins; ++k)
-        if (!(cos_edges[k] > cos_edges[k + 1])) return refuse(fn, "cos_edges must decrease strictly");
-    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
-    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    const float cube = shell_cube(r_hi);
-    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
-    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
-    const size_t lds = adf_lds_bytes(natoms, abins); // at most 109,652 B (natoms 4095, abins 256)
-    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_adf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DevBuf<double> d_e;
-    DevBuf<unsigned long long> d_a;
-    DISTR_CHK(fn, d_e.alloc(abins));
-    DISTR_CHK(fn, d_a.alloc((size_t)cs * abins));
-    DISTR_CHK(fn, hipMemcpy(d_e, cos_edges, (size_t)abins * sizeof(double), hipMemcpyHostToDevice));
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        DISTR_CHK(fn, hipMemset(d_a, 0, (size_t)n * abins * sizeof(unsigned long long)));
-        hipLaunchKernelGGL(nm_adf_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, abins, d_e, d_a);
-        DISTR_CHK(fn, hipGetLastError());
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        DISTR_CHK(fn, hipMemcpy(adf + (size_t)s0 * abins, d_a, (size_t)n * abins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        return NM_OK;
-    });
-}
-
-int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const float *box, int qmax, double *sf_sum, double *sf_max)
-{
-    static const char *const fn = "nm_distr_sfactor";
-    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
-    if (!sf_sum && !sf_max) return refuse(fn, "sf_sum and sf_max are both null");
-    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
-    if (qmax < 1 || qmax > SF_QMAX) return refuse(fn, "qmax must lie in 1..32");
-    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    // the work items (nm_distr.h): every (h >= 0, k >= 0, l0) whose chunk l0 .. l0 + SF_LB - 1 reaches into the sphere, l0 slowest
-    std::vector<unsigned int> items;
-    for (int l0 = 0; l0 <= qmax; l0 += SF_LB)
-        for (int h = 0; h <= qmax; ++h)
-            for (int k = 0; k <= qmax; ++k)
-                if (h * h + k * k + l0 * l0 <= qmax * qmax) items.push_back(sf_item(h, k, l0));
-    const int nitems = (int)items.size();
-    const size_t nsh = (size_t)qmax * qmax + 1;
-    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
-    const size_t lds = sf_lds_bytes(qmax); // below the 64 KiB a kernel gets without asking
-    DevBuf<unsigned int> d_it;
-    DevBuf<double> d_sum, d_max;
-    DISTR_CHK(fn, d_it.alloc(nitems));
-    if (sf_sum) DISTR_CHK(fn, d_sum.alloc((size_t)cs * nsh));
-    if (sf_max) DISTR_CHK(fn, d_max.alloc((size_t)cs * nsh));
-    DISTR_CHK(fn, hipMemcpy(d_it, items.data(), (size_t)nitems * sizeof(unsigned int), hipMemcpyHostToDevice));
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        hipLaunchKernelGGL(nm_sfac_kernel, dim3(n), dim3(SF_BLOCK), lds, 0, natoms, ch.pos, ch.box, qmax, nitems, d_it, d_sum, d_max);
-        DISTR_CHK(fn, hipGetLastError());
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        if (sf_sum) DISTR_CHK(fn, hipMemcpy(sf_sum + (size_t)s0 * nsh, d_sum, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
-        if (sf_max) DISTR_CHK(fn, hipMemcpy(sf_max + (size_t)s0 * nsh, d_max, (size_t)n * nsh * sizeof(double), hipMemcpyDeviceToHost));
-        return NM_OK;
-    });
-}
-
-int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
-                       const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb)
-{
-    static const char *const fn = "nm_distr_bondorder";
-    if (ns < 0 || !pos || !box || !ls) return refuse(fn, "bad argument");
-    if (!q2 && !qbar2 && !Q2 && !nnb) return refuse(fn, "all four outputs are null");
-    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
-    if (nl < 1 || nl > BO_MAXL) return refuse(fn, "nl must lie in 1..6");
-    for (int i = 0; i < nl; ++i)
-        if (ls[i] < 1 || ls[i] > BO_LMAX || (i > 0 && ls[i] <= ls[i - 1]))
-            return refuse(fn, "ls must increase strictly within 1..12");
-    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
-    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
-    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    const BoSet set = bo_set(nl, ls);
-    const int nc2 = 2 * set.nc;
-    const std::vector<double> tab = bo_table();
-    const float cube = shell_cube(r_hi);
-    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
-    const int cs = bo_chunk(ns, (size_t)natoms * nc2 * sizeof(double));
-    const size_t lds1 = bo_lds_bytes(natoms, set.nc, true), lds2 = bo_lds_bytes(natoms, set.nc, false); // at most 98,932 B (4095 atoms, six l from 7 to 12)
-    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    const size_t pa = (size_t)natoms * nl;
-    DevBuf<double> d_tab, d_qlm, d_part, d_q2, d_qb, d_Q;
-    DevBuf<int> d_cnt, d_nnb;
-    DISTR_CHK(fn, d_tab.alloc(tab.size()));
-    DISTR_CHK(fn, d_qlm.alloc((size_t)cs * natoms * nc2));
-    DISTR_CHK(fn, d_part.alloc((size_t)cs * groups * nc2));
-    DISTR_CHK(fn, d_cnt.alloc((size_t)cs * groups));
-    if (q2) DISTR_CHK(fn, d_q2.alloc((size_t)cs * pa));
-    if (qbar2) DISTR_CHK(fn, d_qb.alloc((size_t)cs * pa));
-    if (Q2) DISTR_CHK(fn, d_Q.alloc((size_t)cs * nl));
-    if (nnb) DISTR_CHK(fn, d_nnb.alloc((size_t)cs * natoms));
-    DISTR_CHK(fn, hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, set,
-                           d_tab, d_qlm, d_q2, d_nnb, d_part, d_cnt);
-        DISTR_CHK(fn, hipGetLastError());
-        if (qbar2) {
-            hipLaunchKernelGGL(nm_bo_average_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube,
-                               set, d_qlm, d_qb);
-            DISTR_CHK(fn, hipGetLastError());
-        }
-        if (Q2) {
-            hipLaunchKernelGGL(nm_bo_global_kernel, dim3(n), dim3(128), 0, 0, groups, set, d_part, d_cnt, d_Q);
-            DISTR_CHK(fn, hipGetLastError());
-        }
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        if (q2) DISTR_CHK(fn, hipMemcpy(q2 + (size_t)s0 * pa, d_q2, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
-        if (qbar2) DISTR_CHK(fn, hipMemcpy(qbar2 + (size_t)s0 * pa, d_qb, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
-        if (Q2) DISTR_CHK(fn, hipMemcpy(Q2 + (size_t)s0 * nl, d_Q, (size_t)n * nl * sizeof(double), hipMemcpyDeviceToHost));
-        if (nnb) DISTR_CHK(fn, hipMemcpy(nnb + (size_t)s0 * natoms, d_nnb, (size_t)n * natoms * sizeof(int), hipMemcpyDeviceToHost));
-        return NM_OK;
-    });
-}
-
-int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int l, double s_min,
-                   int n_min, int32_t *nconn, int32_t *label, int32_t *nsolid, int32_t *nclus, int32_t *largest)
-{
-    static const char *const fn = "nm_distr_solid";
-    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
-    if (!nconn && !label && !nsolid && !nclus && !largest) return refuse(fn, "all five outputs are null");
-    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
-    if (l < 1 || l > BO_LMAX) return refuse(fn, "l must lie in 1..12");
-    if (!(s_min >= -1.0) || !(s_min < 1.0)) return refuse(fn, "s_min must lie in [-1, 1)");
-    if (n_min < 1) return refuse(fn, "n_min must be at least 1");
-    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
-    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
-    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    const BoSet set = bo_set(1, &l);
-    const int nc2 = 2 * set.nc;
-    const std::vector<double> tab = bo_table();
-    const float cube = shell_cube(r_hi);
-    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
-    const int cs = bo_chunk(ns, (size_t)natoms * nc2 * sizeof(double));
-    const size_t lds1 = bo_lds_bytes(natoms, set.nc, true), lds2 = solid_lds_bytes(natoms); // at most 92,532 B and 51,284 B (4095 atoms, l = 12)
-    DISTR_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    DevBuf<double> d_tab, d_qlm, d_part;
-    DevBuf<int> d_cnt, d_conn, d_par, d_lab, d_ns, d_nc, d_big;
-    DISTR_CHK(fn, d_tab.alloc(tab.size()));
-    DISTR_CHK(fn, d_qlm.alloc((size_t)cs * natoms * nc2));
-    DISTR_CHK(fn, d_part.alloc((size_t)cs * groups * nc2));
-    DISTR_CHK(fn, d_cnt.alloc((size_t)cs * groups));
-    DISTR_CHK(fn, d_conn.alloc((size_t)cs * natoms));
-    DISTR_CHK(fn, d_par.alloc((size_t)cs * natoms));
-    DISTR_CHK(fn, d_lab.alloc((size_t)cs * natoms));
-    DISTR_CHK(fn, d_ns.alloc((size_t)cs));
-    DISTR_CHK(fn, d_nc.alloc((size_t)cs));
-    DISTR_CHK(fn, d_big.alloc((size_t)cs));
-    DISTR_CHK(fn, hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        // each kernel reads what the one before it wrote for the whole chunk: the launches of one stream run in order
-        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, set,
-                           d_tab, d_qlm, (double *)nullptr, (int *)nullptr, d_part, d_cnt);
-        DISTR_CHK(fn, hipGetLastError());
-        hipLaunchKernelGGL(nm_solid_connect_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, l,
-                           s_min, d_qlm, d_conn, d_par);
-        DISTR_CHK(fn, hipGetLastError());
-        hipLaunchKernelGGL(nm_solid_union_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, n_min,
-                           d_conn, d_par);
-        DISTR_CHK(fn, hipGetLastError());
-        hipLaunchKernelGGL(nm_solid_label_kernel, dim3(n), dim3(SOLID_BLOCK), 0, 0, natoms, n_min, d_conn, d_par, d_lab, d_ns, d_nc, d_big);
-        DISTR_CHK(fn, hipGetLastError());
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        const size_t pa = (size_t)natoms * sizeof(int);
-        if (nconn) DISTR_CHK(fn, hipMemcpy(nconn + (size_t)s0 * natoms, d_conn, (size_t)n * pa, hipMemcpyDeviceToHost));
-        if (label) DISTR_CHK(fn, hipMemcpy(label + (size_t)s0 * natoms, d_lab, (size_t)n * pa, hipMemcpyDeviceToHost));
-        if (nsolid) DISTR_CHK(fn, hipMemcpy(nsolid + s0, d_ns, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        if (nclus) DISTR_CHK(fn, hipMemcpy(nclus + s0, d_nc, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        if (largest) DISTR_CHK(fn, hipMemcpy(largest + s0, d_big, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        return NM_OK;
-    });
-}
-
-int nm_distr_cna(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int mode,
-                 int32_t *type, int32_t *sig, int32_t *ntype, int32_t *nsig)
-{
-    static const char *const fn = "nm_distr_cna";
-    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
-    if (!type && !sig && !ntype && !nsig) return refuse(fn, "all four outputs are null");
-    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
-    if (mode != NM_CNA_FIXED && mode != NM_CNA_ADAPTIVE) return refuse(fn, "mode must be NM_CNA_FIXED or NM_CNA_ADAPTIVE");
-    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
-    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
-    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
-    const size_t lds = cna_lds_bytes(natoms); // at most 51,604 B (4095 atoms)
-    if (lds > 160 * 1024) return refuse(fn, "working set exceeds LDS");
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    const float cube = shell_cube(r_hi);
-    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
-    const size_t pa = (size_t)natoms, ps = pa * CNA_NSIG;
-    const int cs = bo_chunk(ns, ps * sizeof(int)); // the per-atom columns are the largest device array
-    DevBuf<int> d_type, d_sig, d_ntype, d_nsig;
-    if (type) DISTR_CHK(fn, d_type.alloc((size_t)cs * pa));
-    if (sig) DISTR_CHK(fn, d_sig.alloc((size_t)cs * ps));
-    if (ntype) DISTR_CHK(fn, d_ntype.alloc((size_t)cs * CNA_NTYPE));
-    if (nsig) DISTR_CHK(fn, d_nsig.alloc((size_t)cs * CNA_NSIG));
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        // the per-sample sums are added to by every workgroup of the sample
-        if (ntype) DISTR_CHK(fn, hipMemset(d_ntype, 0, (size_t)n * CNA_NTYPE * sizeof(int)));
-        if (nsig) DISTR_CHK(fn, hipMemset(d_nsig, 0, (size_t)n * CNA_NSIG * sizeof(int)));
-        hipLaunchKernelGGL(nm_cna_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube,
-                           mode == NM_CNA_ADAPTIVE, d_type, d_sig, d_ntype, d_nsig);
-        DISTR_CHK(fn, hipGetLastError());
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        if (type) DISTR_CHK(fn, hipMemcpy(type + (size_t)s0 * pa, d_type, (size_t)n * pa * sizeof(int), hipMemcpyDeviceToHost));
-        if (sig) DISTR_CHK(fn, hipMemcpy(sig + (size_t)s0 * ps, d_sig, (size_t)n * ps * sizeof(int), hipMemcpyDeviceToHost));
-        if (ntype) DISTR_CHK(fn, hipMemcpy(ntype + (size_t)s0 * CNA_NTYPE, d_ntype, (size_t)n * CNA_NTYPE * sizeof(int), hipMemcpyDeviceToHost));
-        if (nsig) DISTR_CHK(fn, hipMemcpy(nsig + (size_t)s0 * CNA_NSIG, d_nsig, (size_t)n * CNA_NSIG * sizeof(int), hipMemcpyDeviceToHost));
-        return NM_OK;
-    });
-}
-
-int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const float *box, double r_m, double sigma, int nbins, double r_avg,
-                     double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean, int32_t *nlow)
-{
-    static const char *const fn = "nm_distr_entropy";
-    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
-    if (!s && !sbar && !nnb && !smean && !sbarmean && !nlow) return refuse(fn, "all six outputs are null");
-    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
-    if (nbins < 1 || nbins > ENT_MAXBINS) return refuse(fn, "nbins must lie in 1..1024");
-    if (!(sigma > 0.0) || !std::isfinite(sigma)) return refuse(fn, "sigma must be positive and finite");
-    if (!(r_m > 0.0) || !std::isfinite(r_m)) return refuse(fn, "r_m must be positive and finite");
-    if (!(r_avg > 0.0)) return refuse(fn, "r_avg must be positive");
-    if (s_cut != s_cut) return refuse(fn, "s_cut is not a number");
-    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
-    for (int i = 0; i < ns; ++i)
-        if (!(r_m <= 0.5 * (double)box[i]) || !(r_avg <= 0.5 * (double)box[i])) return refuse(fn, "r_m or r_avg exceeds half the smallest box");
-    if (const int rc = distr_device(fn, device)) return rc;
-    if (ns == 0) return NM_OK;
-    const bool average = sbar || sbarmean || nlow, means = smean || sbarmean || nlow;
-    const float cube_m = shell_cube(r_m), cube_a = shell_cube(r_avg);
-    const double D = r_m / (double)nbins, inv2s2 = 1.0 / (2.0 * (sigma * sigma));
-    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
-    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
-    const size_t lds1 = ent_lds_bytes(natoms, false), lds2 = ent_lds_bytes(natoms, true); // at most 49,284 B and 51,332 B (4095 atoms)
-    DevBuf<double> d_s, d_b, d_ps, d_pb, d_sm, d_bm;
-    DevBuf<int> d_nnb, d_pl, d_low;
-    DISTR_CHK(fn, d_s.alloc((size_t)cs * natoms)); // pass 2 reads it, whether or not the caller asks for s
-    DISTR_CHK(fn, d_ps.alloc((size_t)cs * groups));
-    if (nnb) DISTR_CHK(fn, d_nnb.alloc((size_t)cs * natoms));
-    if (sbar) DISTR_CHK(fn, d_b.alloc((size_t)cs * natoms));
-    if (average) {
-        DISTR_CHK(fn, d_pb.alloc((size_t)cs * groups));
-        DISTR_CHK(fn, d_pl.alloc((size_t)cs * groups));
-    }
-    if (smean) DISTR_CHK(fn, d_sm.alloc((size_t)cs));
-    if (sbarmean) DISTR_CHK(fn, d_bm.alloc((size_t)cs));
-    if (nlow) DISTR_CHK(fn, d_low.alloc((size_t)cs));
-    const int points = nbins + 1; // a lane owns ceil(points / 64) grid points: the next instantiation that holds them
-    DistrChunks ch;
-    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
-        auto local = [&](auto na) {
-            hipLaunchKernelGGL(nm_ent_local_kernel<decltype(na)::value>, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_m,
-                               cube_m, sigma, inv2s2, nbins, D, d_s, d_nnb, d_ps);
-        };
-        if (points <= 64) local(std::integral_constant<int, 1>());
-        else if (points <= 128) local(std::integral_constant<int, 2>());
-        else if (points <= 256) local(std::integral_constant<int, 4>());
-        else if (points <= 512) local(std::integral_constant<int, 8>());
-        else local(std::integral_constant<int, ENT_MAXACC>());
-        DISTR_CHK(fn, hipGetLastError());
-        if (average) {
-            hipLaunchKernelGGL(nm_ent_average_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_avg, cube_a, s_cut,
-                               d_s, d_b, d_pb, d_pl);
-            DISTR_CHK(fn, hipGetLastError());
-        }
-        if (means) {
-            hipLaunchKernelGGL(nm_ent_mean_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, n, natoms, groups, d_ps, d_pb, d_pl, d_sm, d_bm, d_low);
-            DISTR_CHK(fn, hipGetLastError());
-        }
-        DISTR_CHK(fn, hipDeviceSynchronize());
-        const size_t pa = (size_t)natoms;
-        if (s) DISTR_CHK(fn, hipMemcpy(s + (size_t)s0 * pa, d_s, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
-        if (sbar) DISTR_CHK(fn, hipMemcpy(sbar + (size_t)s0 * pa, d_b, (size_t)n * pa * sizeof(double), hipMemcpyDeviceToHost));
-        if (nnb) DISTR_CHK(fn, hipMemcpy(nnb + (size_t)s0 * pa, d_nnb, (size_t)n * pa * sizeof(int), hipMemcpyDeviceToHost));
-        if (smean) DISTR_CHK(fn, hipMemcpy(smean + s0, d_sm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        if (sbarmean) DISTR_CHK(fn, hipMemcpy(sbarmean + s0, d_bm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        if (nlow) DISTR_CHK(fn, hipMemcpy(nlow + s0, d_low, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        return NM_OK;
-    });
-}
-#undef DISTR_CHK
-
-} // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------
-// output formatting (include/nm.h; write_outputs, remcmc:235-286): plain host code
-extern "C" {
-
-int nm_format_thrm(const double *row17, char *out, int cap)
-{
-    if (!row17 || !out || cap < 17 * 14 + 2) return NM_ERR_ARG;
-    return format_thrm(row17, out);
-}
-
-int nm_format_traj(int natoms, double box, const double *x, char *out, int cap)
-{
-    if (natoms < 0 || !x || !out || cap < 32 + 42 * natoms) return NM_ERR_ARG;
-    return format_traj(natoms, box, x, out);
-}
-
-int nm_append_outputs(int nk, int natoms, const char *const *thrm_paths, const char *const *traj_paths, const double *rows,
-                      const double *x, const double *box, int nthreads)
-{
-    if (nk < 0 || natoms < 0 || !thrm_paths || !traj_paths || !rows || !x || !box) return NM_ERR_ARG;
-    if (nthreads <= 0) nthreads = (int)std::thread::hardware_concurrency();
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > nk) nthreads = nk > 0 ? nk : 1;
-    std::vector<int> err((size_t)nthreads, 0);
-    auto work = [&](int t) {
-        std::vector<char> buf((size_t)64 + 42 * (size_t)natoms + 17 * 14);
-        for (int k = t; k < nk; k += nthreads) {
-            int n = format_thrm(rows + 17 * (size_t)k, buf.data());
-            FILE *f = std::fopen(thrm_paths[k], "a");
-            if (!f || std::fwrite(buf.data(), 1, (size_t)n, f) != (size_t)n) err[t] = 1;
-            if (f) std::fclose(f);
-            n = format_traj(natoms, box[k], x + 3 * (size_t)natoms * k, buf.data());
-            f = std::fopen(traj_paths[k], "a");
-            if (!f || std::fwrite(buf.data(), 1, (size_t)n, f) != (size_t)n) err[t] = 1;
-            if (f) std::fclose(f);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthreads; ++t) th.emplace_back(work, t);
-    work(0);
-    for (auto &t : th) t.join();
-    for (int e : err) if (e) return NM_ERR_ARG;
-    return NM_OK;
-}
-
-} // extern "C"
-
-// ------------------------------------------------------------------------------------------------------------------
-// .thrm / .traj reader (include/nm_parse.h; lammps_parse.py:48-49, 88-96)
-// ------------------------------------------------------------------------------------------------------------------
-namespace {
-thread_local std::string g_parse_error;
-}
-extern "C" {
-const char *nm_parse_last_error(void) { return g_parse_error.c_str(); }
-
-int nm_parse_thrm(const char *path, float *rows, long cap_rows, long *nrows, int nthreads)
-{
-    if (!path || (rows && cap_rows < 0)) { g_parse_error = "nm_parse_thrm: bad argument"; return NM_ERR_ARG; }
-    try {
-        return nm::parse_thrm(path, rows, cap_rows, nrows, nthreads, g_parse_error) == 0 ? NM_OK : NM_ERR_ARG;
-    } catch (const std::exception &e) { g_parse_error = e.what(); return NM_ERR_ARG; }
-}
-
-int nm_parse_traj(const char *path, uint16_t *natoms, float *box, float *pos, long cap_frames, long cap_posrows, long *nframes,
-                  long *nposrows, int nthreads)
-{
-    if (!path) { g_parse_error = "nm_parse_traj: bad argument"; return NM_ERR_ARG; }
-    try {
-        return nm::parse_traj(path, natoms, box, pos, cap_frames, cap_posrows, nframes, nposrows, nthreads, g_parse_error) == 0
-                   ? NM_OK : NM_ERR_ARG;
-    } catch (const std::exception &e) { g_parse_error = e.what(); return NM_ERR_ARG; }
-}
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// multistate reweighting of the replica grid (include/nm_reweight.h; kernels: nm_reweight.h)
-// ------------------------------------------------------------------------------------------------------------------
-namespace {
-thread_local std::string g_rw_error;
-int rwfail(int code, const std::string &m) { g_rw_error = m; return code; }
-int rwrefuse(const char *fn, const char *why) { return rwfail(NM_ERR_ARG, std::string(fn) + ": " + why); }
-
-#define RW_CHK(fn, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return rwfail(NM_ERR_HIP, std::string(fn) + ": " + #call + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-bool rw_finite(const double *x, int64_t n)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(x[i])) return false;
-    return true;
-}
-
-// what both entry points ask of the states and the samples
-int rw_check(const char *fn, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
-             const double *e, const double *v)
-{
-    if (nstates < 1 || nstates > RW_MAXSTATES) return rwrefuse(fn, "nstates must lie in 1..4096");
-    if (nsamples < 1) return rwrefuse(fn, "nsamples must be at least 1");
-    if (!b || !c || !count || !f || !e || !v) return rwrefuse(fn, "a needed pointer is null");
-    int64_t sum = 0;
-    for (int k = 0; k < nstates; ++k) {
-        if (count[k] < 0) return rwrefuse(fn, "a count is negative");
-        if (count[k] > nsamples - sum) return rwrefuse(fn, "the counts do not sum to nsamples");
-        sum += count[k];
-    }
-    if (sum != nsamples) return rwrefuse(fn, "the counts do not sum to nsamples");
-    if (!rw_finite(b, nstates) || !rw_finite(c, nstates)) return rwrefuse(fn, "a state's b or c is not finite");
-    if (!rw_finite(f, nstates)) return rwrefuse(fn, "an f is not finite");
-    if (!rw_finite(e, nsamples) || !rw_finite(v, nsamples)) return rwrefuse(fn, "a sample's e or v is not finite");
-    return NM_OK;
-}
-
-int rw_device(const char *fn, int device)
-{
-    if (device < 0) return rwrefuse(fn, "device ordinal out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rwfail(NM_ERR_HIP, std::string(fn) + ": no HIP device available");
-    if (device >= ndev) return rwrefuse(fn, "device ordinal out of range");
-    RW_CHK(fn, hipSetDevice(device));
-    return NM_OK;
-}
-
-// s = b e0 + c v0 as an unevaluated sum: the two rounded products and what their roundings lost (exactly, by fma).  With e0 or v0
-// at 1e6 a long double product is good to 1e-13 only, and the weights would carry that; the differences below cancel the large
-// parts first (sums of doubles of one magnitude are exact in a long double) and add the small parts last.
-struct RwOffset {
-    double p1 = 0.0, p2 = 0.0, lo = 0.0;
-    RwOffset() = default;
-    RwOffset(double b, double c, double e0, double v0)
-    {
-#pragma clang fp contract(off)
-        p1 = b * e0;
-        p2 = c * v0;
-        lo = std::fma(b, e0, -p1) + std::fma(c, v0, -p2);
-    }
-    // x + (this - o)
-    long double add_to(long double x, const RwOffset &o) const { return ((((x + p1) + p2) - o.p1) - o.p2) + ((long double)lo - o.lo); }
-    // (x - y) - (this - o): x and y first, then the large parts pair by pair, so that every partial sum is exact
-    long double take_from(double x, double y, const RwOffset &o) const
-    {
-        return ((((((long double)x - y) - p1) + o.p1) - p2) + o.p2) - ((long double)lo - o.lo);
-    }
-    long double value() const { return ((long double)p1 + p2) + lo; }
-};
-
-// The problem as the device sees it: samples centred on their means, the sampled states as a list, f in the centred gauge
-// (f_centred[k] = (f[k] - f[0]) - (s_k - s_0), s_k = b[k] e0 + c[k] v0: of the size of the centred u whatever f[0], e0 and v0
-// are), and the scratch of the moments kernels.  With logd' and F' what the kernels make of it: logd = logd' + f[0] - s_0 and
-// F[i] = F'[i] + (s_i - s_0) + f[0].
-struct RwProblem {
-    int K = 0, ka = 0;
-    int64_t N = 0, nchunks = 0;
-    double e0 = 0.0, v0 = 0.0;
-    std::vector<RwOffset> s; // s_k
-    RwOffset s0;
-    double f0 = 0.0; // f[0] as it came in
-    DevBuf<double> e, v, logd, b, c, f, ab, ac, alc, part, F;
-    DevBuf<int> aidx;
-    DevBuf<RwStatus> st;
-    int64_t part_doubles = 0;
-
-    // x + (s_t - s_0) + f[0] for a target
-    double shifted(double x, double tb, double tc) const { return (double)(RwOffset(tb, tc, e0, v0).add_to(x, s0) + f0); }
-
-    int setup(const char *fn, int nstates, const double *hb, const double *hc, const int64_t *count, const double *hf, int64_t nsamples,
-              const double *he, const double *hv)
-    {
-        K = nstates;
-        N = nsamples;
-        nchunks = (N + RW_CH - 1) / RW_CH;
-        long double se = 0.0L, sv = 0.0L;
-        for (int64_t i = 0; i < N; ++i) { se += he[i]; sv += hv[i]; }
-        e0 = (double)(se / N);
-        v0 = (double)(sv / N);
-        if (!std::isfinite(e0) || !std::isfinite(v0)) return rwrefuse(fn, "the mean of e or v is not finite");
-        std::vector<double> ce((size_t)N), cv((size_t)N);
-        for (int64_t i = 0; i < N; ++i) { ce[i] = he[i] - e0; cv[i] = hv[i] - v0; }
-        s0 = RwOffset(hb[0], hc[0], e0, v0);
-        f0 = hf[0];
-        s.resize(K);
-        std::vector<double> cf(K), hab, hac, halc;
-        std::vector<int> hidx;
-        for (int k = 0; k < K; ++k) {
-            s[k] = RwOffset(hb[k], hc[k], e0, v0);
-            cf[k] = (double)s[k].take_from(hf[k], hf[0], s0);
-            if (count[k] > 0) {
-                hab.push_back(hb[k]);
-                hac.push_back(hc[k]);
-                halc.push_back(std::log((double)count[k]));
-                hidx.push_back(k);
-            }
-        }
-        ka = (int)hidx.size(); // >= 1: the counts sum to N >= 1
-        const size_t nb = (size_t)N * sizeof(double);
-        RW_CHK(fn, e.alloc(N));
-        RW_CHK(fn, v.alloc(N));
-        RW_CHK(fn, logd.alloc(N));
-        RW_CHK(fn, b.alloc(K));
-        RW_CHK(fn, c.alloc(K));
-        RW_CHK(fn, f.alloc(K));
-        RW_CHK(fn, F.alloc(K));
-        RW_CHK(fn, ab.alloc(ka));
-        RW_CHK(fn, ac.alloc(ka));
-        RW_CHK(fn, alc.alloc(ka));
-        RW_CHK(fn, aidx.alloc(ka));
-        RW_CHK(fn, st.alloc(1));
-        RW_CHK(fn, hipMemcpy(e, ce.data(), nb, hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(v, cv.data(), nb, hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(b, hb, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(c, hc, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(f, cf.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(ab, hab.data(), (size_t)ka * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(ac, hac.data(), (size_t)ka * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(alc, halc.data(), (size_t)ka * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(aidx, hidx.data(), (size_t)ka * sizeof(int), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemset(st, 0, sizeof(RwStatus)));
-        return NM_OK;
-    }
-
-    // how many targets a launch of the moments kernel takes: its partials stay within 128 MiB (but TB targets at least)
-    int batch(int nf, int tb, int most) const
-    {
-        int64_t n = ((int64_t)1 << 24) / (nchunks * nf);
-        n = n / tb * tb;
-        if (n < tb) n = tb;
-        return n < most ? (int)n : most;
-    }
-
-    int scratch(const char *fn, int nf, int nbatch)
-    {
-        part_doubles = (int64_t)nbatch * nchunks * nf;
-        RW_CHK(fn, part.alloc((size_t)part_doubles));
-        return NM_OK;
-    }
-
-    void denominators()
-    {
-        hipLaunchKernelGGL(nm_rw_denom_kernel, dim3((unsigned)((N + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, st, N, e, v, ka, ab, ac, alc,
-                           aidx, f, logd);
-    }
-
-    // the targets t0 .. t0 + nb - 1 of (tb, tc): partials, then F[t] (and sums[t][RW_NF] with MOM); nb is at most the batch
-    template <int TB, bool MOM>
-    void moments(int t0, int nb, const double *tb, const double *tc, int nobs, const double *obs, double *Fout, double *sums)
-    {
-        hipLaunchKernelGGL((nm_rw_moments_kernel<TB, MOM>), dim3((unsigned)nchunks, (unsigned)((nb + TB - 1) / TB)), dim3(RW_BLOCK), 0, 0, st, N, e, v,
-                           logd, t0, t0 + nb, tb, tc, nobs, obs, part);
-        hipLaunchKernelGGL((nm_rw_combine_kernel<MOM>), dim3((unsigned)((nb + RW_WAVES - 1) / RW_WAVES)), dim3(RW_BLOCK), 0, 0, st, nb, nchunks, nobs,
-                           part, Fout + t0, MOM ? sums + (size_t)t0 * RW_NF : nullptr);
-    }
-};
-} // namespace
-
-extern "C" {
-const char *nm_reweight_last_error(void) { return g_rw_error.c_str(); }
-
-int nm_reweight_solve(int device, int nstates, const double *b, const double *c, const int64_t *count, int64_t nsamples, const double *e,
-                      const double *v, double tol, int max_iter, double *f, double *logd, int *iters, double *delta)
-{
-    static const char *const fn = "nm_reweight_solve";
-    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    if (!iters || !delta) return rwrefuse(fn, "a needed pointer is null");
-    if (!(tol >= 0.0)) return rwrefuse(fn, "tol must not be negative");
-    if (max_iter < 1) return rwrefuse(fn, "max_iter must be at least 1");
-    if (const int rc = rw_device(fn, device)) return rc;
-    RwProblem p;
-    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    const int nbatch = p.batch(2, RW_TB, (nstates + RW_TB - 1) / RW_TB * RW_TB);
-    if (const int rc = p.scratch(fn, 2, nbatch)) return rc;
-    RwStatus st = {0, 0, 0.0};
-    for (int it = 0; it < max_iter && !st.done; ++it) {
-        p.denominators();
-        for (int t0 = 0; t0 < nstates; t0 += nbatch)
-            p.moments<RW_TB, false>(t0, (nstates - t0) < nbatch ? (nstates - t0) : nbatch, p.b, p.c, 0, nullptr, p.F, nullptr);
-        hipLaunchKernelGGL(nm_rw_update_kernel, dim3(1), dim3(RW_BLOCK), 0, 0, p.st, nstates, p.F, p.f, it == 0 ? p.f0 : 0.0, tol);
-        RW_CHK(fn, hipGetLastError());
-        if ((it + 1) % RW_POLL == 0 || it + 1 == max_iter) RW_CHK(fn, hipMemcpy(&st, p.st, sizeof(st), hipMemcpyDeviceToHost));
-    }
-    RW_CHK(fn, hipDeviceSynchronize());
-    std::vector<double> cf(nstates);
-    RW_CHK(fn, hipMemcpy(cf.data(), p.f, (size_t)nstates * sizeof(double), hipMemcpyDeviceToHost));
-    if (logd) {
-        std::vector<double> cl((size_t)nsamples);
-        RW_CHK(fn, hipMemcpy(cl.data(), p.logd, (size_t)nsamples * sizeof(double), hipMemcpyDeviceToHost));
-        const long double g = (st.iters == 1 ? (long double)p.f0 : 0.0L) - p.s0.value(); // behind the first application f[0] = 0
-        for (int64_t i = 0; i < nsamples; ++i) logd[i] = (double)((long double)cl[i] + g);
-    }
-    for (int k = 0; k < nstates; ++k) f[k] = (double)p.s[k].add_to(cf[k], p.s0);
-    *iters = st.iters;
-    *delta = st.delta;
-    return NM_OK;
-}
-
-int nm_reweight_expect(int device, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
-                       const double *e, const double *v, int ntargets, const double *tb, const double *tc, int nobs, const double *obs,
-                       double *tf, double *ess, double *mean, double *cov, double *omean)
-{
-    static const char *const fn = "nm_reweight_expect";
-    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    if (ntargets < 1 || ntargets > 65536) return rwrefuse(fn, "ntargets must lie in 1..65536");
-    if (nobs < 0 || nobs > RW_MAXOBS) return rwrefuse(fn, "nobs must lie in 0..8");
-    if (!tb || !tc || !tf || !ess || !mean || !cov || (nobs > 0 && (!obs || !omean))) return rwrefuse(fn, "a needed pointer is null");
-    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return rwrefuse(fn, "a target's tb or tc is not finite");
-    if (const int rc = rw_device(fn, device)) return rc;
-    RwProblem p;
-    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    const int nbatch = p.batch(RW_NF, 1, RW_TGB);
-    if (const int rc = p.scratch(fn, RW_NF, nbatch)) return rc;
-    DevBuf<double> d_tb, d_tc, d_obs, d_F, d_sums;
-    RW_CHK(fn, d_tb.alloc(ntargets));
-    RW_CHK(fn, d_tc.alloc(ntargets));
-    RW_CHK(fn, d_F.alloc(ntargets));
-    RW_CHK(fn, d_sums.alloc((size_t)ntargets * RW_NF));
-    RW_CHK(fn, hipMemcpy(d_tb, tb, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
-    RW_CHK(fn, hipMemcpy(d_tc, tc, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
-    if (nobs > 0) {
-        RW_CHK(fn, d_obs.alloc((size_t)nobs * nsamples));
-        RW_CHK(fn, hipMemcpy(d_obs, obs, (size_t)nobs * nsamples * sizeof(double), hipMemcpyHostToDevice));
-    }
-    p.denominators();
-    for (int t0 = 0; t0 < ntargets; t0 += nbatch)
-        p.moments<1, true>(t0, (ntargets - t0) < nbatch ? (ntargets - t0) : nbatch, d_tb, d_tc, nobs, d_obs, d_F, d_sums);
-    RW_CHK(fn, hipGetLastError());
-    RW_CHK(fn, hipDeviceSynchronize());
-    std::vector<double> hF(ntargets), hs((size_t)ntargets * RW_NF);
-    RW_CHK(fn, hipMemcpy(hF.data(), d_F, (size_t)ntargets * sizeof(double), hipMemcpyDeviceToHost));
-    RW_CHK(fn, hipMemcpy(hs.data(), d_sums, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int t = 0; t < ntargets; ++t) {
-        const double *q = hs.data() + (size_t)t * RW_NF; // max, sum w, sum w^2, sums of w e, w v, w ee, w ev, w vv, w obs (centred e, v)
-        const long double s0 = q[1];
-        const long double me = q[3] / s0, mv = q[4] / s0;
-        tf[t] = p.shifted(hF[t], tb[t], tc[t]);
-        const long double n_eff = s0 * s0 / q[2];
-        ess[t] = (double)(n_eff < 1.0L ? 1.0L : (n_eff > (long double)nsamples ? (long double)nsamples : n_eff));
-        mean[2 * t] = (double)((long double)p.e0 + me);
-        mean[2 * t + 1] = (double)((long double)p.v0 + mv);
-        cov[3 * t] = (double)(q[5] / s0 - me * me);
-        cov[3 * t + 1] = (double)(q[6] / s0 - me * mv);
-        cov[3 * t + 2] = (double)(q[7] / s0 - mv * mv);
-        for (int j = 0; j < nobs; ++j) omean[(size_t)t * nobs + j] = (double)(q[8 + j] / s0);
-    }
-    return NM_OK;
-}
-
-int nm_reweight_histogram(int device, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
-                          const double *e, const double *v, int ntargets, const double *tb, const double *tc, int nq, const double *x,
-                          int nbins, const double *edges, double *hist, double *outside)
-{
-    static const char *const fn = "nm_reweight_histogram";
-    if (nsamples > RW_HIST_MAXN) return rwrefuse(fn, "nsamples must not exceed 2^28");
-    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    if (ntargets < 1 || ntargets > 65536) return rwrefuse(fn, "ntargets must lie in 1..65536");
-    if (nq < 1 || nq > RW_MAXQ) return rwrefuse(fn, "nq must lie in 1..8");
-    if (nbins < 1 || nbins > RW_MAXBINS) return rwrefuse(fn, "nbins must lie in 1..1024");
-    if (!tb || !tc || !x || !edges || !hist) return rwrefuse(fn, "a needed pointer is null");
-    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return rwrefuse(fn, "a target's tb or tc is not finite");
-    if (!rw_finite(edges, (int64_t)nq * (nbins + 1))) return rwrefuse(fn, "an edge is not finite");
-    for (int q = 0; q < nq; ++q)
-        for (int j = 0; j < nbins; ++j)
-            if (!(edges[(size_t)q * (nbins + 1) + j] < edges[(size_t)q * (nbins + 1) + j + 1])) return rwrefuse(fn, "the edges are not strictly increasing");
-    if (!rw_finite(x, (int64_t)nq * nsamples)) return rwrefuse(fn, "an x is not finite");
-    if (const int rc = rw_device(fn, device)) return rc;
-    RwProblem p;
-    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    const int nbatch = p.batch(2, RW_TB, (ntargets + RW_TB - 1) / RW_TB * RW_TB);
-    if (const int rc = p.scratch(fn, 2, nbatch)) return rc;
-    const int nb2 = nbins + 2, per = nq * nb2;                    // a target's counters: per quantity the bins, below, above
-    const int nlaunch = ntargets < RW_TGB ? ntargets : RW_TGB;
-    const size_t ncount = (size_t)nlaunch * per;
-    DevBuf<double> d_tb, d_tc, d_F, d_edges, d_out;
-    DevBuf<uint16_t> d_code;
-    DevBuf<unsigned long long> d_hi, d_lo;
-    RW_CHK(fn, d_tb.alloc(ntargets));
-    RW_CHK(fn, d_tc.alloc(ntargets));
-    RW_CHK(fn, d_F.alloc(ntargets));
-    RW_CHK(fn, d_edges.alloc((size_t)nq * (nbins + 1)));
-    RW_CHK(fn, d_code.alloc((size_t)nq * nsamples));
-    RW_CHK(fn, d_hi.alloc(ncount));
-    RW_CHK(fn, d_lo.alloc(ncount));
-    RW_CHK(fn, d_out.alloc(ncount));
-    RW_CHK(fn, hipMemcpy(d_tb, tb, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
-    RW_CHK(fn, hipMemcpy(d_tc, tc, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
-    RW_CHK(fn, hipMemcpy(d_edges, edges, (size_t)nq * (nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
-    RW_CHK(fn, hipMemset(d_hi, 0, ncount * sizeof(unsigned long long)));
-    RW_CHK(fn, hipMemset(d_lo, 0, ncount * sizeof(unsigned long long)));
-    {   // the bin codes, a quantity at a time: the quantities themselves do not stay on the device
-        DevBuf<double> d_x;
-        RW_CHK(fn, d_x.alloc((size_t)nsamples));
-        for (int q = 0; q < nq; ++q) {
-            RW_CHK(fn, hipMemcpy(d_x, x + (size_t)q * nsamples, (size_t)nsamples * sizeof(double), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(nm_rw_bins_kernel, dim3((unsigned)((nsamples + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, nsamples, d_x, nbins,
-                               d_edges + (size_t)q * (nbins + 1), d_code + (size_t)q * nsamples);
-        }
-        RW_CHK(fn, hipGetLastError());
-        RW_CHK(fn, hipDeviceSynchronize());
-    }
-    p.denominators();
-    for (int t0 = 0; t0 < ntargets; t0 += nbatch)
-        p.moments<RW_TB, false>(t0, (ntargets - t0) < nbatch ? (ntargets - t0) : nbatch, d_tb, d_tc, 0, nullptr, d_F, nullptr);
-    RW_CHK(fn, hipGetLastError());
-    // the tile of targets: four where their counters stay within RW_HIST_LDS, else two, else one (131,328 B at nq = 8, nbins = 1024)
-    const size_t one = (size_t)per * 2 * sizeof(unsigned long long);
-    const int tt = 4 * one <= (size_t)RW_HIST_LDS ? 4 : 2 * one <= (size_t)RW_HIST_LDS ? 2 : 1;
-    const size_t lds = tt * one;
-    const void *kern = tt == 4 ? (const void *)nm_rw_hist_kernel<4> : tt == 2 ? (const void *)nm_rw_hist_kernel<2> : (const void *)nm_rw_hist_kernel<1>;
-    RW_CHK(fn, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned gx = (unsigned)((p.nchunks + RW_HG - 1) / RW_HG);
-    std::vector<double> out(ncount);
-    for (int t0 = 0; t0 < ntargets; t0 += RW_TGB) {
-        const int nb = (ntargets - t0) < RW_TGB ? (ntargets - t0) : RW_TGB;
-        const dim3 grid(gx, (unsigned)((nb + tt - 1) / tt));
-#define RW_HIST_LAUNCH(TT)                                                                                                                   \
-        hipLaunchKernelGGL(nm_rw_hist_kernel<TT>, grid, dim3(RW_BLOCK), lds, 0, p.N, p.e, p.v, p.logd, t0, t0 + nb, d_tb, d_tc, d_F, nq, nb2, d_code, \
-                           d_hi, d_lo)
-        if (tt == 4) RW_HIST_LAUNCH(4);
-        else if (tt == 2) RW_HIST_LAUNCH(2);
-        else RW_HIST_LAUNCH(1);
-#undef RW_HIST_LAUNCH
-        const int64_t cnt = (int64_t)nb * per;
-        hipLaunchKernelGGL(nm_rw_hist_out_kernel, dim3((unsigned)((cnt + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, cnt, d_hi, d_lo, d_out);
-        RW_CHK(fn, hipGetLastError());
-        RW_CHK(fn, hipMemcpy(out.data(), d_out, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
-        for (int t = 0; t < nb; ++t)
-            for (int q = 0; q < nq; ++q) {
-                const double *src = out.data() + ((size_t)t * nq + q) * nb2;
-                std::copy(src, src + nbins, hist + ((size_t)(t0 + t) * nq + q) * nbins);
-                if (outside) {
-                    outside[((size_t)(t0 + t) * nq + q) * 2] = src[nbins];
-                    outside[((size_t)(t0 + t) * nq + q) * 2 + 1] = src[nbins + 1];
-                }
-            }
-    }
-    return NM_OK;
-}
-} // extern "C"
-
-// ------------------------------------------------------------------------------------------------------------------
-// block-bootstrap replicates of the reweighting (include/nm_reweight_boot.h; kernels: nm_reweight_boot.h)
-// ------------------------------------------------------------------------------------------------------------------
-namespace {
-// what both entry points ask of the replicates
-int rb_check(const char *fn, int nrep, const uint16_t *mult, int64_t nsamples)
-{
-    if (nrep < 1 || nrep > RB_MAXREP) return rwrefuse(fn, "nrep must lie in 1..1024");
-    if (!mult) return rwrefuse(fn, "a needed pointer is null");
-    for (int r = 0; r < nrep; ++r) {
-        const uint16_t *m = mult + (size_t)r * nsamples;
-        int64_t sum = 0;
-        for (int64_t i = 0; i < nsamples; ++i) sum += m[i];
-        if (sum != nsamples) return rwrefuse(fn, "a replicate's multiplicities do not sum to nsamples");
-    }
-    return NM_OK;
-}
-
-// the replicates on the device: the multiplicities, the perturbations d [nrep][K], the tile's weights g [RB_RT][N], and the
-// words that freeze a finished replicate
-struct RbWork {
-    int nrep = 0;
-    DevBuf<uint16_t> mult;
-    DevBuf<double> d, g;
-    DevBuf<int> done;
-    DevBuf<RbControl> ctl;
-    std::vector<double> cf; // the centred base solution as the device holds it
-
-    int setup(const char *fn, const RwProblem &p, int nrep_, const uint16_t *hmult, const std::vector<double> &hd)
-    {
-        nrep = nrep_;
-        const RbControl hc = {0, nrep};
-        RW_CHK(fn, mult.alloc((size_t)nrep * p.N));
-        RW_CHK(fn, d.alloc((size_t)nrep * p.K));
-        RW_CHK(fn, g.alloc((size_t)RB_RT * p.N));
-        RW_CHK(fn, done.alloc(nrep));
-        RW_CHK(fn, ctl.alloc(1));
-        RW_CHK(fn, hipMemcpy(mult, hmult, (size_t)nrep * p.N * sizeof(uint16_t), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemcpy(d, hd.data(), (size_t)nrep * p.K * sizeof(double), hipMemcpyHostToDevice));
-        RW_CHK(fn, hipMemset(done, 0, (size_t)nrep * sizeof(int)));
-        RW_CHK(fn, hipMemcpy(ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
-        return NM_OK;
-    }
-
-    template <bool INV>
-    void weights(const RwProblem &p, int r0, int rt)
-    {
-        hipLaunchKernelGGL((nm_rb_weights_kernel<INV>), dim3((unsigned)((p.N + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, 0, ctl, done, p.N, p.e,
-                           p.v, p.logd, p.ka, p.ab, p.ac, p.alc, p.aidx, p.f, p.K, d, r0, rt, mult, g);
-    }
-};
-} // namespace
-
-extern "C" {
-int nm_reweight_boot_solve(int device, int nstates, const double *b, const double *c, const int64_t *count, int64_t nsamples,
-                           const double *e, const double *v, const double *f, int nrep, const uint16_t *mult, double tol, int max_iter,
-                           double *fr, int *iters, double *delta, int *status)
-{
-    static const char *const fn = "nm_reweight_boot_solve";
-    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    if (!fr || !iters || !delta || !status) return rwrefuse(fn, "a needed pointer is null");
-    if (!(tol >= 0.0)) return rwrefuse(fn, "tol must not be negative");
-    if (max_iter < 1) return rwrefuse(fn, "max_iter must be at least 1");
-    if (const int rc = rb_check(fn, nrep, mult, nsamples)) return rc;
-    if (const int rc = rw_device(fn, device)) return rc;
-    RwProblem p;
-    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    RbWork w;
-    if (const int rc = w.setup(fn, p, nrep, mult, std::vector<double>((size_t)nrep * nstates, 0.0))) return rc;
-    DevBuf<double> d_S, d_part, d_delta;
-    DevBuf<int> d_iters, d_status;
-    std::vector<int> hstatus(nrep, 1), hiters(nrep, 0);
-    std::vector<double> hdelta(nrep, 0.0);
-    RW_CHK(fn, d_S.alloc((size_t)nrep * nstates));
-    RW_CHK(fn, d_part.alloc((size_t)RB_RT * nstates * p.nchunks));
-    RW_CHK(fn, d_delta.alloc(nrep));
-    RW_CHK(fn, d_iters.alloc(nrep));
-    RW_CHK(fn, d_status.alloc(nrep));
-    RW_CHK(fn, hipMemcpy(d_status, hstatus.data(), (size_t)nrep * sizeof(int), hipMemcpyHostToDevice));
-    RW_CHK(fn, hipMemset(d_iters, 0, (size_t)nrep * sizeof(int)));
-    RW_CHK(fn, hipMemset(d_delta, 0, (size_t)nrep * sizeof(double)));
-    p.denominators(); // of the base solution, once
-    RbControl hc = {0, nrep};
-    const dim3 sgrid((unsigned)(p.nchunks * ((nstates + RB_SB - 1) / RB_SB))); // chunk-major: nm_rb_sums_kernel
-    for (int it = 0; it < max_iter && hc.ndone < nrep; ++it) {
-        for (int r0 = 0; r0 < nrep; r0 += RB_RT) {
-            const int rt = (nrep - r0) < RB_RT ? (nrep - r0) : RB_RT;
-            const int64_t rows = (int64_t)rt * nstates;
-            w.weights<false>(p, r0, rt);
-            hipLaunchKernelGGL(nm_rb_sums_kernel, sgrid, dim3(RW_BLOCK), 0, 0, w.ctl, w.done, p.N, p.e, p.v, p.logd, nstates, p.b, p.c, p.f, r0, rt,
-                               w.g, d_part);
-            hipLaunchKernelGGL(nm_rb_combine_kernel<1>, dim3((unsigned)((rows + RW_WAVES - 1) / RW_WAVES)), dim3(RW_BLOCK), 0, 0, w.ctl, w.done, r0,
-                               rt, rows, p.nchunks, d_part, d_S + (size_t)r0 * nstates);
-        }
-        hipLaunchKernelGGL(nm_rb_update_kernel, dim3((unsigned)nrep), dim3(RW_BLOCK), 0, 0, w.ctl, w.done, nstates, d_S, w.d, it == 0 ? p.f0 : 0.0,
-                           tol, d_iters, d_delta, d_status);
-        RW_CHK(fn, hipGetLastError());
-        if ((it + 1) % RB_POLL == 0 || it + 1 == max_iter) RW_CHK(fn, hipMemcpy(&hc, w.ctl, sizeof(hc), hipMemcpyDeviceToHost));
-    }
-    RW_CHK(fn, hipDeviceSynchronize());
-    std::vector<double> cf(nstates), hd((size_t)nrep * nstates);
-    RW_CHK(fn, hipMemcpy(cf.data(), p.f, (size_t)nstates * sizeof(double), hipMemcpyDeviceToHost));
-    RW_CHK(fn, hipMemcpy(hd.data(), w.d, hd.size() * sizeof(double), hipMemcpyDeviceToHost));
-    RW_CHK(fn, hipMemcpy(hiters.data(), d_iters, (size_t)nrep * sizeof(int), hipMemcpyDeviceToHost));
-    RW_CHK(fn, hipMemcpy(hdelta.data(), d_delta, (size_t)nrep * sizeof(double), hipMemcpyDeviceToHost));
-    RW_CHK(fn, hipMemcpy(hstatus.data(), d_status, (size_t)nrep * sizeof(int), hipMemcpyDeviceToHost));
-    for (int r = 0; r < nrep; ++r) {
-        for (int k = 0; k < nstates; ++k)
-            fr[(size_t)r * nstates + k] =
-                hstatus[r] == 2 ? NAN : (double)p.s[k].add_to((long double)cf[k] + hd[(size_t)r * nstates + k], p.s0);
-        iters[r] = hiters[r];
-        delta[r] = hdelta[r];
-        status[r] = hstatus[r];
-    }
-    return NM_OK;
-}
-
-int nm_reweight_boot_expect(int device, int nstates, const double *b, const double *c, const int64_t *count, const double *f,
-                            int64_t nsamples, const double *e, const double *v, int nrep, const uint16_t *mult, const double *fr,
-                            int ntargets, const double *tb, const double *tc, int nobs, const double *obs, double *tf, double *ess,
-                            double *mean, double *cov, double *omean)
-{
-    static const char *const fn = "nm_reweight_boot_expect";
-    if (const int rc = rw_check(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    if (ntargets < 1 || ntargets > 65536) return rwrefuse(fn, "ntargets must lie in 1..65536");
-    if (nobs < 0 || nobs > RW_MAXOBS) return rwrefuse(fn, "nobs must lie in 0..8");
-    if (!tb || !tc || !tf || !ess || !mean || !cov || !fr || (nobs > 0 && (!obs || !omean))) return rwrefuse(fn, "a needed pointer is null");
-    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return rwrefuse(fn, "a target's tb or tc is not finite");
-    if (const int rc = rb_check(fn, nrep, mult, nsamples)) return rc;
-    std::vector<char> skip(nrep, 0); // a replicate without a solution: NaN in, NaN out
-    for (int r = 0; r < nrep; ++r)
-        for (int k = 0; k < nstates; ++k) {
-            const double x = fr[(size_t)r * nstates + k];
-            if (std::isinf(x)) return rwrefuse(fn, "an fr is neither finite nor NaN");
-            if (std::isnan(x)) skip[r] = 1;
-        }
-    if (const int rc = rw_device(fn, device)) return rc;
-    RwProblem p;
-    if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;
-    std::vector<double> cf(nstates), hd((size_t)nrep * nstates, 0.0);
-    RW_CHK(fn, hipMemcpy(cf.data(), p.f, (size_t)nstates * sizeof(double), hipMemcpyDeviceToHost));
-    for (int r = 0; r < nrep; ++r) {
-        if (skip[r]) continue;
-        const double *x = fr + (size_t)r * nstates;
-        for (int k = 0; k < nstates; ++k) hd[(size_t)r * nstates + k] = (double)(p.s[k].take_from(x[k], x[0], p.s0) - (long double)cf[k]);
-    }
-    RbWork w;
-    if (const int rc = w.setup(fn, p, nrep, mult, hd)) return rc;
-    DevBuf<double> d_tb, d_tc, d_obs, d_F, d_part, d_sums;
-    RW_CHK(fn, d_tb.alloc(ntargets));
-    RW_CHK(fn, d_tc.alloc(ntargets));
-    RW_CHK(fn, d_F.alloc(ntargets));
-    RW_CHK(fn, hipMemcpy(d_tb, tb, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
-    RW_CHK(fn, hipMemcpy(d_tc, tc, (size_t)ntargets * sizeof(double), hipMemcpyHostToDevice));
-    if (nobs > 0) {
-        RW_CHK(fn, d_obs.alloc((size_t)nobs * nsamples));
-        RW_CHK(fn, hipMemcpy(d_obs, obs, (size_t)nobs * nsamples * sizeof(double), hipMemcpyHostToDevice));
-    }
-    {   // the base tf of every target with the existing kernels: the scale that keeps q_t(n) <= 1
-        const int nb2 = p.batch(2, RW_TB, (ntargets + RW_TB - 1) / RW_TB * RW_TB);
-        if (const int rc = p.scratch(fn, 2, nb2)) return rc;
-        p.denominators();
-        for (int t0 = 0; t0 < ntargets; t0 += nb2)
-            p.moments<RW_TB, false>(t0, (ntargets - t0) < nb2 ? (ntargets - t0) : nb2, d_tb, d_tc, 0, nullptr, d_F, nullptr);
-        RW_CHK(fn, hipGetLastError());
-    }
-    std::vector<double> hF(ntargets);
-    RW_CHK(fn, hipMemcpy(hF.data(), d_F, (size_t)ntargets * sizeof(double), hipMemcpyDeviceToHost));
-    const int64_t nech = (p.N + RB_ECH - 1) / RB_ECH; // the expectation kernel's own chunks
-    int64_t nbatch = ((int64_t)1 << 24) / ((int64_t)RB_RT * nech * RB_NS); // the partials stay within 128 MiB (one target at least)
-    nbatch = nbatch < 1 ? 1 : nbatch > RW_TGB ? RW_TGB : nbatch;
-    RW_CHK(fn, d_part.alloc((size_t)nbatch * RB_RT * nech * RB_NS));
-    RW_CHK(fn, d_sums.alloc((size_t)nbatch * RB_RT * RB_NS));
-    std::vector<double> hs((size_t)nbatch * RB_RT * RB_NS);
-    for (int r0 = 0; r0 < nrep; r0 += RB_RT) {
-        const int rt = (nrep - r0) < RB_RT ? (nrep - r0) : RB_RT;
-        w.weights<true>(p, r0, rt);
-        for (int t0 = 0; t0 < ntargets; t0 += (int)nbatch) {
-            const int nb = (ntargets - t0) < nbatch ? (ntargets - t0) : (int)nbatch;
-            const int64_t rows = (int64_t)nb * rt;
-            const int tt = nobs > 0 ? RB_ETO : RB_ET;
-            const dim3 egrid((unsigned)(nech * ((nb + tt - 1) / tt) * ((rt + RB_RE - 1) / RB_RE)));
-            if (nobs > 0)
-                hipLaunchKernelGGL((nm_rb_expect_kernel<RB_ETO, RB_NS>), egrid, dim3(RW_BLOCK), 0, 0, p.N, p.e, p.v, p.logd, t0, nb, d_tb, d_tc, d_F, nobs,
-                                   d_obs, r0, rt, w.mult, w.g, d_part);
-            else
-                hipLaunchKernelGGL((nm_rb_expect_kernel<RB_ET, 7>), egrid, dim3(RW_BLOCK), 0, 0, p.N, p.e, p.v, p.logd, t0, nb, d_tb, d_tc, d_F, nobs,
-                                   d_obs, r0, rt, w.mult, w.g, d_part);
-            hipLaunchKernelGGL(nm_rb_combine_kernel<RB_NS>, dim3((unsigned)((rows + RW_WAVES - 1) / RW_WAVES)), dim3(RW_BLOCK), 0, 0, w.ctl, nullptr, r0,
-                               rt, rows, nech, d_part, d_sums);
-            RW_CHK(fn, hipGetLastError());
-            RW_CHK(fn, hipMemcpy(hs.data(), d_sums, (size_t)rows * RB_NS * sizeof(double), hipMemcpyDeviceToHost));
-            for (int t = 0; t < nb; ++t) {
-                const RwOffset st(tb[t0 + t], tc[t0 + t], p.e0, p.v0);
-                for (int j = 0; j < rt; ++j) {
-                    const size_t o = (size_t)(r0 + j) * ntargets + t0 + t;
-                    if (skip[r0 + j]) {
-                        tf[o] = ess[o] = mean[2 * o] = mean[2 * o + 1] = cov[3 * o] = cov[3 * o + 1] = cov[3 * o + 2] = NAN;
-                        for (int q = 0; q < nobs; ++q) omean[o * nobs + q] = NAN;
-                        continue;
-                    }
-                    const double *q = hs.data() + ((size_t)t * rt + j) * RB_NS; // sums of x = m w, x w, x e, x v, x ee, x ev, x vv, x obs
-                    const long double s0 = q[0];
-                    const long double me = q[2] / s0, mv = q[3] / s0;
-                    tf[o] = (double)(st.add_to((long double)hF[t0 + t] - logl(s0), p.s0) + fr[(size_t)(r0 + j) * nstates]);
-                    const long double n_eff = s0 * s0 / q[1];
-                    ess[o] = (double)(n_eff < 1.0L ? 1.0L : (n_eff > (long double)nsamples ? (long double)nsamples : n_eff));
-                    mean[2 * o] = (double)((long double)p.e0 + me);
-                    mean[2 * o + 1] = (double)((long double)p.v0 + mv);
-                    cov[3 * o] = (double)(q[4] / s0 - me * me);
-                    cov[3 * o + 1] = (double)(q[5] / s0 - me * mv);
-                    cov[3 * o + 2] = (double)(q[6] / s0 - mv * mv);
-                    for (int k = 0; k < nobs; ++k) omean[o * nobs + k] = (double)(q[7 + k] / s0);
-                }
-            }
-        }
-    }
-    return NM_OK;
-}
 } // extern "C"

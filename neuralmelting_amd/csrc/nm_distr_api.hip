@@ -1,0 +1,490 @@
+// nm_distr_api.hip — the structural histograms and order parameters of include/nm_distr.h over the kernels of nm_distr.h
+// (lammps_distr.py:123-171).  Every entry point takes a device ordinal, owns what it allocates for the length of the call and
+// walks the samples in chunks.
+#include "../../include/nm_distr.h"
+#include "nm_distr.h"
+#include "nm_host.h"
+
+#include <cmath>
+#include <type_traits>
+#include <vector>
+
+using namespace nm;
+
+namespace {
+thread_local std::string g_distr_error;
+std::string &stage_error() { return g_distr_error; }
+
+constexpr int DISTR_CHUNK = 4096; // most samples per launch: bounds device memory (pos 12 N B + results) for long trajectories
+
+// The chunk loop of an entry point: the device copies of `cs` samples' positions and boxes, filled for one chunk after the
+// other; body(s0, n) computes the samples s0 .. s0 + n - 1 from them (launch, synchronise, copy back) and returns NM_OK or
+// what it failed with.
+struct DistrChunks {
+    DevBuf<float> pos, box;
+    template <class Body>
+    int run(const char *fn, int ns, int cs, int natoms, const float *h_pos, const float *h_box, Body &&body)
+    {
+        STAGE_CHK(fn, pos.alloc((size_t)cs * natoms * 3));
+        STAGE_CHK(fn, box.alloc((size_t)cs));
+        for (int s0 = 0; s0 < ns; s0 += cs) {
+            const int n = batch_rest(ns, s0, cs);
+            STAGE_CHK(fn, hipMemcpy(pos, h_pos + (size_t)s0 * natoms * 3, (size_t)n * natoms * 3 * sizeof(float), hipMemcpyHostToDevice));
+            STAGE_CHK(fn, hipMemcpy(box, h_box + s0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+            const int rc = body(s0, n);
+            if (rc != NM_OK) return rc;
+        }
+        return NM_OK;
+    }
+};
+
+int distr_boxes_check(const char *fn, int ns, const float *box)
+{
+    for (int s = 0; s < ns; ++s)
+        if (!(box[s] > 0.0f) || !std::isfinite(box[s])) return refuse(fn, "a box is not finite and positive");
+    return NM_OK;
+}
+
+// the neighbour shell of nm_distr_angles and nm_distr_bondorder
+int shell_check(const char *fn, double r_lo, double r_hi)
+{
+    if (!(r_lo >= 0.0) || !(r_lo < r_hi)) return refuse(fn, "the shell needs 0 <= r_lo < r_hi");
+    return NM_OK;
+}
+
+// beyond half the smallest box an atom could neighbour its own image (a zero angle that is no bond angle)
+int half_box_check(const char *fn, int ns, const float *box, double r_hi)
+{
+    for (int s = 0; s < ns; ++s)
+        if (!(r_hi <= 0.5 * (double)box[s])) return refuse(fn, "r_hi exceeds half the smallest box");
+    return NM_OK;
+}
+
+// the image pre-test of the scan compares float components with a float at or above r_hi; it is switched off for shells
+// so small that the squares of such components could underflow
+float shell_cube(double r_hi) { return r_hi < 1.0e-15 ? INFINITY : nextafterf((float)r_hi, INFINITY); }
+
+// what the bond-order kernels need to know of the requested l (nm_distr.h, BoSet); ls increases strictly within 1..12
+BoSet bo_set(int nl, const int *ls)
+{
+    BoSet set = {nl, 0, ls[nl - 1], 0u, 0ull, 0u};
+    for (int i = 0; i < nl; ++i) {
+        const int l = ls[i];
+        set.lmask |= 1u << l;
+        if (l <= 8) set.off_lo |= (unsigned long long)set.nc << (8 * (l - 1));
+        else set.off_hi |= (unsigned int)set.nc << (8 * (l - 9));
+        set.nc += l + 1;
+    }
+    return set;
+}
+
+// the constants of the harmonics' recurrence (nm_distr.h): long double, rounded once
+std::vector<double> bo_table()
+{
+    const int W = BO_LMAX + 1;
+    std::vector<double> tab((size_t)BO_TAB, 0.0);
+    long double c = sqrtl(1.0L / (4.0L * 3.14159265358979323846264338327950288L));
+    for (int m = 0; m <= BO_LMAX; ++m) {
+        if (m > 0) c = -c * sqrtl((long double)(2 * m + 1) / (long double)(2 * m));
+        tab[m] = (double)c;
+        for (int l = m + 1; l <= BO_LMAX; ++l) {
+            tab[W + l * W + m] = (double)sqrtl((long double)(4 * l * l - 1) / (long double)(l * l - m * m));
+            tab[W + W * W + l * W + m] = (double)sqrtl((long double)((l - 1) * (l - 1) - m * m) / (long double)(4 * (l - 1) * (l - 1) - 1));
+        }
+    }
+    return tab;
+}
+
+// samples per launch of the entry points that keep the moments q_lm in a device scratch of `per` bytes per sample: at most
+// DISTR_CHUNK as the other entry points, fewer where the scratch would pass 256 MiB
+int bo_chunk(int ns, size_t per)
+{
+    size_t fit = ((size_t)256 << 20) / per;
+    if (fit < 1) fit = 1;
+    int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    if ((size_t)cs > fit) cs = (int)fit;
+    return cs;
+}
+
+// An optional per-sample output: the caller's array (null: not wanted), its `per` values per sample, and the chunk's device
+// copy.  The device pointer stays null with the caller's, and the kernels branch on that.  `always`: a later kernel reads the
+// device copy whether or not the caller wants it, so it is allocated (and passed) either way and only the copy-back is optional.
+template <class T> struct DistrOut {
+    T *const host;
+    const size_t per;
+    const bool always;
+    DevBuf<T> d;
+    DistrOut(T *host_, size_t per_, bool always_ = false) : host(host_), per(per_), always(always_) {}
+    hipError_t alloc(int cs) { return host || always ? d.alloc((size_t)cs * per) : hipSuccess; }
+    hipError_t zero(int n) { return host ? d.zero((size_t)n * per) : hipSuccess; }
+    hipError_t fetch(int s0, int n) const { return host ? d.download(host + (size_t)s0 * per, (size_t)n * per) : hipSuccess; }
+    operator T *() const { return d; }
+};
+
+// The first pass of nm_distr_bondorder and nm_distr_solid: the moments q_lm of every atom for the requested l, with what it
+// needs on the device (the recurrence's table, the moments, the per-group partial sums and counts) and the chunk that keeps
+// the moments within bo_chunk's cap.
+struct BoMoments {
+    BoSet set;
+    int nc2, groups, cs;
+    float cube;
+    size_t lds;
+    DevBuf<double> tab, qlm, part;
+    DevBuf<int> cnt;
+
+    int setup(const char *fn, int ns, int natoms, int nl, const int *ls, double r_hi)
+    {
+        set = bo_set(nl, ls);
+        nc2 = 2 * set.nc;
+        const std::vector<double> htab = bo_table();
+        cube = shell_cube(r_hi);
+        groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+        cs = bo_chunk(ns, (size_t)natoms * nc2 * sizeof(double));
+        lds = bo_lds_bytes(natoms, set.nc, true); // at most 98,932 B (4095 atoms, six l from 7 to 12)
+        STAGE_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        STAGE_CHK(fn, tab.upload(htab.data(), htab.size()));
+        STAGE_CHK(fn, qlm.alloc((size_t)cs * natoms * nc2));
+        STAGE_CHK(fn, part.alloc((size_t)cs * groups * nc2));
+        STAGE_CHK(fn, cnt.alloc((size_t)cs * groups));
+        return NM_OK;
+    }
+
+    // the moments of the chunk's n samples; q2 and nnb: null, or where the kernel leaves q_l^2 and the neighbour counts
+    void launch(int n, int natoms, const float *pos, const float *box, double r_lo, double r_hi, double *q2, int *nnb)
+    {
+        hipLaunchKernelGGL(nm_bo_moments_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, pos, box, r_lo, r_hi, cube, set, tab,
+                           qlm, q2, nnb, part, cnt);
+    }
+};
+} // namespace
+
+extern "C" {
+
+const char *nm_distr_last_error(void) { return g_distr_error.c_str(); }
+
+int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const float *box, int sbins, const double *r_edges,
+                        int cbins, const double *rv_edges, float *rdf, float *cdf)
+{
+    static const char *const fn = "nm_distr_histograms";
+    if (ns < 0 || natoms < 1 || !pos || !box) return refuse(fn, "bad argument");
+    if (rdf && (!r_edges || sbins < 2 || sbins > DISTR_MAXS)) return refuse(fn, "bad spherical bins");
+    if (cdf && (!rv_edges || cbins < 1 || cbins > DISTR_MAXC)) return refuse(fn, "bad cartesian bins");
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const int sb = rdf ? sbins : 0, cb = cdf ? cbins : 0;
+    const size_t nc = (size_t)cb * cb * cb;
+    const size_t lds = distr_lds_bytes(natoms, sb, cb);
+    if (lds > 160 * 1024) return refuse(fn, "working set exceeds LDS");
+    // one image block's count of a bin is at most natoms^2, exact as a float below 2^24; the sum of the 27 blocks can exceed
+    // natoms^2 (a displacement on +-l/2 lies in the closed cube in two images per axis) and is checked after the copy-back
+    if (natoms >= 4096) return refuse(fn, "natoms^2 must stay below 2^24 (float32 counts of one periodic image)");
+    STAGE_CHK(fn, hipFuncSetAttribute((const void *)nm_distr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    DevBuf<double> d_re, d_ve;
+    DistrOut<float> d_r(rdf, sbins), d_c(cdf, nc);
+    if (rdf) STAGE_CHK(fn, d_re.upload(r_edges, sbins));
+    STAGE_CHK(fn, d_r.alloc(cs));
+    if (cdf) STAGE_CHK(fn, d_ve.upload(rv_edges, cbins + 1));
+    STAGE_CHK(fn, d_c.alloc(cs));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        STAGE_CHK(fn, d_r.zero(n));
+        STAGE_CHK(fn, d_c.zero(n));
+        hipLaunchKernelGGL(nm_distr_kernel, dim3(n * 27), dim3(DISTR_BLOCK), lds, 0, natoms, ch.pos, ch.box, sb, d_re, cb, d_ve, d_r, d_c);
+        STAGE_CHK(fn, hipGetLastError());
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_r.fetch(s0, n));
+        STAGE_CHK(fn, d_c.fetch(s0, n));
+        // every partial sum below 2^24 is exact, so a total reaches 2^24 exactly when the returned float does; from there on
+        // the float atomics round in the order they land, and the counts are no longer the reference's
+        bool big = false;
+        if (rdf) for (size_t i = 0; i < (size_t)n * sbins; ++i) big |= rdf[(size_t)s0 * sbins + i] >= 16777216.0f;
+        if (cdf) for (size_t i = 0; i < (size_t)n * nc; ++i) big |= cdf[(size_t)s0 * nc + i] >= 16777216.0f;
+        if (big) return refuse(fn, "a bin holds 2^24 counts or more, beyond what float32 counts hold exactly");
+        return NM_OK;
+    });
+}
+
+int nm_distr_angles(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int abins,
+                    const double *cos_edges, uint64_t *adf)
+{
+    static const char *const fn = "nm_distr_angles";
+    if (ns < 0 || !pos || !box || !cos_edges || !adf) return refuse(fn, "bad argument");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (abins < 2 || abins > ADF_MAXB) return refuse(fn, "abins must lie in 2..256");
+    for (int k = 0; k + 1 < abins; ++k)
+        if (!(cos_edges[k] > cos_edges[k + 1])) return refuse(fn, "cos_edges must decrease strictly");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const float cube = shell_cube(r_hi);
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const size_t lds = adf_lds_bytes(natoms, abins); // at most 109,652 B (natoms 4095, abins 256)
+    STAGE_CHK(fn, hipFuncSetAttribute((const void *)nm_adf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DevBuf<double> d_e;
+    DevBuf<unsigned long long> d_a;
+    STAGE_CHK(fn, d_e.upload(cos_edges, abins));
+    STAGE_CHK(fn, d_a.alloc((size_t)cs * abins));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        STAGE_CHK(fn, d_a.zero((size_t)n * abins));
+        hipLaunchKernelGGL(nm_adf_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, abins, d_e, d_a);
+        STAGE_CHK(fn, hipGetLastError());
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, hipMemcpy(adf + (size_t)s0 * abins, d_a, (size_t)n * abins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        return NM_OK;
+    });
+}
+
+int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const float *box, int qmax, double *sf_sum, double *sf_max)
+{
+    static const char *const fn = "nm_distr_sfactor";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!sf_sum && !sf_max) return refuse(fn, "sf_sum and sf_max are both null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (qmax < 1 || qmax > SF_QMAX) return refuse(fn, "qmax must lie in 1..32");
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    // the work items (nm_distr.h): every (h >= 0, k >= 0, l0) whose chunk l0 .. l0 + SF_LB - 1 reaches into the sphere, l0 slowest
+    std::vector<unsigned int> items;
+    for (int l0 = 0; l0 <= qmax; l0 += SF_LB)
+        for (int h = 0; h <= qmax; ++h)
+            for (int k = 0; k <= qmax; ++k)
+                if (h * h + k * k + l0 * l0 <= qmax * qmax) items.push_back(sf_item(h, k, l0));
+    const int nitems = (int)items.size();
+    const size_t nsh = (size_t)qmax * qmax + 1;
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    const size_t lds = sf_lds_bytes(qmax); // below the 64 KiB a kernel gets without asking
+    DevBuf<unsigned int> d_it;
+    DistrOut<double> d_sum(sf_sum, nsh), d_max(sf_max, nsh);
+    STAGE_CHK(fn, d_it.upload(items.data(), nitems));
+    STAGE_CHK(fn, d_sum.alloc(cs));
+    STAGE_CHK(fn, d_max.alloc(cs));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        hipLaunchKernelGGL(nm_sfac_kernel, dim3(n), dim3(SF_BLOCK), lds, 0, natoms, ch.pos, ch.box, qmax, nitems, d_it, d_sum, d_max);
+        STAGE_CHK(fn, hipGetLastError());
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_sum.fetch(s0, n));
+        STAGE_CHK(fn, d_max.fetch(s0, n));
+        return NM_OK;
+    });
+}
+
+int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
+                       const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb)
+{
+    static const char *const fn = "nm_distr_bondorder";
+    if (ns < 0 || !pos || !box || !ls) return refuse(fn, "bad argument");
+    if (!q2 && !qbar2 && !Q2 && !nnb) return refuse(fn, "all four outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (nl < 1 || nl > BO_MAXL) return refuse(fn, "nl must lie in 1..6");
+    for (int i = 0; i < nl; ++i)
+        if (ls[i] < 1 || ls[i] > BO_LMAX || (i > 0 && ls[i] <= ls[i - 1]))
+            return refuse(fn, "ls must increase strictly within 1..12");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    BoMoments m;
+    if (const int rc = m.setup(fn, ns, natoms, nl, ls, r_hi)) return rc;
+    const size_t lds2 = bo_lds_bytes(natoms, m.set.nc, false); // below the moments kernel's
+    STAGE_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    const size_t pa = (size_t)natoms * nl;
+    DistrOut<double> d_q2(q2, pa), d_qb(qbar2, pa), d_Q(Q2, nl);
+    DistrOut<int> d_nnb(nnb, natoms);
+    STAGE_CHK(fn, d_q2.alloc(m.cs));
+    STAGE_CHK(fn, d_qb.alloc(m.cs));
+    STAGE_CHK(fn, d_Q.alloc(m.cs));
+    STAGE_CHK(fn, d_nnb.alloc(m.cs));
+    DistrChunks ch;
+    return ch.run(fn, ns, m.cs, natoms, pos, box, [&](int s0, int n) -> int {
+        m.launch(n, natoms, ch.pos, ch.box, r_lo, r_hi, d_q2, d_nnb);
+        STAGE_CHK(fn, hipGetLastError());
+        if (qbar2) {
+            hipLaunchKernelGGL(nm_bo_average_kernel, dim3(n * m.groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, m.cube,
+                               m.set, m.qlm, d_qb);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        if (Q2) {
+            hipLaunchKernelGGL(nm_bo_global_kernel, dim3(n), dim3(128), 0, 0, m.groups, m.set, m.part, m.cnt, d_Q);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_q2.fetch(s0, n));
+        STAGE_CHK(fn, d_qb.fetch(s0, n));
+        STAGE_CHK(fn, d_Q.fetch(s0, n));
+        STAGE_CHK(fn, d_nnb.fetch(s0, n));
+        return NM_OK;
+    });
+}
+
+int nm_distr_solid(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int l, double s_min,
+                   int n_min, int32_t *nconn, int32_t *label, int32_t *nsolid, int32_t *nclus, int32_t *largest)
+{
+    static const char *const fn = "nm_distr_solid";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!nconn && !label && !nsolid && !nclus && !largest) return refuse(fn, "all five outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (l < 1 || l > BO_LMAX) return refuse(fn, "l must lie in 1..12");
+    if (!(s_min >= -1.0) || !(s_min < 1.0)) return refuse(fn, "s_min must lie in [-1, 1)");
+    if (n_min < 1) return refuse(fn, "n_min must be at least 1");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    BoMoments m;
+    if (const int rc = m.setup(fn, ns, natoms, 1, &l, r_hi)) return rc;
+    const int cs = m.cs, groups = m.groups;
+    const float cube = m.cube;
+    const size_t lds2 = solid_lds_bytes(natoms); // at most 51,284 B (4095 atoms)
+    // the kernels pass all five on to one another, so the device holds them whatever the caller asks for
+    DistrOut<int> d_conn(nconn, natoms, true), d_lab(label, natoms, true), d_ns(nsolid, 1, true), d_nc(nclus, 1, true), d_big(largest, 1, true);
+    DevBuf<int> d_par;
+    STAGE_CHK(fn, d_conn.alloc(cs));
+    STAGE_CHK(fn, d_par.alloc((size_t)cs * natoms));
+    STAGE_CHK(fn, d_lab.alloc(cs));
+    STAGE_CHK(fn, d_ns.alloc(cs));
+    STAGE_CHK(fn, d_nc.alloc(cs));
+    STAGE_CHK(fn, d_big.alloc(cs));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        // each kernel reads what the one before it wrote for the whole chunk: the launches of one stream run in order
+        m.launch(n, natoms, ch.pos, ch.box, r_lo, r_hi, nullptr, nullptr);
+        STAGE_CHK(fn, hipGetLastError());
+        hipLaunchKernelGGL(nm_solid_connect_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, l,
+                           s_min, m.qlm, d_conn, d_par);
+        STAGE_CHK(fn, hipGetLastError());
+        hipLaunchKernelGGL(nm_solid_union_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube, n_min,
+                           d_conn, d_par);
+        STAGE_CHK(fn, hipGetLastError());
+        hipLaunchKernelGGL(nm_solid_label_kernel, dim3(n), dim3(SOLID_BLOCK), 0, 0, natoms, n_min, d_conn, d_par, d_lab, d_ns, d_nc, d_big);
+        STAGE_CHK(fn, hipGetLastError());
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_conn.fetch(s0, n));
+        STAGE_CHK(fn, d_lab.fetch(s0, n));
+        STAGE_CHK(fn, d_ns.fetch(s0, n));
+        STAGE_CHK(fn, d_nc.fetch(s0, n));
+        STAGE_CHK(fn, d_big.fetch(s0, n));
+        return NM_OK;
+    });
+}
+
+int nm_distr_cna(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int mode,
+                 int32_t *type, int32_t *sig, int32_t *ntype, int32_t *nsig)
+{
+    static const char *const fn = "nm_distr_cna";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!type && !sig && !ntype && !nsig) return refuse(fn, "all four outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (mode != NM_CNA_FIXED && mode != NM_CNA_ADAPTIVE) return refuse(fn, "mode must be NM_CNA_FIXED or NM_CNA_ADAPTIVE");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    const size_t lds = cna_lds_bytes(natoms); // at most 51,604 B (4095 atoms)
+    if (lds > 160 * 1024) return refuse(fn, "working set exceeds LDS");
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const float cube = shell_cube(r_hi);
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const size_t pa = (size_t)natoms, ps = pa * CNA_NSIG;
+    const int cs = bo_chunk(ns, ps * sizeof(int)); // the per-atom columns are the largest device array
+    DistrOut<int> d_type(type, pa), d_sig(sig, ps), d_ntype(ntype, CNA_NTYPE), d_nsig(nsig, CNA_NSIG);
+    STAGE_CHK(fn, d_type.alloc(cs));
+    STAGE_CHK(fn, d_sig.alloc(cs));
+    STAGE_CHK(fn, d_ntype.alloc(cs));
+    STAGE_CHK(fn, d_nsig.alloc(cs));
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        // the per-sample sums are added to by every workgroup of the sample
+        STAGE_CHK(fn, d_ntype.zero(n));
+        STAGE_CHK(fn, d_nsig.zero(n));
+        hipLaunchKernelGGL(nm_cna_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds, 0, natoms, ch.pos, ch.box, r_lo, r_hi, cube,
+                           mode == NM_CNA_ADAPTIVE, d_type, d_sig, d_ntype, d_nsig);
+        STAGE_CHK(fn, hipGetLastError());
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_type.fetch(s0, n));
+        STAGE_CHK(fn, d_sig.fetch(s0, n));
+        STAGE_CHK(fn, d_ntype.fetch(s0, n));
+        STAGE_CHK(fn, d_nsig.fetch(s0, n));
+        return NM_OK;
+    });
+}
+
+int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const float *box, double r_m, double sigma, int nbins, double r_avg,
+                     double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean, int32_t *nlow)
+{
+    static const char *const fn = "nm_distr_entropy";
+    if (ns < 0 || !pos || !box) return refuse(fn, "bad argument");
+    if (!s && !sbar && !nnb && !smean && !sbarmean && !nlow) return refuse(fn, "all six outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (nbins < 1 || nbins > ENT_MAXBINS) return refuse(fn, "nbins must lie in 1..1024");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return refuse(fn, "sigma must be positive and finite");
+    if (!(r_m > 0.0) || !std::isfinite(r_m)) return refuse(fn, "r_m must be positive and finite");
+    if (!(r_avg > 0.0)) return refuse(fn, "r_avg must be positive");
+    if (s_cut != s_cut) return refuse(fn, "s_cut is not a number");
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    for (int i = 0; i < ns; ++i)
+        if (!(r_m <= 0.5 * (double)box[i]) || !(r_avg <= 0.5 * (double)box[i])) return refuse(fn, "r_m or r_avg exceeds half the smallest box");
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    const bool average = sbar || sbarmean || nlow, means = smean || sbarmean || nlow;
+    const float cube_m = shell_cube(r_m), cube_a = shell_cube(r_avg);
+    const double D = r_m / (double)nbins, inv2s2 = 1.0 / (2.0 * (sigma * sigma));
+    const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
+    const int cs = ns < DISTR_CHUNK ? ns : DISTR_CHUNK;
+    const size_t lds1 = ent_lds_bytes(natoms, false), lds2 = ent_lds_bytes(natoms, true); // at most 49,284 B and 51,332 B (4095 atoms)
+    DistrOut<double> d_s(s, natoms, true), d_b(sbar, natoms), d_sm(smean, 1), d_bm(sbarmean, 1); // s: pass 2 reads it, whether or not the caller asks for it
+    DistrOut<int> d_nnb(nnb, natoms), d_low(nlow, 1);
+    DevBuf<double> d_ps, d_pb;
+    DevBuf<int> d_pl;
+    STAGE_CHK(fn, d_s.alloc(cs));
+    STAGE_CHK(fn, d_ps.alloc((size_t)cs * groups));
+    STAGE_CHK(fn, d_nnb.alloc(cs));
+    STAGE_CHK(fn, d_b.alloc(cs));
+    if (average) {
+        STAGE_CHK(fn, d_pb.alloc((size_t)cs * groups));
+        STAGE_CHK(fn, d_pl.alloc((size_t)cs * groups));
+    }
+    STAGE_CHK(fn, d_sm.alloc(cs));
+    STAGE_CHK(fn, d_bm.alloc(cs));
+    STAGE_CHK(fn, d_low.alloc(cs));
+    const int points = nbins + 1; // a lane owns ceil(points / 64) grid points: the next instantiation that holds them
+    DistrChunks ch;
+    return ch.run(fn, ns, cs, natoms, pos, box, [&](int s0, int n) -> int {
+        auto local = [&](auto na) {
+            hipLaunchKernelGGL(nm_ent_local_kernel<decltype(na)::value>, dim3(n * groups), dim3(SHELL_BLOCK), lds1, 0, natoms, ch.pos, ch.box, r_m,
+                               cube_m, sigma, inv2s2, nbins, D, d_s, d_nnb, d_ps);
+        };
+        if (points <= 64) local(std::integral_constant<int, 1>());
+        else if (points <= 128) local(std::integral_constant<int, 2>());
+        else if (points <= 256) local(std::integral_constant<int, 4>());
+        else if (points <= 512) local(std::integral_constant<int, 8>());
+        else local(std::integral_constant<int, ENT_MAXACC>());
+        STAGE_CHK(fn, hipGetLastError());
+        if (average) {
+            hipLaunchKernelGGL(nm_ent_average_kernel, dim3(n * groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_avg, cube_a, s_cut,
+                               d_s, d_b, d_pb, d_pl);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        if (means) {
+            hipLaunchKernelGGL(nm_ent_mean_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, n, natoms, groups, d_ps, d_pb, d_pl, d_sm, d_bm, d_low);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_s.fetch(s0, n));
+        STAGE_CHK(fn, d_b.fetch(s0, n));
+        STAGE_CHK(fn, d_nnb.fetch(s0, n));
+        STAGE_CHK(fn, d_sm.fetch(s0, n));
+        STAGE_CHK(fn, d_bm.fetch(s0, n));
+        STAGE_CHK(fn, d_low.fetch(s0, n));
+        return NM_OK;
+    });
+}
+
+} // extern "C"
