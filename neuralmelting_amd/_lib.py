@@ -37,6 +37,8 @@ REWEIGHT_SYMBOLS = ('nm_reweight_solve', 'nm_reweight_expect', 'nm_reweight_last
 REWEIGHT_HIST_SYMBOLS = ('nm_reweight_histogram',)
 # include/nm_reweight_boot.h
 REWEIGHT_BOOT_SYMBOLS = ('nm_reweight_boot_solve', 'nm_reweight_boot_expect')
+# include/nm_pca.h
+PCA_SYMBOLS = ('nm_pca_moments', 'nm_pca_project', 'nm_pca_last_timing', 'nm_pca_last_error')
 
 
 class NMConfig(C.Structure):
@@ -156,5 +158,12 @@ def load():
                                           C.c_int, C.POINTER(C.c_uint16), c_double_p, C.c_int, c_double_p, c_double_p, C.c_int, c_double_p,
                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.nm_reweight_last_error.restype = C.c_char_p
+    L.nm_pca_moments.restype = C.c_int
+    L.nm_pca_moments.argtypes = [C.c_int, C.c_int64, C.c_int, c_float_p, c_double_p, c_double_p, c_double_p, c_double_p]
+    L.nm_pca_project.restype = C.c_int
+    L.nm_pca_project.argtypes = [C.c_int, C.c_int64, C.c_int, c_float_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p]
+    L.nm_pca_last_timing.restype = C.c_int
+    L.nm_pca_last_timing.argtypes = [c_double_p]
+    L.nm_pca_last_error.restype = C.c_char_p
     _lib = L
     return L
