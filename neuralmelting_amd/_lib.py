@@ -39,6 +39,8 @@ REWEIGHT_HIST_SYMBOLS = ('nm_reweight_histogram',)
 REWEIGHT_BOOT_SYMBOLS = ('nm_reweight_boot_solve', 'nm_reweight_boot_expect')
 # include/nm_pca.h
 PCA_SYMBOLS = ('nm_pca_moments', 'nm_pca_project', 'nm_pca_last_timing', 'nm_pca_last_error')
+# include/nm_cluster.h
+CLUSTER_SYMBOLS = ('nm_cluster_dbscan', 'nm_cluster_last_timing', 'nm_cluster_last_error')
 
 
 class NMConfig(C.Structure):
@@ -165,5 +167,10 @@ def load():
     L.nm_pca_last_timing.restype = C.c_int
     L.nm_pca_last_timing.argtypes = [c_double_p]
     L.nm_pca_last_error.restype = C.c_char_p
+    L.nm_cluster_dbscan.restype = C.c_int
+    L.nm_cluster_dbscan.argtypes = [C.c_int, C.c_int64, C.c_int, c_double_p, C.c_double, C.c_int, c_int32_p, c_int32_p, c_int32_p]
+    L.nm_cluster_last_timing.restype = C.c_int
+    L.nm_cluster_last_timing.argtypes = [c_double_p]
+    L.nm_cluster_last_error.restype = C.c_char_p
     _lib = L
     return L

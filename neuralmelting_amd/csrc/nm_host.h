@@ -1,5 +1,5 @@
-// nm_host.h — the host scaffold of the offline stages (nm_distr_api.hip, nm_reweight_api.hip, nm_pca_api.hip): device memory that frees
-// itself, the stage's error channel with its HIP check and device selection, and the rest of a batch.  Internal: every
+// nm_host.h — the host scaffold of the offline stages (nm_distr_api.hip, nm_reweight_api.hip, nm_pca_api.hip, nm_cluster_api.hip):
+// device memory that frees itself, the stage's error channel with its HIP check and device selection, and the rest of a batch.  Internal: every
 // name here has internal linkage, so each stage gets its own copy and its own message.
 #pragma once
 #include "../../include/nm.h"
