@@ -1,9 +1,10 @@
 // nm_api.hip — C-ABI (include/nm.h) over the gfx950 kernels.  The context owns all device memory, one HIP
 // stream and the HIP events used for measurement; nothing here falls back to a CPU path: without a usable
-// HIP device nm_create fails with NM_ERR_HIP.
+// HIP device nm_create fails with NM_ERR_HIP.  Host code only: the kernels, their configuration table and their
+// launchers are nm_rows.hip, reached through the rows of nm_rows.h.
 #include "../../include/nm.h"
-#include "nm_kernels.h"
 #include "nm_lattice.h"
+#include "nm_rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -12,7 +13,6 @@
 #include <cstring>
 #include <deque>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 using namespace nm;
@@ -23,101 +23,6 @@ namespace nm { __attribute__((visibility("hidden"))) thread_local std::string g_
 
 namespace {
 
-// The small kernels run 512 threads, 8 waves: 256 VGPRs per lane, no spills (1024 threads cap at 128 and spilled ~200).
-// cluster variants of the small kernel: Q workgroups per replica, threads-per-atom scaled so that all 512 threads work
-// (a cluster stores the list rows of its own atoms only, and keeps the list twice: a rejected move goes back to the one it started from)
-typedef Cfg<512, 4, 256, 192, unsigned char, true, true, 0, 128, true, true> CfgSmallQ2;
-typedef Cfg<512, 8, 256, 192, unsigned char, true, true, 0, 64, true, true> CfgSmallQ4;
-typedef Cfg<512, 16, 256, 256, unsigned char, true, true, 0, 32, true, true> CfgSmallQ8; // grids of <= 32 replicas
-typedef Cfg<512, 2, 256, 192, unsigned char, true, true, 0, 256, true, true> CfgSmall;     // N <= 256: everything incl. the byte lists in LDS
-// element Al: Sutton-Chen EAM, 4^3 cells only (BASELINE config 4); 200 neighbour slots (134 within rc+skin in the crystal)
-typedef Cfg<512, 2, 256, 256, unsigned char, true, true, 1> CfgSmallSC;
-typedef Cfg<512, 4, 256, 256, unsigned char, true, true, 1, 128, true, true> CfgSmallSCQ2; // (own rows, two lists)
-typedef Cfg<512, 8, 256, 256, unsigned char, true, true, 1, 64, true, true> CfgSmallSCQ4;
-// element Al at 5^3 to 8^3 cells: 16-bit lists in HBM/L2, chunked as CfgMid's and CfgLarge's, full lists (Cfg::HALF stays lj/cut's).  256 slots
-// per atom: the crystal has 134 neighbours within rc + skin = 8.1 A, and the longest row over bench's Al grid (8 x 8, P 1 .. 8 bar, T 256 .. 2560 K,
-// 40 cycles from the lattice) was 149 at 5^3 and 151 at 8^3; more is reported as ST_LIST_OVERFLOW.  Densities in LDS at 864 atoms (141.5 KB in all), in the spill at 2048
-// (Cfg::RHO_LDS: positions, velocities and forces alone take 144 KB there).
-typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 1> CfgMidSC;     // 1 and 2 workgroups per replica
-typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 1> CfgMidSCQ4;   // 4
-typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 1> CfgLargeSC; // 1, 2 and 4
-// elements Cu and Ni: every Al configuration again with the Sutton-Chen exponent n = 9 (Cfg POT 2).  Their cutoff and skin are Al's in units of
-// the lattice constant (nm_lattice.h sc_element), so the list lengths, the 256 slots, the LDS plans and the size thresholds above hold for them unchanged.
-typedef Cfg<512, 2, 256, 256, unsigned char, true, true, 2> CfgSmallSC9;
-typedef Cfg<512, 4, 256, 256, unsigned char, true, true, 2, 128, true, true> CfgSmallSC9Q2;
-typedef Cfg<512, 8, 256, 256, unsigned char, true, true, 2, 64, true, true> CfgSmallSC9Q4;
-typedef Cfg<512, 1, 864, 256, unsigned short, false, true, 2> CfgMidSC9;
-typedef Cfg<512, 2, 864, 256, unsigned short, false, true, 2> CfgMidSC9Q4;
-typedef Cfg<512, 1, 2048, 256, unsigned short, false, false, 2> CfgLargeSC9;
-typedef Cfg<512, 1, 864, 192, unsigned short, false, true> CfgMid;     // N <= 864: list in HBM/L2, saved copies in LDS (here: at 2 workgroups per replica)
-// the same at ONE workgroup per replica (more replicas than CUs: the reference's run.sh setting): every pair lies inside the workgroup and
-// is listed once (Cfg::HALF, nm_kernels.h)
-typedef Cfg<512, 1, 864, 192, unsigned short, false, true, 0, 864, true, false, true> CfgMidH;
-// cluster variants: own atoms 216 / 108
-typedef Cfg<512, 2, 864, 192, unsigned short, false, true> CfgMidQ4;
-// 8 workgroups per replica: 108 own atoms, whose list rows (16-bit, 41 KB at 192 slots) fit in LDS once the saved velocities moved to the spill.
-// 192 list slots per atom since round 4 (160 before): at the skin of 0.55 that these sizes now run with, the dense crystals of the P* = 7.5-8 rows
-// reach 147 entries (scripts/probe_maxrow6.py)
-typedef Cfg<512, 4, 864, 192, unsigned short, true, true, 0, 108, false> CfgMidQ8;
-// N <= 2048: saved copies spill to HBM as well.  224 list slots: the list lives in HBM, so slots are cheap, and at skin 0.6 the dense
-// crystals (P* = 8: 140 neighbours inside 3.1, the next shell of 36 just beyond) came within ~10 % of the 160 there were
-typedef Cfg<512, 1, 2048, 224, unsigned short, false, false> CfgLarge;
-// the same at ONE workgroup per replica (more replicas than CUs): half lists (Cfg::HALF), as CfgMidH.  Measured at 256 replicas of 2048 atoms: 254 k
-// against 231 k sweeps/s sustained (+10 %)
-typedef Cfg<512, 1, 2048, 224, unsigned short, false, false, 0, 2048, false, false, true> CfgLargeH;
-
-// The configuration a context runs: X(pot, kind, Q, Cfg, FUSED) for the potential (nm_ctx::pot), the size class (nm_ctx::kind: the first
-// kind whose NMAX holds N) and the workgroups per replica (nm_ctx::cus).  FUSED: nm_cycles_kernel is instantiated for the row (cycles_kind_ok
-// decides where it runs).  Block launches, the occupancy query, the residency probe, the fused launch and the buffer sizes all find their
-// configuration here (with_row), and pick_q only picks a Q that has a row.  One row per line: tests/helpers.py reads the table.
-#define NM_CFG_ROWS(X)                  \
-    X(0, 0, 1, CfgSmall,          0)    \
-    X(0, 0, 2, CfgSmallQ2,        1)    \
-    X(0, 0, 4, CfgSmallQ4,        1)    \
-    X(0, 0, 8, CfgSmallQ8,        1)    \
-    X(0, 1, 1, CfgMidH,           0)    \
-    X(0, 1, 2, CfgMid,            0)    \
-    X(0, 1, 4, CfgMidQ4,          0)    \
-    X(0, 1, 8, CfgMidQ8,          1)    \
-    X(0, 2, 1, CfgLargeH,         0)    \
-    X(0, 2, 2, CfgLarge,          0)    \
-    X(0, 2, 4, CfgLarge,          0)    \
-    X(1, 0, 1, CfgSmallSC,        0)    \
-    X(1, 0, 2, CfgSmallSCQ2,      1)    \
-    X(1, 0, 4, CfgSmallSCQ4,      1)    \
-    X(1, 1, 1, CfgMidSC,          0)    \
-    X(1, 1, 2, CfgMidSC,          0)    \
-    X(1, 1, 4, CfgMidSCQ4,        0)    \
-    X(1, 2, 1, CfgLargeSC,        0)    \
-    X(1, 2, 2, CfgLargeSC,        0)    \
-    X(1, 2, 4, CfgLargeSC,        0)    \
-    X(2, 0, 1, CfgSmallSC9,       0)    \
-    X(2, 0, 2, CfgSmallSC9Q2,     1)    \
-    X(2, 0, 4, CfgSmallSC9Q4,     1)    \
-    X(2, 1, 1, CfgMidSC9,         0)    \
-    X(2, 1, 2, CfgMidSC9,         0)    \
-    X(2, 1, 4, CfgMidSC9Q4,       0)    \
-    X(2, 2, 1, CfgLargeSC9,       0)    \
-    X(2, 2, 2, CfgLargeSC9,       0)    \
-    X(2, 2, 4, CfgLargeSC9,       0)
-
-// f(Cfg(), std::bool_constant<FUSED>()) for the row (pot, kind, q); `none` where the table has no such row
-template <class R, class F>
-R with_row(int pot, int kind, int q, R none, F &&f)
-{
-#define NM_ROW(P, K, Q, C, FUSED) if (pot == P && kind == K && q == Q) return f(C(), std::bool_constant<FUSED>());
-    NM_CFG_ROWS(NM_ROW)
-#undef NM_ROW
-    return none;
-}
-
-// every row fits the CU's LDS and holds the atoms of its kind (nm_create picks the kind by the Q = 1 row's NMAX); a half list runs at one
-// workgroup per replica only (pair_vec_half takes every listed atom for an own atom)
-#define NM_ROW(P, K, Q, C, FUSED) static_assert(C::LDS_BYTES <= 160 * 1024 && C::NMAX == (K == 0 ? 256 : K == 1 ? 864 : 2048) && (!C::HALF || Q == 1), #C);
-NM_CFG_ROWS(NM_ROW)
-#undef NM_ROW
-static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");
-
 struct EvPair { hipEvent_t a, b; bool used; uint32_t launch_id; };
 
 } // namespace
@@ -126,6 +31,7 @@ struct nm_ctx {
     nm_config cfg;
     int N, nslots, slot0, kind; // kind: 0 small, 1 mid, 2 large
     int cus;                    // workgroups per replica
+    const Row *row;             // the kernels of (pot, kind, cus), nm_rows.h; set with cus (set_q)
     bool whole_rows;            // the slot range is made of whole pressure rows (nm_exchange can run on the device)
     double *d_xbuf;
     uint32_t launch_id;
@@ -248,36 +154,14 @@ void fill_params(const nm_ctx *c, KParams &p)
 unsigned int nm_grid(int nslots, int q) { return q == 1 ? (unsigned int)nslots : (unsigned int)(8 * q * ((nslots + 7) / 8)); }
 size_t census_words(int nslots) { return 1 + (size_t)8 * ((nslots + 7) / 8); } // the grid's counter + one per cluster
 
-// The production form of the block (nm_block_body's PLAIN) is instantiated for the 4^3 rows, kind 0, whose NMAX the static_assert above
-// ties to 256: block and fused kernels.  The 864- and 2048-atom rows keep the general form alone (build time).
-template <class C> constexpr bool has_plain = C::NMAX == 256;
-// ... and runs exactly where the call asks for nothing it leaves out: bulk position moves, no RNG tape, no trace, not nm_run_md, no forces
-// out of nm_eval.  NM_PLAIN_KERNELS=0 forces the general form (tests, A/B); both forms compute the same bits.
+// The production form of the block (nm_kernels.h nm_block_body's PLAIN; the rows that have one: nm_rows.hip) runs exactly where the call asks for
+// nothing it leaves out: bulk position moves, no RNG tape, no trace, not nm_run_md, no forces out of nm_eval.  NM_PLAIN_KERNELS=0 forces the general
+// form (tests, A/B); both forms compute the same bits.
 bool plain_call(const KParams &p)
 {
     const char *e = std::getenv("NM_PLAIN_KERNELS");
     if (e && !std::strcmp(e, "0")) return false;
     return p.bulk && !p.tape && !p.trace && !p.md_mode && !p.evalF;
-}
-
-template <class C, bool PLAIN>
-hipError_t launch_block_form(const nm_ctx *c, const KParams &p)
-{
-    hipLaunchKernelGGL((nm_block_kernel<C, PLAIN>), dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
-    return hipGetLastError();
-}
-
-template <class C>
-hipError_t launch_block(const nm_ctx *c, const KParams &p)
-{
-    if (p.order) { // longest first, by what each slot's previous block took
-        hipLaunchKernelGGL(nm_order_kernel, dim3((c->nslots + 255) / 256), dim3(256), 0, c->stream, c->nslots, c->d_last_ticks, c->d_order);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if constexpr (has_plain<C>)
-        if (plain_call(p)) return launch_block_form<C, true>(c, p);
-    return launch_block_form<C, false>(c, p);
 }
 
 // The census counters only grow (KParams::census_base): zero them and the bases.  At creation, around the residency probes, after a
@@ -288,66 +172,20 @@ hipError_t reset_census(nm_ctx *c)
     return hipMemsetAsync(c->d_census, 0, sizeof(unsigned int) * census_words(c->nslots), c->stream);
 }
 
-template <class C>
-hipError_t launch_probe(const nm_ctx *c, KParams p)
+// the workgroups per replica and the row of the configuration table that goes with them (null: the table has none; every launch then fails)
+void set_q(nm_ctx *c, int q, bool over)
 {
-    hipError_t e = hipFuncSetAttribute((const void *)nm_probe_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(c->d_census, 0, sizeof(unsigned int) * census_words(c->nslots), c->stream);
-    if (e != hipSuccess) return e;
-    p.census_base = p.census_cbase = 0; // (the probe starts from zeroed counters; pick_q zeroes them again behind it)
-    hipLaunchKernelGGL(nm_probe_kernel<C>, dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
-    return hipGetLastError();
+    c->cus = q; c->over = over;
+    c->row = nm_row(c->pot, c->kind, q);
 }
-
-// dynamic LDS above 64 KiB has to be requested per kernel
-template <class C>
-hipError_t request_lds()
-{
-    if constexpr (has_plain<C>) {
-        const hipError_t e = hipFuncSetAttribute((const void *)nm_block_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    return hipFuncSetAttribute((const void *)nm_block_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-}
-
-// workgroups of the block kernel one CU admits (LDS, registers)
-template <class C>
-int blocks_per_cu()
-{
-    int n = 0;
-    if (request_lds<C>() != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, nm_block_kernel<C>, C::BLOCK, C::LDS_BYTES) != hipSuccess) return 0;
-    return n;
-}
-
-template <class C, bool REC, bool PLAIN>
-hipError_t launch_cycles_form(const nm_ctx *c, const KParams &p)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)nm_cycles_kernel<C, REC, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((nm_cycles_kernel<C, REC, PLAIN>), dim3(nm_grid(c->nslots, c->cus)), dim3(C::BLOCK), C::LDS_BYTES, c->stream, p);
-    return hipGetLastError();
-}
-template <class C, bool REC>
-hipError_t launch_cycles_rec(const nm_ctx *c, const KParams &p)
-{
-    if constexpr (has_plain<C>)
-        if (plain_call(p)) return launch_cycles_form<C, REC, true>(c, p);
-    return launch_cycles_form<C, REC, false>(c, p);
-}
-// the recording instantiation where the launch has a ring (KParams::rec), the outputs-off one elsewhere: the same configurations have both
-template <class C>
-hipError_t launch_cycles(const nm_ctx *c, const KParams &p) { return p.rec ? launch_cycles_rec<C, true>(c, p) : launch_cycles_rec<C, false>(c, p); }
 
 // nm_cycles_kernel is instantiated for the FUSED rows (the 4^3 clusters and the 6^3 cluster of eight).  nm_run_cycles uses it where it measured faster
 // than the loop of single launches: the 4^3 clusters of 2 and 4 workgroups (64-128 replicas: +2.4 to +2.9 % LJ, +0.5 % Al).  Clusters of 8 run 32 replicas
 // or fewer, whose rows have little spread to hide, and there the block compiled inside the loop over cycles (~1 % slower) costs more than the rows gain
 // (-0.8 % at 4^3, -2.9 % at 6^3): the loop of single launches, unless NM_FUSED_CYCLES=all.  NM_FUSED_CYCLES=0: never.  DESIGN.md §7.4 (6).
-bool cycles_kind_built(const nm_ctx *c) { return with_row(c->pot, c->kind, c->cus, false, [](auto, auto fused) { return decltype(fused)::value; }); }
 bool cycles_kind_ok(const nm_ctx *c)
 {
-    if (!cycles_kind_built(c)) return false;
+    if (!c->row || !c->row->cycles) return false;
     const char *e = std::getenv("NM_FUSED_CYCLES");
     if (e && !std::strcmp(e, "all")) return true;
     if (e && !std::strcmp(e, "0")) return false;
@@ -356,23 +194,34 @@ bool cycles_kind_ok(const nm_ctx *c)
 
 hipError_t launch_cycles_kind(const nm_ctx *c, const KParams &p)
 {
-    return with_row(c->pot, c->kind, c->cus, hipErrorInvalidDeviceFunction, [&](auto cfg, auto fused) {
-        if constexpr (decltype(fused)::value) return launch_cycles<decltype(cfg)>(c, p);
-        else return hipErrorInvalidDeviceFunction;
-    });
+    if (!c->row || !c->row->cycles) return hipErrorInvalidDeviceFunction;
+    return c->row->cycles(nm_grid(c->nslots, c->cus), c->stream, p, plain_call(p));
 }
 
 hipError_t launch_kind(const nm_ctx *c, const KParams &p)
 {
-    return with_row(c->pot, c->kind, c->cus, hipErrorInvalidDeviceFunction, [&](auto cfg, auto) { return launch_block<decltype(cfg)>(c, p); });
+    if (!c->row) return hipErrorInvalidDeviceFunction;
+    if (p.order) { // longest first, by what each slot's previous block took
+        const hipError_t e = launch_order(c->stream, c->nslots, c->d_last_ticks, c->d_order);
+        if (e != hipSuccess) return e;
+    }
+    return c->row->block(nm_grid(c->nslots, c->cus), c->stream, p, plain_call(p));
 }
 
 // 0 where the table has no configuration at q: pick_q then finds no room for such a grid
-int blocks_per_cu_kind(const nm_ctx *c, int q) { return with_row(c->pot, c->kind, q, 0, [](auto cfg, auto) { return blocks_per_cu<decltype(cfg)>(); }); }
-
-hipError_t probe_kind(const nm_ctx *c, const KParams &p)
+int blocks_per_cu_kind(const nm_ctx *c, int q)
 {
-    return with_row(c->pot, c->kind, c->cus, hipErrorInvalidDeviceFunction, [&](auto cfg, auto) { return launch_probe<decltype(cfg)>(c, p); });
+    const Row *r = nm_row(c->pot, c->kind, q);
+    return r ? r->blocks_per_cu() : 0;
+}
+
+hipError_t probe_kind(const nm_ctx *c, KParams p)
+{
+    if (!c->row) return hipErrorInvalidDeviceFunction;
+    const hipError_t e = hipMemsetAsync(c->d_census, 0, sizeof(unsigned int) * census_words(c->nslots), c->stream);
+    if (e != hipSuccess) return e;
+    p.census_base = p.census_cbase = 0; // (the probe starts from zeroed counters; pick_q zeroes them again behind it)
+    return c->row->probe(nm_grid(c->nslots, c->cus), c->stream, p);
 }
 
 // drain one event pair into the timing accumulators
@@ -416,6 +265,20 @@ void census_advance(nm_ctx *c)
 }
 void fill_census(const nm_ctx *c, KParams &p) { p.census_base = c->census_base; p.census_cbase = c->census_cbase; }
 
+// one launch of the block (launch_kind) or of the fused cycles (launch_cycles_kind); timed: between an event pair that nm_timing_get harvests
+int issue_launch(nm_ctx *c, hipError_t (*launch)(const nm_ctx *, const KParams &), const KParams &p, bool timed, uint32_t id)
+{
+    if (!timed) { HIPCHK(c, launch(c, p)); return NM_OK; }
+    EvPair &e = c->ev[c->ev_next];
+    harvest(c, e);
+    HIPCHK(c, hipEventRecord(e.a, c->stream));
+    HIPCHK(c, launch(c, p));
+    HIPCHK(c, hipEventRecord(e.b, c->stream));
+    e.used = true; e.launch_id = id;
+    c->ev_next = (c->ev_next + 1) % (int)c->ev.size();
+    return NM_OK;
+}
+
 int issue_block(nm_ctx *c, int kind, int arg, uint32_t step, int trace, const int *d_mask, bool timed)
 {
     if (c->journal.size() > 4096 && !d_mask) { // a caller that never looks: bound the journal
@@ -453,15 +316,7 @@ int issue_block(nm_ctx *c, int kind, int arg, uint32_t step, int trace, const in
     // word armed does nothing, and the memset in front of it must not wipe the failed block's bits: they are in status_acc[]
     // (status[]: cleared by each slot's writer inside the kernel; census counters: monotonic — no memsets in front of a launch)
     if (c->cus > 1 && (c->census_base > 0x3F000000u || c->census_cbase > 0x3F000000u)) { HIPCHK(c, reset_census(c)); fill_census(c, p); }
-    if (timed) {
-        EvPair &e = c->ev[c->ev_next];
-        harvest(c, e);
-        HIPCHK(c, hipEventRecord(e.a, c->stream));
-        HIPCHK(c, launch_kind(c, p));
-        HIPCHK(c, hipEventRecord(e.b, c->stream));
-        e.used = true; e.launch_id = c->launch_id;
-        c->ev_next = (c->ev_next + 1) % (int)c->ev.size();
-    } else HIPCHK(c, launch_kind(c, p));
+    if (const int rc = issue_launch(c, launch_kind, p, timed, c->launch_id)) return rc;
     census_advance(c);
     c->journal.push_back({ kind, arg, trace, step, c->launch_id });
     return NM_OK;
@@ -469,19 +324,15 @@ int issue_block(nm_ctx *c, int kind, int arg, uint32_t step, int trace, const in
 
 int issue_adapt(nm_ctx *c)
 {
-    hipLaunchKernelGGL(nm_adapt_kernel, dim3((c->nslots + 63) / 64), dim3(64), 0, c->stream, c->nslots, c->d_slot2buf,
-                       c->d_steps, c->d_count, c->d_ratio, c->d_halt);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch_adapt(c->stream, c->nslots, c->d_slot2buf, c->d_steps, c->d_count, c->d_ratio, c->d_halt));
     c->journal.push_back({ OP_ADAPT, 0, 0, 0u, 0u });
     return NM_OK;
 }
 
 int issue_exchange(nm_ctx *c, uint32_t step)
 {
-    hipLaunchKernelGGL(nm_exchange_kernel, dim3(1), dim3(64), 0, c->stream, c->cfg.nrows, c->cfg.nt,
-                       c->cfg.row0, c->cfg.seed, step, c->d_slot2buf, c->d_therm, c->d_et, c->d_pf,
-                       c->xtape_n ? c->d_xtape : nullptr, c->d_xcrit, c->d_nswaps, c->d_halt);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch_exchange(c->stream, c->cfg.nrows, c->cfg.nt, c->cfg.row0, c->cfg.seed, step, c->d_slot2buf, c->d_therm, c->d_et, c->d_pf,
+                              c->xtape_n ? c->d_xtape : nullptr, c->d_xcrit, c->d_nswaps, c->d_halt));
     c->journal.push_back({ OP_EXCHANGE, 0, 0, step, 0u });
     return NM_OK;
 }
@@ -495,8 +346,7 @@ int issue_record(nm_ctx *c, int r, int j)
     RecArgs a;
     a.x = c->d_x; a.box = c->d_box; a.therm = c->d_therm; a.steps = c->d_steps; a.count = c->d_count; a.ratio = c->d_ratio; a.slot2buf = c->d_slot2buf;
     a.halt = c->d_halt; a.dst = g.d + (size_t)j * rec_cycle_doubles(c); a.nslots = c->nslots; a.N = c->N; a.tag = g.tag0 + (uint32_t)j;
-    hipLaunchKernelGGL(nm_record_kernel, dim3(c->nslots), dim3(256), 0, c->stream, a);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch_record(c->stream, a));
     nm_ctx::Op o{ OP_RECORD, 0, 0, 0u, 0u };
     o.rec = r; o.rec0 = j;
     c->journal.push_back(o);
@@ -550,15 +400,7 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed, int
             if (std::atoi(e) == c->cluster_launches) p.inj_census = 1;
     ++c->cluster_launches;
     if (c->census_base > 0x3F000000u || c->census_cbase > 0x3F000000u) { HIPCHK(c, reset_census(c)); fill_census(c, p); }
-    if (timed) {
-        EvPair &e = c->ev[c->ev_next];
-        harvest(c, e);
-        HIPCHK(c, hipEventRecord(e.a, c->stream));
-        HIPCHK(c, launch_cycles_kind(c, p));
-        HIPCHK(c, hipEventRecord(e.b, c->stream));
-        e.used = true; e.launch_id = first_id;
-        c->ev_next = (c->ev_next + 1) % (int)c->ev.size();
-    } else HIPCHK(c, launch_cycles_kind(c, p));
+    if (const int rc = issue_launch(c, launch_cycles_kind, p, timed, first_id)) return rc;
     census_advance(c);
     nm_ctx::Op o{ OP_CYCLES, mod, ncycles, step, first_id };
     o.rec = rec; o.rec0 = rec0; // (a re-issue records into the same ring)
@@ -577,7 +419,7 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
     int cu = prop.multiProcessorCount;
     if (testing())
         if (const char *e = std::getenv("NM_ASSUME_CUS")) { const int v = std::atoi(e); if (v > 0) cu = v; } // tests of the fallback
-    c->cus = 1; c->over = false;
+    set_q(c, 1, false);
     // The large cells (N > 864) at 4 workgroups per replica when that makes a grid of (nearly) TWICE the chip: the clusters run in
     // two rounds, longest block first, each with its own census.  Their blocks differ by more than 2x across an equilibrated PxT grid
     // (31-73 ms at 8^3, two workgroups each), so a resident grid of two workgroups per replica lasts as long as its slowest member while
@@ -597,7 +439,7 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
         const bool over = pass == 0;
         if (over) { if (qq != 4 || grid > 2 * room || 4 * grid < 7 * room) continue; } // 1.75 .. 2 chips' worth of workgroups
         else if (grid > room) continue;
-        c->cus = qq; c->over = over; // probe: does the grid of this Q gather?
+        set_q(c, qq, over); // probe: does the grid of this Q gather?
         KParams p;
         fill_params(c, p);
         p.status_acc = nullptr; p.halt = nullptr;
@@ -614,7 +456,7 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
         char buf[200];
         std::snprintf(buf, sizeof buf, "%d workgroups per replica (%d in all) did not gather on this device; falling back. ", qq, (int)nm_grid(c->nslots, qq));
         note += buf;
-        c->cus = 1; c->over = false;
+        set_q(c, 1, false);
     }
     return NM_OK;
 }
@@ -623,8 +465,7 @@ int pick_q(nm_ctx *c, int qmax, std::string &note)
 int alloc_cluster_buffers(nm_ctx *c)
 {
     const size_t ns = c->nslots;
-    const size_t aux_doubles = with_row(c->pot, c->kind, c->cus, (size_t)0, [](auto cfg, auto) { return decltype(cfg)::AUX_DOUBLES; });
-    const size_t xbd = with_row(c->pot, c->kind, c->cus, (size_t)0, [](auto cfg, auto) { return decltype(cfg)::XBUF_DOUBLES; });
+    const size_t aux_doubles = c->row ? c->row->aux_doubles : 0, xbd = c->row ? c->row->xbuf_doubles : 0;
     // the new buffers first, swapped in only when both exist: a failure leaves the context with the buffers (and the workgroups per
     // replica) it can still run with
     double *aux = nullptr, *xbuf = nullptr;
@@ -637,7 +478,7 @@ int alloc_cluster_buffers(nm_ctx *c)
     if (e != hipSuccess) {
         if (aux) hipFree(aux);
         if (xbuf) hipFree(xbuf);
-        if (!c->d_xbuf) { c->cus = 1; c->over = false; } // nothing to hand over with: one workgroup per replica (its spill area, if any, is a subset of what is there)
+        if (!c->d_xbuf) set_q(c, 1, false); // nothing to hand over with: one workgroup per replica (its spill area, if any, is a subset of what is there)
         return fail(c, NM_ERR_HIP, std::string("alloc_cluster_buffers: ") + hipGetErrorString(e));
     }
     if (c->d_aux) hipFree(c->d_aux);
@@ -849,10 +690,12 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     }
 
     // size class: the first kind whose configurations hold N atoms (every potential's kind 2 holds the 2048 checked above)
-    for (c->kind = 0; c->kind < 2 && with_row(c->pot, c->kind, 1, 0, [](auto cfg, auto) { return decltype(cfg)::NMAX; }) < c->N; ++c->kind) {}
+    auto nmax = [&](int kind) { const Row *r = nm_row(c->pot, kind, 1); return r ? r->nmax : 0; };
+    for (c->kind = 0; c->kind < 2 && nmax(c->kind) < c->N; ++c->kind) {}
     // the neighbour lists in HBM, per slot: the largest of the kind's rows (a heal can take a 6^3 context from Q = 8, whose lists are in LDS, to Q = 4)
     size_t nbr_elems = 0;
-    for (int q : { 1, 2, 4, 8 }) nbr_elems = std::max(nbr_elems, with_row(c->pot, c->kind, q, (size_t)0, [](auto cfg, auto) { return decltype(cfg)::NBR_G_ELEMS; }));
+    for (int q : { 1, 2, 4, 8 })
+        if (const Row *r = nm_row(c->pot, c->kind, q)) nbr_elems = std::max(nbr_elems, r->nbr_g_elems);
 
 #define CHK(call)                                                                                     \
     do {                                                                                              \
@@ -865,7 +708,7 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     } while (0)
     CHK(hipSetDevice(cfg->device));
     CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    c->cus = 1; c->d_xbuf = nullptr; c->d_aux = nullptr; c->launch_id = 0; c->d_census = nullptr; c->over = false;
+    set_q(c, 1, false); c->d_xbuf = nullptr; c->d_aux = nullptr; c->launch_id = 0; c->d_census = nullptr;
     c->d_status_acc = nullptr; c->d_halt = nullptr; c->d_rerun = nullptr; c->d_order = nullptr; c->d_last_ticks = nullptr; c->use_order = false;
     std::string note;
     {
@@ -934,7 +777,8 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     CHK(hipMemcpy(c->d_et, c->h_et.data(), ns * sizeof(double), hipMemcpyHostToDevice));
     CHK(hipMemcpy(c->d_pf, c->h_pf.data(), ns * sizeof(double), hipMemcpyHostToDevice));
     CHK(hipMemcpy(c->d_tq, c->h_tq.data(), ns * sizeof(double), hipMemcpyHostToDevice));
-    for (int q : { 1, 2, 4, 8 }) CHK(with_row(c->pot, c->kind, q, hipSuccess, [](auto cfg, auto) { return request_lds<decltype(cfg)>(); }));
+    for (int q : { 1, 2, 4, 8 })
+        if (const Row *r = nm_row(c->pot, c->kind, q)) CHK(r->request_lds());
     c->ev.assign(32, EvPair{ nullptr, nullptr, false, 0u });
     for (auto &e : c->ev) { CHK(hipEventCreate(&e.a)); CHK(hipEventCreate(&e.b)); }
 #undef CHK
@@ -1440,9 +1284,7 @@ int nm_prof_oob(nm_ctx *c, unsigned int *count)
 {
     if (!c || !count) return NM_ERR_ARG;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpyFromSymbol(count, HIP_SYMBOL(nm::nm_oob_count), sizeof(unsigned int)));
-    const unsigned int zero = 0;
-    HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(nm::nm_oob_count), &zero, sizeof(unsigned int)));
+    HIPCHK(c, prof_take_count(0, count));
     return NM_OK;
 }
 // diagnostic build only: rows of freshly built neighbour lists that lacked an atom inside rc + skin (exact fp64 check after every
@@ -1451,16 +1293,14 @@ int nm_prof_list_miss(nm_ctx *c, unsigned int *count)
 {
     if (!c || !count) return NM_ERR_ARG;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpyFromSymbol(count, HIP_SYMBOL(nm::nm_list_miss), sizeof(unsigned int)));
-    const unsigned int zero = 0;
-    HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(nm::nm_list_miss), &zero, sizeof(unsigned int)));
+    HIPCHK(c, prof_take_count(1, count));
     return NM_OK;
 }
 int nm_prof_miss_info(nm_ctx *c, double *info16)
 {
     if (!c || !info16) return NM_ERR_ARG;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpyFromSymbol(info16, HIP_SYMBOL(nm::nm_miss_info), 16 * sizeof(double)));
+    HIPCHK(c, prof_miss_info(info16));
     return NM_OK;
 }
 // diagnostic build only: cycle sums per section and slot, [nslots][16]

@@ -141,7 +141,7 @@ struct Cfg {
     // bound by the LDS pipe already (64 unrelated atoms per gather instruction), three atomics per entry make 2.4 times the LDS work of an
     // entry, only the own range's pairs go away (75 % of the entries at two workgroups per replica), and a cluster loses the epilogue that
     // integrates and publishes a row's atom as soon as its force is known.  At ONE workgroup per replica it pays at 2048 atoms too (256 replicas:
-    // +10 %).  So HALF_ is set for the one-workgroup configurations of the lists in HBM only (CfgMidH, CfgLargeH, nm_api.hip).
+    // +10 %).  So HALF_ is set for the one-workgroup configurations of the lists in HBM only (CfgMidH, CfgLargeH, nm_rows.hip).
     static constexpr bool HALF = !LIST_LDS_ && TPA_ == 1 && POT_ == 0 && HALF_;
     static constexpr int BLOCK = BLOCK_, TPA = TPA_, NW = BLOCK_ / 64, G = BLOCK_ / TPA_, NMAX = NMAX_, MAXNB = MAXNB_;
     static constexpr bool LIST_LDS = LIST_LDS_, SAVE_LDS = SAVE_LDS_;
@@ -1111,7 +1111,7 @@ struct Replica {
     // reporting), every row total with 2^15.  The pair's compare is the only one beside the cutoff's: a half list needs no
     // own-range compare (below).
     static constexpr double FIX_RANGE = 32768.0 /* 2^15 */, FIX_R2 = 0.36503;
-    // CfgMidH and CfgLargeH run at one workgroup per replica only (launch_kind picks them at Q = 1; nm_api.hip asserts it for every row
+    // CfgMidH and CfgLargeH run at one workgroup per replica only (the table has them at Q = 1; nm_rows.hip asserts it for every row
     // of its table): every listed atom is an own atom.
     int fr_bad = 0;    // HALF: this thread met an addend or a row total outside the fixed-point range since the last energy evaluation
     int fr_hit = 0;    // HALF, uniform over the cluster: an evaluation since the current move started met one (take_sums); the forces are not
@@ -2646,7 +2646,7 @@ enum : int { PH_INIT = 0, PH_BULK = 1, PH_VMC = 2, PH_HMC_START = 3, PH_HMC_STEP
 // CENSUS: the launch's residency census is taken here (nm_cycles_kernel takes it itself, once, in front of its cycles).
 // PLAIN: the production form of the block.  What only tests, diagnostics and the reference modes ask for is compiled out instead of branched
 // around: the RNG tape (p.tape), the per-move trace (p.trace), the plain NVE run (p.md_mode), nm_eval's force output (p.evalF) and the whole
-// iterative position move (!p.bulk).  The launchers (nm_api.hip) pick it exactly when the call asks for none of them; the general form computes
+// iterative position move (!p.bulk).  The launchers (nm_rows.hip, told by nm_api.hip plain_call) pick it exactly when the call asks for none of them; the general form computes
 // the same bits.  The function is register-allocated as a whole, and these branches cost the hot loops 20 spilled vector registers and a fifth
 // of the instructions.  Fault injection, the census, stats and status reporting are in both forms.
 template <class C, bool CENSUS = true, bool PLAIN = false>
@@ -3024,7 +3024,6 @@ __global__ void nm_order_kernel(int nslots, const unsigned long long *ticks, int
 
 // nm_snapshot, and nm_run_cycles_recorded on the loop of single launches: the record of one cycle (nm_cycles_kernel<C, true>'s layout), queued
 // behind its block.  Workgroup k copies slot k.  Nothing, and no tag, when a block stopped on an error (halt word armed): that record was never taken.
-struct RecArgs { const double *x, *box, *therm, *steps, *count; const float *ratio; const int *slot2buf, *halt; double *dst; int nslots, N; uint32_t tag; };
 __global__ void nm_record_kernel(const RecArgs a)
 {
     const int k = blockIdx.x;

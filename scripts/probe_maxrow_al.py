@@ -1,5 +1,5 @@
 """Longest Verlet-list row the EAM kernels build (stats column 8) on bench's metal grid — 8 x 8, P 1 .. 8 bar, T 256 .. 2560 K — over 40 cycles
-from the lattice, at 5^3, 6^3 and 8^3 cells, against the 256 slots per atom of CfgMidSC / CfgLargeSC (nm_api.hip).  Element Al, or the one
+from the lattice, at 5^3, 6^3 and 8^3 cells, against the 256 slots per atom of CfgMidSC / CfgLargeSC (nm_rows.hip).  Element Al, or the one
 given as the first argument (Cu, Ni: the n = 9 twins)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -7,13 +7,15 @@ import numpy as np
 from neuralmelting_amd import lattice
 
 LAT_LJ = 1.122
-NM_API = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'neuralmelting_amd', 'csrc', 'nm_api.hip')
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'neuralmelting_amd', 'csrc')
+NM_API = os.path.join(CSRC, 'nm_api.hip')       # the sampler's host code
+NM_ROWS = os.path.join(CSRC, 'nm_rows.hip')     # its kernels' configuration table and launchers
 
 
 def cfg_rows():
-    """nm_api.hip's table of kernel configurations (NM_CFG_ROWS): {(pot, kind, Q): (Cfg typedef, fused)}; pot 0 lj/cut, 1 Al, 2 Cu and Ni"""
+    """nm_rows.hip's table of kernel configurations (NM_CFG_ROWS): {(pot, kind, Q): (Cfg typedef, fused)}; pot 0 lj/cut, 1 Al, 2 Cu and Ni"""
     rows = {}
-    for line in open(NM_API).read().split('#define NM_CFG_ROWS(X)', 1)[1].split('\n')[1:]:
+    for line in open(NM_ROWS).read().split('#define NM_CFG_ROWS(X)', 1)[1].split('\n')[1:]:
         m = re.fullmatch(r'\s*X\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(Cfg\w+)\s*,\s*([01])\s*\)\s*(\\?)', line)
         assert m, 'not a row of NM_CFG_ROWS: %r' % line
         key = tuple(int(v) for v in m.group(1, 2, 3))

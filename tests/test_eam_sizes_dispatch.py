@@ -1,4 +1,4 @@
-"""CPU: element Al above 256 atoms.  The GPU test matrix of tests/test_eam_sizes_gpu.py names every row of nm_api.hip's configuration
+"""CPU: element Al above 256 atoms.  The GPU test matrix of tests/test_eam_sizes_gpu.py names every row of nm_rows.hip's configuration
 table (NM_CFG_ROWS) for Al above 256 atoms, and the oracle agrees with the exact all-pairs reference (tests/exact_ref.py) on the Al edge
 states at the 5^3 and 6^3 sizes those tests use."""
 import numpy as np

@@ -1,5 +1,5 @@
 """element Al (Sutton-Chen EAM) at 5^3 to 8^3 cells: the 16-bit-list EAM kernels (CfgMidSC, CfgMidSCQ4, CfgLargeSC, rows of the
-configuration table NM_CFG_ROWS in nm_api.hip) against the exact all-pairs reference and the oracle.
+configuration table NM_CFG_ROWS in nm_rows.hip) against the exact all-pairs reference and the oracle.
 
 - nm_eval at every instantiation and workgroups-per-replica setting on the edge states of tests/exact_ref.py (status, pair counts,
   U and W to 1e-11, forces within the derived bound, the box below 2 rc refused);
@@ -24,7 +24,7 @@ AL_N = (257, 499, 500, 863, 864, 865, 1372, 2047, 2048)
 
 
 def qs(n):
-    """workgroups per replica with a row in the configuration table (nm_api.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
+    """workgroups per replica with a row in the configuration table (nm_rows.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
     if n <= 864:
         return {1: 'CfgMidSC', 2: 'CfgMidSC', 4: 'CfgMidSCQ4'}
     return {1: 'CfgLargeSC', 2: 'CfgLargeSC', 4: 'CfgLargeSC'}

@@ -1,4 +1,4 @@
-"""nm_eval at every lj/cut and 4^3 Al row of the configuration table (nm_api.hip NM_CFG_ROWS), against the exact all-pairs reference
+"""nm_eval at every lj/cut and 4^3 Al row of the configuration table (nm_rows.hip NM_CFG_ROWS), against the exact all-pairs reference
 (tests/exact_ref.py), at ragged atom counts and on the edge states: pairs at the cutoff and at the list radius, through every periodic
 image, at L / 2, on the faces, unwrapped, close contacts, boxes from 2 rc to just above 2 (rc + skin), EAM atoms with nothing inside rc.
 
@@ -24,7 +24,7 @@ def kind(n):
 
 
 def qs(el, n):
-    """workgroups per replica with a row in the configuration table (nm_api.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
+    """workgroups per replica with a row in the configuration table (nm_rows.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
     if el == 'Al':
         return {1: 'CfgSmallSC', 2: 'CfgSmallSCQ2', 4: 'CfgSmallSCQ4'}
     return [{1: 'CfgSmall', 2: 'CfgSmallQ2', 4: 'CfgSmallQ4', 8: 'CfgSmallQ8'},

@@ -2,13 +2,14 @@
 (eval_allpairs) on every edge state the GPU edge tests use.  Pins the reference, and the oracle at the edges: pairs at the cutoff
 and at the list radius, through every periodic image, on the faces, unwrapped, close contacts, boxes from 2 rc to 2 (rc + skin), and
 EAM atoms with nothing inside rc."""
+import os
 import re
 
 import numpy as np
 import pytest
 
 import exact_ref as X
-from helpers import NM_API, cfg_rows
+from helpers import CSRC, NM_API, cfg_rows
 
 REL = 1e-12
 
@@ -75,20 +76,29 @@ def test_edge_states_are_what_they_claim():
 
 def test_the_gpu_edge_matrix_covers_every_lj_and_4cubed_al_row():
     """tests/test_eval_edges_gpu.py names a configuration for every (element, kind, workgroups per replica) of lj/cut and of Al at 4^3:
-    the row of nm_api.hip's configuration table (NM_CFG_ROWS) for each, so that a new row cannot go untested"""
+    the row of nm_rows.hip's configuration table (NM_CFG_ROWS) for each, so that a new row cannot go untested"""
     import test_eval_edges_gpu as G
     tested = {({'LJ': 0, 'Al': 1}[el], G.kind(n), q): G.qs(el, n)[q] for el, n, q in (c.values for c in G.CASES)}
     assert tested == {k: name for k, (name, _) in cfg_rows().items() if k[0] == 0 or k[:2] == (1, 0)}
 
 
 def test_every_launch_finds_its_configuration_in_the_table():
-    """nm_api.hip picks the kernel configuration of a context in one place, NM_CFG_ROWS through with_row: no launcher, occupancy query or
-    kernel reference names a Cfg typedef, so the block launch, the occupancy query and the residency probe cannot disagree.  The rows with a
-    fused nm_cycles_kernel and the workgroups per replica of each (potential, kind) are the measured and tested ones."""
-    src = open(NM_API).read()
-    launcher = r'launch_block|launch_probe|blocks_per_cu|request_lds|launch_cycles(?:_rec)?|nm_(?:block|probe|cycles)_kernel'
-    named = re.findall(r'\b(?:%s)\s*<\s*Cfg\w*' % launcher, src)
-    assert not named, named
+    """The sampler picks the kernel configuration of a context in one place, nm_rows.hip's NM_CFG_ROWS through with_row: no launcher, occupancy
+    query or kernel reference in any of its source files names a Cfg typedef, so the block launch, the occupancy query and the residency probe
+    cannot disagree.  The host code (nm_api.hip) reaches the kernels through nm_rows.h alone: nothing it includes is, or includes, a kernel header.
+    The rows with a fused nm_cycles_kernel and the workgroups per replica of each (potential, kind) are the measured and tested ones."""
+    launcher = r'launch_block|launch_probe|blocks_per_cu|request_lds|launch_cycles(?:_rec|_form)?|launch_block_form|nm_(?:block|probe|cycles)_kernel'
+    for name in ('nm_api.hip', 'nm_rows.hip', 'nm_rows.h', 'nm_params.h', 'nm_kernels.h', 'nm_device.h'):
+        named = re.findall(r'\b(?:%s)\s*<\s*Cfg\w*' % launcher, open(os.path.join(CSRC, name)).read())
+        assert not named, (name, named)
+    seen, todo = set(), [NM_API]
+    while todo:                                  # everything nm_api.hip includes from its own directory
+        for inc in re.findall(r'^\s*#\s*include\s*"([^"/]+)"', open(todo.pop()).read(), flags=re.M):
+            if inc not in seen:
+                seen.add(inc)
+                todo.append(os.path.join(CSRC, inc))
+    assert 'nm_rows.h' in seen and not seen & {'nm_kernels.h', 'nm_device.h', 'nm_math.h'}, seen
+    assert not re.search(r'hipLaunchKernelGGL|<<<|\bCfg\w*|\bnm_\w+_kernel\b', re.sub(r'//.*', '', open(NM_API).read()))   # (its comments may)
     rows = cfg_rows()
     fused = {k for k, (_, f) in rows.items() if f}
     assert fused == {(0, 0, 2), (0, 0, 4), (0, 0, 8), (0, 1, 8), (1, 0, 2), (1, 0, 4), (2, 0, 2), (2, 0, 4)}

@@ -157,7 +157,7 @@ def test_G3_exchange_engine_al(idx):
     e.close()
 
 
-# every Al row of the configuration table (nm_api.hip NM_CFG_ROWS) at 4^3 and 5^3, by workgroups per replica
+# every Al row of the configuration table (nm_rows.hip NM_CFG_ROWS) at 4^3 and 5^3, by workgroups per replica
 AL_CFG = {256: {1: 'CfgSmallSC', 2: 'CfgSmallSCQ2', 4: 'CfgSmallSCQ4'}, 500: {1: 'CfgMidSC', 2: 'CfgMidSC', 4: 'CfgMidSCQ4'}}
 AL_CASES = [pytest.param(tag, sz, q, id='%s-%d-%s-q%d' % (tag, 4 * sz ** 3, AL_CFG[4 * sz ** 3][q], q))
             for sz in (4, 5) for tag in ('bulk', 'iter', 'default_mix') for q in (1, 2, 4)]

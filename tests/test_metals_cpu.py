@@ -138,7 +138,7 @@ def test_driver_refuses_ti_by_name(tmp_path):
 
 
 def test_the_gpu_matrix_covers_every_n9_row():
-    """tests/test_metals_gpu.py names a configuration for every (kind, workgroups per replica) of Cu and Ni: the row of nm_api.hip's
+    """tests/test_metals_gpu.py names a configuration for every (kind, workgroups per replica) of Cu and Ni: the row of nm_rows.hip's
     configuration table (NM_CFG_ROWS) for each.  Those rows are Al's with the n = 9 twins, fused where Al's are."""
     import test_metals_gpu as G
     from helpers import cfg_rows

@@ -1,4 +1,4 @@
-"""Elements Cu and Ni on the n = 9 Sutton-Chen kernels (the Cfg POT 2 twins of Al's configurations, nm_api.hip), without an oracle:
+"""Elements Cu and Ni on the n = 9 Sutton-Chen kernels (the Cfg POT 2 twins of Al's configurations, nm_rows.hip), without an oracle:
 
 - nm_eval at every instantiation and workgroups-per-replica setting against the exact all-pairs reference (tests/metals_ref.py) on
   Al's edge states scaled to the element (status, pair counts, U and W to 1e-11, forces within the derived bound, the box below 2 rc
@@ -27,7 +27,7 @@ NKTV2P = 1.6021765e6
 
 
 def qs(n):
-    """workgroups per replica with an n = 9 row in the configuration table (nm_api.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
+    """workgroups per replica with an n = 9 row in the configuration table (nm_rows.hip NM_CFG_ROWS): the names are the Cfg typedefs"""
     if n <= 256:
         return {1: 'CfgSmallSC9', 2: 'CfgSmallSC9Q2', 4: 'CfgSmallSC9Q4'}
     if n <= 864:

@@ -226,7 +226,7 @@ def test_tape_replay_parity(oracle):
     e.close()
 
 
-# every lj/cut row of nm_api.hip's configuration table (NM_CFG_ROWS) above 256 atoms: 5^3 / 6^3 -> CfgMidH (Q = 1: half lists), CfgMid (Q = 2), CfgMidQ4, CfgMidQ8; 8^3 -> CfgLargeH (Q = 1: half lists), CfgLarge (Q = 2, 4)
+# every lj/cut row of nm_rows.hip's configuration table (NM_CFG_ROWS) above 256 atoms: 5^3 / 6^3 -> CfgMidH (Q = 1: half lists), CfgMid (Q = 2), CfgMidQ4, CfgMidQ8; 8^3 -> CfgLargeH (Q = 1: half lists), CfgLarge (Q = 2, 4)
 LARGE_CELL_CASES = [(sz, q) for sz in (5, 6) for q in (1, 2, 4, 8)] + [(7, 1), (7, 2), (7, 4), (8, 1), (8, 2), (8, 4)]
 
 

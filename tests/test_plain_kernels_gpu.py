@@ -12,7 +12,7 @@ from helpers import grids
 
 pytestmark = pytest.mark.gpu
 
-# (element, workgroups per replica): every 4^3 row of nm_api.hip's table
+# (element, workgroups per replica): every 4^3 row of nm_rows.hip's table
 CASES = [('LJ', 1), ('LJ', 2), ('LJ', 4), ('LJ', 8), ('Al', 1), ('Al', 2), ('Al', 4)]
 STATS_COLS = [0, 1, 2, 3]   # evaluations, list rebuilds, energy evaluations, interacting pairs
 MOD = 16
