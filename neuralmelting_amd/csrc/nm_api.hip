@@ -156,12 +156,13 @@ size_t census_words(int nslots) { return 1 + (size_t)8 * ((nslots + 7) / 8); } /
 
 // The production form of the block (nm_kernels.h nm_block_body's PLAIN; the rows that have one: nm_rows.hip) runs exactly where the call asks for
 // nothing it leaves out: bulk position moves, no RNG tape, no trace, not nm_run_md, no forces out of nm_eval.  NM_PLAIN_KERNELS=0 forces the general
-// form (tests, A/B); both forms compute the same bits.
-bool plain_call(const KParams &p)
+// form (tests, A/B); both forms compute the same bits.  Full cells only: the atom count of the production form is its row's NMAX at compile
+// time (nm_kernels.h Replica::FIXN), so every other atom count of the size class (108, 32, the ragged sizes of the tests) takes the general form.
+bool plain_call(const KParams &p, const Row *row)
 {
     const char *e = std::getenv("NM_PLAIN_KERNELS");
     if (e && !std::strcmp(e, "0")) return false;
-    return p.bulk && !p.tape && !p.trace && !p.md_mode && !p.evalF;
+    return p.bulk && !p.tape && !p.trace && !p.md_mode && !p.evalF && p.N == row->nmax;
 }
 
 // The census counters only grow (KParams::census_base): zero them and the bases.  At creation, around the residency probes, after a
@@ -195,7 +196,7 @@ bool cycles_kind_ok(const nm_ctx *c)
 hipError_t launch_cycles_kind(const nm_ctx *c, const KParams &p)
 {
     if (!c->row || !c->row->cycles) return hipErrorInvalidDeviceFunction;
-    return c->row->cycles(nm_grid(c->nslots, c->cus), c->stream, p, plain_call(p));
+    return c->row->cycles(nm_grid(c->nslots, c->cus), c->stream, p, plain_call(p, c->row));
 }
 
 hipError_t launch_kind(const nm_ctx *c, const KParams &p)
@@ -205,7 +206,7 @@ hipError_t launch_kind(const nm_ctx *c, const KParams &p)
         const hipError_t e = launch_order(c->stream, c->nslots, c->d_last_ticks, c->d_order);
         if (e != hipSuccess) return e;
     }
-    return c->row->block(nm_grid(c->nslots, c->cus), c->stream, p, plain_call(p));
+    return c->row->block(nm_grid(c->nslots, c->cus), c->stream, p, plain_call(p, c->row));
 }
 
 // 0 where the table has no configuration at q: pick_q then finds no room for such a grid

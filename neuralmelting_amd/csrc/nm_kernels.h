@@ -14,6 +14,8 @@
 #include "nm_device.h"
 #include "nm_math.h"
 
+#include <type_traits>
+
 namespace nm {
 
 constexpr int NVMAX = 16; // widest block reduction (the 16 raw moments of hmc_velocities)
@@ -389,6 +391,11 @@ template <class C, bool PLAIN = false>
 struct Replica {
     using IdxT = typename C::IdxT;
     static constexpr int BLOCK = C::BLOCK, TPA = C::TPA, NW = C::NW, G = C::G, NMAX = C::NMAX, MAXNB = C::MAXNB;
+    // The production form runs full cells only (nm_api.hip plain_call: natoms == NMAX), so its N is a compile-time constant: every
+    // `for (i = tid; i < N; i += BLOCK)` is one guarded pass, and N occupies no scalar register across the trajectory loop.  The workgroups per
+    // replica and the own range stay run-time values there too: as constants they took scalar spills away but cost more vector spills than the
+    // parent had (profiles/r23_scalar_diet.txt).
+    static constexpr bool FIXN = PLAIN;
 
     const KParams &p;
     const int tid, N, gslot;
@@ -455,11 +462,21 @@ struct Replica {
     const double *tape = nullptr;
     int tpos = 0, tlen = 0;
     double st_evals = 0.0, st_rebuilds = 0.0, st_eevals = 0.0, st_pairs = 0.0;
+    // the four counters behind stats columns 0-3 (K = 0: evaluations, 1: rebuilds, 2: energy evaluations, 3: pairs).  Production form: the wave's
+    // ust slots 27, 29, 30, 31 instead of eight registers that are alive through every trajectory; a trajectory step touches none of them (its
+    // force-only evaluations are counted once, behind the trajectory: nm_block_body).  The members above stay declared (layout: see layout_pad).
+    static constexpr bool ST_LDS = PLAIN;
+    template <int K>
+    __device__ __forceinline__ double &stc()
+    {
+        if constexpr (ST_LDS) return ust(K == 0 ? 27 : 28 + K);
+        else return K == 0 ? st_evals : K == 1 ? st_rebuilds : K == 2 ? st_eevals : st_pairs;
+    }
     int st_maxc = 0; // longest list row this thread has built (stats column 8)
     PROF_DECL
 
     __device__ Replica(const KParams &p_, int slot, int q_)
-        : p(p_), tid(threadIdx.x), N(p_.N), gslot(p_.slot0 + slot), Q(p_.cus), q(q_), a0((p_.N * q_) / p_.cus),
+        : p(p_), tid(threadIdx.x), N(FIXN ? NMAX : p_.N), gslot(p_.slot0 + slot), Q(p_.cus), q(q_), a0((p_.N * q_) / p_.cus),
           a1((p_.N * (q_ + 1)) / p_.cus)
     {
         xb = p.xbuf ? p.xbuf + (size_t)slot * 2 * C::XBUF_DOUBLES : nullptr;
@@ -988,8 +1005,8 @@ struct Replica {
         for (int i = tid; i < N; i += BLOCK) { x0[i] = px[i]; y0[i] = py[i]; z0[i] = pz[i]; }
         L0 = L;
         flags |= F_LIST_OK;
-        if (p.inj_rebuild >= 0 && (int)st_rebuilds == p.inj_rebuild && q == p.inj_q % Q) ovf = 1; // fault injection (tests)
-        st_rebuilds += 1.0;
+        if (p.inj_rebuild >= 0 && (int)stc<1>() == p.inj_rebuild && q == p.inj_q % Q) ovf = 1; // fault injection (tests)
+        stc<1>() += 1.0;
         if (block_any<NW, NVMAX>(ovf != 0, red, parity)) status |= ST_LIST_OVERFLOW;
         RTL(7);
     }
@@ -1222,7 +1239,9 @@ struct Replica {
     // 360 k at 20 vs 354 k at 10 or 12, 354 k at 26.  A swap point proportional to the row's own length — a run-time compare in every
     // trip instead of one the compiler folds — measured 3 % slower.
     static constexpr int PRIO_SW = TPA >= 16 ? 6 : TPA >= 8 ? 10 : TPA >= 4 ? 20 : 40;
-    __device__ __forceinline__ bool young() const { return (tid >> 6) >= NW / 2; }
+    // (production form: the wave's number as a scalar, so that the priority is set behind a scalar branch and not under a lane mask of "the
+    //  upper half of the workgroup" that is carried through the trajectory loop, spilled and read back three times per row)
+    __device__ __forceinline__ bool young() const { return (PLAIN ? __builtin_amdgcn_readfirstlane(tid >> 6) : (tid >> 6)) >= NW / 2; }
     __device__ __forceinline__ void prio_begin() const { if constexpr (C::LIST_LDS) { if (young()) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); } }
     __device__ __forceinline__ void prio_swap() const { if constexpr (C::LIST_LDS) { if (young()) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); } }
     __device__ __forceinline__ void prio_end() const { if constexpr (C::LIST_LDS) __builtin_amdgcn_s_setprio(0); }
@@ -1719,9 +1738,10 @@ struct Replica {
         bc_thr2 = thr * thr;
         bc_bad = !(thr > 0.0);
     }
-    __device__ __forceinline__ void check_begin(ListCheck &c)
+    // current: the caller knows that bc_* belong to (L, L0) as they are — box_consts() would compare and return
+    __device__ __forceinline__ void check_begin(ListCheck &c, bool current = false)
     {
-        box_consts();
+        if (!current) box_consts();
         c.sc = bc_sc; c.thr2 = bc_thr2; c.invL = bc_invL; c.bad = bc_bad ? 1 : 0;
     }
     __device__ __forceinline__ void check_atom(ListCheck &c, int i, double x, double y, double z) const
@@ -1754,7 +1774,10 @@ struct Replica {
     // that have just saved them (save(true)); velocity_create and wrap wrote them in front of the caller's barrier.  Their velocities are
     // not advanced (they are stale during a trajectory anyway).  The board is usually taken into sf[] while the velocities are drawn
     // (gaussian_fill), so mode 4 is left with the starts whose evaluation comes behind the velocities.
-    __device__ bool advance_and_share(int mode, double dtfm, double h)
+    // Returns the rebuild decision.  Production form: as the reduction's bit in ONE scalar register — as a bool it travelled round the
+    // trajectory loop as a 64-bit lane mask, spilled at the end of every step and read back in front of the next (eval_force).
+    typedef std::conditional_t<PLAIN, int, bool> need_t;
+    __device__ need_t advance_and_share(int mode, double dtfm, double h)
     {
         int timeout = 0, poisoned = 0;
         double *xg = xb ? xb + (size_t)(gen & 1) * C::XBUF_DOUBLES : nullptr;
@@ -1777,7 +1800,7 @@ struct Replica {
             }
         }
         ListCheck c;
-        check_begin(c);
+        check_begin(c, PLAIN && mode == 3); // (mode 3 follows eval_force, whose box_consts() saw this L and L0)
         NM_FOR_OWN(i) check_atom(c, i, px[i], py[i], pz[i]);
         if (Q > 1) {
             const int nown = a1 - a0, nother = N - nown;
@@ -1818,7 +1841,8 @@ struct Replica {
         TLINE_PREV(7);
         if (fl & 1) status |= ST_SYNC_TIMEOUT;
         if (fl & 2) status |= ST_LIST_OVERFLOW;
-        return (fl & 4) != 0;
+        if constexpr (PLAIN) return fl & 4;
+        else return (fl & 4) != 0;
     }
 
     // ------------------------------------------------------------------ lj/cut 2.5 energy, forces, virial
@@ -1863,7 +1887,7 @@ struct Replica {
         PROF_END(3);
         TLINE(3);
         PROF_BEGIN();
-        st_evals += 1.0;
+        stc<0>() += 1.0;
         // HALF: whether a thread left the fixed-point range rides along with the pair count (FR_TAG; the force-only evaluations of a
         // trajectory leave their threads' flags to the energy evaluation that ends it)
         double s[4] = { eacc, wacc, nacc, kacc };
@@ -1881,11 +1905,13 @@ struct Replica {
     // loop integrates the own atoms on the spot (both half kicks around this evaluation, the drift) and publishes their new
     // positions; it ends with the barrier after which positions may be overwritten.  ONE call site (the trajectory loop of the
     // block kernel), so this and eval() hold one pair loop each.
-    __device__ __forceinline__ void eval_force(bool need, double dtfm, double h)
+    __device__ __forceinline__ void eval_force(need_t need, double dtfm, double h)
     {
         TLINE(0);
         TLINE(1);
         PROF_BEGIN();
+        if constexpr (PLAIN) { if (need | (~__builtin_amdgcn_readfirstlane(flags) & F_LIST_OK)) rebuild(); } // (scalar: flags is block-uniform)
+        else
         if (need || !(flags & F_LIST_OK)) rebuild();
         PROF_END(2);
         TLINE(2);
@@ -1900,7 +1926,7 @@ struct Replica {
         PROF_END(3);
         TLINE(3);
         PROF_BEGIN();
-        st_evals += 1.0;
+        if constexpr (!ST_LDS) stc<0>() += 1.0;
         if constexpr (C::HALF) half_end(false, 0.0, kacc); // its barrier is the one below; the caller integrates (advance_and_share mode 2)
         else
         __syncthreads(); // nobody reads positions any more: they may be advanced
@@ -1918,7 +1944,7 @@ struct Replica {
                 fr_hit = 1; set_fresh(false);
                 psum[2] = fmod(psum[2], FR_TAG);
             }
-        st_eevals += 1.0; st_pairs += 0.5 * psum[2];
+        stc<2>() += 1.0; stc<3>() += 0.5 * psum[2];
         if (!(U == U) || isinf(U)) status |= ST_NONFINITE;
     }
     // Read by nothing: four bytes of Replica's layout.  Without them the compiler assigns the registers of the eleven block kernels whose lists
@@ -2672,7 +2698,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     const int tid = threadIdx.x;
     Replica<C, PLAIN> R(p, slot, qq);
     const bool writer = (tid == 0 && qq == 0); // one workgroup of the cluster writes the replica's results
-    const int N = p.N;
+    const int N = Replica<C, PLAIN>::FIXN ? C::NMAX : p.N;
     // status[] holds the bits of the LAST launch that ran: the writer, the only thread that ever reports for this slot, clears it first
     // (a memset in front of every launch was one more dependent operation on the stream per cycle).  A launch that found the halt word
     // armed has returned above and leaves the failed block's bits where they are.
@@ -2709,6 +2735,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     ntp = p.count[6 * slot]; nap = p.count[6 * slot + 1]; ntv = p.count[6 * slot + 2];
     nav = p.count[6 * slot + 3]; nth = p.count[6 * slot + 4]; nah = p.count[6 * slot + 5];
     U0 = 0.0; W0 = 0.0; c_pe = 0.0; c_vol = 0.0; c_volnew = 0.0; c_boxl = 0.0;
+    if constexpr (Replica<C, PLAIN>::ST_LDS) { R.template stc<0>() = 0.0; R.template stc<1>() = 0.0; R.template stc<2>() = 0.0; R.template stc<3>() = 0.0; }
     double &nth_entry = R.ust(22); // (stats column 7)
     nth_entry = nth;
     if constexpr (C::LOCAL_START) {
@@ -2723,7 +2750,8 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
     bool skip_eval = false;
     double &mv2new = R.ust(18); // kinetic-energy sum delivered with the last evaluation of a trajectory
     mv2new = 0.0;
-    bool have_need = false, pre_need = false; // rebuild decision delivered with a position hand-over (HMC steps)
+    bool have_need = false;
+    typename Replica<C, PLAIN>::need_t pre_need = 0; // rebuild decision delivered with a position hand-over (HMC steps)
     double &c_h = R.ust(19), &c_dtfm = R.ust(20), &mv2_0 = R.ust(21);
     c_h = 0.0; c_dtfm = 0.0; mv2_0 = 0.0;
 
@@ -2763,7 +2791,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 if (writer) {
                     p.evalU[slot] = R.U; p.evalW[slot] = R.W; report_status(p, slot, R.status | ((C::HALF && R.fr_hit) ? ST_FORCE_RANGE : 0), false);
                     double *st = p.stats + NM_STATS_COLS * (size_t)slot;
-                    st[0] += R.st_evals; st[1] += R.st_rebuilds; st[2] += R.st_eevals; st[3] += R.st_pairs;
+                    st[0] += R.template stc<0>(); st[1] += R.template stc<1>(); st[2] += R.template stc<2>(); st[3] += R.template stc<3>();
                 }
                 if constexpr (!PLAIN)
                     if (p.evalF) // every workgroup holds the forces of its own atoms
@@ -2814,7 +2842,8 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             pre_need = R.advance_and_share(smode, dtfm_, h_);
             PROF_END(9);
             const int nfo = p.nstps - 1;
-            for (int s = 0; s < nfo; ++s) {
+            int s = 0;
+            for (; s < nfo; ++s) {
                 if (__builtin_amdgcn_readfirstlane(R.status) & fatal) break;
                 R.eval_force(pre_need, dtfm_, h_);
                 if (__builtin_amdgcn_readfirstlane(R.status) & fatal) break; // own list overflowed: what the pair loop published is poisoned
@@ -2822,6 +2851,9 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 pre_need = R.advance_and_share(C::HALF ? 2 : 3, dtfm_, h_);
                 PROF_END(9);
             }
+            // (the force-only evaluations just made, counted here and not in every step; a trajectory left on an error may have made one more,
+            //  and a block that ends on an error reports no statistics)
+            if constexpr (Replica<C, PLAIN>::ST_LDS) R.template stc<0>() += (double)s;
             have_need = true;
             phase = PH_HMC_STEP;
             continue;
@@ -2983,7 +3015,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
             if (R.tape && R.tpos > R.tlen) R.status |= ST_TAPE_EXHAUSTED;
         report_status(p, slot, R.status, false);
         double *st = p.stats + NM_STATS_COLS * (size_t)slot;
-        st[0] += R.st_evals; st[1] += R.st_rebuilds; st[2] += R.st_eevals; st[3] += R.st_pairs;
+        st[0] += R.template stc<0>(); st[1] += R.template stc<1>(); st[2] += R.template stc<2>(); st[3] += R.template stc<3>();
         const unsigned long long ticks = wall_clock64() - t_entry;
         if (p.last_ticks) p.last_ticks[slot] = ticks;
         st[4] += (double)ticks; st[5] += R.same_xcd ? 1.0 : 0.0; st[6] += 1.0; st[7] += nth - nth_entry; st[9] = (double)C::MAXNB;
