@@ -392,10 +392,13 @@ struct Replica {
     using IdxT = typename C::IdxT;
     static constexpr int BLOCK = C::BLOCK, TPA = C::TPA, NW = C::NW, G = C::G, NMAX = C::NMAX, MAXNB = C::MAXNB;
     // The production form runs full cells only (nm_api.hip plain_call: natoms == NMAX), so its N is a compile-time constant: every
-    // `for (i = tid; i < N; i += BLOCK)` is one guarded pass, and N occupies no scalar register across the trajectory loop.  The workgroups per
-    // replica and the own range stay run-time values there too: as constants they took scalar spills away but cost more vector spills than the
-    // parent had (profiles/r23_scalar_diet.txt).
+    // `for (i = tid; i < N; i += BLOCK)` is one guarded pass, and N occupies no scalar register across the trajectory loop.
+    // FIXQ: a cluster row whose lists hold the own rows in LDS runs at NMAX / NLIST workgroups per replica (nm_rows.hip asserts it for the
+    // table), so its production form has Q, the length of the own range and what NM_FOR_OWN and the fetch loop derive from them at compile time
+    // too; only q remains a run-time value.  (Before the hand-over's granule test lost its nested exec regions this cost more vector spills
+    // than it saved scalar ones: profiles/r23_scalar_diet.txt, profiles/r24_flat_handover.txt.)
     static constexpr bool FIXN = PLAIN;
+    static constexpr bool FIXQ = PLAIN && C::LIST_LDS && C::NLIST < C::NMAX;
 
     const KParams &p;
     const int tid, N, gslot;
@@ -476,8 +479,8 @@ struct Replica {
     PROF_DECL
 
     __device__ Replica(const KParams &p_, int slot, int q_)
-        : p(p_), tid(threadIdx.x), N(FIXN ? NMAX : p_.N), gslot(p_.slot0 + slot), Q(p_.cus), q(q_), a0((p_.N * q_) / p_.cus),
-          a1((p_.N * (q_ + 1)) / p_.cus)
+        : p(p_), tid(threadIdx.x), N(FIXN ? NMAX : p_.N), gslot(p_.slot0 + slot), Q(FIXQ ? NMAX / C::NLIST : p_.cus), q(q_),
+          a0(FIXQ ? q_ * C::NLIST : (p_.N * q_) / p_.cus), a1(FIXQ ? q_ * C::NLIST + C::NLIST : (p_.N * (q_ + 1)) / p_.cus)
     {
         xb = p.xbuf ? p.xbuf + (size_t)slot * 2 * C::XBUF_DOUBLES : nullptr;
 #ifdef NM_EXPERIMENT
@@ -1581,7 +1584,7 @@ struct Replica {
     typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     // a workgroup whose own list overflowed publishes under magic ^ POISON: the peers accept the granule and learn the status
     // from it (the only status bit that is not identical in all workgroups of a cluster), so no status words are exchanged
-    static constexpr unsigned long long POISON = 0x5555555555555554ull;
+    static constexpr unsigned long long POISON = GRANULE_POISON;
     __device__ __forceinline__ unsigned long long magic_at(int g) const
     {
         return ((unsigned long long)p.launch_id << 32 | (unsigned long long)(uint32_t)(g + 1)) * 0x9E3779B97F4A7C15ull | 1ull;
@@ -1600,8 +1603,9 @@ struct Replica {
         if (same_xcd) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(g), "v"(w) : "memory");
         else asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(g), "v"(w) : "memory");
     }
-    // up to three granules per call, issued back to back and waited for once; `poisoned` is set when a granule carries the
-    // publisher's overflow mark
+    // up to four granules per call, issued back to back and waited for once; `poisoned` is set when a granule carries the
+    // publisher's overflow mark.  out[] is written by every poll, so a caller may use it without looking at the answer: behind a poll
+    // that gave up (false, `timeout` set) it holds the words read last, and the block ends on ST_SYNC_TIMEOUT before anything is made of them
     template <int K>
     __device__ __forceinline__ bool get_granules(double *const (&g)[K], unsigned long long mg, double (&out)[K], int &timeout, int &poisoned)
     {
@@ -1628,13 +1632,13 @@ struct Replica {
             int po = 0;
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const unsigned long long x = w[k].x ^ w[k].y;
-                ok = ok && (x == mg || x == (mg ^ POISON));
-                po |= (x == (mg ^ POISON)) ? 1 : 0;
+                const GranuleState st = granule_state(w[k].x ^ w[k].y ^ mg); // (no short circuit: nm_math.h)
+                ok = ok & st.valid;
+                po |= st.poisoned ? 1 : 0;
             }
-            if (ok) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) out[k] = __longlong_as_double((long long)w[k].x);
+            for (int k = 0; k < K; ++k) out[k] = __longlong_as_double((long long)w[k].x); // (what was read last, if the poll gives up)
+            if (ok) {
                 poisoned |= po;
                 return true;
             }
@@ -1816,21 +1820,18 @@ struct Replica {
                 double x3[3];
                 const double rx = x0[i], ry = y0[i], rz = z0[i]; // (read before the poll: at 8^3 they come from the global spill, a memory latency that
                 // now lies under the granules' round trip instead of behind it)
-                bool got = true;
                 if constexpr (C::LOCAL_START) {
                     if (mode == 5) { x3[0] = sfx[i]; x3[1] = sfy[i]; x3[2] = sfz[i]; }
-                    else got = get_granules<3>(g3, mgr, x3, timeout, poisoned);
-                    if (local && got) {
+                    else get_granules<3>(g3, mgr, x3, timeout, poisoned);
+                    if (local) {
                         if (mode == 4) { sfx[i] = x3[0]; sfy[i] = x3[1]; sfz[i] = x3[2]; }
                         x3[0] = __builtin_fma(h, __builtin_fma(dtfm, x3[0], vx[i]), px[i]);
                         x3[1] = __builtin_fma(h, __builtin_fma(dtfm, x3[1], vy[i]), py[i]);
                         x3[2] = __builtin_fma(h, __builtin_fma(dtfm, x3[2], vz[i]), pz[i]);
                     }
-                } else got = get_granules<3>(g3, mg, x3, timeout, poisoned);
-                if (got) {
-                    px[i] = x3[0]; py[i] = x3[1]; pz[i] = x3[2];
-                    check_atom(c, x3[0], x3[1], x3[2], rx, ry, rz);
-                }
+                } else get_granules<3>(g3, mg, x3, timeout, poisoned);
+                px[i] = x3[0]; py[i] = x3[1]; pz[i] = x3[2];
+                check_atom(c, x3[0], x3[1], x3[2], rx, ry, rz);
             }
             if (local) flags |= F_SF_ALL;
             else ++gen;

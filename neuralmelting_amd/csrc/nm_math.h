@@ -68,4 +68,16 @@ NM_HD void sincos_turn(double x, double &sn, double &cs)
     if ((n + 1) & 2) cs = -cs;
 }
 
+// The state of one hand-over granule {bits, bits ^ magic} (nm_kernels.h: put_granule, get_granules), from x = word0 ^ word1 ^ magic of the
+// reader's generation: x == 0 is a valid granule, x == GRANULE_POISON a valid one whose publisher's list overflowed, every other x a torn or
+// stale one that is read again.  The exact test — "no bit outside GRANULE_POISON" would take 2^31 torn patterns for valid.  Two plain
+// compares joined without a short circuit: a reader that tests K granules holds two lane masks, not K nested exec regions.
+constexpr unsigned long long GRANULE_POISON = 0x5555555555555554ull;
+struct GranuleState { bool valid, poisoned; };
+NM_HD GranuleState granule_state(unsigned long long x)
+{
+    const bool pz = x == GRANULE_POISON;
+    return { bool((x == 0ull) | pz), pz };
+}
+
 } // namespace nm

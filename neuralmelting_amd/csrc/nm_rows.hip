@@ -107,6 +107,11 @@ R with_row(int pot, int kind, int q, R none, F &&f)
 NM_CFG_ROWS(NM_ROW)
 #undef NM_ROW
 static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, "densities: in LDS at 864 atoms, in the spill at 2048");
+// a cluster row with own-row lists in LDS runs at NMAX / NLIST workgroups per replica and at no other number: its production form has that
+// number and the own range at compile time (Replica::FIXQ), whatever KParams::cus says
+#define NM_ROW(P, K, Q, C, FUSED) static_assert(!(C::LIST_LDS && C::NLIST < C::NMAX) || Q * C::NLIST == C::NMAX, #C);
+NM_CFG_ROWS(NM_ROW)
+#undef NM_ROW
 
 // The production form of the block (nm_block_body's PLAIN) is instantiated for the 4^3 rows, kind 0, whose NMAX the static_assert above
 // ties to 256: block and fused kernels.  The 864- and 2048-atom rows keep the general form alone (build time).
