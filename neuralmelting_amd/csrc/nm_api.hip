@@ -1,9 +1,10 @@
-// nm_api.hip — C-ABI (include/nm.h) over the gfx950 kernels.  The context owns all device memory, one HIP
-// stream and the HIP events used for measurement; nothing here falls back to a CPU path: without a usable
-// HIP device nm_create fails with NM_ERR_HIP.  Host code only: the kernels, their configuration table and their
+// nm_api.hip — C-ABI (include/nm.h) over the gfx950 kernels.  The context owns all device and pinned memory, its two HIP
+// streams and its HIP events through the types of nm_own.h, which release them; nothing here falls back to a CPU path: without a
+// usable HIP device nm_create fails with NM_ERR_HIP.  Host code only: the kernels, their configuration table and their
 // launchers are nm_rows.hip, reached through the rows of nm_rows.h.
 #include "../../include/nm.h"
 #include "nm_lattice.h"
+#include "nm_own.h"
 #include "nm_rows.h"
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -23,7 +25,7 @@ namespace nm { __attribute__((visibility("hidden"))) thread_local std::string g_
 
 namespace {
 
-struct EvPair { hipEvent_t a, b; bool used; uint32_t launch_id; };
+struct EvPair { Event a, b; bool used = false; uint32_t launch_id = 0; };
 
 } // namespace
 
@@ -33,23 +35,24 @@ struct nm_ctx {
     int cus;                    // workgroups per replica
     const Row *row;             // the kernels of (pot, kind, cus), nm_rows.h; set with cus (set_q)
     bool whole_rows;            // the slot range is made of whole pressure rows (nm_exchange can run on the device)
-    double *d_xbuf;
     uint32_t launch_id;
     int start_handover = 0; // NM_START_HANDOVER=1 (read once, nm_create): the 4^3 cluster kernels start every trajectory with a hand-over
     double lat, mass, kB, mvv2e, ftm2v, nktv2p, skin, rc;
     int pot; // 0 lj/cut, 1 Sutton-Chen EAM n = 7 (Al), 2 Sutton-Chen EAM n = 9 (Cu, Ni): the kernels' Cfg POT
     double sc_eps, sc_a2, sc_c; // Sutton-Chen constants of the element (nm_lattice.h sc_element); unused by lj/cut
     uint32_t step;
-    hipStream_t stream;
+    // The streams stand in front of everything that work on them can touch: members go in reverse order, so every buffer and event below is
+    // released before the streams are destroyed, and ~nm_ctx has waited for both streams before the first member goes.  side: the rings' copies
+    Stream stream, side;
     // device
-    double *d_x, *d_v, *d_box, *d_steps, *d_therm, *d_count, *d_et, *d_pf, *d_tq, *d_stats;
-    float *d_ratio;
-    int *d_slot2buf, *d_status, *d_status_acc, *d_halt, *d_rerun, *d_nswaps, *d_order;
-    unsigned long long *d_last_ticks;
+    DevBuf<double> d_x, d_v, d_box, d_steps, d_therm, d_count, d_et, d_pf, d_tq, d_stats, d_xbuf;
+    DevBuf<float> d_ratio;
+    DevBuf<int> d_slot2buf, d_status, d_status_acc, d_halt, d_rerun, d_nswaps, d_order;
+    DevBuf<unsigned long long> d_last_ticks;
     bool use_order; // one workgroup per replica and more replicas than CUs: launch the slowest slots first (nm_order_kernel)
-    unsigned int *d_census; // residency census of cluster launches (nm_kernels.h): the grid's counter, then one per cluster
+    DevBuf<unsigned int> d_census; // residency census of cluster launches (nm_kernels.h): the grid's counter, then one per cluster
     unsigned int census_base = 0, census_cbase = 0; // what those counters stand at (they only grow; reset_census zeroes both)
-    unsigned int *d_rowsync = nullptr; // nm_run_cycles: per local row an arrival counter and a release word, then the abort word (KParams::rowbar, rowgo, cyc_abort)
+    DevBuf<unsigned int> d_rowsync; // nm_run_cycles: per local row an arrival counter and a release word, then the abort word (KParams::rowbar, rowgo, cyc_abort)
     bool over;              // the grid holds twice the clusters the chip does at once (pick_q)
     // Calls queued on the stream since the host last looked at the outcome (settle): if a block of them stopped because its
     // cluster grid was not resident or a hand-over timed out, nothing after it has run (KParams::halt) and the same calls are
@@ -59,24 +62,23 @@ struct nm_ctx {
     int heals = 0;              // blocks re-issued at a lower Q so far
     int cluster_launches = 0;   // (NM_INJECT_CENSUS counts these)
     std::string note;           // what nm_create's residency probe and later re-issues had to give up (nm_create_note)
-    double *d_tape, *d_xtape, *d_trace, *d_xcrit, *d_evalU, *d_evalW, *d_evalF, *d_aux;
-    int *d_tape_off;
-    void *d_nbr;
-    unsigned long long *d_prof; // diagnostic build only (NM_PROF)
-    unsigned long long *d_tline; // experiment build only
+    DevBuf<double> d_tape, d_xtape, d_trace, d_xcrit, d_evalU, d_evalW, d_evalF, d_aux; // d_trace: grown on demand (issue_block)
+    DevBuf<int> d_tape_off;
+    DevBuf<unsigned short> d_nbr;
+    DevBuf<unsigned long long> d_prof; // diagnostic build only (NM_PROF)
+    DevBuf<unsigned long long> d_tline; // experiment build only
     // recorded cycles: rings 0 and 1 hold the records of nm_run_cycles_recorded calls, rings 2 and 3 those of nm_snapshot (one cycle each).  A ring
     // is a device buffer of cap cycles' records (nslots x (3N + NM_REC_HEAD) doubles per cycle) and its pinned host copy, which lands in one D2H on
     // the side stream (the main stream never waits for it) behind the ring's last record.  n: records of the call in it, next: the next one
     // nm_snapshot_fetch hands out (the ring is free when n == 0); tag0: the tag of its first record; dirty: settle re-issued launches that write it,
     // the host copy is stale
-    hipStream_t side = nullptr;
-    struct Ring { double *d = nullptr, *h = nullptr; hipEvent_t taken = nullptr, landed = nullptr; int cap = 0, n = 0, next = 0; uint32_t tag0 = 0;
+    struct Ring { DevBuf<double> d; PinBuf<double> h; Event taken, landed; int cap = 0, n = 0, next = 0; uint32_t tag0 = 0;
                   bool dirty = false; } ring[4];
     uint32_t rec_calls = 0;
     std::deque<int> fetchq; // the rings whose next records nm_snapshot_fetch hands out, oldest first
-    double *h_stage = nullptr;   // pinned host staging area (nm_set_state / nm_get_state)
-    size_t stage_cap = 0;
-    size_t trace_cap;
+    // pinned host staging area, grown on demand: whole device arrays on their way between the caller's arrays and HBM (copy_staged), and the
+    // volumes that go with a few boxes (copy_slots)
+    PinBuf<double> h_stage;
     int trace_on, trace_mod;
     int xtape_n;
     std::vector<double> h_et, h_pf, h_tq;
@@ -86,6 +88,11 @@ struct nm_ctx {
     int launches;
     double total_ms;
     std::string err;
+    ~nm_ctx()
+    {
+        if (stream) hipStreamSynchronize(stream);
+        if (side) hipStreamSynchronize(side);
+    }
 };
 
 namespace {
@@ -102,9 +109,6 @@ int fail(nm_ctx *c, int code, const std::string &msg)
         if (e_ != hipSuccess)                                                                        \
             return fail((c), NM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));         \
     } while (0)
-
-template <class T>
-hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(T)); }
 
 // test-only environment hooks (NM_ASSUME_CUS, NM_INJECT_OVERFLOW, NM_INJECT_CENSUS) are honoured only under NM_TESTING=1, so that a
 // stray variable cannot change Q or stop a production run
@@ -132,7 +136,7 @@ void fill_params(const nm_ctx *c, KParams &p)
     p.nbr_g = c->d_nbr; p.aux_g = c->d_aux;
     p.prof = c->d_prof;
     p.cus = c->cus; p.xbuf = c->d_xbuf; p.launch_id = c->launch_id;
-    p.census = c->cus > 1 ? c->d_census : nullptr; p.over = (c->cus > 1 && c->over) ? 1 : 0;
+    p.census = c->cus > 1 ? c->d_census.p : nullptr; p.over = (c->cus > 1 && c->over) ? 1 : 0;
     p.census_base = c->census_base; p.census_cbase = c->census_cbase;
     p.plain_granules = 1;
     if (const char *e = std::getenv("NM_PLAIN_GRANULES")) p.plain_granules = std::atoi(e);
@@ -147,7 +151,7 @@ void fill_params(const nm_ctx *c, KParams &p)
         if (std::sscanf(e, "%d,%d", &n, &q) >= 1) { p.inj_rebuild = n; p.inj_q = q; }
     }
     p.status_acc = c->d_status_acc; p.halt = c->d_halt; p.rerun_mask = nullptr; p.inj_census = 0;
-    p.order = (c->use_order && (c->cus == 1 || c->over)) ? c->d_order : nullptr; p.last_ticks = c->d_last_ticks;
+    p.order = (c->use_order && (c->cus == 1 || c->over)) ? c->d_order.p : nullptr; p.last_ticks = c->d_last_ticks;
 }
 
 // workgroups of a launch: 8 Q ceil(nslots / 8), the block kernel's cluster mapping (nm_kernels.h); nslots x Q when 8 divides nslots or Q = 1
@@ -298,12 +302,7 @@ int issue_block(nm_ctx *c, int kind, int arg, uint32_t step, int trace, const in
         p.mod = arg;
         if (trace) {
             const size_t need = (size_t)c->nslots * arg * NM_TRACE_COLS;
-            if (need > c->trace_cap) {
-                if (c->d_trace) HIPCHK(c, hipFree(c->d_trace));
-                c->d_trace = nullptr;
-                HIPCHK(c, dalloc(&c->d_trace, need));
-                c->trace_cap = need;
-            }
+            HIPCHK(c, c->d_trace.reserve(need));
             if (!d_mask) HIPCHK(c, hipMemsetAsync(c->d_trace, 0, need * sizeof(double), c->stream));
             p.trace = c->d_trace;
             c->trace_mod = arg;
@@ -333,7 +332,7 @@ int issue_adapt(nm_ctx *c)
 int issue_exchange(nm_ctx *c, uint32_t step)
 {
     HIPCHK(c, launch_exchange(c->stream, c->cfg.nrows, c->cfg.nt, c->cfg.row0, c->cfg.seed, step, c->d_slot2buf, c->d_therm, c->d_et, c->d_pf,
-                              c->xtape_n ? c->d_xtape : nullptr, c->d_xcrit, c->d_nswaps, c->d_halt));
+                              c->xtape_n ? c->d_xtape.p : nullptr, c->d_xcrit, c->d_nswaps, c->d_halt));
     c->journal.push_back({ OP_EXCHANGE, 0, 0, step, 0u });
     return NM_OK;
 }
@@ -381,7 +380,7 @@ int issue_cycles(nm_ctx *c, int ncycles, int mod, uint32_t step, bool timed, int
         return NM_OK;
     }
     const int nrows = c->cfg.nrows;
-    if (!c->d_rowsync) HIPCHK(c, dalloc(&c->d_rowsync, (size_t)2 * nrows + 2));
+    if (!c->d_rowsync) HIPCHK(c, c->d_rowsync.alloc((size_t)2 * nrows + 2));
     HIPCHK(c, hipMemsetAsync(c->d_rowsync, 0, sizeof(unsigned int) * ((size_t)2 * nrows + 2), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_nswaps, 0, sizeof(int), c->stream));
     const uint32_t first_id = c->launch_id + 1;
@@ -469,22 +468,15 @@ int alloc_cluster_buffers(nm_ctx *c)
     const size_t aux_doubles = c->row ? c->row->aux_doubles : 0, xbd = c->row ? c->row->xbuf_doubles : 0;
     // the new buffers first, swapped in only when both exist: a failure leaves the context with the buffers (and the workgroups per
     // replica) it can still run with
-    double *aux = nullptr, *xbuf = nullptr;
+    DevBuf<double> aux, xbuf;
     hipError_t e = hipSuccess;
-    if (aux_doubles) e = dalloc(&aux, ns * c->cus * aux_doubles);
-    if (e == hipSuccess && c->cus > 1) {
-        e = dalloc(&xbuf, ns * 2 * xbd);
-        if (e == hipSuccess) e = hipMemset(xbuf, 0, ns * 2 * xbd * sizeof(double));
-    }
+    if (aux_doubles) e = aux.alloc(ns * c->cus * aux_doubles);
+    if (e == hipSuccess && c->cus > 1) e = xbuf.alloc_zeroed(ns * 2 * xbd);
     if (e != hipSuccess) {
-        if (aux) hipFree(aux);
-        if (xbuf) hipFree(xbuf);
         if (!c->d_xbuf) set_q(c, 1, false); // nothing to hand over with: one workgroup per replica (its spill area, if any, is a subset of what is there)
         return fail(c, NM_ERR_HIP, std::string("alloc_cluster_buffers: ") + hipGetErrorString(e));
     }
-    if (c->d_aux) hipFree(c->d_aux);
-    if (c->d_xbuf) hipFree(c->d_xbuf);
-    c->d_aux = aux; c->d_xbuf = xbuf;
+    c->d_aux = std::move(aux); c->d_xbuf = std::move(xbuf); // (empty where the row needs none: what was held is released either way)
     return NM_OK;
 }
 
@@ -579,30 +571,107 @@ int check_status(nm_ctx *c)
     return settle(c);
 }
 
-void free_ring(nm_ctx::Ring &g)
+// the context's device, then the outcome of everything queued: a halted queue is re-issued, or its error reported, before anything
+// it touches is read or replaced.  The opening of every entry point that does either, behind its argument checks
+int settled(nm_ctx *c)
 {
-    if (g.d) hipFree(g.d);
-    if (g.h) hipHostFree(g.h);
-    if (g.taken) hipEventDestroy(g.taken);
-    if (g.landed) hipEventDestroy(g.landed);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return check_status(c);
 }
 
-// everything a context owns; safe on a half-built one (nm_create's failure paths: `new nm_ctx()` zero-initialises the pointers)
-void free_ctx(nm_ctx *c)
+// slot -> buffer, as everything queued has left it (settled: it has run, or has been re-issued, before state is read or replaced)
+int slot_map(nm_ctx *c, std::vector<int> &m)
 {
-    if (c->stream) hipStreamSynchronize(c->stream);
-    for (auto &e : c->ev) { if (e.a) hipEventDestroy(e.a); if (e.b) hipEventDestroy(e.b); }
-    void *ptrs[] = { c->d_x, c->d_v, c->d_box, c->d_steps, c->d_therm, c->d_count, c->d_ratio, c->d_et, c->d_pf, c->d_tq,
-                     c->d_stats, c->d_slot2buf, c->d_status, c->d_nswaps, c->d_evalU, c->d_evalW, c->d_evalF, c->d_xcrit,
-                     c->d_xtape, c->d_tape, c->d_tape_off, c->d_trace, c->d_nbr, c->d_aux, c->d_prof, c->d_tline, c->d_xbuf, c->d_census,
-                     c->d_status_acc, c->d_halt, c->d_rerun, c->d_order, c->d_last_ticks, c->d_rowsync };
-    for (void *q : ptrs) if (q) hipFree(q);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->side) hipStreamSynchronize(c->side);
-    for (auto &g : c->ring) free_ring(g);
-    if (c->side) hipStreamDestroy(c->side);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    if (const int rc = settled(c)) return rc;
+    m.resize(c->nslots);
+    HIPCHK(c, hipMemcpy(m.data(), c->d_slot2buf, sizeof(int) * c->nslots, hipMemcpyDeviceToHost));
+    return NM_OK;
+}
+
+// ---- state in and out.  Both directions, a range or a list of slots, any subset of the arrays (a null one is skipped) go through two routines:
+// copy_slots, one small copy per slot and array, for a few slots, and copy_staged, whole device arrays through the pinned staging area, for
+// many.  put: from the caller's arrays to the device (they are not written then); x, v [..][3N], box [..], dxdvdt [..][3], th [..][5] = temp,
+// pe, ke, virial, vol (nm_set_thermo's columns), row q belonging to slot slot_of(q).  A box that is put takes its volume along (therm column 4).
+hipError_t copy_row(nm_ctx *c, bool put, double *host, double *dev, size_t n)
+{
+    return put ? hipMemcpyAsync(dev, host, n * sizeof(double), hipMemcpyHostToDevice, c->stream)
+               : hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+}
+
+// The listed buffers copied back to back on the context's stream, ONE wait (the split-row exchange re-seats the replicas that swapped,
+// neuralmelting_amd/exchange.py).  The volumes go through the pinned staging area, so that nothing on this stack frame is read after return;
+// a thermo row that is put lands behind its slot's box and volume
+template <class SlotOf>
+int copy_slots(nm_ctx *c, const std::vector<int> &m, bool put, int nk, SlotOf slot_of, double *x, double *v, double *box, double *dxdvdt, double *th)
+{
+    const size_t n3 = (size_t)3 * c->N;
+    if (put) HIPCHK(c, c->h_stage.reserve((size_t)nk + 1));
+    double *vol = c->h_stage;
+    for (int q = 0; q < nk; ++q) {
+        const size_t bq = (size_t)m[slot_of(q)];
+        if (x) HIPCHK(c, copy_row(c, put, x + q * n3, c->d_x + bq * n3, n3));
+        if (v) HIPCHK(c, copy_row(c, put, v + q * n3, c->d_v + bq * n3, n3));
+        if (box) HIPCHK(c, copy_row(c, put, box + q, c->d_box + bq, 1));
+        if (box && put) {
+            vol[q] = std::pow(box[q], 3.0);
+            HIPCHK(c, copy_row(c, put, vol + q, c->d_therm + 5 * bq + 4, 1));
+        }
+        if (dxdvdt) HIPCHK(c, copy_row(c, put, dxdvdt + 3 * q, c->d_steps + 3 * bq, 3));
+        if (th) HIPCHK(c, copy_row(c, put, th + 5 * q, c->d_therm + 5 * bq, 5));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // the caller's arrays (pageable: staged by the runtime) and the staging area are free again
+    return NM_OK;
+}
+
+// Slots k0 .. k0 + nk - 1 through whole device arrays: one asynchronous copy per array and direction and one wait each way, instead of up
+// to four small copies per replica.  A get reads the arrays back and gathers; a put scatters into the staging area, which a partial range
+// first fills from the device (the merge; set-up path, not timed), and writes the arrays
+int copy_staged(nm_ctx *c, const std::vector<int> &m, bool put, int k0, int nk, double *x, double *v, double *box, double *dxdvdt)
+{
+    const size_t n3 = (size_t)3 * c->N, ns = (size_t)c->nslots;
+    HIPCHK(c, c->h_stage.reserve(2 * ns * n3 + 9 * ns));
+    double *const hx = c->h_stage, *const ht = hx + 2 * ns * n3 + 4 * ns; // (therm: read and written with a box that is put, for its column 4)
+    struct { double *host, *stage, *dev; size_t w; } const arr[] = { { x, hx, c->d_x, n3 }, { v, hx + ns * n3, c->d_v, n3 },
+        { box, hx + 2 * ns * n3, c->d_box, 1 }, { dxdvdt, hx + 2 * ns * n3 + ns, c->d_steps, 3 } };
+    const bool read_back = !put || nk != c->nslots;
+    for (const auto &a : arr)
+        if (a.host && read_back) HIPCHK(c, copy_row(c, false, a.stage, a.dev, ns * a.w));
+    if (put && box) HIPCHK(c, copy_row(c, false, ht, c->d_therm, 5 * ns));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int q = 0; q < nk; ++q) {
+        const size_t bq = (size_t)m[k0 + q];
+        for (const auto &a : arr)
+            if (a.host) {
+                double *const h = a.host + q * a.w, *const s = a.stage + bq * a.w;
+                std::memcpy(put ? s : h, put ? h : s, a.w * sizeof(double));
+            }
+        if (put && box) ht[5 * bq + 4] = std::pow(box[q], 3.0);
+    }
+    if (!put) return NM_OK;
+    for (const auto &a : arr)
+        if (a.host) HIPCHK(c, copy_row(c, true, a.stage, a.dev, ns * a.w));
+    if (box) HIPCHK(c, copy_row(c, true, ht, c->d_therm, 5 * ns));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging area is reused by the next call
+    return NM_OK;
+}
+
+// a range of slots: the few-slots path for at most 8 of them that are not all (the split-row exchange), else the staged arrays
+int copy_range(nm_ctx *c, bool put, int k0, int nk, double *x, double *v, double *box, double *dxdvdt)
+{
+    std::vector<int> m;
+    if (const int rc = slot_map(c, m)) return rc;
+    if (nk <= 8 && nk < c->nslots) return copy_slots(c, m, put, nk, [k0](int q) { return k0 + q; }, x, v, box, dxdvdt, nullptr);
+    return copy_staged(c, m, put, k0, nk, x, v, box, dxdvdt);
+}
+
+int copy_list(nm_ctx *c, const char *fn, bool put, int nk, const int *slots, double *x, double *v, double *box, double *dxdvdt, double *th)
+{
+    if (!c || nk < 0 || (nk && !slots)) return fail(c, NM_ERR_ARG, std::string(fn) + ": bad argument");
+    for (int q = 0; q < nk; ++q)
+        if (slots[q] < 0 || slots[q] >= c->nslots) return fail(c, NM_ERR_ARG, std::string(fn) + ": slot out of range");
+    std::vector<int> m;
+    if (const int rc = slot_map(c, m)) return rc;
+    return copy_slots(c, m, put, nk, [slots](int q) { return slots[q]; }, x, v, box, dxdvdt, th);
 }
 
 } // namespace
@@ -616,28 +685,10 @@ int nm_natoms(const nm_ctx *ctx) { return ctx ? ctx->N : NM_ERR_ARG; }
 int nm_cus_per_replica(const nm_ctx *ctx) { return ctx ? ctx->cus : NM_ERR_ARG; }
 int nm_heal_count(const nm_ctx *ctx) { return ctx ? ctx->heals : NM_ERR_ARG; }
 
-int nm_create(const nm_config *cfg, nm_ctx **out)
+// everything of nm_create behind its argument checks; a failure leaves its message in c->err and what was built so far to ~nm_ctx
+static int init_ctx(nm_ctx *c, const nm_config *cfg)
 {
-    if (!cfg || !out) return fail(nullptr, NM_ERR_ARG, "nm_create: null argument");
-    *out = nullptr;
-    if (cfg->size != (int32_t)sizeof(nm_config)) return fail(nullptr, NM_ERR_ARG, "nm_create: nm_config size mismatch (ABI)");
-    if (cfg->natoms < 2 || cfg->natoms > 2048) return fail(nullptr, NM_ERR_ARG, "nm_create: natoms must be in [2, 2048]");
     const bool by_slots = cfg->nslots > 0;
-    if (cfg->np < 1 || cfg->nt < 1) return fail(nullptr, NM_ERR_ARG, "nm_create: bad grid");
-    if (by_slots ? (cfg->slot0 < 0 || cfg->slot0 + cfg->nslots > cfg->np * cfg->nt)
-                 : (cfg->nrows < 1 || cfg->row0 < 0 || cfg->row0 + cfg->nrows > cfg->np))
-        return fail(nullptr, NM_ERR_ARG, "nm_create: bad row / slot range");
-    if (!cfg->P || !cfg->T) return fail(nullptr, NM_ERR_ARG, "nm_create: P and T grids are required");
-    if (cfg->nstps < 1 || cfg->ppos < 0 || cfg->pvol < 0 || cfg->ppos + cfg->pvol > 1.0)
-        return fail(nullptr, NM_ERR_ARG, "nm_create: bad move parameters");
-    if (cfg->element != NM_EL_LJ && !lat::sc_element(cfg->element))
-        return fail(nullptr, NM_ERR_UNSUPPORTED, "nm_create: elements LJ (0), Al (1), Ni (2) and Cu (3) have device force kernels in this build");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, NM_ERR_HIP, "nm_create: no HIP device available (this engine has no CPU fallback)");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, NM_ERR_ARG, "nm_create: device ordinal out of range");
-
-    nm_ctx *c = new nm_ctx();
     c->cfg = *cfg;
     c->h_P.assign(cfg->P, cfg->P + cfg->np); c->h_T.assign(cfg->T, cfg->T + cfg->nt);
     c->cfg.P = c->h_P.data(); c->cfg.T = c->h_T.data();
@@ -647,9 +698,7 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     c->whole_rows = (c->slot0 % cfg->nt == 0) && (c->nslots % cfg->nt == 0);
     c->cfg.row0 = c->slot0 / cfg->nt;                       // meaningful only for whole rows
     c->cfg.nrows = c->whole_rows ? c->nslots / cfg->nt : 0;
-    c->step = 0;
-    c->trace_on = 0; c->trace_mod = 0; c->trace_cap = 0; c->xtape_n = 0;
-    c->ev_next = 0; c->launches = 0; c->total_ms = 0.0;
+    // (step, launch_id, the trace and tape settings, the timing accumulators: zero from `new nm_ctx()`)
     // material tables, remcmc:873-893
     // Verlet-list skin: not observable in results, only in the rebuild rate.  (Round 1 took 0.3, LAMMPS's lj default, as best at 256 atoms —
     // measured in the first cycles after the lattice start, when HMC steps are still short and rebuilds rare;
@@ -698,94 +747,96 @@ int nm_create(const nm_config *cfg, nm_ctx **out)
     for (int q : { 1, 2, 4, 8 })
         if (const Row *r = nm_row(c->pot, c->kind, q)) nbr_elems = std::max(nbr_elems, r->nbr_g_elems);
 
-#define CHK(call)                                                                                     \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            fail(nullptr, NM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));             \
-            free_ctx(c);                                                                              \
-            return NM_ERR_HIP;                                                                        \
-        }                                                                                             \
-    } while (0)
-    CHK(hipSetDevice(cfg->device));
-    CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    set_q(c, 1, false); c->d_xbuf = nullptr; c->d_aux = nullptr; c->launch_id = 0; c->d_census = nullptr;
-    c->d_status_acc = nullptr; c->d_halt = nullptr; c->d_rerun = nullptr; c->d_order = nullptr; c->d_last_ticks = nullptr; c->use_order = false;
+    HIPCHK(c, hipSetDevice(cfg->device));
+    HIPCHK(c, c->stream.create());
+    set_q(c, 1, false);
+    const size_t ns = c->nslots, n3 = (size_t)3 * c->N;
     std::string note;
     {
         int want = 8;
         if (const char *e = std::getenv("NM_CUS_PER_REPLICA")) want = std::atoi(e);
-        CHK(dalloc(&c->d_census, census_words(c->nslots)));
-        CHK(dalloc(&c->d_status, (size_t)c->nslots));
-        CHK(hipMemset(c->d_status, 0, sizeof(int) * c->nslots));
-        CHK(dalloc(&c->d_status_acc, (size_t)c->nslots));
-        CHK(hipMemset(c->d_status_acc, 0, sizeof(int) * c->nslots));
-        CHK(dalloc(&c->d_rerun, (size_t)c->nslots));
-        CHK(dalloc(&c->d_order, (size_t)c->nslots));
-        CHK(dalloc(&c->d_last_ticks, (size_t)c->nslots));
-        CHK(hipMemset(c->d_last_ticks, 0, sizeof(unsigned long long) * c->nslots)); // (first launch: all ties, i.e. index order)
-        CHK(dalloc(&c->d_halt, 1));
-        CHK(hipMemset(c->d_halt, 0, sizeof(int)));
-        CHK(dalloc(&c->d_slot2buf, (size_t)c->nslots));
+        // what the census probe needs
+        HIPCHK(c, c->d_census.alloc(census_words(c->nslots)));
+        HIPCHK(c, c->d_status.alloc_zeroed(ns));
+        HIPCHK(c, c->d_status_acc.alloc_zeroed(ns));
+        HIPCHK(c, c->d_rerun.alloc(ns));
+        HIPCHK(c, c->d_order.alloc(ns));
+        HIPCHK(c, c->d_last_ticks.alloc_zeroed(ns)); // (first launch: all ties, i.e. index order)
+        HIPCHK(c, c->d_halt.alloc_zeroed(1));
         {
-            std::vector<int> ident((size_t)c->nslots);
+            std::vector<int> ident(ns);
             for (int k = 0; k < c->nslots; ++k) ident[k] = k;
-            CHK(hipMemcpy(c->d_slot2buf, ident.data(), sizeof(int) * c->nslots, hipMemcpyHostToDevice));
+            HIPCHK(c, c->d_slot2buf.upload(ident.data(), ns));
         }
-        if (pick_q(c, want, note) != NM_OK) { g_create_error = c->err; free_ctx(c); return NM_ERR_HIP; } // (workgroups per replica: see pick_q)
+        if (const int rc = pick_q(c, want, note)) return rc; // (workgroups per replica: see pick_q)
         if (!note.empty()) note = "nm_create: " + note;
         if (testing())
             if (const char *e = std::getenv("NM_TEST_CENSUS_BASE")) { // tests: start the monotonic census counters just below the value at
                 // which issue_block zeroes them (a wrap is otherwise 16 million launches away)
                 const unsigned int b = (unsigned int)std::strtoul(e, nullptr, 0);
                 std::vector<unsigned int> w(census_words(c->nslots), b);
-                CHK(hipMemcpy(c->d_census, w.data(), sizeof(unsigned int) * w.size(), hipMemcpyHostToDevice));
+                HIPCHK(c, hipMemcpy(c->d_census, w.data(), sizeof(unsigned int) * w.size(), hipMemcpyHostToDevice));
                 c->census_base = c->census_cbase = b;
             }
         {
             hipDeviceProp_t prop;
-            CHK(hipGetDeviceProperties(&prop, cfg->device));
+            HIPCHK(c, hipGetDeviceProperties(&prop, cfg->device));
             c->use_order = c->over || c->nslots > prop.multiProcessorCount; // (more workgroups / clusters than the chip holds at once: longest first)
             if (const char *e = std::getenv("NM_LAUNCH_ORDER")) c->use_order = std::atoi(e) != 0;
         }
     }
-    const size_t ns = c->nslots, n3 = (size_t)3 * c->N;
-    CHK(dalloc(&c->d_x, ns * n3)); CHK(dalloc(&c->d_v, ns * n3));
-    CHK(dalloc(&c->d_box, ns)); CHK(dalloc(&c->d_steps, ns * 3)); CHK(dalloc(&c->d_therm, ns * 5));
-    CHK(dalloc(&c->d_count, ns * 6)); CHK(dalloc(&c->d_ratio, ns * 3));
-    CHK(dalloc(&c->d_et, ns)); CHK(dalloc(&c->d_pf, ns)); CHK(dalloc(&c->d_tq, ns));
-    CHK(dalloc(&c->d_stats, ns * NM_STATS_COLS));
-    CHK(dalloc(&c->d_nswaps, 1)); // (d_slot2buf, d_status: allocated for the census probe above)
-    CHK(dalloc(&c->d_evalU, ns)); CHK(dalloc(&c->d_evalW, ns)); CHK(dalloc(&c->d_evalF, ns * n3));
+    HIPCHK(c, c->d_x.alloc_zeroed(ns * n3)); HIPCHK(c, c->d_v.alloc_zeroed(ns * n3));
+    HIPCHK(c, c->d_box.alloc_zeroed(ns)); HIPCHK(c, c->d_steps.alloc_zeroed(ns * 3)); HIPCHK(c, c->d_therm.alloc_zeroed(ns * 5));
+    HIPCHK(c, c->d_count.alloc_zeroed(ns * 6)); HIPCHK(c, c->d_ratio.alloc_zeroed(ns * 3));
+    HIPCHK(c, c->d_et.upload(c->h_et.data(), ns)); HIPCHK(c, c->d_pf.upload(c->h_pf.data(), ns)); HIPCHK(c, c->d_tq.upload(c->h_tq.data(), ns));
+    HIPCHK(c, c->d_stats.alloc_zeroed(ns * NM_STATS_COLS));
+    HIPCHK(c, c->d_nswaps.alloc_zeroed(1)); // (the allocations stand in the order they always had: where a buffer lies is not free)
+    HIPCHK(c, c->d_evalU.alloc(ns)); HIPCHK(c, c->d_evalW.alloc(ns)); HIPCHK(c, c->d_evalF.alloc(ns * n3));
     const int npairs = c->cfg.nrows * cfg->nt * (cfg->nt - 1) / 2;
-    CHK(dalloc(&c->d_xcrit, (size_t)npairs)); CHK(dalloc(&c->d_xtape, (size_t)npairs));
-    c->d_prof = nullptr;
-    c->d_tline = nullptr;
+    HIPCHK(c, c->d_xcrit.alloc((size_t)npairs)); HIPCHK(c, c->d_xtape.alloc((size_t)npairs));
 #ifdef NM_EXPERIMENT
-    CHK(dalloc(&c->d_tline, (size_t)8 * 8 * 512 * 8)); CHK(hipMemset(c->d_tline, 0, (size_t)8 * 8 * 512 * 8 * sizeof(unsigned long long)));
+    HIPCHK(c, c->d_tline.alloc_zeroed((size_t)8 * 8 * 512 * 8));
 #endif
 #ifdef NM_PROF
-    CHK(dalloc(&c->d_prof, ns * 16)); CHK(hipMemset(c->d_prof, 0, ns * 16 * sizeof(unsigned long long)));
+    HIPCHK(c, c->d_prof.alloc_zeroed(ns * 16));
 #endif
-    c->d_tape = nullptr; c->d_tape_off = nullptr; c->d_trace = nullptr; c->d_nbr = nullptr;
-    if (nbr_elems) CHK(hipMalloc(&c->d_nbr, ns * 2 * nbr_elems * sizeof(unsigned short))); // two lists per slot (Cfg::LIST2)
-    if (alloc_cluster_buffers(c) != NM_OK) { g_create_error = c->err; free_ctx(c); return NM_ERR_HIP; }
-    CHK(hipMemset(c->d_x, 0, ns * n3 * sizeof(double))); CHK(hipMemset(c->d_v, 0, ns * n3 * sizeof(double)));
-    CHK(hipMemset(c->d_box, 0, ns * sizeof(double))); CHK(hipMemset(c->d_steps, 0, ns * 3 * sizeof(double)));
-    CHK(hipMemset(c->d_therm, 0, ns * 5 * sizeof(double))); CHK(hipMemset(c->d_count, 0, ns * 6 * sizeof(double)));
-    CHK(hipMemset(c->d_ratio, 0, ns * 3 * sizeof(float))); CHK(hipMemset(c->d_stats, 0, ns * NM_STATS_COLS * sizeof(double)));
-    CHK(hipMemset(c->d_nswaps, 0, sizeof(int)));
-    CHK(hipMemcpy(c->d_et, c->h_et.data(), ns * sizeof(double), hipMemcpyHostToDevice));
-    CHK(hipMemcpy(c->d_pf, c->h_pf.data(), ns * sizeof(double), hipMemcpyHostToDevice));
-    CHK(hipMemcpy(c->d_tq, c->h_tq.data(), ns * sizeof(double), hipMemcpyHostToDevice));
+    if (nbr_elems) HIPCHK(c, c->d_nbr.alloc(ns * 2 * nbr_elems)); // two lists per slot (Cfg::LIST2)
+    if (const int rc = alloc_cluster_buffers(c)) return rc;
     for (int q : { 1, 2, 4, 8 })
-        if (const Row *r = nm_row(c->pot, c->kind, q)) CHK(r->request_lds());
-    c->ev.assign(32, EvPair{ nullptr, nullptr, false, 0u });
-    for (auto &e : c->ev) { CHK(hipEventCreate(&e.a)); CHK(hipEventCreate(&e.b)); }
-#undef CHK
-    c->err.clear();
+        if (const Row *r = nm_row(c->pot, c->kind, q)) HIPCHK(c, r->request_lds());
+    c->ev.resize(32);
+    for (auto &e : c->ev) { HIPCHK(c, e.a.create()); HIPCHK(c, e.b.create()); }
     c->note = note; // nm_create_note(ctx): what the residency probe had to give up, if anything
-    *out = c;
+    return NM_OK;
+}
+
+int nm_create(const nm_config *cfg, nm_ctx **out)
+{
+    if (!cfg || !out) return fail(nullptr, NM_ERR_ARG, "nm_create: null argument");
+    *out = nullptr;
+    if (cfg->size != (int32_t)sizeof(nm_config)) return fail(nullptr, NM_ERR_ARG, "nm_create: nm_config size mismatch (ABI)");
+    if (cfg->natoms < 2 || cfg->natoms > 2048) return fail(nullptr, NM_ERR_ARG, "nm_create: natoms must be in [2, 2048]");
+    const bool by_slots = cfg->nslots > 0;
+    if (cfg->np < 1 || cfg->nt < 1) return fail(nullptr, NM_ERR_ARG, "nm_create: bad grid");
+    if (by_slots ? (cfg->slot0 < 0 || cfg->slot0 + cfg->nslots > cfg->np * cfg->nt)
+                 : (cfg->nrows < 1 || cfg->row0 < 0 || cfg->row0 + cfg->nrows > cfg->np))
+        return fail(nullptr, NM_ERR_ARG, "nm_create: bad row / slot range");
+    if (!cfg->P || !cfg->T) return fail(nullptr, NM_ERR_ARG, "nm_create: P and T grids are required");
+    if (cfg->nstps < 1 || cfg->ppos < 0 || cfg->pvol < 0 || cfg->ppos + cfg->pvol > 1.0)
+        return fail(nullptr, NM_ERR_ARG, "nm_create: bad move parameters");
+    if (cfg->element != NM_EL_LJ && !lat::sc_element(cfg->element))
+        return fail(nullptr, NM_ERR_UNSUPPORTED, "nm_create: elements LJ (0), Al (1), Ni (2) and Cu (3) have device force kernels in this build");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, NM_ERR_HIP, "nm_create: no HIP device available (this engine has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, NM_ERR_ARG, "nm_create: device ordinal out of range");
+
+    std::unique_ptr<nm_ctx> c(new nm_ctx());
+    if (init_ctx(c.get(), cfg) != NM_OK) { // (every failure in there is a HIP call's)
+        g_create_error = c->err;
+        return NM_ERR_HIP;
+    }
+    *out = c.release();
     return NM_OK;
 }
 
@@ -793,7 +844,7 @@ int nm_destroy(nm_ctx *c)
 {
     if (!c) return NM_ERR_ARG;
     hipSetDevice(c->cfg.device);
-    free_ctx(c);
+    delete c;
     return NM_OK;
 }
 
@@ -812,80 +863,28 @@ int nm_set_step(nm_ctx *c, uint32_t step)
     return NM_OK;
 }
 
-static int slot_map(nm_ctx *c, std::vector<int> &m)
-{
-    m.resize(c->nslots);
-    const int rc = check_status(c); // everything queued has run (or has been re-issued) before state is read or replaced
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(m.data(), c->d_slot2buf, sizeof(int) * c->nslots, hipMemcpyDeviceToHost));
-    return NM_OK;
-}
-
-// pinned staging area of the context (grown on demand): state moves between the caller's arrays and HBM as whole device
-// arrays, one asynchronous copy each on the context's stream and one wait, instead of up to four small copies per replica
-static int stage_reserve(nm_ctx *c, size_t doubles)
-{
-    if (doubles <= c->stage_cap) return NM_OK;
-    if (c->h_stage) HIPCHK(c, hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->stage_cap = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_stage, doubles * sizeof(double), hipHostMallocDefault));
-    c->stage_cap = doubles;
-    return NM_OK;
-}
-
 int nm_set_state(nm_ctx *c, int k0, int nk, const double *x, const double *v, const double *box, const double *dxdvdt)
 {
     if (!c || k0 < 0 || nk < 0 || k0 + nk > c->nslots) return fail(c, NM_ERR_ARG, "nm_set_state: slot range");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    std::vector<int> m;
-    int rc = slot_map(c, m);
-    if (rc) return rc;
-    const size_t n3 = (size_t)3 * c->N, ns = (size_t)c->nslots;
-    const bool all = nk == c->nslots;
-    if (!all && nk <= 8) { // a few replicas (the split-row exchange re-seats the ones that swapped): copy just those
-        for (int q = 0; q < nk; ++q) {
-            const size_t bq = (size_t)m[k0 + q];
-            if (x) HIPCHK(c, hipMemcpyAsync(c->d_x + bq * n3, x + q * n3, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            if (v) HIPCHK(c, hipMemcpyAsync(c->d_v + bq * n3, v + q * n3, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            if (box) {
-                const double vol = std::pow(box[q], 3.0);
-                HIPCHK(c, hipMemcpyAsync(c->d_box + bq, box + q, sizeof(double), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->d_therm + 5 * bq + 4, &vol, sizeof(double), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream)); // (vol lives on this stack frame)
-            }
-            if (dxdvdt) HIPCHK(c, hipMemcpyAsync(c->d_steps + 3 * bq, dxdvdt + 3 * q, 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return NM_OK;
-    }
-    // a partial range is merged into the device arrays: read them back first (set-up path, not timed)
-    if ((rc = stage_reserve(c, 2 * ns * n3 + 9 * ns))) return rc;
-    double *hx = c->h_stage, *hv = hx + ns * n3, *hb = hv + ns * n3, *hs = hb + ns, *ht = hs + 3 * ns;
-    if (!all) {
-        if (x) HIPCHK(c, hipMemcpyAsync(hx, c->d_x, ns * n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (v) HIPCHK(c, hipMemcpyAsync(hv, c->d_v, ns * n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (box) HIPCHK(c, hipMemcpyAsync(hb, c->d_box, ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (dxdvdt) HIPCHK(c, hipMemcpyAsync(hs, c->d_steps, 3 * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (box) HIPCHK(c, hipMemcpyAsync(ht, c->d_therm, 5 * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int q = 0; q < nk; ++q) {
-        const size_t bq = (size_t)m[k0 + q];
-        if (x) std::memcpy(hx + bq * n3, x + q * n3, n3 * sizeof(double));
-        if (v) std::memcpy(hv + bq * n3, v + q * n3, n3 * sizeof(double));
-        if (box) { hb[bq] = box[q]; ht[5 * bq + 4] = std::pow(box[q], 3.0); }
-        if (dxdvdt) std::memcpy(hs + 3 * bq, dxdvdt + 3 * q, 3 * sizeof(double));
-    }
-    if (x) HIPCHK(c, hipMemcpyAsync(c->d_x, hx, ns * n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (v) HIPCHK(c, hipMemcpyAsync(c->d_v, hv, ns * n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (box) {
-        HIPCHK(c, hipMemcpyAsync(c->d_box, hb, ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_therm, ht, 5 * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    if (dxdvdt) HIPCHK(c, hipMemcpyAsync(c->d_steps, hs, 3 * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging area is reused by the next call
-    return NM_OK;
+    return copy_range(c, true, k0, nk, const_cast<double *>(x), const_cast<double *>(v), const_cast<double *>(box), const_cast<double *>(dxdvdt));
+}
+
+int nm_get_state(nm_ctx *c, int k0, int nk, double *x, double *v, double *box, double *dxdvdt)
+{
+    if (!c || k0 < 0 || nk < 0 || k0 + nk > c->nslots) return fail(c, NM_ERR_ARG, "nm_get_state: slot range");
+    return copy_range(c, false, k0, nk, x, v, box, dxdvdt);
+}
+
+int nm_get_slots(nm_ctx *c, int nk, const int *slots, double *x, double *v, double *box, double *dxdvdt, double *th)
+{
+    return copy_list(c, "nm_get_slots", false, nk, slots, x, v, box, dxdvdt, th);
+}
+
+int nm_set_slots(nm_ctx *c, int nk, const int *slots, const double *x, const double *v, const double *box, const double *dxdvdt,
+                 const double *th)
+{
+    return copy_list(c, "nm_set_slots", true, nk, slots, const_cast<double *>(x), const_cast<double *>(v), const_cast<double *>(box),
+                     const_cast<double *>(dxdvdt), const_cast<double *>(th));
 }
 
 int nm_init_lattice(nm_ctx *c, double dx, double dv, int interpolate)
@@ -912,100 +911,10 @@ int nm_init_lattice(nm_ctx *c, double dx, double dv, int interpolate)
 int nm_set_thermo(nm_ctx *c, int k0, int nk, const double *th)
 {
     if (!c || !th || k0 < 0 || nk < 0 || k0 + nk > c->nslots) return fail(c, NM_ERR_ARG, "nm_set_thermo: bad argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
     std::vector<int> m;
-    int rc = slot_map(c, m);
-    if (rc) return rc;
+    if (const int rc = slot_map(c, m)) return rc;
     for (int q = 0; q < nk; ++q)
         HIPCHK(c, hipMemcpy(c->d_therm + 5 * (size_t)m[k0 + q], th + 5 * q, 5 * sizeof(double), hipMemcpyHostToDevice));
-    return NM_OK;
-}
-
-int nm_get_state(nm_ctx *c, int k0, int nk, double *x, double *v, double *box, double *dxdvdt)
-{
-    if (!c || k0 < 0 || nk < 0 || k0 + nk > c->nslots) return fail(c, NM_ERR_ARG, "nm_get_state: slot range");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    std::vector<int> m;
-    int rc = slot_map(c, m);
-    if (rc) return rc;
-    const size_t n3 = (size_t)3 * c->N, ns = (size_t)c->nslots;
-    if (nk <= 8 && nk < c->nslots) { // a few replicas: copy just those
-        for (int q = 0; q < nk; ++q) {
-            const size_t bq = (size_t)m[k0 + q];
-            if (x) HIPCHK(c, hipMemcpyAsync(x + q * n3, c->d_x + bq * n3, n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            if (v) HIPCHK(c, hipMemcpyAsync(v + q * n3, c->d_v + bq * n3, n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            if (box) HIPCHK(c, hipMemcpyAsync(box + q, c->d_box + bq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            if (dxdvdt) HIPCHK(c, hipMemcpyAsync(dxdvdt + 3 * q, c->d_steps + 3 * bq, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return NM_OK;
-    }
-    if ((rc = stage_reserve(c, 2 * ns * n3 + 9 * ns))) return rc;
-    double *hx = c->h_stage, *hv = hx + ns * n3, *hb = hv + ns * n3, *hs = hb + ns;
-    if (x) HIPCHK(c, hipMemcpyAsync(hx, c->d_x, ns * n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (v) HIPCHK(c, hipMemcpyAsync(hv, c->d_v, ns * n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (box) HIPCHK(c, hipMemcpyAsync(hb, c->d_box, ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (dxdvdt) HIPCHK(c, hipMemcpyAsync(hs, c->d_steps, 3 * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int q = 0; q < nk; ++q) {
-        const size_t bq = (size_t)m[k0 + q];
-        if (x) std::memcpy(x + q * n3, hx + bq * n3, n3 * sizeof(double));
-        if (v) std::memcpy(v + q * n3, hv + bq * n3, n3 * sizeof(double));
-        if (box) box[q] = hb[bq];
-        if (dxdvdt) std::memcpy(dxdvdt + 3 * q, hs + 3 * bq, 3 * sizeof(double));
-    }
-    return NM_OK; // (slot_map has looked at the outcome of everything queued)
-}
-
-// The replicas named in slots[] only (the split-row exchange re-seats the ones that swapped, neuralmelting_amd/exchange.py): ONE look at
-// the queue's outcome, the listed buffers copied back to back on the context's stream, ONE wait.  th[nk][5] = temp, pe, ke, virial, vol
-// (nm_set_thermo's columns); small items go through the pinned staging area so that nothing on this stack frame is read after return.
-int nm_get_slots(nm_ctx *c, int nk, const int *slots, double *x, double *v, double *box, double *dxdvdt, double *th)
-{
-    if (!c || nk < 0 || (nk && !slots)) return fail(c, NM_ERR_ARG, "nm_get_slots: bad argument");
-    for (int q = 0; q < nk; ++q) if (slots[q] < 0 || slots[q] >= c->nslots) return fail(c, NM_ERR_ARG, "nm_get_slots: slot out of range");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    std::vector<int> m;
-    int rc = slot_map(c, m);
-    if (rc) return rc;
-    const size_t n3 = (size_t)3 * c->N;
-    for (int q = 0; q < nk; ++q) {
-        const size_t bq = (size_t)m[slots[q]];
-        if (x) HIPCHK(c, hipMemcpyAsync(x + q * n3, c->d_x + bq * n3, n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (v) HIPCHK(c, hipMemcpyAsync(v + q * n3, c->d_v + bq * n3, n3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (box) HIPCHK(c, hipMemcpyAsync(box + q, c->d_box + bq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (dxdvdt) HIPCHK(c, hipMemcpyAsync(dxdvdt + 3 * q, c->d_steps + 3 * bq, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (th) HIPCHK(c, hipMemcpyAsync(th + 5 * q, c->d_therm + 5 * bq, 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return NM_OK;
-}
-
-int nm_set_slots(nm_ctx *c, int nk, const int *slots, const double *x, const double *v, const double *box, const double *dxdvdt,
-                 const double *th)
-{
-    if (!c || nk < 0 || (nk && !slots)) return fail(c, NM_ERR_ARG, "nm_set_slots: bad argument");
-    for (int q = 0; q < nk; ++q) if (slots[q] < 0 || slots[q] >= c->nslots) return fail(c, NM_ERR_ARG, "nm_set_slots: slot out of range");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    std::vector<int> m;
-    int rc = slot_map(c, m);
-    if (rc) return rc;
-    const size_t n3 = (size_t)3 * c->N;
-    if ((rc = stage_reserve(c, (size_t)nk + 1))) return rc;
-    double *vol = c->h_stage; // the volumes that go with the boxes (therm column 4), pinned
-    for (int q = 0; q < nk; ++q) {
-        const size_t bq = (size_t)m[slots[q]];
-        if (x) HIPCHK(c, hipMemcpyAsync(c->d_x + bq * n3, x + q * n3, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (v) HIPCHK(c, hipMemcpyAsync(c->d_v + bq * n3, v + q * n3, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (box) {
-            vol[q] = std::pow(box[q], 3.0);
-            HIPCHK(c, hipMemcpyAsync(c->d_box + bq, box + q, sizeof(double), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_therm + 5 * bq + 4, vol + q, sizeof(double), hipMemcpyHostToDevice, c->stream));
-        }
-        if (dxdvdt) HIPCHK(c, hipMemcpyAsync(c->d_steps + 3 * bq, dxdvdt + 3 * q, 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (th) HIPCHK(c, hipMemcpyAsync(c->d_therm + 5 * bq, th + 5 * q, 5 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // the caller's arrays (pageable: staged by the runtime) and the staging area are free again
     return NM_OK;
 }
 
@@ -1030,23 +939,19 @@ static int record_capacity(const nm_ctx *c)
 static int ring_alloc(nm_ctx *c, int r0, int cap, const char *who)
 {
     const size_t nd = (size_t)cap * rec_cycle_doubles(c);
+    Stream side;
     nm_ctx::Ring g[2];
-    hipStream_t side = nullptr;
-    hipError_t e = c->side ? hipSuccess : hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
+    hipError_t e = c->side ? hipSuccess : side.create();
     for (auto &q : g) {
-        if (e == hipSuccess) e = dalloc(&q.d, nd);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&q.h, nd * sizeof(double), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&q.taken, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&q.landed, hipEventDisableTiming);
+        if (e == hipSuccess) e = q.d.alloc(nd);
+        if (e == hipSuccess) e = q.h.alloc(nd);
+        if (e == hipSuccess) e = q.taken.create(hipEventDisableTiming);
+        if (e == hipSuccess) e = q.landed.create(hipEventDisableTiming);
+        q.cap = cap;
     }
-    if (e != hipSuccess) {
-        for (auto &q : g) free_ring(q);
-        if (side) hipStreamDestroy(side);
-        return fail(c, NM_ERR_HIP, std::string(who) + ": ring allocation: " + hipGetErrorString(e));
-    }
-    if (side) c->side = side;
-    g[0].cap = g[1].cap = cap;
-    c->ring[r0] = g[0]; c->ring[r0 + 1] = g[1];
+    if (e != hipSuccess) return fail(c, NM_ERR_HIP, std::string(who) + ": ring allocation: " + hipGetErrorString(e)); // (the locals take all of it back)
+    if (side) c->side = std::move(side);
+    c->ring[r0] = std::move(g[0]); c->ring[r0 + 1] = std::move(g[1]);
     return NM_OK;
 }
 
@@ -1181,10 +1086,8 @@ int nm_run_cycles(nm_ctx *c, int ncycles, int mod)
 int nm_get_thermo(nm_ctx *c, double *rows)
 {
     if (!c || !rows) return fail(c, NM_ERR_ARG, "nm_get_thermo: null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
     std::vector<int> m;
-    int rc = slot_map(c, m);
-    if (rc) return rc;
+    if (const int rc = slot_map(c, m)) return rc;
     const size_t ns = c->nslots;
     std::vector<double> th(ns * 5), st(ns * 3), cn(ns * 6);
     std::vector<float> ra(ns * 3);
@@ -1228,8 +1131,7 @@ int nm_exchange(nm_ctx *c, int *nswaps)
 int nm_synchronize(nm_ctx *c)
 {
     if (!c) return NM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    return check_status(c);
+    return settled(c);
 }
 
 int nm_get_status(nm_ctx *c, int *status)
@@ -1261,8 +1163,7 @@ int nm_timing_get(nm_ctx *c, int *launches, double *total_ms)
 int nm_stats_get(nm_ctx *c, double *stats, int reset)
 {
     if (!c || !stats) return fail(c, NM_ERR_ARG, "nm_stats_get: null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
+    if (const int rc = settled(c)) return rc;
     const size_t n = (size_t)c->nslots * NM_STATS_COLS;
     HIPCHK(c, hipMemcpy(stats, c->d_stats, n * sizeof(double), hipMemcpyDeviceToHost));
     if (reset) HIPCHK(c, hipMemset(c->d_stats, 0, n * sizeof(double)));
@@ -1318,9 +1219,7 @@ int nm_prof_get(nm_ctx *c, unsigned long long *out, int reset)
 int nm_eval(nm_ctx *c, double *U, double *W, double *f)
 {
     if (!c || !U || !W) return fail(c, NM_ERR_ARG, "nm_eval: null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc0 = check_status(c); // (whatever is queued first: an evaluation is not re-issued)
-    if (rc0) return rc0;
+    if (const int rc = settled(c)) return rc; // (whatever is queued first: an evaluation is not re-issued)
     ++c->launch_id;
     KParams p;
     fill_params(c, p);
@@ -1339,25 +1238,23 @@ int nm_eval(nm_ctx *c, double *U, double *W, double *f)
 int nm_set_rng_tape(nm_ctx *c, const double *tape, const int *offsets)
 {
     if (!c) return NM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
-    if (c->d_tape) { HIPCHK(c, hipFree(c->d_tape)); c->d_tape = nullptr; }
-    if (c->d_tape_off) { HIPCHK(c, hipFree(c->d_tape_off)); c->d_tape_off = nullptr; }
+    if (const int rc = settled(c)) return rc;
+    c->d_tape = {}; c->d_tape_off = {}; // (the tape that was set goes in any case)
     if (!tape || !offsets) return NM_OK;
     const int total = offsets[c->nslots];
     if (total < 0) return fail(c, NM_ERR_ARG, "nm_set_rng_tape: bad offsets");
-    HIPCHK(c, dalloc(&c->d_tape, (size_t)total));
-    HIPCHK(c, dalloc(&c->d_tape_off, (size_t)c->nslots + 1));
-    HIPCHK(c, hipMemcpy(c->d_tape, tape, sizeof(double) * total, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_tape_off, offsets, sizeof(int) * (c->nslots + 1), hipMemcpyHostToDevice));
+    DevBuf<double> t;
+    DevBuf<int> off;
+    HIPCHK(c, t.upload(tape, (size_t)total));
+    HIPCHK(c, off.upload(offsets, (size_t)c->nslots + 1));
+    c->d_tape = std::move(t); c->d_tape_off = std::move(off);
     return NM_OK;
 }
 
 int nm_set_exchange_tape(nm_ctx *c, const double *tape, int n)
 {
     if (!c) return NM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
+    if (const int rc = settled(c)) return rc;
     const int npairs = c->cfg.nrows * c->cfg.nt * (c->cfg.nt - 1) / 2;
     if (!tape) { c->xtape_n = 0; return NM_OK; }
     if (n != npairs) return fail(c, NM_ERR_ARG, "nm_set_exchange_tape: need one uniform per pair of the sweep");
@@ -1377,8 +1274,7 @@ int nm_get_trace(nm_ctx *c, double *trace, int mod)
 {
     if (!c || !trace) return fail(c, NM_ERR_ARG, "nm_get_trace: null argument");
     if (!c->d_trace || mod != c->trace_mod) return fail(c, NM_ERR_ARG, "nm_get_trace: no trace of that length recorded");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
+    if (const int rc = settled(c)) return rc;
     HIPCHK(c, hipMemcpy(trace, c->d_trace, (size_t)c->nslots * mod * NM_TRACE_COLS * sizeof(double), hipMemcpyDeviceToHost));
     return NM_OK;
 }
@@ -1386,8 +1282,7 @@ int nm_get_trace(nm_ctx *c, double *trace, int mod)
 int nm_set_counters(nm_ctx *c, const double *count, const float *ratio)
 {
     if (!c) return NM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
+    if (const int rc = settled(c)) return rc;
     if (count) HIPCHK(c, hipMemcpy(c->d_count, count, sizeof(double) * 6 * c->nslots, hipMemcpyHostToDevice));
     if (ratio) HIPCHK(c, hipMemcpy(c->d_ratio, ratio, sizeof(float) * 3 * c->nslots, hipMemcpyHostToDevice));
     return NM_OK;
@@ -1396,8 +1291,7 @@ int nm_set_counters(nm_ctx *c, const double *count, const float *ratio)
 int nm_get_perm(nm_ctx *c, int *perm)
 {
     if (!c || !perm) return fail(c, NM_ERR_ARG, "nm_get_perm: null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
+    if (const int rc = settled(c)) return rc;
     HIPCHK(c, hipMemcpy(perm, c->d_slot2buf, sizeof(int) * c->nslots, hipMemcpyDeviceToHost));
     return NM_OK;
 }
@@ -1407,8 +1301,7 @@ int nm_get_exchange_crit(nm_ctx *c, double *crit, int n)
     if (!c || !crit) return fail(c, NM_ERR_ARG, "nm_get_exchange_crit: null argument");
     const int npairs = c->cfg.nrows * c->cfg.nt * (c->cfg.nt - 1) / 2;
     if (n != npairs) return fail(c, NM_ERR_ARG, "nm_get_exchange_crit: wrong pair count");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc_ = check_status(c); if (rc_) return rc_; } // (a halted queue is re-issued, or its error reported, before anything is read or replaced)
+    if (const int rc = settled(c)) return rc;
     HIPCHK(c, hipMemcpy(crit, c->d_xcrit, sizeof(double) * n, hipMemcpyDeviceToHost));
     return NM_OK;
 }

@@ -1,33 +1,15 @@
 // nm_host.h — the host scaffold of the offline stages (nm_distr_api.hip, nm_reweight_api.hip, nm_pca_api.hip, nm_cluster_api.hip):
-// device memory that frees itself, the stage's error channel with its HIP check and device selection, and the rest of a batch.  Internal: every
-// name here has internal linkage, so each stage gets its own copy and its own message.
+// the stage's error channel with its HIP check and device selection, and the rest of a batch; the device memory that frees itself is
+// nm_own.h's, which the sampler shares.  Internal: every name here has internal linkage, so each stage gets its own copy and its own message.
 #pragma once
 #include "../../include/nm.h"
 
-#include <hip/hip_runtime.h>
+#include "nm_own.h"
 
 #include <cstdint>
 #include <string>
 
 namespace {
-
-// device memory that is freed on every way out of the scope that holds it; sizes are counts of T
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
-    hipError_t zero(size_t count) { return hipMemset(p, 0, count * sizeof(T)); }
-    hipError_t upload(const T *host, size_t count)
-    {
-        const hipError_t e = alloc(count);
-        return e != hipSuccess ? e : hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice);
-    }
-    hipError_t download(T *host, size_t count) const { return hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost); }
-    operator T *() const { return p; }
-};
 
 // The message behind the stage's nm_*_last_error: each stage defines this over a thread_local string of its own file, so that
 // a failure in one stage leaves the other's message alone.
