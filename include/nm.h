@@ -44,11 +44,12 @@ extern "C" {
 
 #define NM_THERMO_COLS 17     /* temp pe ke virial vol dx dv dt ntp nap ntv nav nth nah ap av ah (remcmc:208) */
 #define NM_TRACE_COLS 4       /* branch (0 bulk PMC, 1 VMC, 2 HMC, 3 iter PMC), accepted, criterion, U after */
-#define NM_STATS_COLS 11      /* per slot: evaluations, list rebuilds, energy evaluations, sum of interacting pairs over those,
+#define NM_STATS_COLS 12      /* per slot: evaluations, list rebuilds, energy evaluations, sum of interacting pairs over those,
                                  time of the slot's blocks (ticks of the chip's 100 MHz clock, kernel entry to exit of the replica's
                                  first workgroup), blocks whose cluster handed over inside one XCD's L2, blocks run, HMC moves, longest neighbour-list
                                  row built (a maximum, not a sum), list slots per atom of the kernel in use, HMC moves whose trajectory started without a
-                                 hand-over inside the cluster (4^3 cells at more than one workgroup per replica; 0 elsewhere) */
+                                 hand-over inside the cluster (4^3 cells at more than one workgroup per replica; 0 elsewhere), moves whose random numbers were drawn
+                                 under the exchange of the energy evaluation in front of them (production form of the 4^3 kernels; 0 elsewhere) */
 
 typedef struct nm_ctx nm_ctx;
 

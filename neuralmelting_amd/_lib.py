@@ -15,7 +15,7 @@ c_int64_p = C.POINTER(C.c_int64)
 
 NM_OK, NM_ERR_ARG, NM_ERR_HIP, NM_ERR_STATE, NM_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 NM_EL_LJ, NM_EL_AL, NM_EL_NI, NM_EL_CU = 0, 1, 2, 3
-NM_THERMO_COLS, NM_TRACE_COLS, NM_STATS_COLS = 17, 4, 11
+NM_THERMO_COLS, NM_TRACE_COLS, NM_STATS_COLS = 17, 4, 12
 
 # every symbol include/nm.h declares (tests check that the library exports all of them)
 SYMBOLS = ('nm_create', 'nm_destroy', 'nm_last_error', 'nm_create_note', 'nm_nslots', 'nm_natoms', 'nm_cus_per_replica', 'nm_heal_count', 'nm_get_const',

@@ -37,6 +37,7 @@ struct nm_ctx {
     bool whole_rows;            // the slot range is made of whole pressure rows (nm_exchange can run on the device)
     uint32_t launch_id;
     int start_handover = 0; // NM_START_HANDOVER=1 (read once, nm_create): the 4^3 cluster kernels start every trajectory with a hand-over
+    int draw_ahead = 1;     // NM_DRAW_AHEAD=0 (read once, nm_create): the production form of the 4^3 kernels draws behind the energy exchange, not under it
     double lat, mass, kB, mvv2e, ftm2v, nktv2p, skin, rc;
     int pot; // 0 lj/cut, 1 Sutton-Chen EAM n = 7 (Al), 2 Sutton-Chen EAM n = 9 (Cu, Ni): the kernels' Cfg POT
     double sc_eps, sc_a2, sc_c; // Sutton-Chen constants of the element (nm_lattice.h sc_element); unused by lj/cut
@@ -141,6 +142,7 @@ void fill_params(const nm_ctx *c, KParams &p)
     p.plain_granules = 1;
     if (const char *e = std::getenv("NM_PLAIN_GRANULES")) p.plain_granules = std::atoi(e);
     p.start_handover = c->start_handover;
+    p.draw_ahead = c->draw_ahead;
     p.dbg = 0;
     p.tline = c->d_tline;
     if (const char *e = std::getenv("NM_DBG")) p.dbg = std::atoi(e);
@@ -710,6 +712,7 @@ static int init_ctx(nm_ctx *c, const nm_config *cfg)
     //  864 atoms: C3 share (Q = 8) 352 / 359 / 368 / 372 / 370 k at 0.40 / 0.45 / 0.50 / 0.55 / 0.60, 256 replicas at Q = 1 615 / 617 / 632 / 642 k at
     //  0.40 / 0.45 / 0.50 / 0.55: the O(N^2) rebuild of the larger cells wants fewer rebuilds; 0.45 for both until then)
     if (const char *e = std::getenv("NM_START_HANDOVER")) c->start_handover = std::atoi(e) != 0;
+    if (const char *e = std::getenv("NM_DRAW_AHEAD")) c->draw_ahead = std::atoi(e) != 0;
     if (const char *e = std::getenv("NM_SKIN")) { const double v = std::atof(e); if (v > 0.0 && v < 1.0) c->skin = v; }
     c->lat = 1.122; c->mass = 1.0; c->kB = 1.0; c->mvv2e = 1.0; c->ftm2v = 1.0; c->nktv2p = 1.0;
     c->rc = 2.5; c->pot = 0; c->sc_eps = 0.0; c->sc_a2 = 0.0; c->sc_c = 0.0;

@@ -49,11 +49,29 @@ constexpr int NVMAX = 16; // widest block reduction (the 16 raw moments of hmc_v
 #else
 #define TLINE_START() do { } while (0)
 #endif
+#if defined(NM_TL_DRAW) && !defined(NM_TL_REBUILD) && !defined(NM_TL_START) // a fourth one (scripts/probe_draw_ahead.py): slots 3 .. 7 of an energy
+// evaluation hold its exchange of the partial sums and the draws that run under it or behind it — 3: entry of the exchange, in front of its first
+// put_granule; 4: return of its get_granules; 5, 6: entry of draw_ahead and the end of its loop over the atoms; 7: the phase the evaluation
+// belongs to, + 1 (Replica::tl_kind, set by nm_block_body in this build alone).  DTL_ARM keeps the wave's row in its scalar slot DA_TLP for the functions outside Replica.
+#undef TLINE
+#undef TLINE_PREV
+#define TLINE(k) do { if ((k) < 3 && tl && tl_n < TL_EVALS && (tid & 63) == 0) tl[((size_t)(q * NW + (tid >> 6)) * TL_EVALS + tl_n) * 8 + (k)] = wall_clock64(); } while (0)
+#define TLINE_PREV(k) do { } while (0)
+#define DTL_ARM() do { if constexpr (C::STAGE) { unsigned long long *r_ = (tl && tl_n > 0 && tl_n <= TL_EVALS) ? tl + ((size_t)(q * NW + (tid >> 6)) * TL_EVALS + tl_n - 1) * 8 : nullptr; \
+    dau(C::DA_TLP) = (unsigned long long)(uintptr_t)r_; if (r_ && (tid & 63) == 0) r_[7] = (unsigned long long)tl_kind; } } while (0)
+#define DTL(k) do { if constexpr (C::STAGE) { unsigned long long *r_ = (unsigned long long *)(uintptr_t)((unsigned long long *)(nm_lds + C::OFF_DA))[(threadIdx.x >> 6) * C::DA_PER_WAVE + C::DA_TLP]; \
+    if (r_ && (threadIdx.x & 63) == 0) r_[k] = wall_clock64(); } } while (0)
+#else
+#define DTL_ARM() do { } while (0)
+#define DTL(k) do { } while (0)
+#endif
 #else
 #define TLINE(k) do { } while (0)
 #define TLINE_PREV(k) do { } while (0)
 #define RTL(k) do { } while (0)
 #define TLINE_START() do { } while (0)
+#define DTL_ARM() do { } while (0)
+#define DTL(k) do { } while (0)
 #endif
 #ifdef NM_PROF
 #define NM_PROF_SLOTS 16
@@ -174,7 +192,18 @@ struct Cfg {
     static constexpr bool RHO_LDS = POT_ != 0 && OFF_RHO + (size_t)NMAX * sizeof(double) <= (size_t)160 * 1024;
     static constexpr size_t OFF_X0S = OFF_RHO + (RHO_LDS ? (size_t)NMAX * sizeof(double) : 0); // LDS_LIST2: reference positions of the saved list
     static constexpr size_t OFF_CNTS = OFF_X0S + (LDS_LIST2 ? A3 : 0);                     //            and its row lengths
-    static constexpr size_t LDS_NATURAL = OFF_CNTS + (LDS_LIST2 ? pad8((size_t)NMAX * sizeof(unsigned short)) : 0);
+    static constexpr size_t LDS_LAYOUT = OFF_CNTS + (LDS_LIST2 ? pad8((size_t)NMAX * sizeof(unsigned short)) : 0);
+    // STAGE (the 4^3 configurations, the only ones whose production form exists: nm_rows.hip has_plain): the random numbers of the NEXT move,
+    // drawn under the exchange of the energy evaluation in front of it (draw_ahead below) — 3 NMAX doubles (the gaussians of a trajectory's
+    // velocities or the displacement uniforms of a position move) and DA_PER_WAVE uniform scalars per wave.  Behind everything else: no other
+    // offset moves.  6.5 KB: every 4^3 configuration still fits the CU and still has it to itself (nm_rows.hip asserts both).
+    static constexpr bool STAGE = NMAX_ == 256;
+    static constexpr int DA_PER_WAVE = 8;
+    enum : int { DA_ROLL = 0, DA_ACC = 1, DA_VOL = 2, DA_COUNT = 3, DA_TLP = 4 }; // the staged roll, acceptance and volume uniforms; moves that were
+                                                                                 // drawn ahead (stats column 11); experiment build: the wave's stamp row
+    static constexpr size_t OFF_STAGE = LDS_LAYOUT;
+    static constexpr size_t OFF_DA = OFF_STAGE + (STAGE ? A3 : 0);
+    static constexpr size_t LDS_NATURAL = OFF_DA + (STAGE ? (size_t)NW * DA_PER_WAVE * sizeof(double) : 0);
     // One workgroup per CU, by construction: a cluster's census and the Q selection count on it (nm_probe_kernel asserts it), and
     // two workgroups of different replicas on one CU measured slower.  A configuration that would fit twice
     // into the CU's 160 KB asks for a little more than half of them.
@@ -222,6 +251,143 @@ struct Cfg {
 // parity) and returns sum m |v|^2 of the velocities it leaves.
 // the gaussians of `velocity all create ... dist gaussian`, divided by sqrt(m): 2N work items over all threads — item w < N draws
 // (vx, vy) of atom w, item N + w draws vz — written to the velocities.  A function of its own (Philox, log, sin, cos: ~400 instructions).
+// The draw loop itself, ONE body for its two callers: gaussian_fill writes the velocities (gx = vx), draw_ahead the stage.  Over the caller's
+// BLOCK, tid, N, tag, step, seed, gslot, twopi, fac and gx, gy, gz.  A macro and not a function: gaussian_fill then is, token for token, what it
+// was before there was a second caller, and the kernels that call it (the general form, the 864- and 2048-atom rows) do not move by an instruction
+// (as a force-inlined function the loop came out one instruction shorter with two operands swapped).
+// (sqrt, log_pos, sincos_2pi — nm_math.h: the same functions of the same arguments, within 1 ulp like the library's)
+#define NM_GAUSSIAN_ITEMS()                                                                                 \
+    for (int w = tid; w < 2 * N; w += BLOCK) {                                                              \
+        const int part = w >= N ? 1 : 0, i = w - part * N;                                                  \
+        uint32_t o[4];                                                                                      \
+        philox4x32_10((uint32_t)i, part ? S_VEL_B : S_VEL_A, tag, step, seed, (uint32_t)gslot, o);          \
+        const double u1 = u01(o[0], o[1]), u2 = u01(o[2], o[3]);                                            \
+        const double r = sqrt(-2.0 * log_pos(1.0 - u1));                                                    \
+        double sn, cs;                                                                                      \
+        sincos_2pi(twopi * u2, sn, cs);                                                                     \
+        if (part) gz[i] = r * cs * fac;                                                                     \
+        else { gx[i] = r * cs * fac; gy[i] = r * sn * fac; }                                                \
+    }
+
+// The random numbers of move m_next and the acceptance uniform of move m_acc (either may be -1: none), into the stage (Cfg::STAGE) and the
+// wave's DA_* slots.  Every draw of a move is a function of (move, step, seed, slot, atom) alone — Philox is counter based and the production
+// form's draw_tag(m) is m — so nothing here depends on the state, and the production form calls this between the publication and the poll of
+// the exchange that completes the energy evaluation in front of the move (Replica::exchange_sums): the arithmetic runs while the peers'
+// partial sums travel.  The roll decides what the move needs: the displacement uniforms of a position move (atom i on thread i, which is
+// also their reader), the uniform of a volume move, or the 2N gaussian items of a trajectory's velocities, computed exactly as gaussian_fill
+// computes them (NM_GAUSSIAN_ITEMS).  Readers come behind the barrier that ends the exchange.  A function of its own like gaussian_fill, and for
+// the same reason; everything it leaves is in LDS, nothing of it lives in a register afterwards.
+template <class C>
+__device__ __attribute__((noinline)) void draw_ahead(int m_next, int m_acc, uint32_t step, uint32_t seed, int gslot, int N, double mass, double ppos,
+                                                     double pvol)
+{
+    static_assert(C::STAGE, "only the configurations that have a stage");
+    constexpr int BLOCK = C::BLOCK;
+    const int tid = threadIdx.x;
+    m_next = __builtin_amdgcn_readfirstlane(m_next); m_acc = __builtin_amdgcn_readfirstlane(m_acc);
+    N = __builtin_amdgcn_readfirstlane(N); gslot = __builtin_amdgcn_readfirstlane(gslot);
+    seed = __builtin_amdgcn_readfirstlane(seed); step = __builtin_amdgcn_readfirstlane(step);
+    mass = uniform(mass); ppos = uniform(ppos); pvol = uniform(pvol);
+    double *const da = (double *)(nm_lds + C::OFF_DA) + (tid >> 6) * C::DA_PER_WAVE;
+    double *const st = (double *)(nm_lds + C::OFF_STAGE);
+    DTL(5);
+    if (m_acc >= 0) {
+        uint32_t o[4];
+        philox4x32_10(0u, S_ACC, (uint32_t)m_acc, step, seed, (uint32_t)gslot, o);
+        da[C::DA_ACC] = u01(o[0], o[1]);
+    }
+    if (m_next >= 0) {
+        const uint32_t tag = (uint32_t)m_next; // (Replica::draw_tag of the production form)
+        uint32_t o[4];
+        philox4x32_10(0u, S_ROLL, tag, step, seed, (uint32_t)gslot, o);
+        const double roll = uniform(u01(o[0], o[1]));
+        da[C::DA_ROLL] = roll;
+        if (roll <= ppos) { // bulk_position_mc: displace_atoms all random a a a seed units box
+            for (int i = tid; i < N; i += BLOCK) {
+                uint32_t q[4];
+                philox4x32_10((uint32_t)i, S_DISP_XY, tag, step, seed, (uint32_t)gslot, o);
+                philox4x32_10((uint32_t)i, S_DISP_Z, tag, step, seed, (uint32_t)gslot, q);
+                st[i] = u01(o[0], o[1]);
+                st[C::NMAX + i] = u01(o[2], o[3]);
+                st[2 * C::NMAX + i] = u01(q[0], q[1]);
+            }
+        } else if (roll <= ppos + pvol) { // volume_mc
+            philox4x32_10(0u, S_VOL, tag, step, seed, (uint32_t)gslot, o);
+            da[C::DA_VOL] = u01(o[0], o[1]);
+        } else { // hamiltonian_mc: gaussian_fill's constants and its loop, onto the stage
+            double *const gx = st, *const gy = gx + C::NMAX, *const gz = gy + C::NMAX;
+            const double twopi = 6.283185307179586476925286766559;
+            const double fac = 1.0 / sqrt(mass);
+            NM_GAUSSIAN_ITEMS();
+        }
+    }
+    DTL(6);
+}
+
+// LOCAL_START: the fetch of the peers' forces from the board as gaussian_fill below makes it, in two halves for velocity_create of the
+// production form, whose gaussians are drawn already: asked for at its top, taken behind the moment pass and its block reduction.
+// gaussian_fill keeps its own text of the same fetch: built on this struct it compiles to the same 575 instructions in another order in the
+// seven 4^3 cluster rows (profiles/r26_draw_ahead.txt section 3), and the general form's code is not to move.  Whoever changes one changes both.
+template <class C>
+struct BoardFetch {
+    unsigned long long bw[6] = { 0, 0, 0, 0, 0, 0 }, bmg = 0;
+    const unsigned long long *bg = nullptr;
+    unsigned long long *us = nullptr;
+    int bi = -1;
+    // the caller armed it (Replica::hmc_velocities: ust slot UST_BOARD holds the board of the exchange just made): the peers' forces that the
+    // coming trajectory starts from are asked for here — one atom per thread, three granules as six 8-byte loads past L1
+    __device__ __forceinline__ void issue(int N)
+    {
+        static_assert(C::NMAX <= C::BLOCK, "one atom per thread");
+        const int tid = threadIdx.x;
+        us = (unsigned long long *)(nm_lds + C::OFF_UST) + (tid >> 6) * C::UST_PER_WAVE;
+        const unsigned long long b = us[C::UST_BOARD];
+        bg = (const unsigned long long *)(uintptr_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
+                                                     (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+        if (bg) {
+            bmg = us[C::UST_BOARD_MAGIC];
+            const int a0 = (int)(us[C::UST_BOARD_OWN] & 0xffffu), a1 = (int)(us[C::UST_BOARD_OWN] >> 16), nown = a1 - a0;
+            if (tid < N - nown) {
+                bi = tid < a0 ? tid : tid + nown;
+                bg += 2 * (size_t)bi;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    bw[2 * c] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    bw[2 * c + 1] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
+    // ... and taken into sf[] once the arithmetic in between has covered the round trip
+    __device__ __forceinline__ void take()
+    {
+        if (bg) {
+            int late = 0;
+            if (bi >= 0) {
+                unsigned long long t0 = 0;
+                int spins = 0;
+                while (((bw[0] ^ bw[1]) != bmg) | ((bw[2] ^ bw[3]) != bmg) | ((bw[4] ^ bw[5]) != bmg)) {
+                    __builtin_amdgcn_s_sleep(1);
+                    if ((++spins & 63) == 0) { // bounded like every poll of a granule: 2 s of the 100 MHz clock
+                        const unsigned long long now = wall_clock64();
+                        if (t0 == 0) t0 = now | 1ull;
+                        else if (now - t0 > 200000000ull) { late = 1; break; }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        bw[2 * c] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        bw[2 * c + 1] = __hip_atomic_load(bg + 2 * (size_t)c * C::NMAX + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                double *const sf = (double *)(nm_lds + C::OFF_SAVF);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) sf[(size_t)c * C::NMAX + bi] = __longlong_as_double((long long)bw[2 * c]);
+            }
+            if (__ballot(late) != 0) us[C::UST_BOARD_LATE] = 1; // the start that follows reports it (ST_SYNC_TIMEOUT)
+        }
+    }
+};
+
 template <class C>
 __device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int gslot, double mass, uint32_t seed, uint32_t step)
 {
@@ -262,17 +428,7 @@ __device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int
             }
         }
     }
-    for (int w = tid; w < 2 * N; w += BLOCK) {
-        const int part = w >= N ? 1 : 0, i = w - part * N;
-        uint32_t o[4];
-        philox4x32_10((uint32_t)i, part ? S_VEL_B : S_VEL_A, tag, step, seed, (uint32_t)gslot, o);
-        const double u1 = u01(o[0], o[1]), u2 = u01(o[2], o[3]);
-        const double r = sqrt(-2.0 * log_pos(1.0 - u1)); // (nm_math.h: the same functions of the same arguments, within 1 ulp like the library's)
-        double sn, cs;
-        sincos_2pi(twopi * u2, sn, cs);
-        if (part) gz[i] = r * cs * fac;
-        else { gx[i] = r * cs * fac; gy[i] = r * sn * fac; }
-    }
+    NM_GAUSSIAN_ITEMS();
     if constexpr (C::LOCAL_START)
         if (bg) {
             int late = 0;
@@ -300,10 +456,13 @@ __device__ __attribute__((noinline)) void gaussian_fill(uint32_t tag, int N, int
         }
 }
 
-template <class C>
+// STAGED (the production form): the gaussians stand on the stage already (draw_ahead, ordered by a barrier of the caller's) and the first pass
+// reads them there; the board fetch that gaussian_fill hides under its draws lies under the moment pass and the block reduction instead.
+template <class C, bool STAGED = false>
 __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t tag, double L, int N, int gslot, int parity, double mass,
                                                          double mvv2e, double kB, uint32_t seed, uint32_t step, short *im_g)
 {
+    static_assert(!STAGED || C::STAGE, "");
     constexpr int BLOCK = C::BLOCK, NW = C::NW;
     constexpr size_t A1 = (size_t)C::NMAX * sizeof(double);
     const int tid = threadIdx.x;
@@ -322,13 +481,21 @@ __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t t
     tag = __builtin_amdgcn_readfirstlane(tag); seed = __builtin_amdgcn_readfirstlane(seed); step = __builtin_amdgcn_readfirstlane(step);
     t = uniform(t); L = uniform(L); mass = uniform(mass); mvv2e = uniform(mvv2e); kB = uniform(kB);
     const double m = mass, mt = m * N;
-    gaussian_fill<C>(tag, N, gslot, mass, seed, step);
-    __syncthreads();
+    // the unscaled gaussians: the velocities themselves, or the stage (the second pass then writes the velocities from it)
+    constexpr size_t OFF_G = STAGED ? C::OFF_STAGE : C::OFF_VEL;
+    LdsArr<double, OFF_G> gx; LdsArr<double, OFF_G + A1> gy; LdsArr<double, OFF_G + 2 * A1> gz;
+    [[maybe_unused]] BoardFetch<C> bf;
+    if constexpr (STAGED) {
+        if constexpr (C::LOCAL_START) bf.issue(N);
+    } else {
+        gaussian_fill<C>(tag, N, gslot, mass, seed, step);
+        __syncthreads();
+    }
     double a[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = 0.0;
     for (int i = tid; i < N; i += BLOCK) {
-        const double ax = vx[i], ay = vy[i], az = vz[i];
+        const double ax = gx[i], ay = gy[i], az = gz[i];
         const double X = px[i] + im[3 * i] * L, Y = py[i] + im[3 * i + 1] * L, Z = pz[i] + im[3 * i + 2] * L;
         a[0] += m * ax; a[1] += m * ay; a[2] += m * az;
         a[3] += m * X; a[4] += m * Y; a[5] += m * Z;
@@ -344,6 +511,7 @@ __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t t
         a[15] -= m * X * Z;
     }
     block_sum<16, NW, NVMAX>(a, red, parity, min(NW, (N + 63) >> 6)); // (atoms are dealt out by thread index: N <= 256 leaves half the waves empty)
+    if constexpr (STAGED && C::LOCAL_START) bf.take(); // (the move in front is decided: sf[] of the peers' atoms is free)
     const double imt = 1.0 / mt; // (one division instead of six, and one for the inertia tensor below instead of three: every thread does all of this)
     const double c0 = a[0] * imt, c1 = a[1] * imt, c2 = a[2] * imt;   // COM velocity
     const double cx = a[3] * imt, cy = a[4] * imt, cz = a[5] * imt;   // centre of mass (unwrapped)
@@ -369,9 +537,9 @@ __device__ __attribute__((noinline)) double velocity_create(double t, uint32_t t
     }
     for (int i = tid; i < N; i += BLOCK) {
         const double dx = px[i] + im[3 * i] * L - cx, dy = py[i] + im[3 * i + 1] * L - cy, dz = pz[i] + im[3 * i + 2] * L - cz;
-        vx[i] = (vx[i] - c0) * sc - (w1 * dz - w2 * dy);
-        vy[i] = (vy[i] - c1) * sc - (w2 * dx - w0 * dz);
-        vz[i] = (vz[i] - c2) * sc - (w0 * dy - w1 * dx);
+        vx[i] = (gx[i] - c0) * sc - (w1 * dz - w2 * dy);
+        vy[i] = (gy[i] - c1) * sc - (w2 * dx - w0 * dz);
+        vz[i] = (gz[i] - c2) * sc - (w0 * dy - w1 * dx);
     }
     // sum m |v'|^2 of what was just written, from the same moments: with u = sc (v - c), r = X - Xc and I omega = L,
     // sum m |u - omega x r|^2 = sc^2 sum m |v - c|^2 - 2 omega.L + omega.I.omega = sc^2 s2 - omega.L   (the caller's H0 needs no pass of its own)
@@ -408,6 +576,9 @@ struct Replica {
     int gen = 0;
     unsigned long long *tl = nullptr; // experiment build
     int tl_n = 0;
+#ifdef NM_TL_DRAW
+    int tl_kind = 0;                  // the phase of the evaluation whose exchange is being stamped, + 1
+#endif
     static constexpr size_t A1 = (size_t)C::NMAX * sizeof(double);
     LdsArr<double, C::OFF_POS> px; LdsArr<double, C::OFF_POS + A1> py; LdsArr<double, C::OFF_POS + 2 * A1> pz;
     LdsArr<double, C::OFF_VEL> vx; LdsArr<double, C::OFF_VEL + A1> vy; LdsArr<double, C::OFF_VEL + 2 * A1> vz;
@@ -439,6 +610,12 @@ struct Replica {
     // slot k of this wave's copy of the rarely-touched uniform scalars (every lane of the wave reads / writes the same value)
     __device__ __forceinline__ double &ust(int k) const { return ((double *)(nm_lds + C::OFF_UST))[(tid >> 6) * C::UST_PER_WAVE + k]; }
     __device__ __forceinline__ unsigned long long &ustu(int k) const { return ((unsigned long long *)(nm_lds + C::OFF_UST))[(tid >> 6) * C::UST_PER_WAVE + k]; }
+    // the same for the scalars that go with the stage (Cfg::STAGE, draw_ahead)
+    __device__ __forceinline__ double &da(int k) const { return ((double *)(nm_lds + C::OFF_DA))[(tid >> 6) * C::DA_PER_WAVE + k]; }
+    __device__ __forceinline__ unsigned long long &dau(int k) const { return ((unsigned long long *)(nm_lds + C::OFF_DA))[(tid >> 6) * C::DA_PER_WAVE + k]; }
+    // AHEAD: the production form of a configuration that has a stage takes every move's random numbers from it (nm_block_body); they are
+    // drawn under the exchange of the energy evaluation in front of the move (KParams::draw_ahead) or, with that switched off, behind it
+    static constexpr bool AHEAD = PLAIN && C::STAGE;
     // block-uniform flags in ONE scalar register (three separate bools cost lane masks and spilled scalars in the hot loops)
     // LOCAL_START only — F_BOARD: the peers' forces that belong to f[] of the own atoms stand on the board of the exchange just made (generation
     // gen - 1): set by finish_sums, gone with the forces (set_fresh(false): a restore, a move, a hand-over — whatever takes the next generation
@@ -551,7 +728,10 @@ struct Replica {
     {
         const double metcrit = exp(-c);
         if (isinf(metcrit)) return false;
-        const double u = draw_scalar(stream, m, index);
+        // (drawn ahead: the move's acceptance uniform was staged by the exchange of the evaluation just made; unused, it has no side effect)
+        double u;
+        if constexpr (AHEAD) u = da(C::DA_ACC);
+        else u = draw_scalar(stream, m, index);
         const double mm = (metcrit != metcrit) ? metcrit : (metcrit < 1.0 ? metcrit : 1.0);
         return u <= mm;
     }
@@ -1666,11 +1846,24 @@ struct Replica {
     // of every workgroup ends with the identical bits.  Ends with a barrier.
     // board (LOCAL_START, the exchange of an energy evaluation a trajectory can follow): the own atoms' threads also publish the forces of their
     // atoms, behind the partial sums the peers are waiting for; nobody waits for them here (advance_and_share mode 4 reads them).
-    template <int K>
-    __device__ void exchange_sums(double (&s)[K], bool board = false)
+    // DRAW (finish_sums of the production form, Replica::AHEAD): the random numbers of move m_next and the acceptance uniform of move m_acc
+    // are drawn between the publication and the poll (draw_ahead; -1: none), so their arithmetic runs while the granules travel; every
+    // workgroup of the cluster does the same work at the same point, and the closing barrier orders the stage for its readers.  With one
+    // workgroup per replica there is nothing to wait for: the draws run here all the same, in front of a barrier of their own.
+    template <int K, bool DRAW = false>
+    __device__ void exchange_sums(double (&s)[K], bool board = false, [[maybe_unused]] int m_next = -1, [[maybe_unused]] int m_acc = -1)
     {
         static_assert(K == 4, "one instantiation: callers pad with zeros");
-        if (Q == 1) return;
+        static_assert(!DRAW || AHEAD, "");
+        if (Q == 1) {
+            if constexpr (DRAW)
+                if (m_next >= 0 || m_acc >= 0) {
+                    draw_ahead<C>(m_next, m_acc, p.step, p.seed, gslot, N, p.mass, p.ppos, p.pvol);
+                    __syncthreads();
+                }
+            return;
+        }
+        if constexpr (DRAW) { DTL_ARM(); DTL(3); }
         double *xg = xb + (size_t)(gen & 1) * C::XBUF_DOUBLES;
         const unsigned long long mg = magic();
         if (tid < K) {
@@ -1688,6 +1881,8 @@ struct Replica {
                     put_granule(xg + 2 * (C::XG_BOARD + (size_t)(2 * NMAX + i)), fz[i], mgp);
                 }
             }
+        if constexpr (DRAW)
+            if (p.draw_ahead && (m_next >= 0 || m_acc >= 0)) draw_ahead<C>(m_next, m_acc, p.step, p.seed, gslot, N, p.mass, p.ppos, p.pvol);
         int timeout = 0, poisoned = 0;
         const int lane = tid & 63;
         double v[K];
@@ -1699,6 +1894,7 @@ struct Replica {
             for (int k = 0; k < K; ++k) gs[k] = xg + 2 * (C::XG_PART + 4 * lane + k);
             get_granules<K>(gs, mg, v, timeout, poisoned);
         }
+        if constexpr (DRAW) DTL(4);
         double t[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -1712,6 +1908,12 @@ struct Replica {
         if (fl & 2) status |= ST_LIST_OVERFLOW; // a peer's list overflowed
 #pragma unroll
         for (int k = 0; k < K; ++k) s[k] = uniform(t[k]);
+        // NM_DRAW_AHEAD=0 (the A/B): the same draws behind the exchange, on the serial path where every draw used to stand
+        if constexpr (DRAW)
+            if (!p.draw_ahead && (m_next >= 0 || m_acc >= 0)) {
+                draw_ahead<C>(m_next, m_acc, p.step, p.seed, gslot, N, p.mass, p.ppos, p.pvol);
+                __syncthreads();
+            }
     }
 
     // a workgroup that leaves the block on its own finding (list overflow) marks everything its peers could be waiting for
@@ -1955,10 +2157,12 @@ struct Replica {
     int layout_pad = -1;
     // completes an energy evaluation; `extra` is one more per-workgroup partial sum that rides along.
     // board: a trajectory can start from this evaluation's forces, so they go on the board (exchange_sums).
-    __device__ double finish_sums(double extra, bool board = false)
+    // m_next, m_acc (production form with a stage): the move whose random numbers, and the move whose acceptance uniform, are drawn under the
+    // exchange (-1: none).
+    __device__ double finish_sums(double extra, bool board = false, int m_next = -1, int m_acc = -1)
     {
         double s[4] = { psum[0], psum[1], psum[2], extra };
-        exchange_sums<4>(s, board);
+        exchange_sums<4, AHEAD>(s, board, m_next, m_acc);
         psum[0] = s[0]; psum[1] = s[1]; psum[2] = s[2];
         take_sums();
         if constexpr (C::LOCAL_START)
@@ -1993,7 +2197,7 @@ struct Replica {
             ustu(C::UST_BOARD_MAGIC) = magic_at(gen - 1);
             ustu(C::UST_BOARD_OWN) = (unsigned long long)a0 | (unsigned long long)a1 << 16;
         }
-        const double mv2 = velocity_create<C>(t, tag, L, N, gslot, parity, p.mass, p.mvv2e, p.kB, p.seed, p.step, img);
+        const double mv2 = velocity_create<C, AHEAD>(t, tag, L, N, gslot, parity, p.mass, p.mvv2e, p.kB, p.seed, p.step, img);
         if constexpr (C::LOCAL_START)
             if (pre) flags = (flags & ~F_BOARD) | F_SF_ALL;
         parity ^= 1;
@@ -2743,6 +2947,9 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         R.ust(23) = 0.0; // trajectory starts without a hand-over (stats column 10)
         R.ustu(C::UST_BOARD_LATE) = 0;
     }
+    // nothing is staged across a block boundary (LDS survives from cycle to cycle in nm_cycles_kernel): the exchange of PH_INIT draws move 0
+    constexpr bool AHEAD = Replica<C, PLAIN>::AHEAD;
+    if constexpr (AHEAD) { R.da(C::DA_COUNT) = 0.0; R.dau(C::DA_TLP) = 0; } // moves drawn ahead (stats column 11)
     // (ST_FORCE_RANGE is set here only by nm_run_md: a plain NVE run has no move to reject, so it stops)
     const int fatal = ST_BOX_TOO_SMALL | ST_LIST_OVERFLOW | ST_SYNC_TIMEOUT | ST_FORCE_RANGE;
 
@@ -2769,7 +2976,20 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 bool board = false;
                 if constexpr (C::LOCAL_START)
                     board = !p.start_handover && !p.eval_only && ((phase == PH_INIT || phase == PH_HMC_START) ? m : m + 1) < p.mod;
-                mv2new = R.finish_sums(phase == PH_HMC_STEP ? R.psum[3] : 0.0, board);
+                // Drawn under this exchange (draw_ahead), by the expression that decides `board`: the move about to start — the block's first
+                // behind PH_INIT, none behind PH_HMC_START (that move's draws are consumed), else the one behind the move that this
+                // evaluation ends — and that ending move's acceptance uniform.
+                int m_next = -1, m_acc = -1;
+                if constexpr (AHEAD)
+                    if (!p.eval_only) {
+                        if (phase != PH_HMC_START) m_next = phase == PH_INIT ? m : m + 1;
+                        if (m_next >= p.mod) m_next = -1;
+                        if (phase != PH_INIT && phase != PH_HMC_START) m_acc = m;
+                    }
+#ifdef NM_TL_DRAW
+                R.tl_kind = phase + 1;
+#endif
+                mv2new = R.finish_sums(phase == PH_HMC_STEP ? R.psum[3] : 0.0, board, m_next, m_acc);
             }
         }
         skip_eval = false;
@@ -2892,13 +3112,27 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         bool pending = false;
         while (m < p.mod && !pending) {
             PROF_BEGIN();
-            const double roll = (!PLAIN && p.md_mode) ? 2.0 : R.draw_scalar(S_ROLL, (uint32_t)m, 0);
+            double roll;
+            if constexpr (AHEAD) {
+                // the move's random numbers stand on the stage: drawn under the exchange of the evaluation just made (NM_DRAW_AHEAD=0, the
+                // A/B: behind it)
+                if (p.draw_ahead) R.da(C::DA_COUNT) += 1.0;
+                roll = uniform(R.da(C::DA_ROLL));
+            } else roll = (!PLAIN && p.md_mode) ? 2.0 : R.draw_scalar(S_ROLL, (uint32_t)m, 0);
             if (roll <= p.ppos && (PLAIN || p.bulk)) { // bulk_position_mc, remcmc:477-484
                 ntp += 1.0;
                 R.save(false);
                 U0 = R.U; W0 = R.W; c_pe = R.U / et;
                 const uint32_t tag = R.draw_tag((uint32_t)m);
                 const double a = q6(dx * p.lat);
+                if constexpr (AHEAD) { // the three uniforms of atom i were staged by this thread
+                    const double *const su = (const double *)(nm_lds + C::OFF_STAGE);
+                    for (int i = tid; i < N; i += BLOCK) {
+                        R.px[i] += a * 2.0 * (su[i] - 0.5);
+                        R.py[i] += a * 2.0 * (su[C::NMAX + i] - 0.5);
+                        R.pz[i] += a * 2.0 * (su[2 * C::NMAX + i] - 0.5);
+                    }
+                } else
                 for (int i = tid; i < N; i += BLOCK) { // displace_atoms all random a a a seed units box
                     uint32_t o[4], q[4];
                     philox4x32_10((uint32_t)i, S_DISP_XY, tag, p.step, p.seed, (uint32_t)R.gslot, o);
@@ -2934,7 +3168,9 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
                 c_boxl = R.L; c_vol = uniform(pow(c_boxl, 3.0));
                 R.save(false);
                 U0 = R.U; W0 = R.W; c_pe = R.U / et;
-                const double u = R.draw_scalar(S_VOL, (uint32_t)m, 0);
+                double u;
+                if constexpr (AHEAD) u = uniform(R.da(C::DA_VOL));
+                else u = R.draw_scalar(S_VOL, (uint32_t)m, 0);
                 c_volnew = uniform(exp(log(c_vol) + 2.0 * (u - 0.5) * dv));
                 const double boxnew = cbrt(c_volnew);
                 const double scale = boxnew / c_boxl;
@@ -3021,6 +3257,7 @@ __device__ __forceinline__ int nm_block_body(const KParams &p)
         if (p.last_ticks) p.last_ticks[slot] = ticks;
         st[4] += (double)ticks; st[5] += R.same_xcd ? 1.0 : 0.0; st[6] += 1.0; st[7] += nth - nth_entry; st[9] = (double)C::MAXNB;
         if constexpr (C::LOCAL_START) st[10] += R.ust(23);
+        if constexpr (AHEAD) st[11] += R.da(C::DA_COUNT);
 #ifdef NM_PROF
         if (p.prof) for (int q = 0; q < NM_PROF_SLOTS; ++q) p.prof[(size_t)slot * NM_PROF_SLOTS + q] += R.prof_acc[q];
 #endif

@@ -59,6 +59,9 @@ struct KParams {
     // nm_run_cycles (nm_cycles_kernel): several cycles of block / adapt / exchange in ONE launch; the replicas of a pressure row meet at the end of
     // every block, the rows never wait for one another
     int ncycles, nt, row0;         // cycles of this launch; temperatures per row; global index of the context's first row
+    int draw_ahead;                // 1: the production form of the 4^3 kernels draws a move's random numbers under the exchange of the energy
+                                   // evaluation in front of it; NM_DRAW_AHEAD=0: behind that exchange (A/B, tests).  (In the four bytes that
+                                   // padded row0: no other member moves, and the kernels that do not read it stay what they were.)
     unsigned int *rowbar, *rowgo;  // per local row: workgroups arrived (monotonic within the launch), cycles released by the row's leader
     int *cyc_abort;                // set by whoever leaves the launch early: nobody waits for a row that will not complete
     int *nswaps;                   // accepted swaps of the launch (atomic)

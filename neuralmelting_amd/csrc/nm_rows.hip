@@ -113,6 +113,14 @@ static_assert(CfgMidSC::RHO_LDS && CfgMidSCQ4::RHO_LDS && !CfgLargeSC::RHO_LDS, 
 NM_CFG_ROWS(NM_ROW)
 #undef NM_ROW
 
+// the stage of the random numbers drawn ahead (Cfg::STAGE: 6.5 KB) exists for the 4^3 rows and no others, and none of them shares its CU with it
+// any more than without it: every row asks for more than half of the 160 KB (and fits them: above).  CfgSmallQ8 stays inside the 82 KB floor;
+// CfgSmallQ4, which laid out 79.25 KB, now asks for 85.75 KB; the other rows were above the floor before.
+// Headroom: CfgSmall, the one-workgroup row with both lists of all 256 rows, now takes 161536 of the CU's 163840 bytes — 2304 are left.
+#define NM_ROW(P, K, Q, C, FUSED) static_assert(C::STAGE == (K == 0) && (K != 0 || 2 * C::LDS_BYTES > 160 * 1024), #C);
+NM_CFG_ROWS(NM_ROW)
+#undef NM_ROW
+
 // The production form of the block (nm_block_body's PLAIN) is instantiated for the 4^3 rows, kind 0, whose NMAX the static_assert above
 // ties to 256: block and fused kernels.  The 864- and 2048-atom rows keep the general form alone (build time).
 template <class C> constexpr bool has_plain = C::NMAX == 256;
