@@ -41,6 +41,8 @@ REWEIGHT_BOOT_SYMBOLS = ('nm_reweight_boot_solve', 'nm_reweight_boot_expect')
 PCA_SYMBOLS = ('nm_pca_moments', 'nm_pca_project', 'nm_pca_last_timing', 'nm_pca_last_error')
 # include/nm_cluster.h
 CLUSTER_SYMBOLS = ('nm_cluster_dbscan', 'nm_cluster_last_timing', 'nm_cluster_last_error')
+# include/nm_tsne.h
+TSNE_SYMBOLS = ('nm_tsne_affinities', 'nm_tsne_gradient', 'nm_tsne_descend', 'nm_tsne_last_timing', 'nm_tsne_last_error')
 
 
 class NMConfig(C.Structure):
@@ -172,5 +174,16 @@ def load():
     L.nm_cluster_last_timing.restype = C.c_int
     L.nm_cluster_last_timing.argtypes = [c_double_p]
     L.nm_cluster_last_error.restype = C.c_char_p
+    L.nm_tsne_affinities.restype = C.c_int
+    L.nm_tsne_affinities.argtypes = [C.c_int, C.c_int64, C.c_int, c_double_p, C.c_double, C.c_int, c_int32_p, c_double_p, c_double_p]
+    L.nm_tsne_gradient.restype = C.c_int
+    L.nm_tsne_gradient.argtypes = [C.c_int, C.c_int64, C.c_int, c_int32_p, c_double_p, C.c_int, c_double_p, C.c_double, c_double_p,
+                                   c_double_p, c_double_p]
+    L.nm_tsne_descend.restype = C.c_int
+    L.nm_tsne_descend.argtypes = [C.c_int, C.c_int64, C.c_int, c_int32_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int,
+                                  C.c_double, C.c_double, C.c_double, c_double_p]
+    L.nm_tsne_last_timing.restype = C.c_int
+    L.nm_tsne_last_timing.argtypes = [c_double_p]
+    L.nm_tsne_last_error.restype = C.c_char_p
     _lib = L
     return L

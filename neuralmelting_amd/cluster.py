@@ -37,6 +37,8 @@ def parse_args(argv=None):
     p.add_argument('-n', '--name', type=str, default='remcmc_init')
     p.add_argument('-e', '--element', type=str, default='LJ')
     p.add_argument('-ft', '--feature', type=str, default='cdf', help='the feature F whose projections <PREFIX>.F.pcz.npy are clustered')
+    p.add_argument('-em', '--embedding', type=str, default='pcz', choices=('pcz', 'mfy'),
+                   help="what is clustered: pca's projections <PREFIX>.F.pcz.npy, or manifold's embedding <PREFIX>.F.mfy.npy of the same -sk and -sd")
     p.add_argument('-nd', '--dimensions', type=int, default=2, help='leading components used, 1..16 and at most LD')
     p.add_argument('-nc', '--neighbourhood', type=float, required=True, metavar='EPS',
                    help='the radius of a neighbourhood as a fraction of the range of component 0')
@@ -109,25 +111,31 @@ def main(argv=None):
     a = parse_args(argv)
     el, ft, nd = a.element, a.feature, a.dimensions
     prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, el.lower(), LAT[el])
-    paths = {key: prefix + '.%s.npy' % key for key in ('virial.trgt', 'temp.trgt', 'pe', ft + '.pcz')}
+    src = ft + '.' + a.embedding
+    paths = {key: prefix + '.%s.npy' % key for key in ('virial.trgt', 'temp.trgt', 'pe', src)}
     for path in paths.values():                                      # every input is checked before anything is written
         if not os.path.isfile(path):
             raise SystemExit('cluster: %s is missing' % path)
     P, T, pe = np.load(paths['virial.trgt']), np.load(paths['temp.trgt']), np.load(paths['pe'], mmap_mode='r')
-    pcz = np.load(paths[ft + '.pcz'], mmap_mode='r')
+    pcz = np.load(paths[src], mmap_mode='r')
     pn, tn = P.size, T.size
     if pe.ndim != 3 or pe.shape[:2] != (pn, tn):
         raise SystemExit('cluster: %s has shape %s and does not fit the %d x %d grid' % (paths['pe'], pe.shape, pn, tn))
     if pcz.ndim != 4 or pcz.shape[:3] != pe.shape:
-        raise SystemExit('cluster: %s has shape %s, not %s followed by the components' % (paths[ft + '.pcz'], pcz.shape, pe.shape))
+        raise SystemExit('cluster: %s has shape %s, not %s followed by the components' % (paths[src], pcz.shape, pe.shape))
     sn, ld = pcz.shape[2:]
     if nd > ld:
-        raise SystemExit('cluster: -nd %d is more than the %d components of %s' % (nd, ld, paths[ft + '.pcz']))
+        raise SystemExit('cluster: -nd %d is more than the %d components of %s' % (nd, ld, paths[src]))
     kept = len(range(a.skip, sn, a.stride))
     n = pn * tn * kept
     if not 1 <= n <= MAX_POINTS:
-        raise SystemExit('cluster: -sk %d -sd %d leave %d samples of %s, not 1..%d' % (a.skip, a.stride, n, paths[ft + '.pcz'], MAX_POINTS))
+        raise SystemExit('cluster: -sk %d -sd %d leave %d samples of %s, not 1..%d' % (a.skip, a.stride, n, paths[src], MAX_POINTS))
     z = np.ascontiguousarray(pcz[:, :, a.skip::a.stride, :nd], dtype=np.float64).reshape(n, nd)
+    if a.embedding == 'mfy':                                         # manifold left out what this run leaves out, NaN there and nowhere else
+        out = np.ones(sn, dtype=bool)
+        out[a.skip::a.stride] = False
+        if np.isnan(z).any() or not np.isnan(pcz[:, :, out]).all():
+            raise SystemExit('cluster: -sk %d -sd %d are not those that %s was written with' % (a.skip, a.stride, paths[src]))
     temp = np.broadcast_to(np.asarray(T, dtype=np.float64)[None, :, None], (pn, tn, kept)).reshape(n)
     if a.verbose:
         print('clustering %d of %d samples of %s in %d components, eps %g of the range of pc0, min_pts %d' % (
@@ -135,7 +143,7 @@ def main(argv=None):
     try:
         label, degree, ncl = dbscan(scaled(z), a.neighbourhood, a.min_samples, a.device)
     except (RuntimeError, ValueError) as err:
-        raise SystemExit('cluster: %s: %s' % (paths[ft + '.pcz'], err))
+        raise SystemExit('cluster: %s: %s' % (paths[src], err))
     tab = table(label, degree, a.min_samples, temp, z)
     order = phases(tab, a.clusters_kept)
     full = spread(label.reshape(pn, tn, kept), pe.shape, a.skip, a.stride, -1)
