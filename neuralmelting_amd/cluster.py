@@ -16,13 +16,13 @@ sample, is the data to choose it from.  Of the NK largest clusters the one with 
 melting grid the solid), the next cl1 (the liquid).
 """
 import argparse
-import os
 import sys
 
 import numpy as np
 
 from . import _lib as B
-from .parse import LAT
+from . import _stage as S
+from ._stage import spread
 
 MAX_POINTS, MAX_DIM, MAX_KEPT = 2 ** 21, 16, 8     # include/nm_cluster.h: npoints and ndim; the indicators of -nk
 
@@ -100,42 +100,24 @@ def phases(tab, nk):
     return sorted(largest, key=lambda c: (tab[c, 2], c))
 
 
-def spread(values, shape, skip, stride, fill):
-    """values (PN, TN, kept) of the clustered samples skip, skip + stride, ... in an array of `shape` (PN, TN, SN) filled with `fill`"""
-    out = np.full(shape, fill, dtype=np.asarray(values).dtype)
-    out[:, :, skip::stride] = values
-    return out
-
-
 def main(argv=None):
     a = parse_args(argv)
     el, ft, nd = a.element, a.feature, a.dimensions
-    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, el.lower(), LAT[el])
-    src = ft + '.' + a.embedding
-    paths = {key: prefix + '.%s.npy' % key for key in ('virial.trgt', 'temp.trgt', 'pe', src)}
-    for path in paths.values():                                      # every input is checked before anything is written
-        if not os.path.isfile(path):
-            raise SystemExit('cluster: %s is missing' % path)
-    P, T, pe = np.load(paths['virial.trgt']), np.load(paths['temp.trgt']), np.load(paths['pe'], mmap_mode='r')
-    pcz = np.load(paths[src], mmap_mode='r')
-    pn, tn = P.size, T.size
-    if pe.ndim != 3 or pe.shape[:2] != (pn, tn):
-        raise SystemExit('cluster: %s has shape %s and does not fit the %d x %d grid' % (paths['pe'], pe.shape, pn, tn))
-    if pcz.ndim != 4 or pcz.shape[:3] != pe.shape:
-        raise SystemExit('cluster: %s has shape %s, not %s followed by the components' % (paths[src], pcz.shape, pe.shape))
-    sn, ld = pcz.shape[2:]
+    prefix = S.prefix(a.name, el)
+    P, T, pe, pcz, path = S.grid_inputs('cluster', prefix, ft + '.' + a.embedding, 'the components')
+    pn, tn, sn, ld = pcz.shape
     if nd > ld:
-        raise SystemExit('cluster: -nd %d is more than the %d components of %s' % (nd, ld, paths[src]))
-    kept = len(range(a.skip, sn, a.stride))
+        raise SystemExit('cluster: -nd %d is more than the %d components of %s' % (nd, ld, path))
+    kept, zk = S.kept(pcz, a.skip, a.stride)
     n = pn * tn * kept
     if not 1 <= n <= MAX_POINTS:
-        raise SystemExit('cluster: -sk %d -sd %d leave %d samples of %s, not 1..%d' % (a.skip, a.stride, n, paths[src], MAX_POINTS))
-    z = np.ascontiguousarray(pcz[:, :, a.skip::a.stride, :nd], dtype=np.float64).reshape(n, nd)
+        raise SystemExit('cluster: -sk %d -sd %d leave %d samples of %s, not 1..%d' % (a.skip, a.stride, n, path, MAX_POINTS))
+    z = np.ascontiguousarray(zk[..., :nd], dtype=np.float64).reshape(n, nd)
     if a.embedding == 'mfy':                                         # manifold left out what this run leaves out, NaN there and nowhere else
         out = np.ones(sn, dtype=bool)
         out[a.skip::a.stride] = False
         if np.isnan(z).any() or not np.isnan(pcz[:, :, out]).all():
-            raise SystemExit('cluster: -sk %d -sd %d are not those that %s was written with' % (a.skip, a.stride, paths[src]))
+            raise SystemExit('cluster: -sk %d -sd %d are not those that %s was written with' % (a.skip, a.stride, path))
     temp = np.broadcast_to(np.asarray(T, dtype=np.float64)[None, :, None], (pn, tn, kept)).reshape(n)
     if a.verbose:
         print('clustering %d of %d samples of %s in %d components, eps %g of the range of pc0, min_pts %d' % (
@@ -143,7 +125,7 @@ def main(argv=None):
     try:
         label, degree, ncl = dbscan(scaled(z), a.neighbourhood, a.min_samples, a.device)
     except (RuntimeError, ValueError) as err:
-        raise SystemExit('cluster: %s: %s' % (paths[src], err))
+        raise SystemExit('cluster: %s: %s' % (path, err))
     tab = table(label, degree, a.min_samples, temp, z)
     order = phases(tab, a.clusters_kept)
     full = spread(label.reshape(pn, tn, kept), pe.shape, a.skip, a.stride, -1)

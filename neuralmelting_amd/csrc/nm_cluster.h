@@ -2,22 +2,19 @@
 // row-major, as three all-pairs scans over one skeleton and two small kernels around them.  No N x N array exists: the device
 // holds x (N ndim doubles) and five int arrays of N.
 //
-// The skeleton (cl_scan).  A workgroup of CL_BLOCK threads owns CL_ROWS = CL_RPT CL_BLOCK rows: thread t keeps the coordinates of
-// rows r0 + t and r0 + CL_BLOCK + t in registers (ndim is a template parameter, 1..16).  The columns are walked in tiles of CL_TILE
-// points: a tile is one contiguous piece of x and is copied into LDS as it lies, together with one int per column that the pass
-// defines.  Every thread then reads the same column at the same time (a broadcast read of LDS, free of bank conflicts) and tests it
-// against its two rows, so a column's LDS read is paid once per two pairs.  The grid is (row blocks) x (column slices): slice s
-// of S walks the tiles s, s + S, s + 2 S, ... so a small N still fills the device and a triangular range (the union pass) stays
-// balanced.  A tile's last column comes from the loop bound, which is the same in every thread: no test per pair.  A row past the
-// end is given eps2 = -1, which no distance meets.
+// The skeleton is described in nm_scan.h, which holds its row loader, grid and screen; the shape here is ClScan: CL_ROWS = CL_RPT
+// CL_BLOCK rows of a workgroup in registers, tiles of CL_TILE columns in LDS, a grid of (row blocks) x (column slices).  The tile
+// loop (cl_scan) stands here, with what is this stage's own: one int per column that the pass defines, a wave without a row at work
+// walks the barriers only, a column whose int says so is skipped by the whole workgroup, and a pass hears of the columns within eps2
+// of a row.  A row past the end is given eps2 = -1, which no distance meets.
 //
 // cl_d2 is the one distance: d = a[c] - b[c], acc = fma(d, d, acc), c ascending, the first square a plain product.  Negating every
 // d changes no bit, so d2(i, j) == d2(j, i); a pair gets the same bits in every pass.  A difference rounds once, so its square
 // carries two roundings; the first product rounds once more and then passes through the ndim - 1 fused multiply-adds, one
 // rounding each, and no other term passes through more: the error is at most (ndim + 2) u d2, the header's bound.
 //
-//   nm_cluster_screen_kernel  one thread per point: the first point with a value that is not finite (integer atomicMin),
-//                             parent[i] = i, degree[i] = 0.
+//   nm_cluster_init_kernel    behind nm_scan.h's screen for values that are not finite, one thread per point: parent[i] = i,
+//                             degree[i] = 0.
 //   nm_cluster_degree_kernel  the scan over all tiles: a row counts the columns within eps2 (itself among them); the slices are
 //                             joined by integer atomicAdd on degree[i].
 //   nm_cluster_union_kernel   the scan over the tiles up to the block's own last row (an edge is united from its larger end; in
@@ -52,6 +49,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nm_scan.h"
+
 namespace nm {
 
 constexpr int CL_BLOCK = 256;                       // threads of a workgroup
@@ -61,10 +60,10 @@ constexpr int CL_TILE = 256;                        // columns staged in LDS at 
 constexpr int CL_MAXDIM = 16;
 constexpr int64_t CL_MAXN = (int64_t)1 << 21;
 constexpr int CL_NONE = 0x7f7f7f7f;                 // no cluster (yet): the byte pattern that hipMemset writes
-constexpr int CL_NOBAD = 0x7fffffff;
 constexpr int CL_GRID = 2048;                       // workgroups a scan aims at at least: 8 per compute unit
 constexpr int CL_SPAN = 128;                        // tiles a workgroup walks at most
 
+using ClScan = ScanShape<CL_BLOCK, CL_RPT, CL_TILE, CL_GRID, CL_SPAN>;
 static_assert(CL_TILE <= CL_BLOCK, "a tile's ints are staged by one thread each");
 
 // the squared distance of the header, in the one order that every pass uses
@@ -109,19 +108,15 @@ __device__ __forceinline__ int cl_unite(int *parent, int x, int y)
     }
 }
 
-__global__ void __launch_bounds__(CL_BLOCK)
-nm_cluster_screen_kernel(int n, int ndim, const double *__restrict__ x, int *__restrict__ parent, int *__restrict__ degree, int *bad)
+__global__ void __launch_bounds__(CL_BLOCK) nm_cluster_init_kernel(int n, int *__restrict__ parent, int *__restrict__ degree)
 {
     const int i = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (i >= n) return;
-    bool ok = true;
-    for (int c = 0; c < ndim; ++c) ok = ok && isfinite(x[(size_t)i * ndim + c]);
-    if (!ok) atomicMin(bad, i);
     parent[i] = i;
     degree[i] = 0;
 }
 
-// The skeleton.  stage(j) is the tile's int of column j (called by one thread per column); skip(v) says that a column with the
+// The tile loop.  stage(j) is the tile's int of column j (called by one thread per column); skip(v) says that a column with the
 // int v concerns no row (the same answer in every thread); hit(r, j, v) is called for row slot r where column j lies within
 // eps2[r].  `busy` is the wave's: a wave with nothing to do stages and walks the barriers only.  Tiles t0, t0 + tstep, ... < tend.
 template <int ND, class Stage, class Skip, class Hit>
@@ -152,30 +147,13 @@ __device__ __forceinline__ void cl_scan(int n, const double *__restrict__ x, con
     }
 }
 
-// the rows of thread tid of row block rb: their indices, whether they exist, and their coordinates (of point 0 where they do not).
-// The rows are 0 .. nrows - 1 themselves, or, with a list, the points list[0 .. nrows - 1].
-template <int ND>
-__device__ __forceinline__ void cl_rows(const double *__restrict__ x, const int *__restrict__ list, int nrows, int rb, int (&idx)[CL_RPT],
-                                        bool (&valid)[CL_RPT], double (&row)[CL_RPT][ND])
-{
-#pragma unroll
-    for (int r = 0; r < CL_RPT; ++r) {
-        const int k = rb * CL_ROWS + r * CL_BLOCK + (int)threadIdx.x;
-        valid[r] = k < nrows;
-        idx[r] = !valid[r] ? 0 : list ? list[k] : k;
-        const double *src = x + (size_t)idx[r] * ND;
-#pragma unroll
-        for (int c = 0; c < ND; ++c) row[r][c] = src[c];
-    }
-}
-
 template <int ND> __global__ void __launch_bounds__(CL_BLOCK)
 nm_cluster_degree_kernel(int n, const double *__restrict__ x, double e2, int *degree)
 {
     int idx[CL_RPT], count[CL_RPT];
     bool valid[CL_RPT];
     double row[CL_RPT][ND], eps2[CL_RPT];
-    cl_rows<ND>(x, nullptr, n, blockIdx.x, idx, valid, row);
+    scan_rows<ClScan, ND>(x, nullptr, n, blockIdx.x, idx, valid, row);
 #pragma unroll
     for (int r = 0; r < CL_RPT; ++r) { eps2[r] = valid[r] ? e2 : -1.0; count[r] = 0; }
     const int ntiles = (n + CL_TILE - 1) / CL_TILE;
@@ -193,7 +171,7 @@ nm_cluster_union_kernel(int n, const double *__restrict__ x, double e2, int min_
     bool valid[CL_RPT];
     double row[CL_RPT][ND], eps2[CL_RPT];
     const int rb = gridDim.x - 1 - blockIdx.x;                  // the last row block has the most tiles: it starts first
-    cl_rows<ND>(x, nullptr, n, rb, idx, valid, row);
+    scan_rows<ClScan, ND>(x, nullptr, n, rb, idx, valid, row);
     bool any = false;
 #pragma unroll
     for (int r = 0; r < CL_RPT; ++r) {
@@ -230,7 +208,7 @@ nm_cluster_border_kernel(int n, const double *__restrict__ x, double e2, const i
     int idx[CL_RPT], best[CL_RPT];
     bool valid[CL_RPT];
     double row[CL_RPT][ND], eps2[CL_RPT];
-    cl_rows<ND>(x, open, nopen, blockIdx.x, idx, valid, row);
+    scan_rows<ClScan, ND>(x, open, nopen, blockIdx.x, idx, valid, row);
 #pragma unroll
     for (int r = 0; r < CL_RPT; ++r) {
         eps2[r] = valid[r] ? e2 : -1.0;

@@ -13,65 +13,26 @@ namespace {
 thread_local std::string g_cluster_error;
 std::string &stage_error() { return g_cluster_error; }
 
-// Where a call's device time went, for nm_cluster_last_timing: lap(w) books the time since the lap before to w.
+// the slots of nm_cluster_last_timing
 enum { CL_T_UPLOAD, CL_T_DEGREE, CL_T_UNION, CL_T_NUMBER, CL_T_BORDER, CL_T_COUNT };
 thread_local double g_cluster_ms[CL_T_COUNT];
-struct ClusterLaps {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> what;
-    ~ClusterLaps() { for (hipEvent_t e : ev) hipEventDestroy(e); }
-    void lap(int w)
-    {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        hipEventRecord(e, 0);
-        ev.push_back(e);
-        what.push_back(w);
-    }
-    // behind the call's last synchronisation
-    void book()
-    {
-        for (double &m : g_cluster_ms) m = 0.0;
-        for (size_t i = 1; i < ev.size(); ++i) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) g_cluster_ms[what[i]] += ms;
-        }
-    }
-};
 
-// the grid of a scan of nrows rows over n columns: every row block, and as many column slices as bring it to CL_GRID workgroups
-// and leave a workgroup at most CL_SPAN tiles (at most one slice per tile).  Many short workgroups, not one resident set of long
-// ones: the union pass's are of unequal length, and the device hands out the next as one ends.
-dim3 scan_grid(int nrows, int n)
-{
-    const int blocks = (nrows + CL_ROWS - 1) / CL_ROWS, tiles = (n + CL_TILE - 1) / CL_TILE;
-    int slices = (CL_GRID + blocks - 1) / blocks;
-    if (slices < (tiles + CL_SPAN - 1) / CL_SPAN) slices = (tiles + CL_SPAN - 1) / CL_SPAN;
-    if (slices > tiles) slices = tiles;
-    return dim3((unsigned)blocks, (unsigned)slices);
-}
-
-// the three scans for one ndim; the kernels' coordinates live in registers, so ndim is a template parameter
+// the three scans for one ndim (the union pass's workgroups are of unequal length: scan_grid's many short ones suit it)
 struct Scans {
     void (*degree)(int, const double *, double, int *);
     void (*unite)(int, const double *, double, int, const int *, int *);
     void (*border)(int, const double *, double, const int *, const int *, int, int *);
 };
-template <int ND> Scans scans_of() { return {nm_cluster_degree_kernel<ND>, nm_cluster_union_kernel<ND>, nm_cluster_border_kernel<ND>}; }
-const Scans SCANS[CL_MAXDIM] = {scans_of<1>(),  scans_of<2>(),  scans_of<3>(),  scans_of<4>(),  scans_of<5>(),  scans_of<6>(),
-                                scans_of<7>(),  scans_of<8>(),  scans_of<9>(),  scans_of<10>(), scans_of<11>(), scans_of<12>(),
-                                scans_of<13>(), scans_of<14>(), scans_of<15>(), scans_of<16>()};
+const auto SCANS = scan_table<CL_MAXDIM>([](auto nd) {
+    constexpr int ND = decltype(nd)::value;
+    return Scans{nm_cluster_degree_kernel<ND>, nm_cluster_union_kernel<ND>, nm_cluster_border_kernel<ND>};
+});
 } // namespace
 
 extern "C" {
 const char *nm_cluster_last_error(void) { return g_cluster_error.c_str(); }
 
-int nm_cluster_last_timing(double *ms)
-{
-    if (!ms) return refuse("nm_cluster_last_timing", "a needed pointer is null");
-    for (int i = 0; i < CL_T_COUNT; ++i) ms[i] = g_cluster_ms[i];
-    return NM_OK;
-}
+int nm_cluster_last_timing(double *ms) { return last_timing("nm_cluster_last_timing", g_cluster_ms, ms); }
 
 int nm_cluster_dbscan(int device, int64_t npoints, int ndim, const double *x, double eps, int min_pts, int32_t *label, int32_t *degree,
                       int32_t *nclusters)
@@ -86,10 +47,10 @@ int nm_cluster_dbscan(int device, int64_t npoints, int ndim, const double *x, do
     const int n = (int)npoints;
     const double e2 = eps * eps;                                // rounded once, here
     const Scans &k = SCANS[ndim - 1];
-    const dim3 grid = scan_grid(n, n), flat((unsigned)((n + CL_BLOCK - 1) / CL_BLOCK));
-    ClusterLaps laps;
+    const dim3 grid = scan_grid<ClScan>(n, n), flat((unsigned)((n + CL_BLOCK - 1) / CL_BLOCK));
+    Laps<CL_T_COUNT> laps;
     DevBuf<double> d_x;
-    DevBuf<int> d_parent, d_degree, d_root, d_cnum, d_blab, d_bad;    // d_root holds the roots, then the list of the points that are not core
+    DevBuf<int> d_parent, d_degree, d_root, d_cnum, d_blab;     // d_root holds the roots, then the list of the points that are not core
     laps.lap(CL_T_UPLOAD);
     STAGE_CHK(fn, d_x.upload(x, (size_t)n * ndim));
     STAGE_CHK(fn, d_parent.alloc(n));
@@ -98,13 +59,11 @@ int nm_cluster_dbscan(int device, int64_t npoints, int ndim, const double *x, do
     STAGE_CHK(fn, d_cnum.alloc(n));
     STAGE_CHK(fn, d_blab.alloc(n));
     STAGE_CHK(fn, hipMemset(d_blab, 0x7f, (size_t)n * sizeof(int)));        // CL_NONE
-    const int none = CL_NOBAD;
-    STAGE_CHK(fn, d_bad.upload(&none, 1));
-    hipLaunchKernelGGL(nm_cluster_screen_kernel, flat, dim3(CL_BLOCK), 0, 0, n, ndim, d_x, d_parent, d_degree, d_bad);
+    int first = -1;
+    STAGE_CHK(fn, scan_screen<ClScan>(n, ndim, d_x, first));
+    if (first >= 0) return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in point " + std::to_string(first));
+    hipLaunchKernelGGL(nm_cluster_init_kernel, flat, dim3(CL_BLOCK), 0, 0, n, d_parent, d_degree);
     STAGE_CHK(fn, hipGetLastError());
-    int first = CL_NOBAD;
-    STAGE_CHK(fn, d_bad.download(&first, 1));
-    if (first != CL_NOBAD) return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in point " + std::to_string(first));
     laps.lap(CL_T_UPLOAD);
     hipLaunchKernelGGL(k.degree, grid, dim3(CL_BLOCK), 0, 0, n, d_x, e2, d_degree);
     STAGE_CHK(fn, hipGetLastError());
@@ -126,12 +85,12 @@ int nm_cluster_dbscan(int device, int64_t npoints, int ndim, const double *x, do
     if (nopen) STAGE_CHK(fn, hipMemcpy(d_root, root.data(), (size_t)nopen * sizeof(int), hipMemcpyHostToDevice));
     laps.lap(CL_T_NUMBER);
     if (nopen && count) {                                       // without a cluster every point that is not core is noise
-        hipLaunchKernelGGL(k.border, scan_grid(nopen, n), dim3(CL_BLOCK), 0, 0, n, d_x, e2, d_cnum, d_root, nopen, d_blab);
+        hipLaunchKernelGGL(k.border, scan_grid<ClScan>(nopen, n), dim3(CL_BLOCK), 0, 0, n, d_x, e2, d_cnum, d_root, nopen, d_blab);
         STAGE_CHK(fn, hipGetLastError());
     }
     laps.lap(CL_T_BORDER);
     STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book();
+    laps.book(g_cluster_ms);
     STAGE_CHK(fn, d_blab.download(root.data(), n));             // the borders' numbers, in the buffer the roots have left
     STAGE_CHK(fn, d_degree.download(degree, n));
     for (int i = 0; i < n; ++i) label[i] = cnum[i] != CL_NONE ? cnum[i] : root[i] != CL_NONE ? root[i] : -1;

@@ -14,13 +14,6 @@ namespace {
 thread_local std::string g_pca_error;
 std::string &stage_error() { return g_pca_error; }
 
-bool pca_finite(const double *x, int64_t n)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(x[i])) return false;
-    return true;
-}
-
 // what both entry points ask of the samples
 int pca_check(const char *fn, int64_t nsamples, int nfeat)
 {
@@ -30,31 +23,9 @@ int pca_check(const char *fn, int64_t nsamples, int nfeat)
     return NM_OK;
 }
 
-// Where a call's device time went, for nm_pca_last_timing: lap(w) books the time since the lap before to w.
+// the slots of nm_pca_last_timing
 enum { PCA_T_UPLOAD, PCA_T_COLSUM, PCA_T_GRAM, PCA_T_PROJECT, PCA_T_COUNT };
 thread_local double g_pca_ms[PCA_T_COUNT];
-struct PcaLaps {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> what;
-    ~PcaLaps() { for (hipEvent_t e : ev) hipEventDestroy(e); }
-    void lap(int w)
-    {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        hipEventRecord(e, 0);
-        ev.push_back(e);
-        what.push_back(w);
-    }
-    // behind the call's last synchronisation
-    void book()
-    {
-        for (double &m : g_pca_ms) m = 0.0;
-        for (size_t i = 1; i < ev.size(); ++i) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) g_pca_ms[what[i]] += ms;
-        }
-    }
-};
 
 // x on the device, a batch of PCA_BATCH samples at a time: all of it where it fits half of the free memory (then a second pass
 // uploads nothing), else one batch's buffer that every pass fills again.  The batches, and so the arithmetic, are the same in
@@ -66,7 +37,7 @@ struct PcaSamples {
     bool resident = false, filled = false;
     DevBuf<float> buf;
     DevBuf<unsigned long long> bad;
-    PcaLaps laps;
+    Laps<PCA_T_COUNT> laps;
 
     int64_t batches() const { return (n + PCA_BATCH - 1) / PCA_BATCH; }
     int rest(int64_t b) const { return (int)((n - b * PCA_BATCH) < PCA_BATCH ? (n - b * PCA_BATCH) : PCA_BATCH); }
@@ -113,12 +84,7 @@ struct PcaSamples {
 extern "C" {
 const char *nm_pca_last_error(void) { return g_pca_error.c_str(); }
 
-int nm_pca_last_timing(double *ms)
-{
-    if (!ms) return refuse("nm_pca_last_timing", "a needed pointer is null");
-    for (int i = 0; i < PCA_T_COUNT; ++i) ms[i] = g_pca_ms[i];
-    return NM_OK;
-}
+int nm_pca_last_timing(double *ms) { return last_timing("nm_pca_last_timing", g_pca_ms, ms); }
 
 int nm_pca_moments(int device, int64_t nsamples, int nfeat, const float *x, double *mean, double *lo, double *hi, double *gram)
 {
@@ -172,7 +138,7 @@ int nm_pca_moments(int device, int64_t nsamples, int nfeat, const float *x, doub
     STAGE_CHK(fn, hipGetLastError());
     xs.laps.lap(PCA_T_GRAM);
     STAGE_CHK(fn, hipDeviceSynchronize());
-    xs.laps.book();
+    xs.laps.book(g_pca_ms);
     STAGE_CHK(fn, d_mean.download(mean, D));
     STAGE_CHK(fn, d_lo.download(lo, D));
     STAGE_CHK(fn, d_hi.download(hi, D));
@@ -187,7 +153,7 @@ int nm_pca_project(int device, int64_t nsamples, int nfeat, const float *x, cons
     if (const int rc = pca_check(fn, nsamples, nfeat)) return rc;
     if (ncomp < 1 || ncomp > PCA_MAXCOMP || ncomp > nfeat) return refuse(fn, "ncomp must lie in 1..64 and not exceed nfeat");
     if (!x || !mean || !inv_scale || !comp || !z) return refuse(fn, "a needed pointer is null");
-    if (!pca_finite(mean, nfeat) || !pca_finite(inv_scale, nfeat) || !pca_finite(comp, (int64_t)ncomp * nfeat))
+    if (first_not_finite(mean, nfeat) >= 0 || first_not_finite(inv_scale, nfeat) >= 0 || first_not_finite(comp, (int64_t)ncomp * nfeat) >= 0)
         return refuse(fn, "a value of mean, inv_scale or comp is not finite");
     if (const int rc = stage_device(fn, device)) return rc;
     PcaSamples xs;
@@ -209,7 +175,7 @@ int nm_pca_project(int device, int64_t nsamples, int nfeat, const float *x, cons
         xs.laps.lap(PCA_T_PROJECT);
     }
     if (const int rc = xs.screen(fn)) return rc;
-    xs.laps.book();
+    xs.laps.book(g_pca_ms);
     STAGE_CHK(fn, d_z.download(z, (size_t)nsamples * ncomp));
     if (norm2) STAGE_CHK(fn, d_norm.download(norm2, (size_t)nsamples));
     return NM_OK;

@@ -17,13 +17,6 @@ namespace {
 thread_local std::string g_rw_error;
 std::string &stage_error() { return g_rw_error; }
 
-bool rw_finite(const double *x, int64_t n)
-{
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(x[i])) return false;
-    return true;
-}
-
 // what both entry points ask of the states and the samples
 int rw_check(const char *fn, int nstates, const double *b, const double *c, const int64_t *count, const double *f, int64_t nsamples,
              const double *e, const double *v)
@@ -38,9 +31,9 @@ int rw_check(const char *fn, int nstates, const double *b, const double *c, cons
         sum += count[k];
     }
     if (sum != nsamples) return refuse(fn, "the counts do not sum to nsamples");
-    if (!rw_finite(b, nstates) || !rw_finite(c, nstates)) return refuse(fn, "a state's b or c is not finite");
-    if (!rw_finite(f, nstates)) return refuse(fn, "an f is not finite");
-    if (!rw_finite(e, nsamples) || !rw_finite(v, nsamples)) return refuse(fn, "a sample's e or v is not finite");
+    if (first_not_finite(b, nstates) >= 0 || first_not_finite(c, nstates) >= 0) return refuse(fn, "a state's b or c is not finite");
+    if (first_not_finite(f, nstates) >= 0) return refuse(fn, "an f is not finite");
+    if (first_not_finite(e, nsamples) >= 0 || first_not_finite(v, nsamples) >= 0) return refuse(fn, "a sample's e or v is not finite");
     return NM_OK;
 }
 
@@ -53,7 +46,7 @@ int rw_targets_check(const char *fn, int ntargets, const double *tb, const doubl
     if (ntargets < 1 || ntargets > 65536) return refuse(fn, "ntargets must lie in 1..65536");
     if (nobs < 0 || nobs > RW_MAXOBS) return refuse(fn, "nobs must lie in 0..8");
     if (!tb || !tc || !rest || (nobs > 0 && (!obs || !omean))) return refuse(fn, "a needed pointer is null");
-    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return refuse(fn, "a target's tb or tc is not finite");
+    if (first_not_finite(tb, ntargets) >= 0 || first_not_finite(tc, ntargets) >= 0) return refuse(fn, "a target's tb or tc is not finite");
     return NM_OK;
 }
 
@@ -299,12 +292,12 @@ int nm_reweight_histogram(int device, int nstates, const double *b, const double
     if (nq < 1 || nq > RW_MAXQ) return refuse(fn, "nq must lie in 1..8");
     if (nbins < 1 || nbins > RW_MAXBINS) return refuse(fn, "nbins must lie in 1..1024");
     if (!tb || !tc || !x || !edges || !hist) return refuse(fn, "a needed pointer is null");
-    if (!rw_finite(tb, ntargets) || !rw_finite(tc, ntargets)) return refuse(fn, "a target's tb or tc is not finite");
-    if (!rw_finite(edges, (int64_t)nq * (nbins + 1))) return refuse(fn, "an edge is not finite");
+    if (first_not_finite(tb, ntargets) >= 0 || first_not_finite(tc, ntargets) >= 0) return refuse(fn, "a target's tb or tc is not finite");
+    if (first_not_finite(edges, (int64_t)nq * (nbins + 1)) >= 0) return refuse(fn, "an edge is not finite");
     for (int q = 0; q < nq; ++q)
         for (int j = 0; j < nbins; ++j)
             if (!(edges[(size_t)q * (nbins + 1) + j] < edges[(size_t)q * (nbins + 1) + j + 1])) return refuse(fn, "the edges are not strictly increasing");
-    if (!rw_finite(x, (int64_t)nq * nsamples)) return refuse(fn, "an x is not finite");
+    if (first_not_finite(x, (int64_t)nq * nsamples) >= 0) return refuse(fn, "an x is not finite");
     if (const int rc = stage_device(fn, device)) return rc;
     RwProblem p;
     if (const int rc = p.setup(fn, nstates, b, c, count, f, nsamples, e, v)) return rc;

@@ -2,15 +2,15 @@
 // exists: the device holds x (N ndim doubles), the lists (N k ints and doubles), the symmetric lists (at most 2 N k entries) and a
 // few arrays of N.
 //
-// The skeleton (ts_scan) is nm_cluster.h's cl_scan: a workgroup of TS_BLOCK threads owns TS_ROWS = TS_RPT TS_BLOCK rows, thread t
-// keeps the coordinates of rows r0 + t and r0 + TS_BLOCK + t in registers, the columns are walked in tiles of TS_TILE points staged
-// in LDS as they lie in memory, every thread reads the same column at the same time (a broadcast read), and the grid is (row
-// blocks) x (column slices), slice s of S walking the tiles s, s + S, ...  A row past the end is point 0 again and its results are
-// dropped.  ts_d2 is the header's distance: with contraction off for this whole file (the pragma below) the template and the loop
-// over a run-time ndim round the same way, so a pair has the same bits in the select, the gather and the sort.
+// The skeleton is described in nm_scan.h, which holds its row loader, grid and screen; the shape here is TsScan: TS_ROWS = TS_RPT
+// TS_BLOCK rows of a workgroup in registers, tiles of TS_TILE columns in LDS, a grid of (row blocks) x (column slices).  The tile
+// loop (ts_scan) stands here, with what is this stage's own: the tiles that may hold the block's own rows are walked by a loop of
+// their own.  A row past the end is point 0 again and its results are dropped.
+// ts_d2 is the header's distance: with contraction off for this whole file (the pragma below) the template and the loop over a
+// run-time ndim round the same way, so a pair has the same bits in the select, the gather and the sort.
 //
 // Affinities.
-//   nm_tsne_screen_kernel  one thread per point: the first point with a value that is not finite (integer atomicMin).
+//   (nm_scan.h)            the screen for values that are not finite.
 //   nm_tsne_bit_kernel     between two counting scans, one thread per row: the bit tried last stays in key[i] where fewer than k
 //                          columns lay below the threshold; the next threshold is key[i] with the next bit; the count is cleared.
 //   nm_tsne_count_kernel   the scan: a row counts the columns j != i whose d2, read as an integer, is below thr[i] (a non-negative
@@ -57,6 +57,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nm_scan.h"
+
 #include <type_traits>
 
 #pragma clang fp contract(off)      // every product and sum below rounds on its own; a fused multiply-add is written as one
@@ -71,13 +73,13 @@ constexpr int TS_MAXDIM = 16;
 constexpr int TS_MAXCOMP = 3;
 constexpr int TS_MAXK = 4096;
 constexpr int64_t TS_MAXN = (int64_t)1 << 20;
-constexpr int TS_NOBAD = 0x7fffffff;
 constexpr int TS_GRID = 2048;                       // workgroups a scan aims at at least: 8 per compute unit
 constexpr int TS_SPAN = 256;                        // tiles a workgroup walks at most
 constexpr int TS_STEPS = 200;                       // evaluations of the search for beta
 constexpr int TS_ATT = 4;                           // doubles per row of the attractive sums: ncomp components, then sum P ln q
 constexpr int TS_PART = 4;                          // doubles per row and slice of the all-pairs pass: ncomp components, then Z's row
 
+using TsScan = ScanShape<TS_BLOCK, TS_RPT, TS_TILE, TS_GRID, TS_SPAN>;
 static_assert(TS_TILE <= TS_BLOCK && TS_ROWS % TS_TILE == 0, "the tiles of a block's own rows are whole tiles");
 
 template <int ND> __device__ __forceinline__ double ts_d2(const double *a, const double *b)
@@ -103,17 +105,8 @@ __device__ __forceinline__ double ts_d2n(const double *a, const double *b, int n
     return acc;
 }
 
-__global__ void __launch_bounds__(TS_BLOCK) nm_tsne_screen_kernel(int n, int ndim, const double *__restrict__ x, int *bad)
-{
-    const int i = blockIdx.x * TS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    bool ok = true;
-    for (int c = 0; c < ndim; ++c) ok = ok && isfinite(x[(size_t)i * ndim + c]);
-    if (!ok) atomicMin(bad, i);
-}
-
-// The skeleton.  pair(r, j, col) is called for row slot r and every column j of the walked tiles, col its coordinates; `own` is a type that says
-// whether the tile may hold the block's own rows.  Tiles t0, t0 + tstep, ... < tend.
+// The tile loop.  pair(r, j, col, own) is called for row slot r and every column j of the walked tiles, col its coordinates; `own` is a
+// type that says whether the tile may hold the block's own rows.  Tiles t0, t0 + tstep, ... < tend.
 template <int ND, class Pair>
 __device__ __forceinline__ void ts_scan(int n, const double *__restrict__ x, int t0, int tstep, int tend, Pair pair)
 {
@@ -140,21 +133,6 @@ __device__ __forceinline__ void ts_scan(int n, const double *__restrict__ x, int
     }
 }
 
-// the rows of thread tid of row block blockIdx.x: their indices, whether they exist, their coordinates (of point 0 where not)
-template <int ND>
-__device__ __forceinline__ void ts_rows(const double *__restrict__ x, int n, int (&idx)[TS_RPT], bool (&valid)[TS_RPT], double (&row)[TS_RPT][ND])
-{
-#pragma unroll
-    for (int r = 0; r < TS_RPT; ++r) {
-        const int i = blockIdx.x * TS_ROWS + r * TS_BLOCK + (int)threadIdx.x;
-        valid[r] = i < n;
-        idx[r] = valid[r] ? i : 0;
-        const double *src = x + (size_t)idx[r] * ND;
-#pragma unroll
-        for (int c = 0; c < ND; ++c) row[r][c] = src[c];
-    }
-}
-
 // ---- affinities: the radix select
 
 __global__ void __launch_bounds__(TS_BLOCK)
@@ -176,7 +154,7 @@ nm_tsne_count_kernel(int n, const double *__restrict__ x, const unsigned long lo
     bool valid[TS_RPT];
     double row[TS_RPT][ND];
     unsigned long long lim[TS_RPT];
-    ts_rows<ND>(x, n, idx, valid, row);
+    scan_rows<TsScan, ND>(x, nullptr, n, blockIdx.x, idx, valid, row);
 #pragma unroll
     for (int r = 0; r < TS_RPT; ++r) { lim[r] = valid[r] ? thr[idx[r]] : 0ull; cnt[r] = 0; }
     const int ntiles = (n + TS_TILE - 1) / TS_TILE;
@@ -198,7 +176,7 @@ nm_tsne_gather_kernel(int n, int k, const double *__restrict__ x, const unsigned
     bool valid[TS_RPT];
     double row[TS_RPT][ND];
     unsigned long long lim[TS_RPT];
-    ts_rows<ND>(x, n, idx, valid, row);
+    scan_rows<TsScan, ND>(x, nullptr, n, blockIdx.x, idx, valid, row);
 #pragma unroll
     for (int r = 0; r < TS_RPT; ++r) {
         lim[r] = key[idx[r]];
@@ -403,7 +381,7 @@ nm_tsne_pairs_kernel(int n, const double *__restrict__ y, double *__restrict__ p
     int idx[TS_RPT];
     bool valid[TS_RPT];
     double row[TS_RPT][NC], rep[TS_RPT][NC], zr[TS_RPT];
-    ts_rows<NC>(y, n, idx, valid, row);
+    scan_rows<TsScan, NC>(y, nullptr, n, blockIdx.x, idx, valid, row);
 #pragma unroll
     for (int r = 0; r < TS_RPT; ++r) {
         zr[r] = 0.0;

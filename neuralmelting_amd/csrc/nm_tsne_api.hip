@@ -14,59 +14,28 @@ namespace {
 thread_local std::string g_tsne_error;
 std::string &stage_error() { return g_tsne_error; }
 
-// Where a call's device time went, for nm_tsne_last_timing: lap(w) books the time since the lap before to w.
+// the slots of nm_tsne_last_timing
 enum { TS_T_SETUP, TS_T_A, TS_T_B, TS_T_C, TS_T_ALL, TS_T_COUNT };
 thread_local double g_tsne_ms[TS_T_COUNT];
-struct TsneLaps {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> what;
-    ~TsneLaps() { for (hipEvent_t e : ev) hipEventDestroy(e); }
-    void lap(int w)
-    {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        hipEventRecord(e, 0);
-        ev.push_back(e);
-        what.push_back(w);
-    }
-    // behind the call's last synchronisation
-    void book()
-    {
-        for (double &m : g_tsne_ms) m = 0.0;
-        for (size_t i = 1; i < ev.size(); ++i) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) g_tsne_ms[what[i]] += ms;
-        }
-    }
-};
 
-// the grid of a scan over n points: every row block, and as many column slices as bring it to TS_GRID workgroups and leave a
-// workgroup at most TS_SPAN tiles (at most one slice per tile).  A function of n alone: so is the order of every sum.
-dim3 scan_grid(int n)
-{
-    const int blocks = (n + TS_ROWS - 1) / TS_ROWS, tiles = (n + TS_TILE - 1) / TS_TILE;
-    int slices = (TS_GRID + blocks - 1) / blocks;
-    if (slices < (tiles + TS_SPAN - 1) / TS_SPAN) slices = (tiles + TS_SPAN - 1) / TS_SPAN;
-    if (slices > tiles) slices = tiles;
-    return dim3((unsigned)blocks, (unsigned)slices);
-}
-
-// the scans over x for one ndim; the kernels' coordinates live in registers, so ndim is a template parameter
+// the scans over x for one ndim
 struct Scans {
     void (*count)(int, const double *, const unsigned long long *, int *);
     void (*gather)(int, int, const double *, const unsigned long long *, const int *, int *);
 };
-template <int ND> Scans scans_of() { return {nm_tsne_count_kernel<ND>, nm_tsne_gather_kernel<ND>}; }
-const Scans SCANS[TS_MAXDIM] = {scans_of<1>(),  scans_of<2>(),  scans_of<3>(),  scans_of<4>(),  scans_of<5>(),  scans_of<6>(),
-                                scans_of<7>(),  scans_of<8>(),  scans_of<9>(),  scans_of<10>(), scans_of<11>(), scans_of<12>(),
-                                scans_of<13>(), scans_of<14>(), scans_of<15>(), scans_of<16>()};
+const auto SCANS = scan_table<TS_MAXDIM>([](auto nd) {
+    constexpr int ND = decltype(nd)::value;
+    return Scans{nm_tsne_count_kernel<ND>, nm_tsne_gather_kernel<ND>};
+});
 // and those over y for one ncomp
 struct Steps {
     void (*attract)(int, const long long *, const int *, const double *, const double *, double *);
     void (*pairs)(int, const double *, double *);
 };
-template <int NC> Steps steps_of() { return {nm_tsne_attract_kernel<NC>, nm_tsne_pairs_kernel<NC>}; }
-const Steps STEPS[TS_MAXCOMP] = {steps_of<1>(), steps_of<2>(), steps_of<3>()};
+const auto STEPS = scan_table<TS_MAXCOMP>([](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    return Steps{nm_tsne_attract_kernel<NC>, nm_tsne_pairs_kernel<NC>};
+});
 
 const char *check_lists(int64_t npoints, int k, int ncomp)
 {
@@ -132,26 +101,19 @@ int64_t symmetric_lists(int n, int k, const int32_t *nbr, const double *p, std::
     return -1;
 }
 
-// the first point of a [npoints][ncomp] that holds a value that is not finite, or -1
-int64_t first_not_finite(const double *a, int n, int ncomp)
-{
-    for (size_t e = 0; e < (size_t)n * ncomp; ++e)
-        if (!std::isfinite(a[e])) return (int64_t)(e / ncomp);
-    return -1;
-}
-
 // nm_tsne_gradient (niter == 0: one evaluation, grad, kl and z are written) and nm_tsne_descend behind their checks
 int run_steps(const char *fn, int device, int n, int k, const int32_t *nbr, const double *p, int ncomp, double *y, double *update,
               double *gains, int niter, double exaggeration, double momentum, double rate, double *grad, double *kl, double *z, double *trace)
 {
     const bool descend = niter > 0;
     const int steps = descend ? niter : 1;
-    int64_t bad = first_not_finite(y, n, ncomp);
-    if (bad >= 0) return fail(NM_ERR_ARG, std::string(fn) + ": y is not finite in point " + std::to_string(bad));
-    if (descend && (bad = first_not_finite(update, n, ncomp)) >= 0)
-        return fail(NM_ERR_ARG, std::string(fn) + ": update is not finite in point " + std::to_string(bad));
-    if (descend && (bad = first_not_finite(gains, n, ncomp)) >= 0)
-        return fail(NM_ERR_ARG, std::string(fn) + ": gains is not finite in point " + std::to_string(bad));
+    const size_t ne = (size_t)n * ncomp;
+    int64_t bad = first_not_finite(y, ne);
+    if (bad >= 0) return fail(NM_ERR_ARG, std::string(fn) + ": y is not finite in point " + std::to_string(bad / ncomp));
+    if (descend && (bad = first_not_finite(update, ne)) >= 0)
+        return fail(NM_ERR_ARG, std::string(fn) + ": update is not finite in point " + std::to_string(bad / ncomp));
+    if (descend && (bad = first_not_finite(gains, ne)) >= 0)
+        return fail(NM_ERR_ARG, std::string(fn) + ": gains is not finite in point " + std::to_string(bad / ncomp));
     std::vector<long long> rowptr;
     std::vector<int> col;
     std::vector<double> val;
@@ -164,11 +126,10 @@ int run_steps(const char *fn, int device, int n, int k, const int32_t *nbr, cons
                                               " holds an entry that is no other point, or a p that is not finite or negative");
     if (const int rc = stage_device(fn, device)) return rc;
     const Steps &kern = STEPS[ncomp - 1];
-    const dim3 grid = scan_grid(n), block(TS_BLOCK);
+    const dim3 grid = scan_grid<TsScan>(n, n), block(TS_BLOCK);
     const int slices = (int)grid.y, rblocks = (n + TS_BLOCK - 1) / TS_BLOCK, eblocks = (n * ncomp + TS_BLOCK - 1) / TS_BLOCK;
     const dim3 waves((unsigned)((n + TS_BLOCK / 64 - 1) / (TS_BLOCK / 64)));
-    const size_t ne = (size_t)n * ncomp;
-    TsneLaps laps;
+    Laps<TS_T_COUNT> laps;
     DevBuf<long long> d_rowptr;
     DevBuf<int> d_col;
     DevBuf<double> d_val, d_y, d_update, d_gains, d_grad, d_pconst, d_att, d_part, d_rep, d_bsum, d_tot, d_bnorm, d_trace;
@@ -208,7 +169,7 @@ int run_steps(const char *fn, int device, int n, int k, const int32_t *nbr, cons
     }
     laps.lap(TS_T_ALL);
     STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book();
+    laps.book(g_tsne_ms);
     g_tsne_ms[TS_T_ALL] += g_tsne_ms[TS_T_A] + g_tsne_ms[TS_T_B] + g_tsne_ms[TS_T_C];
     if (descend) {
         std::vector<double> ny(ne), nu(ne), ng(ne);             // all of them arrive before one is written
@@ -233,12 +194,7 @@ int run_steps(const char *fn, int device, int n, int k, const int32_t *nbr, cons
 extern "C" {
 const char *nm_tsne_last_error(void) { return g_tsne_error.c_str(); }
 
-int nm_tsne_last_timing(double *ms)
-{
-    if (!ms) return refuse("nm_tsne_last_timing", "a needed pointer is null");
-    for (int i = 0; i < TS_T_COUNT; ++i) ms[i] = g_tsne_ms[i];
-    return NM_OK;
-}
+int nm_tsne_last_timing(double *ms) { return last_timing("nm_tsne_last_timing", g_tsne_ms, ms); }
 
 int nm_tsne_affinities(int device, int64_t npoints, int ndim, const double *x, double perplexity, int k, int32_t *nbr, double *p,
                        double *beta)
@@ -252,12 +208,12 @@ int nm_tsne_affinities(int device, int64_t npoints, int ndim, const double *x, d
     if (const int rc = stage_device(fn, device)) return rc;
     const int n = (int)npoints;
     const Scans &kern = SCANS[ndim - 1];
-    const dim3 grid = scan_grid(n), block(TS_BLOCK), flat((unsigned)((n + TS_BLOCK - 1) / TS_BLOCK));
+    const dim3 grid = scan_grid<TsScan>(n, n), block(TS_BLOCK), flat((unsigned)((n + TS_BLOCK - 1) / TS_BLOCK));
     const size_t nk = (size_t)n * k;
-    TsneLaps laps;
+    Laps<TS_T_COUNT> laps;
     DevBuf<double> d_x, d_p, d_beta;
     DevBuf<unsigned long long> d_key, d_thr;
-    DevBuf<int> d_count, d_nbr, d_bad;
+    DevBuf<int> d_count, d_nbr;
     laps.lap(TS_T_SETUP);
     STAGE_CHK(fn, d_x.upload(x, (size_t)n * ndim));
     STAGE_CHK(fn, d_key.alloc(n));
@@ -266,13 +222,9 @@ int nm_tsne_affinities(int device, int64_t npoints, int ndim, const double *x, d
     STAGE_CHK(fn, d_nbr.alloc_zeroed(nk));
     STAGE_CHK(fn, d_p.alloc(nk));
     STAGE_CHK(fn, d_beta.alloc(n));
-    const int none = TS_NOBAD;
-    STAGE_CHK(fn, d_bad.upload(&none, 1));
-    hipLaunchKernelGGL(nm_tsne_screen_kernel, flat, block, 0, 0, n, ndim, d_x, d_bad);
-    STAGE_CHK(fn, hipGetLastError());
-    int first = TS_NOBAD;
-    STAGE_CHK(fn, d_bad.download(&first, 1));
-    if (first != TS_NOBAD) return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in point " + std::to_string(first));
+    int first = -1;
+    STAGE_CHK(fn, scan_screen<TsScan>(n, ndim, d_x, first));
+    if (first >= 0) return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in point " + std::to_string(first));
     laps.lap(TS_T_SETUP);
     // bits 62 .. 0 of the k-th smallest d2 of every row (the sign is 0), then the count strictly below it
     for (int b = 62; b >= -1; --b) {
@@ -288,7 +240,7 @@ int nm_tsne_affinities(int device, int64_t npoints, int ndim, const double *x, d
     STAGE_CHK(fn, hipGetLastError());
     laps.lap(TS_T_C);
     STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book();
+    laps.book(g_tsne_ms);
     // into buffers of the library first: a failure on the way leaves the caller's untouched
     std::vector<int> hn(nk);
     std::vector<double> hp(nk);

@@ -33,8 +33,8 @@ import os
 import numpy as np
 
 from . import _lib as B
+from ._stage import prefix as run_prefix
 
-LAT = {'Ti': 'bcc', 'Al': 'fcc', 'Ni': 'fcc', 'Cu': 'fcc', 'LJ': 'fcc'}
 CNA_MODES = {'fixed': 0, 'adaptive': 1}                     # NM_CNA_FIXED, NM_CNA_ADAPTIVE (include/nm_distr.h)
 
 
@@ -431,7 +431,7 @@ def entropy_functional(g, r, nrho):
 def main(argv=None):
     a = parse_args(argv)
     dev = _device()
-    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, a.element.lower(), LAT[a.element])
+    prefix = run_prefix(a.name, a.element)
     P = np.load(prefix + '.virial.trgt.npy')
     T = np.load(prefix + '.temp.trgt.npy')
     pn, tn = P.size, T.size

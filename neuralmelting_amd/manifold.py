@@ -12,13 +12,12 @@ standard deviation of component 0 and multiplied by 1e-4 (init='pca'), XI steps 
 the NI steps at exaggeration 1 with momentum 0.8.  There is no random number anywhere: two runs write the same bytes.
 """
 import argparse
-import os
 import sys
 
 import numpy as np
 
 from . import _lib as B
-from .parse import LAT
+from . import _stage as S
 
 MAX_POINTS, MAX_DIM, MAX_COMP, MAX_K = 2 ** 20, 16, 3, 4096     # include/nm_tsne.h
 
@@ -134,48 +133,36 @@ def embed(x, nc, perplexity, exaggeration, learning_rate, niter, nexag, device=0
 
 def spread(values, shape, skip, stride):
     """values (PN, TN, kept, ...) of the embedded samples skip, skip + stride, ... in a float64 array of `shape` filled with NaN"""
-    out = np.full(shape, np.nan)
-    out[:, :, skip::stride] = values
-    return out
+    return S.spread(np.asarray(values, dtype=np.float64), shape, skip, stride, np.nan)
 
 
 def main(argv=None):
     a = parse_args(argv)
     el, ft, nc = a.element, a.feature, a.components
-    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, el.lower(), LAT[el])
-    paths = {key: prefix + '.%s.npy' % key for key in ('virial.trgt', 'temp.trgt', 'pe', ft + '.pcz')}
-    for path in paths.values():                                      # every input is checked before anything is written
-        if not os.path.isfile(path):
-            raise SystemExit('manifold: %s is missing' % path)
-    P, T, pe = np.load(paths['virial.trgt']), np.load(paths['temp.trgt']), np.load(paths['pe'], mmap_mode='r')
-    pcz = np.load(paths[ft + '.pcz'], mmap_mode='r')
-    pn, tn = P.size, T.size
-    if pe.ndim != 3 or pe.shape[:2] != (pn, tn):
-        raise SystemExit('manifold: %s has shape %s and does not fit the %d x %d grid' % (paths['pe'], pe.shape, pn, tn))
-    if pcz.ndim != 4 or pcz.shape[:3] != pe.shape:
-        raise SystemExit('manifold: %s has shape %s, not %s followed by the components' % (paths[ft + '.pcz'], pcz.shape, pe.shape))
-    sn, ld = pcz.shape[2:]
+    prefix = S.prefix(a.name, el)
+    P, T, pe, pcz, path = S.grid_inputs('manifold', prefix, ft + '.pcz', 'the components')
+    pn, tn, sn, ld = pcz.shape
     nd = ld if a.dimensions is None else a.dimensions
     if nd > ld or nd > MAX_DIM:
-        raise SystemExit('manifold: -nd %d is more than the %d components of %s or than %d' % (nd, ld, paths[ft + '.pcz'], MAX_DIM))
+        raise SystemExit('manifold: -nd %d is more than the %d components of %s or than %d' % (nd, ld, path, MAX_DIM))
     if nc > nd:
         raise SystemExit('manifold: -nc %d is more than the %d input components' % (nc, nd))
-    kept = len(range(a.skip, sn, a.stride))
+    kept, xk = S.kept(pcz, a.skip, a.stride)
     n = pn * tn * kept
     if not 3 <= n <= MAX_POINTS:
-        raise SystemExit('manifold: -sk %d -sd %d leave %d samples of %s, not 3..%d' % (a.skip, a.stride, n, paths[ft + '.pcz'], MAX_POINTS))
+        raise SystemExit('manifold: -sk %d -sd %d leave %d samples of %s, not 3..%d' % (a.skip, a.stride, n, path, MAX_POINTS))
     px = float(kept) if a.perplexity is None else a.perplexity
     k = neighbours(n, px)
     if not (1.0 < px < k <= MAX_K):
         raise SystemExit('manifold: the perplexity %g wants %d neighbours of %d samples: need 1 < PX < k <= %d' % (px, k, n, MAX_K))
-    x = np.ascontiguousarray(pcz[:, :, a.skip::a.stride, :nd], dtype=np.float64).reshape(n, nd)
+    x = np.ascontiguousarray(xk[..., :nd], dtype=np.float64).reshape(n, nd)
     if a.verbose:
         print('embedding %d of %d samples of %s from %d to %d components, perplexity %g, %d neighbours, %d steps (%d at exaggeration %g)' % (
             n, pn * tn * sn, ft, nd, nc, px, k, a.iterations, a.exaggerated, a.exaggeration))
     try:
         y, beta, trace = embed(x, nc, px, a.exaggeration, a.learning_rate, a.iterations, a.exaggerated, a.device)
     except (RuntimeError, ValueError) as err:
-        raise SystemExit('manifold: %s: %s' % (paths[ft + '.pcz'], err))
+        raise SystemExit('manifold: %s: %s' % (path, err))
     np.save(prefix + '.%s.mfy.npy' % ft, spread(y.reshape(pn, tn, kept, nc), pe.shape + (nc,), a.skip, a.stride))
     np.save(prefix + '.%s.mfb.npy' % ft, spread(beta.reshape(pn, tn, kept), pe.shape, a.skip, a.stride))
     np.save(prefix + '.%s.mft.npy' % ft, trace)

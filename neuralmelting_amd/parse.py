@@ -15,8 +15,8 @@ import os
 import numpy as np
 
 from . import _lib as B
+from ._stage import prefix as run_prefix
 
-LAT = {'Ti': 'bcc', 'Al': 'fcc', 'Ni': 'fcc', 'Cu': 'fcc', 'LJ': 'fcc'}
 # column order of the .thrm rows (remcmc:208) = suffixes of the files written (parse:69-85)
 COLUMNS = ('temp', 'pe', 'ke', 'virial', 'vol', 'dx', 'dv', 'dt', 'ntp', 'nap', 'ntv', 'nav', 'nth', 'nah', 'ap', 'av', 'ah')
 
@@ -64,7 +64,7 @@ def read_traj(path, nthreads=0):
 def main(argv=None):
     args = parse_args(argv)
     el = args.element
-    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (args.name, el.lower(), LAT[el])
+    prefix = run_prefix(args.name, el)
     p = np.load(prefix + '.virial.trgt.npy')
     t = np.load(prefix + '.temp.trgt.npy')
     pn, tn = p.size, t.size

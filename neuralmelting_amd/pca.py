@@ -17,13 +17,12 @@ deviation (sklearn's StandardScaler), 1 for a constant feature.  minmax: s_j = m
 Each component's sign is fixed so that its mean over the hottest temperature column is not below that over the coldest one.
 """
 import argparse
-import os
 import sys
 
 import numpy as np
 
 from . import _lib as B
-from .parse import LAT
+from . import _stage as S
 
 SCALERS = ('none', 'global', 'standard', 'minmax')
 MAX_FEAT, MAX_COMP = 4096, 64       # include/nm_pca.h: nfeat and ncomp
@@ -134,29 +133,19 @@ def orient(comp, hot, cold):
 def main(argv=None):
     a = parse_args(argv)
     el, ft, ld = a.element, a.feature, a.latent_dimension
-    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, el.lower(), LAT[el])
-    paths = {key: prefix + '.%s.npy' % key for key in ('virial.trgt', 'temp.trgt', 'pe', ft)}
-    for path in paths.values():                                      # every input is checked before anything is written
-        if not os.path.isfile(path):
-            raise SystemExit('pca: %s is missing' % path)
-    P, T, pe = np.load(paths['virial.trgt']), np.load(paths['temp.trgt']), np.load(paths['pe'], mmap_mode='r')
-    feat = np.load(paths[ft], mmap_mode='r')
-    pn, tn = P.size, T.size
-    if pe.ndim != 3 or pe.shape[:2] != (pn, tn):
-        raise SystemExit('pca: %s has shape %s and does not fit the %d x %d grid' % (paths['pe'], pe.shape, pn, tn))
-    if feat.ndim < 4 or feat.shape[:3] != pe.shape:
-        raise SystemExit('pca: %s has shape %s, not %s followed by the feature axes' % (paths[ft], feat.shape, pe.shape))
-    sn, d = feat.shape[2], int(np.prod(feat.shape[3:]))
+    prefix = S.prefix(a.name, el)
+    P, T, pe, feat, path = S.grid_inputs('pca', prefix, ft, 'the feature axes', more_axes=True)
+    (pn, tn, sn), d = pe.shape, int(np.prod(feat.shape[3:]))
     if not 1 <= d <= MAX_FEAT:
-        raise SystemExit('pca: %s has %d features per sample, more than %d' % (paths[ft], d, MAX_FEAT))
+        raise SystemExit('pca: %s has %d features per sample, more than %d' % (path, d, MAX_FEAT))
     if ld > d:
-        raise SystemExit('pca: -ld %d is more than the %d features of %s' % (ld, d, paths[ft]))
-    kept = len(range(a.skip, sn, a.stride))
-    if pn * tn * kept < 2:
-        raise SystemExit('pca: -sk %d -sd %d leave %d samples of %s, fewer than two' % (a.skip, a.stride, pn * tn * kept, paths[ft]))
+        raise SystemExit('pca: -ld %d is more than the %d features of %s' % (ld, d, path))
     x = np.ascontiguousarray(feat, dtype=np.float32).reshape(pn, tn, sn, d)
-    xfit = x if (a.skip, a.stride) == (0, 1) else np.ascontiguousarray(x[:, :, a.skip::a.stride])
+    kept, xfit = S.kept(x, a.skip, a.stride)
     n = pn * tn * kept
+    if n < 2:
+        raise SystemExit('pca: -sk %d -sd %d leave %d samples of %s, fewer than two' % (a.skip, a.stride, n, path))
+    xfit = np.ascontiguousarray(xfit)                                # (x itself where no sample is left out)
     if a.verbose:
         print('pca of %s: %d features, fit on %d of %d samples, scaler %s' % (ft, d, n, pn * tn * sn, a.scaler))
     try:
@@ -164,7 +153,7 @@ def main(argv=None):
         s, comp, pcv = fit(lo, hi, gram, n, a.scaler, ld)
         z, norm2 = project(x.reshape(-1, d), mean, 1.0 / s, comp, a.device)
     except (RuntimeError, ValueError) as err:
-        raise SystemExit('pca: %s: %s' % (paths[ft], err))
+        raise SystemExit('pca: %s: %s' % (path, err))
     z = z.reshape(pn, tn, sn, ld)
     sign = orient(comp, z[:, int(np.argmax(T))].mean(axis=(0, 1)), z[:, int(np.argmin(T))].mean(axis=(0, 1)))
     comp, z = comp * sign[:, None], z * sign

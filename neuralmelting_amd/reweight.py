@@ -31,7 +31,7 @@ import sys
 import numpy as np
 
 from . import _lib as B
-from .parse import LAT
+from ._stage import prefix as run_prefix
 from .remcmc import init_constant
 
 MAX_OBS = 8
@@ -350,7 +350,7 @@ def load_observables(prefix, names, shape, flag='-ob'):
 def main(argv=None):
     a = parse_args(argv)
     el = a.element
-    prefix = os.getcwd() + '/' + '%s.%s.%s.lammps' % (a.name, el.lower(), LAT[el])
+    prefix = run_prefix(a.name, el)
     P = np.load(prefix + '.virial.trgt.npy')
     T = np.load(prefix + '.temp.trgt.npy')
     pe = np.load(prefix + '.pe.npy')
