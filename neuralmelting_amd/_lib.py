@@ -43,6 +43,11 @@ PCA_SYMBOLS = ('nm_pca_moments', 'nm_pca_project', 'nm_pca_last_timing', 'nm_pca
 CLUSTER_SYMBOLS = ('nm_cluster_dbscan', 'nm_cluster_last_timing', 'nm_cluster_last_error')
 # include/nm_tsne.h
 TSNE_SYMBOLS = ('nm_tsne_affinities', 'nm_tsne_gradient', 'nm_tsne_descend', 'nm_tsne_last_timing', 'nm_tsne_last_error')
+# include/nm_vae.h
+VAE_SYMBOLS = ('nm_vae_nparams', 'nm_vae_layout', 'nm_vae_conv', 'nm_vae_conv_grad', 'nm_vae_dense', 'nm_vae_dense_grad', 'nm_vae_create',
+               'nm_vae_destroy', 'nm_vae_set_params', 'nm_vae_get_params', 'nm_vae_data', 'nm_vae_eval', 'nm_vae_grad', 'nm_vae_epoch',
+               'nm_vae_last_timing', 'nm_vae_last_error')
+NM_VAE_ACT_NONE, NM_VAE_ACT_RELU, NM_VAE_ACT_TANH, NM_VAE_NTENSORS = 0, 1, 2, 26
 
 
 class NMConfig(C.Structure):
@@ -185,5 +190,26 @@ def load():
     L.nm_tsne_last_timing.restype = C.c_int
     L.nm_tsne_last_timing.argtypes = [c_double_p]
     L.nm_tsne_last_error.restype = C.c_char_p
+    i, f = C.c_int, c_float_p
+    L.nm_vae_nparams.restype = C.c_int64
+    L.nm_vae_nparams.argtypes = [i, i]
+    L.nm_vae_layout.argtypes = [i, i, c_int64_p]
+    L.nm_vae_conv.argtypes = [i, i, i, i, i, i, i, i, f, f, f, f]
+    L.nm_vae_conv_grad.argtypes = [i, i, i, i, i, i, i, i, f, f, f, f, f, f, f]
+    L.nm_vae_dense.argtypes = [i, i, i, i, i, f, f, f, f]
+    L.nm_vae_dense_grad.argtypes = [i, i, i, i, i, f, f, f, f, f, f, f]
+    L.nm_vae_create.argtypes = [i, i, i, C.POINTER(vp)]
+    L.nm_vae_destroy.argtypes = [vp]
+    L.nm_vae_set_params.argtypes = [vp, f]
+    L.nm_vae_get_params.argtypes = [vp, f]
+    L.nm_vae_data.argtypes = [vp, C.c_int64, f]
+    L.nm_vae_eval.argtypes = [vp, C.c_int64, c_int64_p, f, f, f, f, f, f]
+    L.nm_vae_grad.argtypes = [vp, C.c_int64, c_int64_p, f, f, c_double_p]
+    L.nm_vae_epoch.argtypes = [vp, C.c_int64, c_int64_p, f, i, C.c_double, c_double_p]
+    L.nm_vae_last_timing.argtypes = [c_double_p]
+    for s in VAE_SYMBOLS:
+        if s not in ('nm_vae_nparams', 'nm_vae_last_error'):
+            getattr(L, s).restype = C.c_int
+    L.nm_vae_last_error.restype = C.c_char_p
     _lib = L
     return L
