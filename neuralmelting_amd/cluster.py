@@ -61,11 +61,7 @@ def dbscan(x, eps, min_pts, device=0):
         raise ValueError('x wants the shape (N, ND)')
     n, nd = x.shape
     label, degree, ncl = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.zeros(1, dtype=np.int32)
-    L = B.load()
-    rc = L.nm_cluster_dbscan(device, n, nd, x.ctypes.data_as(B.c_double_p), float(eps), int(min_pts), label.ctypes.data_as(B.c_int32_p),
-                             degree.ctypes.data_as(B.c_int32_p), ncl.ctypes.data_as(B.c_int32_p))
-    if rc != B.NM_OK:
-        raise RuntimeError('nm_cluster_dbscan failed (%d): %s' % (rc, L.nm_cluster_last_error().decode()))
+    B.call('nm_cluster_dbscan', device, n, nd, x, float(eps), int(min_pts), label, degree, ncl)
     return label, degree, int(ncl[0])
 
 

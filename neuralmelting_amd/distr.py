@@ -27,7 +27,6 @@ entropy of each sample (.s2.npy).
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -le -lt -5.0 -ef
 """
 import argparse
-import ctypes as C
 import os
 
 import numpy as np
@@ -245,15 +244,8 @@ def calculate_spatial(natoms, box, sbins, cbins):
 
 
 def _frames(pos, box):
-    """pos and box as the entry points of include/nm_distr.h take them: contiguous float32, and their pointers"""
-    pos = np.ascontiguousarray(pos, dtype=np.float32)
-    box = np.ascontiguousarray(box, dtype=np.float32)
-    return pos, box, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p)
-
-
-def _check(L, name, rc):
-    if rc != 0:
-        raise RuntimeError('%s failed (%d): %s' % (name, rc, L.nm_distr_last_error().decode()))
+    """pos and box as the entry points of include/nm_distr.h take them: contiguous float32"""
+    return np.ascontiguousarray(pos, dtype=np.float32), np.ascontiguousarray(box, dtype=np.float32)
 
 
 def _device():
@@ -264,8 +256,7 @@ def _device():
 def histograms(natoms, box, pos, r, rv, device=0, want_rdf=True, want_cdf=True):
     """raw counts of calculate_rdf / calculate_cdf for all samples, divided by natoms as the reference does:
     rdf[ns][sbins] float32, cdf[ns][cb][cb][cb] float32"""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     r = np.ascontiguousarray(r, dtype=np.float64)
     ve = np.ascontiguousarray(rv[0], dtype=np.float64)
@@ -274,9 +265,7 @@ def histograms(natoms, box, pos, r, rv, device=0, want_rdf=True, want_cdf=True):
     sb, cb = len(r), len(ve) - 1
     rdf = np.zeros((ns, sb), dtype=np.float32) if want_rdf else None
     cdf = np.zeros((ns, cb, cb, cb), dtype=np.float32) if want_cdf else None
-    fp = lambda a: None if a is None else a.ctypes.data_as(B.c_float_p)
-    _check(L, 'nm_distr_histograms', L.nm_distr_histograms(device, ns, n, ppos, pbox, sb, r.ctypes.data_as(B.c_double_p), cb,
-                                                           ve.ctypes.data_as(B.c_double_p), fp(rdf), fp(cdf)))
+    B.call('nm_distr_histograms', device, ns, n, pos, box, sb, r, cb, ve, rdf, cdf)
     na = np.asarray(natoms).reshape(-1)
     if want_rdf:
         rdf = rdf / na[:, None]                           # rd/natoms (distr:135): float32 / uint16 -> float32
@@ -290,13 +279,11 @@ def angles(natoms, box, pos, a, r_lo, r_hi, device=0):
     shell r_lo < d <= r_hi: the raw counts of nm_distr_angles (each unordered neighbour pair of a centre once, unsigned 64-bit,
     adf[:, 0] = 0) divided by natoms in float64 and cast to float32 [ns][sbins], the dtype of the other histogram files.  The
     exact integers are available through the C-ABI."""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     ce = np.ascontiguousarray(np.cos(np.asarray(a, dtype=np.float64)))   # bins are compared in cosine space
     adf = np.zeros((ns, len(ce)), dtype=np.uint64)
-    _check(L, 'nm_distr_angles', L.nm_distr_angles(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), len(ce),
-                                                   ce.ctypes.data_as(B.c_double_p), adf.ctypes.data_as(B.c_uint64_p)))
+    B.call('nm_distr_angles', device, ns, n, pos, box, float(r_lo), float(r_hi), len(ce), ce, adf)
     na = np.asarray(natoms).reshape(-1).astype(np.float64)
     return (adf.astype(np.float64) / na[:, None]).astype(np.float32)
 
@@ -319,15 +306,13 @@ def sfactor(natoms, box, pos, qmax, device=0):
     """static structure factor of all samples on the shells of sfactor_shells(qmax): the shell mean (nm_distr_sfactor's shell
     sum divided by the number of vectors of the shell) and the shell maximum, both float64 [ns][nshell].  natoms is accepted
     for symmetry with histograms() and angles(); the atom count is pos.shape[1]."""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     shells, mult = sfactor_shells(qmax)
     nsh = int(qmax) * int(qmax) + 1
     ssum = np.zeros((ns, nsh), dtype=np.float64)
     smax = np.zeros((ns, nsh), dtype=np.float64)
-    _check(L, 'nm_distr_sfactor', L.nm_distr_sfactor(device, ns, n, ppos, pbox, int(qmax), ssum.ctypes.data_as(B.c_double_p),
-                                                     smax.ctypes.data_as(B.c_double_p)))
+    B.call('nm_distr_sfactor', device, ns, n, pos, box, int(qmax), ssum, smax)
     return ssum[:, shells] / mult[None, :], smax[:, shells]
 
 
@@ -337,8 +322,7 @@ def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
     [ns][nl] (all bonds of the frame) and nb int32 [ns][natoms] (neighbours per atom).  nm_distr_bondorder returns the squares; the
     roots sqrt(max(x, 0)) are taken here in float64.  natoms is accepted for symmetry with histograms(); the atom count is
     pos.shape[1]."""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     ls = np.ascontiguousarray(ls, dtype=np.int32).reshape(-1)
     nl = len(ls)
@@ -346,9 +330,7 @@ def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
     b2 = np.zeros((ns, n, nl), dtype=np.float64)
     g2 = np.zeros((ns, nl), dtype=np.float64)
     nb = np.zeros((ns, n), dtype=np.int32)
-    _check(L, 'nm_distr_bondorder', L.nm_distr_bondorder(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), nl, ls.ctypes.data_as(B.c_int_p),
-                                                         q2.ctypes.data_as(B.c_double_p), b2.ctypes.data_as(B.c_double_p),
-                                                         g2.ctypes.data_as(B.c_double_p), nb.ctypes.data_as(B.c_int32_p)))
+    B.call('nm_distr_bondorder', device, ns, n, pos, box, float(r_lo), float(r_hi), nl, ls, q2, b2, g2, nb)
     root = lambda x: np.sqrt(np.maximum(x, 0.0))
     return root(q2), root(b2), root(g2), nb
 
@@ -359,17 +341,15 @@ def solid(natoms, box, pos, l, r_lo, r_hi, s_min, n_min, device=0):
     (connections per atom), label int32 [ns][natoms] (the smallest atom index of the atom's cluster, -1 if the atom is not solid-like),
     nsolid, nclus and largest int32 [ns] (solid-like atoms, clusters, size of the largest cluster).  natoms is accepted for symmetry
     with histograms(); the atom count is pos.shape[1]."""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     nconn = np.zeros((ns, n), dtype=np.int32)
     label = np.zeros((ns, n), dtype=np.int32)
     nsolid = np.zeros(ns, dtype=np.int32)
     nclus = np.zeros(ns, dtype=np.int32)
     largest = np.zeros(ns, dtype=np.int32)
-    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
-    _check(L, 'nm_distr_solid', L.nm_distr_solid(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), int(l), float(s_min), int(n_min),
-                                                 ip(nconn), ip(label), ip(nsolid), ip(nclus), ip(largest)))
+    B.call('nm_distr_solid', device, ns, n, pos, box, float(r_lo), float(r_hi), int(l), float(s_min), int(n_min), nconn, label, nsolid,
+           nclus, largest)
     return nconn, label, nsolid, nclus, largest
 
 
@@ -379,16 +359,13 @@ def cna(natoms, box, pos, r_lo, r_hi, mode, device=0):
     3 bcc, 4 ico), sig int32 [ns][natoms][8] (the atom's entries per signature column 421 422 444 666 555 544 433 other), ntype int32
     [ns][5] and nsig int32 [ns][8] (their sums over the atoms).  natoms is accepted for symmetry with histograms(); the atom count is
     pos.shape[1]."""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     typ = np.zeros((ns, n), dtype=np.int32)
     sig = np.zeros((ns, n, 8), dtype=np.int32)
     ntype = np.zeros((ns, 5), dtype=np.int32)
     nsig = np.zeros((ns, 8), dtype=np.int32)
-    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
-    _check(L, 'nm_distr_cna', L.nm_distr_cna(device, ns, n, ppos, pbox, float(r_lo), float(r_hi), int(CNA_MODES.get(mode, mode)),
-                                             ip(typ), ip(sig), ip(ntype), ip(nsig)))
+    B.call('nm_distr_cna', device, ns, n, pos, box, float(r_lo), float(r_hi), int(CNA_MODES.get(mode, mode)), typ, sig, ntype, nsig)
     return typ, sig, ntype, nsig
 
 
@@ -397,8 +374,7 @@ def local_entropy(natoms, box, pos, r_m, sigma, nbins, r_avg, s_cut=None, device
     width sigma, averaged over the entries within r_avg: s and sbar float64 [ns][natoms], nnb int32 [ns][natoms] (entries within r_m),
     smean and sbarmean float64 [ns] and nlow int32 [ns], the atoms with sbar < s_cut (none for s_cut None).  natoms is accepted for
     symmetry with histograms(); the atom count is pos.shape[1]."""
-    L = B.load()
-    pos, box, ppos, pbox = _frames(pos, box)
+    pos, box = _frames(pos, box)
     ns, n = pos.shape[0], pos.shape[1]
     s = np.zeros((ns, n), dtype=np.float64)
     sbar = np.zeros((ns, n), dtype=np.float64)
@@ -406,11 +382,8 @@ def local_entropy(natoms, box, pos, r_m, sigma, nbins, r_avg, s_cut=None, device
     smean = np.zeros(ns, dtype=np.float64)
     sbarmean = np.zeros(ns, dtype=np.float64)
     nlow = np.zeros(ns, dtype=np.int32)
-    dp = lambda x: x.ctypes.data_as(B.c_double_p)
-    ip = lambda x: x.ctypes.data_as(B.c_int32_p)
-    _check(L, 'nm_distr_entropy', L.nm_distr_entropy(device, ns, n, ppos, pbox, float(r_m), float(sigma), int(nbins), float(r_avg),
-                                                     -np.inf if s_cut is None else float(s_cut), dp(s), dp(sbar), ip(nnb), dp(smean),
-                                                     dp(sbarmean), ip(nlow)))
+    B.call('nm_distr_entropy', device, ns, n, pos, box, float(r_m), float(sigma), int(nbins), float(r_avg),
+           -np.inf if s_cut is None else float(s_cut), s, sbar, nnb, smean, sbarmean, nlow)
     return s, sbar, nnb, smean, sbarmean, nlow
 
 

@@ -14,10 +14,6 @@ class NMError(RuntimeError):
         self.code = code
 
 
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(B.c_double_p)
-
-
 class Engine:
     """batched replica engine on one MI355X"""
 
@@ -41,8 +37,7 @@ class Engine:
         cfg.ppos, cfg.pvol = float(ppos), float(pvol)
         if nslots is not None:  # an arbitrary global slot range (a pressure row split across GPUs)
             cfg.slot0, cfg.nslots = int(slot0 or 0), int(nslots)
-        cfg.P = self._P.ctypes.data_as(B.c_float_p)
-        cfg.T = self._T.ctypes.data_as(B.c_float_p)
+        cfg.P, cfg.T = B.c_float_p.from_param(self._P), B.c_float_p.from_param(self._T)     # (a structure's field takes no array)
         h = C.c_void_p()
         rc = self.lib.nm_create(C.byref(cfg), C.byref(h))
         if rc != B.NM_OK:
@@ -88,7 +83,7 @@ class Engine:
     def constants(self):
         """(et, pf) per local slot: init_constants, remcmc:114-141"""
         et, pf = np.empty(self.nslots), np.empty(self.nslots)
-        self._chk(self.lib.nm_get_const(self.h, _dp(et), _dp(pf)))
+        self._chk(self.lib.nm_get_const(self.h, et, pf))
         return et, pf
 
     def set_state(self, x=None, v=None, box=None, dxdvdt=None, k0=0, nk=None):
@@ -103,7 +98,7 @@ class Engine:
                 raise ValueError('bad array size %d, expected %s' % (a.size, shape))
             return a
         x, v, box, dxdvdt = prep(x, (nk, n3)), prep(v, (nk, n3)), prep(box, (nk,)), prep(dxdvdt, (nk, 3))
-        self._settled(self.lib.nm_set_state(self.h, k0, nk, _dp(x), _dp(v), _dp(box), _dp(dxdvdt)))
+        self._settled(self.lib.nm_set_state(self.h, k0, nk, x, v, box, dxdvdt))
 
     def get_state(self, k0=0, nk=None, velocities=True):
         """x, v, box, (dx, dv, dt) of slots [k0, k0+nk); velocities=False skips the copy of v (returned as None)"""
@@ -112,7 +107,7 @@ class Engine:
         x = np.empty((nk, n3))
         v = np.empty((nk, n3)) if velocities else None
         box, d = np.empty(nk), np.empty((nk, 3))
-        self._settled(self.lib.nm_get_state(self.h, k0, nk, _dp(x), _dp(v) if velocities else None, _dp(box), _dp(d)))
+        self._settled(self.lib.nm_get_state(self.h, k0, nk, x, v, box, d))
         return x, v, box, d
 
     def get_slots(self, slots, velocities=True):
@@ -122,8 +117,7 @@ class Engine:
         x = np.empty((nk, n3))
         v = np.empty((nk, n3)) if velocities else None
         box, d, th = np.empty(nk), np.empty((nk, 3)), np.empty((nk, 5))
-        self._settled(self.lib.nm_get_slots(self.h, nk, sl.ctypes.data_as(B.c_int_p), _dp(x), _dp(v) if velocities else None, _dp(box),
-                                            _dp(d), _dp(th)))
+        self._settled(self.lib.nm_get_slots(self.h, nk, sl, x, v, box, d, th))
         return x, v, box, d, th
 
     def set_slots(self, slots, x=None, v=None, box=None, dxdvdt=None, th=None):
@@ -139,7 +133,7 @@ class Engine:
                 raise ValueError('bad array size %d, expected %d' % (a.size, size))
             return a
         x, v, box, dxdvdt, th = prep(x, nk * n3), prep(v, nk * n3), prep(box, nk), prep(dxdvdt, 3 * nk), prep(th, 5 * nk)
-        self._settled(self.lib.nm_set_slots(self.h, nk, sl.ctypes.data_as(B.c_int_p), _dp(x), _dp(v), _dp(box), _dp(dxdvdt), _dp(th)))
+        self._settled(self.lib.nm_set_slots(self.h, nk, sl, x, v, box, dxdvdt, th))
 
     def init_lattice(self, dx=0.03125, dv=0.03125, interpolate=False):
         """init_samples (remcmc:394-456) through the C-ABI: the states lattice.init_states builds, without the Python front end"""
@@ -151,7 +145,7 @@ class Engine:
         th = np.ascontiguousarray(th, dtype=np.float64)
         if th.size != 5 * nk:
             raise ValueError('bad thermo array')
-        self._settled(self.lib.nm_set_thermo(self.h, k0, nk, _dp(th)))
+        self._settled(self.lib.nm_set_thermo(self.h, k0, nk, th))
 
     def set_step(self, step):
         self._chk(self.lib.nm_set_step(self.h, int(step)))
@@ -188,7 +182,7 @@ class Engine:
     def thermo(self):
         """rows[nslots][17] in the .thrm column order (remcmc:208)"""
         rows = np.empty((self.nslots, B.NM_THERMO_COLS))
-        self._settled(self.lib.nm_get_thermo(self.h, _dp(rows)))
+        self._settled(self.lib.nm_get_thermo(self.h, rows))
         return rows
 
     def snapshot(self):
@@ -201,7 +195,7 @@ class Engine:
         rows = np.empty((self.nslots, B.NM_THERMO_COLS))
         x = np.empty((self.nslots, 3 * self.natoms)) if positions else None
         box = np.empty(self.nslots)
-        self._settled(self.lib.nm_snapshot_fetch(self.h, _dp(rows), _dp(x) if positions else None, _dp(box)))  # (a record's fetch may settle)
+        self._settled(self.lib.nm_snapshot_fetch(self.h, rows, x, box))  # (a record's fetch may settle)
         return rows, x, box
 
     def adapt(self):
@@ -228,7 +222,7 @@ class Engine:
     def status(self):
         """per-slot status bits (include/nm.h NM_ST_*) of the last block; 0 = fine"""
         st = np.empty(self.nslots, dtype=np.int32)
-        self._settled(self.lib.nm_get_status(self.h, st.ctypes.data_as(B.c_int_p)))
+        self._settled(self.lib.nm_get_status(self.h, st))
         return st
 
     # -- measurement
@@ -246,14 +240,14 @@ class Engine:
         blocks handed over inside one XCD, blocks, HMC moves, longest list row built, list slots per atom, HMC moves whose trajectory
         started without a hand-over inside the cluster) since the last reset"""
         s = np.empty((self.nslots, B.NM_STATS_COLS))
-        self._settled(self.lib.nm_stats_get(self.h, _dp(s), int(reset)))
+        self._settled(self.lib.nm_stats_get(self.h, s, int(reset)))
         return s
 
     # -- test-only
     def eval(self, forces=True):
         U, W = np.empty(self.nslots), np.empty(self.nslots)
         f = np.empty((self.nslots, 3 * self.natoms)) if forces else None
-        self._chk(self.lib.nm_eval(self.h, _dp(U), _dp(W), _dp(f)))
+        self._chk(self.lib.nm_eval(self.h, U, W, f))
         return U, W, f
 
     def set_rng_tape(self, tapes):
@@ -266,36 +260,36 @@ class Engine:
         flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64) for t in tapes]))
         if flat.size == 0:
             flat = np.zeros(1)
-        self._chk(self.lib.nm_set_rng_tape(self.h, _dp(flat), off.ctypes.data_as(B.c_int_p)))
+        self._chk(self.lib.nm_set_rng_tape(self.h, flat, off))
 
     def set_exchange_tape(self, tape):
         if tape is None:
             self._chk(self.lib.nm_set_exchange_tape(self.h, None, 0))
             return
         t = np.ascontiguousarray(tape, dtype=np.float64)
-        self._chk(self.lib.nm_set_exchange_tape(self.h, _dp(t), len(t)))
+        self._chk(self.lib.nm_set_exchange_tape(self.h, t, len(t)))
 
     def set_trace(self, on):
         self._chk(self.lib.nm_set_trace(self.h, int(bool(on))))
 
     def trace(self, mod):
         tr = np.empty((self.nslots, mod, B.NM_TRACE_COLS))
-        self._settled(self.lib.nm_get_trace(self.h, _dp(tr), int(mod)))
+        self._settled(self.lib.nm_get_trace(self.h, tr, int(mod)))
         return tr
 
     def set_counters(self, count=None, ratio=None):
         """counters [nslots][6] and float32 ratios [nslots][3] as a block would have left them (input of adapt)"""
         cn = None if count is None else np.ascontiguousarray(count, dtype=np.float64)
         ra = None if ratio is None else np.ascontiguousarray(ratio, dtype=np.float32)
-        self._settled(self.lib.nm_set_counters(self.h, _dp(cn), None if ra is None else ra.ctypes.data_as(B.c_float_p)))
+        self._settled(self.lib.nm_set_counters(self.h, cn, ra))
 
     def perm(self):
         p = np.empty(self.nslots, dtype=np.int32)
-        self._settled(self.lib.nm_get_perm(self.h, p.ctypes.data_as(B.c_int_p)))
+        self._settled(self.lib.nm_get_perm(self.h, p))
         return p
 
     def exchange_crit(self):
         n = self.nrows * self.nt * (self.nt - 1) // 2
         c = np.empty(max(n, 1))
-        self._settled(self.lib.nm_get_exchange_crit(self.h, _dp(c), n))
+        self._settled(self.lib.nm_get_exchange_crit(self.h, c, n))
         return c[:n]

@@ -50,11 +50,6 @@ def parse_args(argv=None):
     return a
 
 
-def _check(rc, fn):
-    if rc != B.NM_OK:
-        raise RuntimeError('%s failed (%d): %s' % (fn, rc, B.load().nm_tsne_last_error().decode()))
-
-
 def affinities(x, perplexity, k, device=0):
     """nm_tsne_affinities of x (N, ND): (nbr (N, k) int32, p (N, k), beta (N,))"""
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -62,8 +57,7 @@ def affinities(x, perplexity, k, device=0):
         raise ValueError('x wants the shape (N, ND)')
     n, nd = x.shape
     nbr, p, beta = np.empty((n, max(k, 0)), dtype=np.int32), np.empty((n, max(k, 0))), np.empty(n)
-    _check(B.load().nm_tsne_affinities(device, n, nd, x.ctypes.data_as(B.c_double_p), float(perplexity), int(k), nbr.ctypes.data_as(B.c_int32_p),
-                                       p.ctypes.data_as(B.c_double_p), beta.ctypes.data_as(B.c_double_p)), 'nm_tsne_affinities')
+    B.call('nm_tsne_affinities', device, n, nd, x, float(perplexity), int(k), nbr, p, beta)
     return nbr, p, beta
 
 
@@ -81,9 +75,7 @@ def gradient(nbr, p, y, exaggeration=1.0, device=0):
     if y.ndim != 2 or y.shape[0] != nbr.shape[0]:
         raise ValueError('y wants the shape (N, NC)')
     grad, kl, z = np.empty_like(y), np.empty(1), np.empty(1)
-    _check(B.load().nm_tsne_gradient(device, nbr.shape[0], nbr.shape[1], nbr.ctypes.data_as(B.c_int32_p), p.ctypes.data_as(B.c_double_p),
-                                     y.shape[1], y.ctypes.data_as(B.c_double_p), float(exaggeration), grad.ctypes.data_as(B.c_double_p),
-                                     kl.ctypes.data_as(B.c_double_p), z.ctypes.data_as(B.c_double_p)), 'nm_tsne_gradient')
+    B.call('nm_tsne_gradient', device, nbr.shape[0], nbr.shape[1], nbr, p, y.shape[1], y, float(exaggeration), grad, kl, z)
     return grad, float(kl[0]), float(z[0])
 
 
@@ -95,10 +87,8 @@ def descend(nbr, p, y, update, gains, niter, exaggeration, momentum, learning_ra
                 and a.shape == y.shape and a.shape[0] == nbr.shape[0]):
             raise ValueError('y, update and gains want one shape (N, NC), float64, C-contiguous and writeable')
     trace = np.empty((max(niter, 0), 3))
-    _check(B.load().nm_tsne_descend(device, nbr.shape[0], nbr.shape[1], nbr.ctypes.data_as(B.c_int32_p), p.ctypes.data_as(B.c_double_p),
-                                    y.shape[1], y.ctypes.data_as(B.c_double_p), update.ctypes.data_as(B.c_double_p),
-                                    gains.ctypes.data_as(B.c_double_p), int(niter), float(exaggeration), float(momentum), float(learning_rate),
-                                    trace.ctypes.data_as(B.c_double_p)), 'nm_tsne_descend')
+    B.call('nm_tsne_descend', device, nbr.shape[0], nbr.shape[1], nbr, p, y.shape[1], y, update, gains, int(niter), float(exaggeration),
+           float(momentum), float(learning_rate), trace)
     return trace
 
 

@@ -30,34 +30,27 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
-def _fail(what):
-    raise RuntimeError('%s: %s' % (what, B.load().nm_parse_last_error().decode()))
+def _call(name, *args):
+    B.call(name, *args, form='{0}: {2}')
 
 
 def read_thrm(path, nthreads=0):
     """np.loadtxt(path, dtype=np.float32) for a .thrm file: (rows, 17) float32"""
-    L = B.load()
     n = C.c_long(0)
-    if L.nm_parse_thrm(os.fsencode(path), None, 0, C.byref(n), nthreads) != 0:
-        _fail('nm_parse_thrm')
+    _call('nm_parse_thrm', os.fsencode(path), None, 0, C.byref(n), nthreads)
     rows = np.empty((n.value, 17), np.float32)
-    if L.nm_parse_thrm(os.fsencode(path), rows.ctypes.data_as(B.c_float_p), n.value, C.byref(n), nthreads) != 0:
-        _fail('nm_parse_thrm')
+    _call('nm_parse_thrm', os.fsencode(path), rows, n.value, C.byref(n), nthreads)
     return rows
 
 
 def read_traj(path, nthreads=0):
     """the three flat arrays of parse:88-94: natoms (frames,) uint16, box (frames,) float32, x (coordinate lines, 3) float32"""
-    L = B.load()
     nf, nr = C.c_long(0), C.c_long(0)
-    if L.nm_parse_traj(os.fsencode(path), None, None, None, 0, 0, C.byref(nf), C.byref(nr), nthreads) != 0:
-        _fail('nm_parse_traj')
+    _call('nm_parse_traj', os.fsencode(path), None, None, None, 0, 0, C.byref(nf), C.byref(nr), nthreads)
     natoms = np.empty(nf.value, np.uint16)
     box = np.empty(nf.value, np.float32)
     x = np.empty((nr.value, 3), np.float32)
-    if L.nm_parse_traj(os.fsencode(path), natoms.ctypes.data_as(C.POINTER(C.c_uint16)), box.ctypes.data_as(B.c_float_p),
-                       x.ctypes.data_as(B.c_float_p), nf.value, nr.value, C.byref(nf), C.byref(nr), nthreads) != 0:
-        _fail('nm_parse_traj')
+    _call('nm_parse_traj', os.fsencode(path), natoms, box, x, nf.value, nr.value, C.byref(nf), C.byref(nr), nthreads)
     return natoms, box, x
 
 

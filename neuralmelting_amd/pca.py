@@ -55,14 +55,6 @@ def _f64(x):
     return np.ascontiguousarray(x, dtype=np.float64)
 
 
-def _dp(a):
-    return a.ctypes.data_as(B.c_double_p)
-
-
-def _fail(fn, rc):
-    raise RuntimeError('%s failed (%d): %s' % (fn, rc, B.load().nm_pca_last_error().decode()))
-
-
 def moments(x, device=0):
     """nm_pca_moments of x (N, D) float32: (mean (D,), lo (D,), hi (D,), gram (D, D))"""
     x = np.ascontiguousarray(x, dtype=np.float32)
@@ -70,9 +62,7 @@ def moments(x, device=0):
         raise ValueError('x wants the shape (N, D)')
     n, d = x.shape
     mean, lo, hi, gram = np.empty(d), np.empty(d), np.empty(d), np.empty((d, d))
-    rc = B.load().nm_pca_moments(device, n, d, x.ctypes.data_as(B.c_float_p), _dp(mean), _dp(lo), _dp(hi), _dp(gram))
-    if rc != B.NM_OK:
-        _fail('nm_pca_moments', rc)
+    B.call('nm_pca_moments', device, n, d, x, mean, lo, hi, gram)
     return mean, lo, hi, gram
 
 
@@ -84,10 +74,7 @@ def project(x, mean, inv_scale, comp, device=0):
         raise ValueError('x wants the shape (N, D), mean and inv_scale (D,), comp (C, D)')
     n, d = x.shape
     z, norm2 = np.empty((n, comp.shape[0])), np.empty(n)
-    rc = B.load().nm_pca_project(device, n, d, x.ctypes.data_as(B.c_float_p), _dp(mean), _dp(inv_scale), comp.shape[0], _dp(comp), _dp(z),
-                                 _dp(norm2))
-    if rc != B.NM_OK:
-        _fail('nm_pca_project', rc)
+    B.call('nm_pca_project', device, n, d, x, mean, inv_scale, comp.shape[0], comp, z, norm2)
     return z, norm2
 
 

@@ -191,7 +191,7 @@ class Run:
         from . import _lib as B
         r = np.ascontiguousarray(row, dtype=np.float64)
         buf = C.create_string_buffer(17 * 14 + 8)
-        n = B.load().nm_format_thrm(r.ctypes.data_as(B.c_double_p), buf, len(buf))
+        n = B.load().nm_format_thrm(r, buf, len(buf))
         if n < 0:
             raise RuntimeError('nm_format_thrm failed')
         return buf.raw[:n].decode()
@@ -203,7 +203,7 @@ class Run:
         from . import _lib as B
         xx = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         buf = C.create_string_buffer(64 + 42 * int(natoms))
-        n = B.load().nm_format_traj(int(natoms), float(box), xx.ctypes.data_as(B.c_double_p), buf, len(buf))
+        n = B.load().nm_format_traj(int(natoms), float(box), xx, buf, len(buf))
         if n < 0:
             raise RuntimeError('nm_format_traj failed')
         return buf.raw[:n].decode()
@@ -226,8 +226,7 @@ class Run:
         rows = np.ascontiguousarray(rows, dtype=np.float64)
         x = np.ascontiguousarray(x, dtype=np.float64)
         box = np.ascontiguousarray(box, dtype=np.float64)
-        rc = B.load().nm_append_outputs(self.nloc, self.natoms, thrm, traj, rows.ctypes.data_as(B.c_double_p),
-                                        x.ctypes.data_as(B.c_double_p), box.ctypes.data_as(B.c_double_p), 0)
+        rc = B.load().nm_append_outputs(self.nloc, self.natoms, thrm, traj, rows, x, box, 0)
         if rc != 0:
             raise IOError('nm_append_outputs failed (%d)' % rc)
 

@@ -99,14 +99,6 @@ def _f64(x):
     return np.ascontiguousarray(x, dtype=np.float64)
 
 
-def _dp(a):
-    return a.ctypes.data_as(B.c_double_p)
-
-
-def _fail(fn, rc):
-    raise RuntimeError('%s failed (%d): %s' % (fn, rc, B.load().nm_reweight_last_error().decode()))
-
-
 def states(P, T, el):
     """(b, c) of the K = PN x TN states, k = p * TN + t: 1/et and pf of remcmc.init_constant"""
     et, pf = np.array([init_constant(P, T, el, i, j) for i in range(len(P)) for j in range(len(T))], dtype=np.float64).T
@@ -122,10 +114,7 @@ def solve(b, c, count, e, v, f0=None, tol=1e-9, max_iter=20000, device=0, want_l
         raise ValueError('b, c, count, f0 want one length and e, v another')
     logd = np.empty(e.size) if want_logd else None
     iters, delta = C.c_int(0), C.c_double(0.0)
-    rc = B.load().nm_reweight_solve(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), e.size, _dp(e), _dp(v), tol,
-                                    max_iter, _dp(f), _dp(logd) if want_logd else None, C.byref(iters), C.byref(delta))
-    if rc != B.NM_OK:
-        _fail('nm_reweight_solve', rc)
+    B.call('nm_reweight_solve', device, b.size, b, c, count, e.size, e, v, tol, max_iter, f, logd, C.byref(iters), C.byref(delta))
     return (f, iters.value, delta.value, logd) if want_logd else (f, iters.value, delta.value)
 
 
@@ -140,11 +129,8 @@ def expect(b, c, count, f, e, v, tb, tc, obs=None, device=0):
         raise ValueError('b, c, count, f want one length, e, v and every observable another, tb, tc a third')
     nt = tb.size
     out = dict(tf=np.empty(nt), ess=np.empty(nt), mean=np.empty((nt, 2)), cov=np.empty((nt, 3)), omean=np.empty((nt, nobs)))
-    rc = B.load().nm_reweight_expect(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), _dp(f), e.size, _dp(e), _dp(v),
-                                     nt, _dp(tb), _dp(tc), nobs, _dp(obs) if nobs else None, _dp(out['tf']), _dp(out['ess']),
-                                     _dp(out['mean']), _dp(out['cov']), _dp(out['omean']) if nobs else None)
-    if rc != B.NM_OK:
-        _fail('nm_reweight_expect', rc)
+    B.call('nm_reweight_expect', device, b.size, b, c, count, f, e.size, e, v, nt, tb, tc, nobs, obs, out['tf'], out['ess'], out['mean'],
+           out['cov'], out['omean'] if nobs else None)
     return out
 
 
@@ -159,10 +145,7 @@ def histogram(b, c, count, f, e, v, tb, tc, x, edges, device=0):
         raise ValueError('b, c, count, f want one length, e, v another, tb, tc a third; x (nq, N) and edges (nq, nbins + 1)')
     nt, nq, nbins = tb.size, x.shape[0], edges.shape[1] - 1
     hist, outside = np.empty((nt, nq, nbins)), np.empty((nt, nq, 2))
-    rc = B.load().nm_reweight_histogram(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), _dp(f), e.size, _dp(e), _dp(v),
-                                        nt, _dp(tb), _dp(tc), nq, _dp(x), nbins, _dp(edges), _dp(hist), _dp(outside))
-    if rc != B.NM_OK:
-        _fail('nm_reweight_histogram', rc)
+    B.call('nm_reweight_histogram', device, b.size, b, c, count, f, e.size, e, v, nt, tb, tc, nq, x, nbins, edges, hist, outside)
     return hist, outside
 
 
@@ -176,11 +159,7 @@ def boot_solve(b, c, count, e, v, f, mult, tol=1e-9, max_iter=20000, device=0):
     nrep = mult.shape[0]
     fr, delta = np.empty((nrep, b.size)), np.empty(nrep)
     iters, status = np.empty(nrep, dtype=np.intc), np.empty(nrep, dtype=np.intc)
-    rc = B.load().nm_reweight_boot_solve(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), e.size, _dp(e), _dp(v), _dp(f),
-                                         nrep, mult.ctypes.data_as(C.POINTER(C.c_uint16)), tol, max_iter, _dp(fr),
-                                         iters.ctypes.data_as(B.c_int_p), _dp(delta), status.ctypes.data_as(B.c_int_p))
-    if rc != B.NM_OK:
-        _fail('nm_reweight_boot_solve', rc)
+    B.call('nm_reweight_boot_solve', device, b.size, b, c, count, e.size, e, v, f, nrep, mult, tol, max_iter, fr, iters, delta, status)
     return fr, iters, delta, status
 
 
@@ -198,12 +177,8 @@ def boot_expect(b, c, count, f, e, v, mult, fr, tb, tc, obs=None, device=0):
     nrep, nt = mult.shape[0], tb.size
     out = dict(tf=np.empty((nrep, nt)), ess=np.empty((nrep, nt)), mean=np.empty((nrep, nt, 2)), cov=np.empty((nrep, nt, 3)),
                omean=np.empty((nrep, nt, nobs)))
-    rc = B.load().nm_reweight_boot_expect(device, b.size, _dp(b), _dp(c), count.ctypes.data_as(B.c_int64_p), _dp(f), e.size, _dp(e), _dp(v),
-                                          nrep, mult.ctypes.data_as(C.POINTER(C.c_uint16)), _dp(fr), nt, _dp(tb), _dp(tc), nobs,
-                                          _dp(obs) if nobs else None, _dp(out['tf']), _dp(out['ess']), _dp(out['mean']), _dp(out['cov']),
-                                          _dp(out['omean']) if nobs else None)
-    if rc != B.NM_OK:
-        _fail('nm_reweight_boot_expect', rc)
+    B.call('nm_reweight_boot_expect', device, b.size, b, c, count, f, e.size, e, v, nrep, mult, fr, nt, tb, tc, nobs, obs, out['tf'],
+           out['ess'], out['mean'], out['cov'], out['omean'] if nobs else None)
     return out
 
 

@@ -63,29 +63,18 @@ def parse_args(argv=None):
     return a
 
 
-def _fp(a):
-    return None if a is None else a.ctypes.data_as(B.c_float_p)
-
-
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
 
 
-def _check(fn, rc):
-    if rc != B.NM_OK:
-        raise RuntimeError('%s failed (%d): %s' % (fn, rc, B.load().nm_vae_last_error().decode()))
-
-
 def nparams(side, latent):
-    n = B.load().nm_vae_nparams(side, latent)
-    _check('nm_vae_nparams', min(n, 0))
-    return n
+    return B.call('nm_vae_nparams', side, latent)
 
 
 def layout(side, latent):
     """the 27 offsets of the parameter tensors in the flat vector (include/nm_vae.h)"""
     off = np.zeros(B.NM_VAE_NTENSORS + 1, dtype=np.int64)
-    _check('nm_vae_layout', B.load().nm_vae_layout(side, latent, off.ctypes.data_as(B.c_int64_p)))
+    B.call('nm_vae_layout', side, latent, off)
     return off
 
 
@@ -118,7 +107,7 @@ class Model:
 
     def __init__(self, side, latent, device=0):
         self.L, self.side, self.latent, self.ctx = B.load(), side, latent, C.c_void_p()
-        _check('nm_vae_create', self.L.nm_vae_create(device, side, latent, C.byref(self.ctx)))
+        B.call('nm_vae_create', device, side, latent, C.byref(self.ctx))
         self.nparams = nparams(side, latent)
 
     def close(self):
@@ -136,16 +125,16 @@ class Model:
         theta = _f32(theta)
         if theta.shape != (self.nparams,):
             raise ValueError('theta wants the shape (%d,)' % self.nparams)
-        _check('nm_vae_set_params', self.L.nm_vae_set_params(self.ctx, _fp(theta)))
+        B.call('nm_vae_set_params', self.ctx, theta)
 
     def get_params(self):
         theta = np.empty(self.nparams, dtype=np.float32)
-        _check('nm_vae_get_params', self.L.nm_vae_get_params(self.ctx, _fp(theta)))
+        B.call('nm_vae_get_params', self.ctx, theta)
         return theta
 
     def data(self, x):
         x = _f32(x).reshape(-1, self.side ** 3)
-        _check('nm_vae_data', self.L.nm_vae_data(self.ctx, x.shape[0], _fp(x)))
+        B.call('nm_vae_data', self.ctx, x.shape[0], x)
 
     def _idx(self, idx, eps):
         idx, eps = np.ascontiguousarray(idx, dtype=np.int64), _f32(eps)
@@ -160,26 +149,26 @@ class Model:
         mu, lv = np.empty((n, self.latent), dtype=np.float32), np.empty((n, self.latent), dtype=np.float32)
         rec, kl = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.float32)
         y = np.empty((n, self.side ** 3), dtype=np.float32) if recon else None
-        _check('nm_vae_eval', self.L.nm_vae_eval(self.ctx, n, idx.ctypes.data_as(B.c_int64_p), _fp(eps), _fp(mu), _fp(lv), _fp(y), _fp(rec), _fp(kl)))
+        B.call('nm_vae_eval', self.ctx, n, idx, eps, mu, lv, y, rec, kl)
         return (mu, lv, rec, kl, y) if recon else (mu, lv, rec, kl)
 
     def grad(self, idx, eps=None):
         """(the gradient of the batch's mean loss, (mean rec, mean kl))"""
         idx, eps = self._idx(idx, eps)
         g, loss = np.empty(self.nparams, dtype=np.float32), np.empty(2)
-        _check('nm_vae_grad', self.L.nm_vae_grad(self.ctx, idx.size, idx.ctypes.data_as(B.c_int64_p), _fp(eps), _fp(g), loss.ctypes.data_as(B.c_double_p)))
+        B.call('nm_vae_grad', self.ctx, idx.size, idx, eps, g, loss)
         return g, loss
 
     def epoch(self, idx, eps, batch, lr):
         """Nadam steps over the consecutive batches of idx: (mean rec, mean kl)"""
         idx, eps = self._idx(idx, eps)
         loss = np.empty(2)
-        _check('nm_vae_epoch', self.L.nm_vae_epoch(self.ctx, idx.size, idx.ctypes.data_as(B.c_int64_p), _fp(eps), batch, lr, loss.ctypes.data_as(B.c_double_p)))
+        B.call('nm_vae_epoch', self.ctx, idx.size, idx, eps, batch, lr, loss)
         return loss
 
     def timing(self):
         ms = np.empty(4)
-        _check('nm_vae_last_timing', self.L.nm_vae_last_timing(ms.ctypes.data_as(B.c_double_p)))
+        B.call('nm_vae_last_timing', ms)
         return ms
 
 
