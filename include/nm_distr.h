@@ -104,6 +104,32 @@ int nm_distr_sfactor(int device, int ns, int natoms, const float *pos, const flo
 int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
                        const int *ls, double *q2, double *qbar2, double *Q2, int32_t *nnb);
 
+/* Steinhardt's third-order invariants: per atom w_l, its neighbour-averaged form and the global W_l of a frame, all returned as the
+ * UNNORMALISED cubic forms, beside the squares of nm_distr_bondorder.  Definition (the build's own), for sample s and centre atom c:
+ *   entries, directions, moments   q_lm(c), qbar_lm(c) and the frame's Q_lm exactly those of nm_distr_bondorder;
+ *   T_l(a)      for a vector a_m, m = -l..l, with a_-m = (-1)^m conj(a_m):
+ *               T_l(a) = (4 pi / (2l+1))^(3/2) Re sum_{m1+m2+m3=0} (l l l; m1 m2 m3) a_m1 a_m2 a_m3, with Wigner's 3j symbol; the sum is real
+ *               in exact arithmetic, so only the real part is formed;
+ *   w3[s][c][i]    = T_l(q_lm(c)) for l = ls[i];   wbar3[s][c][i] = T_l(qbar_lm(c));   W3[s][i] = T_l(Q_lm); each 0 where the vector is 0;
+ *   q2, qbar2, Q2, nnb   as in nm_distr_bondorder, and bit for bit what that function returns for the same arguments.
+ * Steinhardt's w_l (hat) = w3 / q2^(3/2) lies in [-1, 1]: sum_{m1,m2} (3j)^2 = 1, so by Cauchy-Schwarz |T_l(a)| <= (4 pi / (2l+1) sum |a_m|^2)^(3/2).
+ * The ratio is left to the caller, for the reason the squares are returned: it is ill-conditioned wherever q_l vanishes (l = 2 on a
+ * cubic lattice, l = 4 on the icosahedron), while w3 itself is a polynomial in the moments with an absolute error bound.
+ * Even l only: for odd 3l the symbol changes its sign under the exchange of two columns, so T_l vanishes identically.
+ * Error bound, u = 2^-53 (derivation: csrc/nm_distr_w.h): with x the matching square (q2, qbar2, Q2), e the matching e_q, e_qbar, e_Q of
+ * nm_distr_bondorder and n_l the number of symbols that do not vanish (19, 61, 127, 205, 331, 469 for l = 2, 4, .., 12), each returned
+ * cubic form is off by at most 3 e x + 3 e^2 sqrt(x) + e^3 + (n_l + 12) u (sqrt(x) + e)^3: below 5e-13 up to M = 529 neighbours.
+ * The result is the same bit for bit on every call: the terms in a fixed order (m1 ascending, then m2, 64 at a time through a fixed
+ * tree), float64 sums in a fixed order, no floating-point atomics.
+ * ls[nl]: 1 to 6 strictly increasing EVEN values in 2..12.  pos[ns][natoms][3], box[ns] float32; w3, wbar3, q2, qbar2 [ns][natoms][nl]
+ * and W3, Q2 [ns][nl] float64, nnb[ns][natoms] int32.  Any output may be NULL (it is then not written), but not all seven.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_bondorder_w:".  NM_ERR_ARG, checked
+ * before the device is looked for and with the outputs left untouched, for everything nm_distr_bondorder refuses, in its order, and
+ * for an odd l (the message says why).  ns == 0 as in nm_distr_bondorder. */
+int nm_distr_bondorder_w(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi,
+                         int nl, const int *ls, double *w3, double *wbar3, double *W3,
+                         double *q2, double *qbar2, double *Q2, int32_t *nnb);
+
 /* Solid-like atoms and crystal clusters: ten Wolde, Ruiz-Montero and Frenkel's criterion on the normalised dot products of the
  * q_lm vectors of neighbouring atoms, and the connected components of the solid-like atoms.  Definition (the build's own), for
  * sample s, one l and centre atom c:

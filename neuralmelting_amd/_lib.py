@@ -115,6 +115,7 @@ def _prototypes():
             'nm_distr_angles': (i, frames + [d, d, i, D, U64]),
             'nm_distr_sfactor': (i, frames + [i, D, D]),
             'nm_distr_bondorder': (i, frames + [d, d, i, I, D, D, D, I32]),
+            'nm_distr_bondorder_w': (i, frames + [d, d, i, I, D, D, D, D, D, D, I32]),
             'nm_distr_solid': (i, frames + [d, d, i, d, i, I32, I32, I32, I32, I32]),
             'nm_distr_cna': (i, frames + [d, d, i, I32, I32, I32, I32]),
             'nm_distr_entropy': (i, frames + [d, d, i, d, d, D, D, I32, D, D, I32])}),

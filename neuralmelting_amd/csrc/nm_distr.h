@@ -590,8 +590,9 @@ nm_sfac_kernel(int natoms, const float *__restrict__ pos, const float *__restric
 // keeps the unnormalised sums for Q2; the workgroup's partial sums and bond count go to [sample][group].
 // Pass 2 (nm_bo_average_kernel, only if qbar2 is asked for): the same scan, indices only; lane = component gathers q_lm(a) of
 // the batch's entries in list order (one coalesced read of the atom's moments per entry, the reads of up to eight entries in
-// flight), then qbar_lm and its invariant.
-// nm_bo_global_kernel adds the partials of a sample's groups in order and forms Q2.
+// flight), then qbar_lm and its invariant.  The pass is bo_average_centres with the invariant as its finish; nm_distr_w.h runs the
+// same centres with the cubic invariant beside it.
+// nm_bo_global_kernel adds the partials of a sample's groups in order (bo_global_moments, shared with nm_distr_w.h) and forms Q2.
 // Every sum runs in a fixed order (entries in scan order, centres in order per wave, waves in order, groups in order): the
 // result is the same bits on every call, without a floating-point atomic.
 //
@@ -817,9 +818,12 @@ __device__ __forceinline__ void bo_gather(const double *__restrict__ qs, const i
     }
 }
 
-__global__ void __launch_bounds__(SHELL_BLOCK)
-nm_bo_average_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
-                     BoSet set, const double *__restrict__ qlm, double *__restrict__ qbar2)
+// Pass 2's centres: the staging, the scan and the gather of the workgroup's centres.  Where qbar_lm(c) stands in the wave's LDS row
+// (m >= 0, real and imaginary parts in turn, the l in the set's order), finish(s, c, qbar, lane) is called by the whole wave: what is
+// formed from the averaged moments (nm_bo_average_kernel's invariant, nm_distr_w.h's cubic one) reads the same bits.
+template <class E>
+__device__ __forceinline__ void bo_average_centres(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo,
+                                                   double r_hi, float cube, const BoSet &set, const double *__restrict__ qlm, E &&finish)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int groups = (natoms + SHELL_CPB - 1) / SHELL_CPB;
@@ -855,20 +859,35 @@ nm_bo_average_kernel(int natoms, const float *__restrict__ pos, const float *__r
         if (own0) acc[lane] = (rc[lane] + a0) / den;
         if (own1) acc[lane + 64] = (rc[lane + 64] + a1) / den;
         adf_wave_sync();
-        if (lane < set.nl) {
-            const int l = bo_l_of(set, lane);
-            qbar2[((size_t)s * natoms + c) * set.nl + lane] = bo_invariant(acc + 2 * bo_off(set, l), l);
-        }
+        finish(s, c, acc, lane);
         adf_wave_sync();
     }
 }
 
-// one workgroup of 128 threads per sample: the groups' partial sums in order, the moments of all bonds, Q2
-__global__ void __launch_bounds__(128)
-nm_bo_global_kernel(int groups, BoSet set, const double *__restrict__ partial, const int *__restrict__ pcount, double *__restrict__ Q2)
+// qbar2 of a centre from its averaged moments in LDS: lane = requested l
+__device__ __forceinline__ void bo_average_invariant(const BoSet &set, int natoms, int s, int c, const double *qbar, int lane,
+                                                     double *__restrict__ qbar2)
 {
-    __shared__ double q[2 * BO_MAXL * (BO_LMAX + 1)];
-    const int s = blockIdx.x, tid = threadIdx.x, nc2 = 2 * set.nc;
+    if (lane < set.nl) {
+        const int l = bo_l_of(set, lane);
+        qbar2[((size_t)s * natoms + c) * set.nl + lane] = bo_invariant(qbar + 2 * bo_off(set, l), l);
+    }
+}
+
+__global__ void __launch_bounds__(SHELL_BLOCK)
+nm_bo_average_kernel(int natoms, const float *__restrict__ pos, const float *__restrict__ box, double r_lo, double r_hi, float cube,
+                     BoSet set, const double *__restrict__ qlm, double *__restrict__ qbar2)
+{
+    bo_average_centres(natoms, pos, box, r_lo, r_hi, cube, set, qlm,
+                       [&](int s, int c, const double *qbar, int lane) { bo_average_invariant(set, natoms, s, c, qbar, lane, qbar2); });
+}
+
+// the moments of all bonds of sample s in q (LDS, 2 nc doubles): the groups' partial sums in order, divided by the groups' bonds; a
+// workgroup barrier stands behind them
+__device__ __forceinline__ void bo_global_moments(int groups, const BoSet &set, const double *__restrict__ partial,
+                                                  const int *__restrict__ pcount, int s, double *q)
+{
+    const int tid = threadIdx.x, nc2 = 2 * set.nc;
     if (tid < nc2) {
         double t = 0.0;
         long long n = 0;
@@ -879,6 +898,15 @@ nm_bo_global_kernel(int groups, BoSet set, const double *__restrict__ partial, c
         q[tid] = n > 0 ? t / (double)n : 0.0;
     }
     __syncthreads();
+}
+
+// one workgroup of 128 threads per sample: the groups' partial sums in order, the moments of all bonds, Q2
+__global__ void __launch_bounds__(128)
+nm_bo_global_kernel(int groups, BoSet set, const double *__restrict__ partial, const int *__restrict__ pcount, double *__restrict__ Q2)
+{
+    __shared__ double q[2 * BO_MAXL * (BO_LMAX + 1)];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    bo_global_moments(groups, set, partial, pcount, s, q);
     if (tid < set.nl) {
         const int l = bo_l_of(set, tid);
         Q2[(size_t)s * set.nl + tid] = bo_invariant(q + 2 * bo_off(set, l), l);

@@ -3,6 +3,7 @@
 // walks the samples in chunks.
 #include "../../include/nm_distr.h"
 #include "nm_distr.h"
+#include "nm_distr_w.h"
 #include "nm_host.h"
 
 #include <cmath>
@@ -93,6 +94,42 @@ std::vector<double> bo_table()
         }
     }
     return tab;
+}
+
+// The table of nm_distr_w.h: for l = 2, 4, .., 12 the terms (m1, m2) in that header's order, a symbol whose S is 0 left out, each the position triple and the
+// coefficient (4 pi / (2l+1))^(3/2) (l l l; m1 m2 m3).  Racah's formula with the alternating sum in integers: for j1 = j2 = j3 = l
+//   (l l l; m1 m2 m3) = (-1)^m3 S sqrt(prod_i (l + m_i)! (l - m_i)! / ((3l+1)! l!^3)),   S = sum_k (-1)^k C(l, k) C(l, l - m1 - k) C(l, l + m2 - k),
+// S exact (each binomial is at most C(12, 6) = 924, at most 13 terms), the root's argument a product and quotient of factorials up to
+// 37! in long double, the whole rounded to double once.
+void bo_w_table(std::vector<double> &coef, std::vector<int> &idx)
+{
+    long double fact[3 * BO_LMAX + 2];
+    fact[0] = 1.0L;
+    for (int k = 1; k <= 3 * BO_LMAX + 1; ++k) fact[k] = fact[k - 1] * (long double)k;
+    auto binom = [](int n, int k) -> long long {
+        if (k < 0 || k > n) return 0;
+        long long b = 1;
+        for (int i = 1; i <= k; ++i) b = b * (n - k + i) / i;
+        return b;
+    };
+    coef.clear();
+    idx.clear();
+    for (int l = 2; l <= BO_LMAX; l += 2) {
+        const long double pre = powl(4.0L * 3.14159265358979323846264338327950288L / (long double)(2 * l + 1), 1.5L);
+        const long double den = fact[3 * l + 1] * fact[l] * fact[l] * fact[l];
+        for (int m1 = -l; m1 <= l; ++m1)
+            for (int m2 = -l; m2 <= l; ++m2) {
+                const int m3 = -m1 - m2;
+                if (m3 < -l || m3 > l) continue;
+                long long S = 0;
+                for (int k = 0; k <= l; ++k) S += ((k & 1) ? -1 : 1) * binom(l, k) * binom(l, l - m1 - k) * binom(l, l + m2 - k);
+                if (S == 0) continue;
+                const long double num = fact[l + m1] * fact[l - m1] * fact[l + m2] * fact[l - m2] * fact[l + m3] * fact[l - m3];
+                const long double t = pre * (long double)S * sqrtl(num / den);
+                coef.push_back((double)((m3 & 1) ? -t : t));
+                idx.push_back((m1 + l) | ((m2 + l) << 8) | ((m3 + l) << 16));
+            }
+    }
 }
 
 // samples per launch of the entry points that keep the moments q_lm in a device scratch of `per` bytes per sample: at most
@@ -315,6 +352,86 @@ int nm_distr_bondorder(int device, int ns, int natoms, const float *pos, const f
             STAGE_CHK(fn, hipGetLastError());
         }
         STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_q2.fetch(s0, n));
+        STAGE_CHK(fn, d_qb.fetch(s0, n));
+        STAGE_CHK(fn, d_Q.fetch(s0, n));
+        STAGE_CHK(fn, d_nnb.fetch(s0, n));
+        return NM_OK;
+    });
+}
+
+int nm_distr_bondorder_w(int device, int ns, int natoms, const float *pos, const float *box, double r_lo, double r_hi, int nl,
+                         const int *ls, double *w3, double *wbar3, double *W3, double *q2, double *qbar2, double *Q2, int32_t *nnb)
+{
+    static const char *const fn = "nm_distr_bondorder_w";
+    if (ns < 0 || !pos || !box || !ls) return refuse(fn, "bad argument");
+    if (!w3 && !wbar3 && !W3 && !q2 && !qbar2 && !Q2 && !nnb) return refuse(fn, "all seven outputs are null");
+    if (natoms < 1 || natoms > 4095) return refuse(fn, "natoms must lie in 1..4095");
+    if (nl < 1 || nl > BO_MAXL) return refuse(fn, "nl must lie in 1..6");
+    for (int i = 0; i < nl; ++i)
+        if (ls[i] < 1 || ls[i] > BO_LMAX || (i > 0 && ls[i] <= ls[i - 1]))
+            return refuse(fn, "ls must increase strictly within 1..12");
+    for (int i = 0; i < nl; ++i)
+        if (ls[i] & 1)
+            return refuse(fn, "an odd l: the 3j symbol (l l l; m1 m2 m3) is antisymmetric under the exchange of two columns for odd 3l, "
+                              "so the third-order invariant vanishes identically; ls takes even values only");
+    if (const int rc = shell_check(fn, r_lo, r_hi)) return rc;
+    if (const int rc = distr_boxes_check(fn, ns, box)) return rc;
+    if (const int rc = half_box_check(fn, ns, box, r_hi)) return rc;
+    if (const int rc = stage_device(fn, device)) return rc;
+    if (ns == 0) return NM_OK;
+    BoMoments m;
+    if (const int rc = m.setup(fn, ns, natoms, nl, ls, r_hi)) return rc;
+    std::vector<double> hcoef;
+    std::vector<int> hidx;
+    bo_w_table(hcoef, hidx);
+    DevBuf<double> d_coef;
+    DevBuf<int> d_idx;
+    STAGE_CHK(fn, d_coef.upload(hcoef.data(), hcoef.size()));
+    STAGE_CHK(fn, d_idx.upload(hidx.data(), hidx.size()));
+    const BoW w = {d_coef, d_idx};
+    const size_t lds2 = bo_lds_bytes(natoms, m.set.nc, false), lds2w = bo_w_lds_bytes(natoms, m.set.nc); // below the moments kernel's
+    STAGE_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    STAGE_CHK(fn, hipFuncSetAttribute((const void *)nm_bo_w_average_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2w));
+    const size_t pa = (size_t)natoms * nl;
+    DistrOut<double> d_w3(w3, pa), d_wb(wbar3, pa), d_W(W3, nl), d_q2(q2, pa), d_qb(qbar2, pa), d_Q(Q2, nl);
+    DistrOut<int> d_nnb(nnb, natoms);
+    STAGE_CHK(fn, d_w3.alloc(m.cs));
+    STAGE_CHK(fn, d_wb.alloc(m.cs));
+    STAGE_CHK(fn, d_W.alloc(m.cs));
+    STAGE_CHK(fn, d_q2.alloc(m.cs));
+    STAGE_CHK(fn, d_qb.alloc(m.cs));
+    STAGE_CHK(fn, d_Q.alloc(m.cs));
+    STAGE_CHK(fn, d_nnb.alloc(m.cs));
+    DistrChunks ch;
+    return ch.run(fn, ns, m.cs, natoms, pos, box, [&](int s0, int n) -> int {
+        m.launch(n, natoms, ch.pos, ch.box, r_lo, r_hi, d_q2, d_nnb);
+        STAGE_CHK(fn, hipGetLastError());
+        if (w3) {
+            const int nvec = n * natoms; // at most 4096 * 4095
+            hipLaunchKernelGGL(nm_bo_w_kernel, dim3((nvec + SHELL_WAVES - 1) / SHELL_WAVES), dim3(SHELL_BLOCK), 0, 0, nvec, m.set, m.qlm, w, d_w3);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        if (wbar3) {
+            hipLaunchKernelGGL(nm_bo_w_average_kernel, dim3(n * m.groups), dim3(SHELL_BLOCK), lds2w, 0, natoms, ch.pos, ch.box, r_lo, r_hi,
+                               m.cube, m.set, m.qlm, w, d_qb, d_wb);
+            STAGE_CHK(fn, hipGetLastError());
+        } else if (qbar2) {
+            hipLaunchKernelGGL(nm_bo_average_kernel, dim3(n * m.groups), dim3(SHELL_BLOCK), lds2, 0, natoms, ch.pos, ch.box, r_lo, r_hi, m.cube,
+                               m.set, m.qlm, d_qb);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        if (W3) {
+            hipLaunchKernelGGL(nm_bo_w_global_kernel, dim3(n), dim3(128), 0, 0, m.groups, m.set, m.part, m.cnt, w, d_Q, d_W);
+            STAGE_CHK(fn, hipGetLastError());
+        } else if (Q2) {
+            hipLaunchKernelGGL(nm_bo_global_kernel, dim3(n), dim3(128), 0, 0, m.groups, m.set, m.part, m.cnt, d_Q);
+            STAGE_CHK(fn, hipGetLastError());
+        }
+        STAGE_CHK(fn, hipDeviceSynchronize());
+        STAGE_CHK(fn, d_w3.fetch(s0, n));
+        STAGE_CHK(fn, d_wb.fetch(s0, n));
+        STAGE_CHK(fn, d_W.fetch(s0, n));
         STAGE_CHK(fn, d_q2.fetch(s0, n));
         STAGE_CHK(fn, d_qb.fetch(s0, n));
         STAGE_CHK(fn, d_Q.fetch(s0, n));

@@ -9,8 +9,9 @@ files with the same shapes and dtypes.  With -ad it also writes the angular (bon
 static structure factor on the reciprocal lattice of each sample's box, averaged and maximised over the shells |q| = const
 (.q.npy / .sf.npy / .sfm.npy; definition: include/nm_distr.h, nm_distr_sfactor), and the number densities (.nrho.npy).
 With -bo it also writes the Steinhardt bond-order parameters q_l, their neighbour average and the global Q_l (.bo*.npy;
-definition: include/nm_distr.h, nm_distr_bondorder).  With -so it also writes the solid-like atoms and crystal clusters of each
-sample: the solid fraction, the largest cluster's share, the number of clusters and the mean number of connections (.so*.npy;
+definition: include/nm_distr.h, nm_distr_bondorder), and with -bw beside them the third-order invariants w_l, their neighbour average
+and the global W_l (.bow*.npy; definition: include/nm_distr.h, nm_distr_bondorder_w).  With -so it also writes the solid-like atoms
+and crystal clusters of each sample: the solid fraction, the largest cluster's share, the number of clusters and the mean number of connections (.so*.npy;
 definition: include/nm_distr.h, nm_distr_solid).  With -cn it also writes the common neighbour analysis of each sample: the shares
 of fcc, hcp, bcc and icosahedral atoms and of the eight signature columns (.cn*.npy; definition: include/nm_distr.h, nm_distr_cna).
 With -le it also writes the pair entropy per atom (Piaggi and Parrinello's local-entropy fingerprint) and its neighbour average as
@@ -22,6 +23,7 @@ entropy of each sample (.s2.npy).
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -ad -ac 0.2125
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -sf -sq 16
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -bo -bl 4 6
+    python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -bo -bl 4 6 -bw
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -so -sl 6 -st 0.5 -sx 8
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -cn -cm adaptive
     python -m neuralmelting_amd.distr -v -n remcmc_init -e LJ -sb 64 -cb 16 -le -lt -5.0 -ef
@@ -81,6 +83,10 @@ def _parser():
     p.add_argument('-ba', '--bond_atoms', action='store_true',
                    help='with -bo also write the per-atom values: <PREFIX>.boqa.npy, .boba.npy and .bona.npy; 8 nl + 4 bytes per atom '
                         'and sample for nl values of l, about 10 GB for a grid of 2^20 samples of 500 atoms at two l')
+    p.add_argument('-bw', '--bond_w', action='store_true',
+                   help='with -bo also write Steinhardt\'s third-order invariants, normalised to [-1, 1]: <PREFIX>.bow.npy (mean over the '
+                        'atoms of w_l), .bowb.npy (mean of the neighbour-averaged w_l) and .bowg.npy (the global W_l), with -ba also '
+                        '.bowa.npy and .bowba.npy per atom; the values of -bl must be even (w_l vanishes for odd l)')
     p.add_argument('-so', '--solid', action='store_true',
                    help='also write the solid-like atoms and crystal clusters (ten Wolde, Ruiz-Montero and Frenkel): <PREFIX>.sof.npy '
                         '(solid-like atoms / natoms), .sol.npy (largest cluster / natoms), .soc.npy (number of clusters) and .son.npy '
@@ -197,6 +203,10 @@ def parse_args(argv=None):
     a.bond_l = sorted(a.bond_l)
     if not 1 <= len(a.bond_l) <= 6 or len(set(a.bond_l)) != len(a.bond_l) or a.bond_l[0] < 1 or a.bond_l[-1] > 12:
         p.error('-bl/--bond_l takes 1 to 6 distinct values in 1..12')
+    if a.bond_w and not a.bond_order:
+        p.error('-bw/--bond_w needs -bo/--bond_order')
+    if a.bond_w and any(l % 2 for l in a.bond_l):
+        p.error('-bw/--bond_w takes even -bl/--bond_l values only: the third-order invariant vanishes for odd l')
     if not 0.0 < a.angular_cutoff <= 0.5:
         p.error('-ac/--angular_cutoff must lie in (0, 0.5]')
     if not 1 <= a.q_max <= 32:
@@ -335,6 +345,27 @@ def bond_order(natoms, box, pos, ls, r_lo, r_hi, device=0):
     return root(q2), root(b2), root(g2), nb
 
 
+def bond_order_w(natoms, box, pos, ls, r_lo, r_hi, device=0):
+    """Steinhardt's third-order invariants of all samples for the even l values ls (strictly increasing, 2..12, at most six), neighbour
+    shell r_lo < d <= r_hi, beside what bond_order returns, from one call of nm_distr_bondorder_w: w and wbar float64 [ns][natoms][nl]
+    (per atom, wbar of the moments averaged over the atom and its neighbours), W float64 [ns][nl] (all bonds of the frame), then q, qbar,
+    Q and nb exactly as bond_order gives them.  The library returns the cubic forms w3 and the squares q2; the normalised
+    w = w3 / q2^(3/2), in [-1, 1] up to rounding, is formed here in float64 and is 0 where q2 == 0.  Where q_l all but vanishes (l = 2 on
+    a cubic lattice, l = 4 on an icosahedron) the ratio is rounding noise: such a w carries no information.  natoms is accepted for
+    symmetry with histograms(); the atom count is pos.shape[1]."""
+    pos, box = _frames(pos, box)
+    ns, n = pos.shape[0], pos.shape[1]
+    ls = np.ascontiguousarray(ls, dtype=np.int32).reshape(-1)
+    nl = len(ls)
+    w3, wb3, q2, b2 = (np.zeros((ns, n, nl), dtype=np.float64) for _ in range(4))
+    W3, g2 = (np.zeros((ns, nl), dtype=np.float64) for _ in range(2))
+    nb = np.zeros((ns, n), dtype=np.int32)
+    B.call('nm_distr_bondorder_w', device, ns, n, pos, box, float(r_lo), float(r_hi), nl, ls, w3, wb3, W3, q2, b2, g2, nb)
+    root = lambda x: np.sqrt(np.maximum(x, 0.0))
+    hat = lambda w, x: np.divide(w, np.maximum(x, 0.0) ** 1.5, out=np.zeros_like(w), where=x > 0.0)
+    return hat(w3, q2), hat(wb3, b2), hat(W3, g2), root(q2), root(b2), root(g2), nb
+
+
 def solid(natoms, box, pos, l, r_lo, r_hi, s_min, n_min, device=0):
     """solid-like atoms and crystal clusters of all samples (include/nm_distr.h, nm_distr_solid) for one l in 1..12, neighbour shell
     r_lo < d <= r_hi, connection threshold s_min in [-1, 1) and n_min >= 1 connections for a solid-like atom: nconn int32 [ns][natoms]
@@ -456,7 +487,10 @@ def main(argv=None):
     if a.bond_order:
         l = float(np.min(box))
         n, nl = int(natoms[0]), len(a.bond_l)
-        q, qb, qg, nb = bond_order(natoms, box, pos, a.bond_l, 1e-16 * l, bcut * l, device=dev)
+        if a.bond_w:
+            w, wb, wg, q, qb, qg, nb = bond_order_w(natoms, box, pos, a.bond_l, 1e-16 * l, bcut * l, device=dev)
+        else:
+            q, qb, qg, nb = bond_order(natoms, box, pos, a.bond_l, 1e-16 * l, bcut * l, device=dev)
         np.save(prefix + '.bol.npy', np.array(a.bond_l, dtype=np.int64))
         np.save(prefix + '.boq.npy', q.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
         np.save(prefix + '.bob.npy', qb.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
@@ -466,6 +500,13 @@ def main(argv=None):
             np.save(prefix + '.boqa.npy', q.astype(np.float32).reshape(pn, tn, rns, n, nl))
             np.save(prefix + '.boba.npy', qb.astype(np.float32).reshape(pn, tn, rns, n, nl))
             np.save(prefix + '.bona.npy', nb.reshape(pn, tn, rns, n))
+        if a.bond_w:
+            np.save(prefix + '.bow.npy', w.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
+            np.save(prefix + '.bowb.npy', wb.mean(axis=1).astype(np.float32).reshape(pn, tn, rns, nl))
+            np.save(prefix + '.bowg.npy', wg.astype(np.float32).reshape(pn, tn, rns, nl))
+            if a.bond_atoms:
+                np.save(prefix + '.bowa.npy', w.astype(np.float32).reshape(pn, tn, rns, n, nl))
+                np.save(prefix + '.bowba.npy', wb.astype(np.float32).reshape(pn, tn, rns, n, nl))
     if a.solid:
         l = float(np.min(box))
         n = int(natoms[0])

@@ -4,6 +4,7 @@
     python scripts/bench_distr.py --angles [ns=4096] [cells=4] [cutoff=0.5] [repeats=5]
     python scripts/bench_distr.py --sfactor [ns=4096] [natoms=256] [qmax=16] [repeats=5]
     python scripts/bench_distr.py --bondorder [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l ...=4 6]
+    python scripts/bench_distr.py --bond-w [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l ...=4 6]
     python scripts/bench_distr.py --solid [ns=4096] [cells=4] [cutoff=0] [repeats=5] [l=6] [s_min=0.5] [n_min=8]
     python scripts/bench_distr.py --cna [ns=4096] [cells=4] [cutoff=0] [repeats=5] [mode=adaptive]
     python scripts/bench_distr.py --entropy [ns=4096] [cells=4] [repeats=5] [r_m=0] [sigma=0] [nbins=0] [r_avg=0]
@@ -23,6 +24,12 @@ outputs: the time of the whole call as above, bonds/s, the same call of nm_distr
 restatement on one host core over one sample (imported from tests/bondorder_ref.py, as --angles imports tests/adf_ref.py: the
 script needs the tests directory next to it).  The kernels' own times come from the same rocprofv3 line
 (nm_bo_moments_kernel, nm_bo_average_kernel, nm_bo_global_kernel, nm_adf_kernel).
+
+--bond-w: nm_distr_bondorder_w with all seven outputs on the frames and shapes of --bondorder (even l only), and next to it
+nm_distr_bondorder with all four outputs on the same frames, shell and l (the yardstick: the same two scans; the new call adds the three
+contractions and three more arrays to copy back): the time of each whole call as above and their ratio.  The kernels' own times come
+from the same rocprofv3 line (nm_bo_moments_kernel, nm_bo_w_kernel, nm_bo_w_average_kernel, nm_bo_w_global_kernel against
+nm_bo_moments_kernel, nm_bo_average_kernel, nm_bo_global_kernel).
 
 --solid: nm_distr_solid on the frames and shapes of --bondorder, all five outputs: the time of the whole call as above, entries/s,
 and next to it nm_distr_bondorder with qbar2 alone for the same single l on the same frames and shell (the yardstick: two scans
@@ -181,6 +188,58 @@ def bench_bondorder(argv):
     R.bond_order2(pos[:1], box[:1], ls.tolist(), 1e-16 * l, cut * l)
     dt = time.perf_counter() - t
     print('numpy restatement, one core, sample 0: %.3f s = %.2f samples/s, %.1f centres/s' % (dt, 1 / dt, n / dt))
+
+
+def bench_bond_w(argv):
+    from neuralmelting_amd import _lib as B, lattice
+    ns = int(argv[0]) if len(argv) > 0 else 4096
+    cells = int(argv[1]) if len(argv) > 1 else 4
+    cut = float(argv[2]) if len(argv) > 2 else 0.0
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    ls = np.array([int(x) for x in argv[4:]] or [4, 6], dtype=np.int32)
+    rng = np.random.default_rng(3)                                            # the frames of bench_angles
+    n = 4 * cells ** 3
+    cut = distr.bond_cutoff(cut, n)
+    a0 = lattice.lattice_constant('LJ')
+    box = (cells * a0 * (1.0 + 0.05 * rng.random(ns))).astype(np.float32)
+    frac = lattice.fcc_fractional(cells)
+    pos = ((frac[None] + 0.08 / cells * rng.normal(size=(ns, n, 3))) % 1.0 * box[:, None, None]).astype(np.float32)
+    pos = np.minimum(pos, np.nextafter(box, np.float32(0))[:, None, None])
+    l = float(box.min())
+    L = B.load()
+    nl = len(ls)
+    w3, wb3, q2, b2 = (np.zeros((ns, n, nl)) for _ in range(4))
+    W3, g2 = np.zeros((ns, nl)), np.zeros((ns, nl))
+    nb = np.zeros((ns, n), dtype=np.int32)
+    P = lambda a: a.ctypes.data_as(B.c_double_p)
+    head = lambda m: (0, m, n, pos.ctypes.data_as(B.c_float_p), box.ctypes.data_as(B.c_float_p), 1e-16 * l, cut * l, nl,
+                      ls.ctypes.data_as(B.c_int_p))
+
+    def run_w(m):
+        rc = L.nm_distr_bondorder_w(*head(m), P(w3), P(wb3), P(W3), P(q2), P(b2), P(g2), nb.ctypes.data_as(B.c_int32_p))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+
+    def run(m):
+        rc = L.nm_distr_bondorder(*head(m), P(q2), P(b2), P(g2), nb.ctypes.data_as(B.c_int32_p))
+        if rc != 0:
+            raise RuntimeError(L.nm_distr_last_error().decode())
+    med = {}
+    for name, f in (('bondorder_w', run_w), ('bondorder', run)):
+        f(min(ns, 8))
+        f(ns)                                                                 # warm-up at the timed shape
+        ts = []
+        for _ in range(reps):
+            t = time.perf_counter(); f(ns); ts.append(time.perf_counter() - t)
+        med[name] = (float(np.median(ts)), min(ts), max(ts))
+    hat = lambda w, x: np.divide(w, np.maximum(x, 0.0) ** 1.5, out=np.zeros_like(w), where=x > 0.0)
+    dt = med['bondorder_w'][0]
+    print('bond-w: %d samples x %d atoms, cutoff %.4f l, l = %s: %.1f neighbours per centre; nm_distr_bondorder_w, seven outputs, call (H2D '
+          '+ kernels + D2H) median of %d: %.4f s (min %.4f, max %.4f) = %.1f M centres/s; mean w %s, wbar %s, W %s'
+          % (ns, n, cut, ls.tolist(), nb.sum() / (ns * n), reps, dt, med['bondorder_w'][1], med['bondorder_w'][2], ns * n / dt / 1e6,
+             hat(w3, q2).mean(axis=(0, 1)).round(5), hat(wb3, b2).mean(axis=(0, 1)).round(5), hat(W3, g2).mean(axis=0).round(5)))
+    print('nm_distr_bondorder on the same frames, shell and l, four outputs: call median of %d: %.4f s (min %.4f, max %.4f); '
+          'bondorder_w / bondorder = %.2f' % (reps, med['bondorder'][0], med['bondorder'][1], med['bondorder'][2], dt / med['bondorder'][0]))
 
 
 def bench_solid(argv):
@@ -347,6 +406,10 @@ if '--solid' in sys.argv:
 
 if '--bondorder' in sys.argv:
     bench_bondorder([x for x in sys.argv[1:] if x != '--bondorder'])
+    sys.exit(0)
+
+if '--bond-w' in sys.argv:
+    bench_bond_w([x for x in sys.argv[1:] if x != '--bond-w'])
     sys.exit(0)
 
 if '--sfactor' in sys.argv:
