@@ -246,6 +246,49 @@ int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const flo
                      double r_avg, double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean,
                      int32_t *nlow);
 
+/* nm_distr_lof — the local outlier factor of many small sets of points at once: not a histogram of frames
+ * but the distribution of a grid point's samples among themselves.  The reference's inlier selection (lammps_vae.py -ad) fits
+ * sklearn.neighbors.LocalOutlierFactor(contamination='auto'), 20 neighbours, to the samples of every (P, T) grid point alone.  The
+ * definitions below are the build's own; off ties they are sklearn's LocalOutlierFactor(n_neighbors=k, algorithm='brute') applied to
+ * each set alone.  Every array is float64 (nbr int32) in host memory; calls are stateless.  u = 2^-53.
+ *
+ * Points.  x[s][i][c], s = 0..nsets-1 sets of i = 0..npts-1 points of c = 0..ndim-1 coordinates, row-major.  i, j and every stored
+ *   index count within a set; no quantity of a set depends on another set.
+ * Distance.  d2(i, j) = sum_c (x[s][i][c] - x[s][j][c])^2 in float64, c ascending, every difference, product and sum rounded on its
+ *   own (no fused multiply-add), as in include/nm_tsne.h: the same bits wherever a pair is formed and d2(i, j) == d2(j, i).  Error
+ *   at most (ndim + 2) u d2.
+ * Neighbours.  nbr[s][i][0..k-1] are the k points j != i of set s with the smallest (d2(i, j), j) in lexicographic order, stored in
+ *   that order: duplicates and ties are decided by the index.  The selection is exact (one pass over the set's pairs that keeps the
+ *   k best of each point, then their ranks).
+ * kdist.  kdist[i] = sqrt(d2(i, nbr[i][k-1])).
+ * reach.  reach(i, m) = max(sqrt(d2(i, nbr[i][m])), kdist[nbr[i][m]]).
+ * lrd.  lrd[i] = 1 / ((sum_m reach(i, m)) / k + 1e-10), the sum over m ascending from 0.  The 1e-10 is sklearn's and is absolute:
+ *   it bounds lrd by 1e10 and is felt wherever the mean reach is not far above it, so the caller's scale matters (the outlier stage
+ *   hands over pca's projections as they are, as the reference does).
+ * lof.  lof[i] = (sum_m lrd[nbr[i][m]] / lrd[i]) / k, the sum over m ascending, one division per term.  sklearn's
+ *   negative_outlier_factor_ is -lof, and its 'auto' rule calls i an outlier iff lof[i] > 1.5.
+ * Degenerate input is defined, no error: a set whose points all coincide gives kdist = 0, lrd = 1e10, lof = 1.
+ * Determinism.  Every sum runs in the fixed order above; there are no floating-point atomics and no atomics at all.  Every output
+ *   is the same bytes on every call, and a set's outputs do not depend on which other sets are in the batch.
+ * Bounds, with the lists given (csrc/nm_lof.h derives them): kdist to (ndim / 2 + 3) u, lrd to (ndim / 2 + k + 8) u, lof to
+ *   (ndim + 3 k + 16) u of itself.
+ * Memory.  O(nsets npts (ndim + k)) on the device; no npts x npts array exists at any time.  The work is npts^2 distances per set,
+ *   each pair read once.
+ *
+ * x [nsets][npts][ndim]; lof, lrd, kdist [nsets][npts]; nbr [nsets][npts][k] (int32, indices within the set) or null.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_distr_lof:".  NM_ERR_ARG, checked
+ * before the device is looked for and with every output left untouched, for, in this order: nsets outside 1..2^20, npts outside
+ * 2..4096, nsets npts above 2^21, ndim outside 1..16, k outside 1..min(npts - 1, 64), a null pointer other than nbr, a negative
+ * device ordinal.  A value of x that is not finite is found on the device by a first screen, as include/nm_cluster.h's is:
+ * NM_ERR_ARG, the message names the set and the first such point, the outputs are left untouched. */
+int nm_distr_lof(int device, int64_t nsets, int npts, int ndim, const double *x, int k, double *lof, double *lrd, double *kdist,
+                 int32_t *nbr);
+
+/* Where the device time of the calling thread's last successful nm_distr_lof went, in milliseconds between device events: ms[0] the
+ * upload of x and the screen, ms[1] the neighbour pass, ms[2] the lrd pass, ms[3] the lof pass.  The downloads of the results are
+ * not in it.  NM_ERR_ARG for a null pointer. */
+int nm_distr_last_timing(double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,7 +118,9 @@ def _prototypes():
             'nm_distr_bondorder_w': (i, frames + [d, d, i, I, D, D, D, D, D, D, I32]),
             'nm_distr_solid': (i, frames + [d, d, i, d, i, I32, I32, I32, I32, I32]),
             'nm_distr_cna': (i, frames + [d, d, i, I32, I32, I32, I32]),
-            'nm_distr_entropy': (i, frames + [d, d, i, d, d, D, D, I32, D, D, I32])}),
+            'nm_distr_entropy': (i, frames + [d, d, i, d, d, D, D, I32, D, D, I32]),
+            'nm_distr_lof': (i, [i, i64, i, i, D, i, D, D, D, I32]),
+            'nm_distr_last_timing': (i, [D])}),
         'nm_parse.h': ('nm_parse_last_error', {
             'nm_parse_thrm': (i, [s, F, l, L, i]),
             'nm_parse_traj': (i, [s, U16, F, F, l, l, L, L, i]),

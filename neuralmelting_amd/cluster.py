@@ -46,6 +46,8 @@ def parse_args(argv=None):
     p.add_argument('-nk', '--clusters_kept', type=int, default=2, help='phase indicators written, 1..8')
     p.add_argument('-sk', '--skip', type=int, default=0, help='samples of every grid point left out at its start')
     p.add_argument('-sd', '--stride', type=int, default=1, help='every STRIDE-th sample is clustered')
+    p.add_argument('-il', '--inliers', action='store_true',
+                   help="cluster only the inliers of `outlier` (<PREFIX>.F.lof.npy and .F.loi.npy of the same -sk and -sd); its outliers get label -1")
     p.add_argument('-dv', '--device', type=int, default=0)
     a = p.parse_args(argv)
     if (a.skip < 0 or a.stride < 1 or not 1 <= a.dimensions <= MAX_DIM or not 1 <= a.clusters_kept <= MAX_KEPT or a.min_samples < 1
@@ -105,16 +107,18 @@ def main(argv=None):
     if nd > ld:
         raise SystemExit('cluster: -nd %d is more than the %d components of %s' % (nd, ld, path))
     kept, zk = S.kept(pcz, a.skip, a.stride)
-    n = pn * tn * kept
+    keep = S.inliers('cluster', prefix, ft, pe.shape, a.skip, a.stride) if a.inliers else np.ones((pn, tn, kept), dtype=bool)
+    n = int(keep.sum())
     if not 1 <= n <= MAX_POINTS:
-        raise SystemExit('cluster: -sk %d -sd %d leave %d samples of %s, not 1..%d' % (a.skip, a.stride, n, path, MAX_POINTS))
-    z = np.ascontiguousarray(zk[..., :nd], dtype=np.float64).reshape(n, nd)
+        raise SystemExit('cluster: -sk %d -sd %d%s leave %d samples of %s, not 1..%d' % (a.skip, a.stride, ' -il' if a.inliers else '', n, path,
+                                                                                       MAX_POINTS))
+    z = np.ascontiguousarray(zk[..., :nd], dtype=np.float64)[keep]
     if a.embedding == 'mfy':                                         # manifold left out what this run leaves out, NaN there and nowhere else
         out = np.ones(sn, dtype=bool)
         out[a.skip::a.stride] = False
-        if np.isnan(z).any() or not np.isnan(pcz[:, :, out]).all():
-            raise SystemExit('cluster: -sk %d -sd %d are not those that %s was written with' % (a.skip, a.stride, path))
-    temp = np.broadcast_to(np.asarray(T, dtype=np.float64)[None, :, None], (pn, tn, kept)).reshape(n)
+        if np.isnan(z).any() or not np.isnan(pcz[:, :, out]).all() or not np.isnan(zk[~keep]).all():
+            raise SystemExit('cluster: -sk %d -sd %d%s are not those that %s was written with' % (a.skip, a.stride, ' -il' if a.inliers else '', path))
+    temp = np.broadcast_to(np.asarray(T, dtype=np.float64)[None, :, None], (pn, tn, kept))[keep]
     if a.verbose:
         print('clustering %d of %d samples of %s in %d components, eps %g of the range of pc0, min_pts %d' % (
             n, pn * tn * sn, ft, nd, a.neighbourhood, a.min_samples))
@@ -124,9 +128,9 @@ def main(argv=None):
         raise SystemExit('cluster: %s: %s' % (path, err))
     tab = table(label, degree, a.min_samples, temp, z)
     order = phases(tab, a.clusters_kept)
-    full = spread(label.reshape(pn, tn, kept), pe.shape, a.skip, a.stride, -1)
+    full = S.spread_kept(label, keep, pe.shape, a.skip, a.stride, -1)
     np.save(prefix + '.%s.cll.npy' % ft, full)
-    np.save(prefix + '.%s.cld.npy' % ft, spread(degree.reshape(pn, tn, kept), pe.shape, a.skip, a.stride, 0))
+    np.save(prefix + '.%s.cld.npy' % ft, S.spread_kept(degree, keep, pe.shape, a.skip, a.stride, 0))
     np.save(prefix + '.%s.cls.npy' % ft, tab)
     for k in range(a.clusters_kept):
         np.save(prefix + '.%s.cl%d.npy' % (ft, k), (full == order[k]).astype(np.float64) if k < len(order) else np.zeros(pe.shape))

@@ -1,9 +1,11 @@
 // nm_distr_api.hip — the structural histograms and order parameters of include/nm_distr.h over the kernels of nm_distr.h
 // (lammps_distr.py:123-171).  Every entry point takes a device ordinal, owns what it allocates for the length of the call and
-// walks the samples in chunks.
+// walks the samples in chunks.  The last one, nm_distr_lof, is the outlier stage's (kernels: nm_lof.h): float64 points in sets, one
+// upload, the screen of nm_scan.h, the neighbour pass and two gathers.
 #include "../../include/nm_distr.h"
 #include "nm_distr.h"
 #include "nm_distr_w.h"
+#include "nm_lof.h"
 #include "nm_host.h"
 
 #include <cmath>
@@ -193,11 +195,19 @@ struct BoMoments {
                            qlm, q2, nnb, part, cnt);
     }
 };
+
+// nm_distr_lof: its slots of nm_distr_last_timing and its neighbour pass for one ndim
+enum { LOF_T_UPLOAD, LOF_T_NEIGHBOURS, LOF_T_LRD, LOF_T_LOF, LOF_T_COUNT };
+thread_local double g_distr_ms[LOF_T_COUNT];
+using LofNeighbours = void (*)(int, int, int, const double *, int *, double *, double *);
+const auto LOF_NEIGHBOURS = scan_table<LOF_MAXDIM>([](auto nd) -> LofNeighbours { return nm_lof_neighbours_kernel<decltype(nd)::value>; });
 } // namespace
 
 extern "C" {
 
 const char *nm_distr_last_error(void) { return g_distr_error.c_str(); }
+
+int nm_distr_last_timing(double *ms) { return last_timing("nm_distr_last_timing", g_distr_ms, ms); }
 
 int nm_distr_histograms(int device, int ns, int natoms, const float *pos, const float *box, int sbins, const double *r_edges,
                         int cbins, const double *rv_edges, float *rdf, float *cdf)
@@ -602,6 +612,53 @@ int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const flo
         STAGE_CHK(fn, d_low.fetch(s0, n));
         return NM_OK;
     });
+}
+
+int nm_distr_lof(int device, int64_t nsets, int npts, int ndim, const double *x, int k, double *lof, double *lrd, double *kdist,
+                 int32_t *nbr)
+{
+    static const char *const fn = "nm_distr_lof";
+    if (nsets < 1 || nsets > LOF_MAXSETS) return refuse(fn, "nsets must lie in 1..2^20");
+    if (npts < 2 || npts > LOF_MAXPTS) return refuse(fn, "npts must lie in 2..4096");
+    if (nsets * npts > LOF_MAXN) return refuse(fn, "nsets * npts must not exceed 2^21 points");
+    if (ndim < 1 || ndim > LOF_MAXDIM) return refuse(fn, "ndim must lie in 1..16");
+    if (k < 1 || k > npts - 1 || k > LOF_MAXK) return refuse(fn, "k must lie in 1..min(npts - 1, 64)");
+    if (!x || !lof || !lrd || !kdist) return refuse(fn, "a needed pointer is null");
+    if (const int rc = stage_device(fn, device)) return rc;
+    const int n = (int)(nsets * npts), rows = lof_rows(k), blocks = (npts + rows - 1) / rows;
+    const dim3 flat((unsigned)((n + LOF_BLOCK - 1) / LOF_BLOCK));
+    Laps<LOF_T_COUNT> laps;
+    DevBuf<double> d_x, d_dist, d_kdist, d_lrd, d_lof;
+    DevBuf<int> d_nbr;
+    laps.lap(LOF_T_UPLOAD);
+    STAGE_CHK(fn, d_x.upload(x, (size_t)n * ndim));
+    STAGE_CHK(fn, d_nbr.alloc((size_t)n * k));
+    STAGE_CHK(fn, d_dist.alloc((size_t)n * k));
+    STAGE_CHK(fn, d_kdist.alloc(n));
+    STAGE_CHK(fn, d_lrd.alloc(n));
+    STAGE_CHK(fn, d_lof.alloc(n));
+    int first = -1;
+    STAGE_CHK(fn, scan_screen<LofScreen>(n, ndim, d_x, first));
+    if (first >= 0)
+        return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in set " + std::to_string(first / npts) + ", point " + std::to_string(first % npts));
+    laps.lap(LOF_T_UPLOAD);
+    hipLaunchKernelGGL(LOF_NEIGHBOURS[ndim - 1], dim3((unsigned)(nsets * blocks)), dim3((unsigned)rows), lof_list_bytes(k), 0, npts, k, blocks,
+                       d_x, d_nbr, d_dist, d_kdist);
+    STAGE_CHK(fn, hipGetLastError());
+    laps.lap(LOF_T_NEIGHBOURS);
+    hipLaunchKernelGGL(nm_lof_lrd_kernel, flat, dim3(LOF_BLOCK), 0, 0, n, npts, k, d_nbr, d_dist, d_kdist, d_lrd);
+    STAGE_CHK(fn, hipGetLastError());
+    laps.lap(LOF_T_LRD);
+    hipLaunchKernelGGL(nm_lof_lof_kernel, flat, dim3(LOF_BLOCK), 0, 0, n, npts, k, d_nbr, d_lrd, d_lof);
+    STAGE_CHK(fn, hipGetLastError());
+    laps.lap(LOF_T_LOF);
+    STAGE_CHK(fn, hipDeviceSynchronize());
+    laps.book(g_distr_ms);
+    STAGE_CHK(fn, d_lof.download(lof, n));
+    STAGE_CHK(fn, d_lrd.download(lrd, n));
+    STAGE_CHK(fn, d_kdist.download(kdist, n));
+    if (nbr) STAGE_CHK(fn, d_nbr.download(nbr, (size_t)n * k));
+    return NM_OK;
 }
 
 } // extern "C"

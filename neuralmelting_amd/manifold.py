@@ -40,6 +40,8 @@ def parse_args(argv=None):
     p.add_argument('-nc', '--components', type=int, default=2, help='output components, 1..3 and at most ND')
     p.add_argument('-sk', '--skip', type=int, default=0, help='samples of every grid point left out at its start')
     p.add_argument('-sd', '--stride', type=int, default=1, help='every STRIDE-th sample is embedded')
+    p.add_argument('-il', '--inliers', action='store_true',
+                   help="embed only the inliers of `outlier` (<PREFIX>.F.lof.npy and .F.loi.npy of the same -sk and -sd); NaN for its outliers")
     p.add_argument('-dv', '--device', type=int, default=0)
     a = p.parse_args(argv)
     if (a.skip < 0 or a.stride < 1 or (a.dimensions is not None and not 1 <= a.dimensions <= MAX_DIM) or not 1 <= a.components <= MAX_COMP
@@ -138,14 +140,16 @@ def main(argv=None):
     if nc > nd:
         raise SystemExit('manifold: -nc %d is more than the %d input components' % (nc, nd))
     kept, xk = S.kept(pcz, a.skip, a.stride)
-    n = pn * tn * kept
+    keep = S.inliers('manifold', prefix, ft, pe.shape, a.skip, a.stride) if a.inliers else np.ones((pn, tn, kept), dtype=bool)
+    n = int(keep.sum())
     if not 3 <= n <= MAX_POINTS:
-        raise SystemExit('manifold: -sk %d -sd %d leave %d samples of %s, not 3..%d' % (a.skip, a.stride, n, path, MAX_POINTS))
+        raise SystemExit('manifold: -sk %d -sd %d%s leave %d samples of %s, not 3..%d' % (a.skip, a.stride, ' -il' if a.inliers else '', n, path,
+                                                                                        MAX_POINTS))
     px = float(kept) if a.perplexity is None else a.perplexity
     k = neighbours(n, px)
     if not (1.0 < px < k <= MAX_K):
         raise SystemExit('manifold: the perplexity %g wants %d neighbours of %d samples: need 1 < PX < k <= %d' % (px, k, n, MAX_K))
-    x = np.ascontiguousarray(xk[..., :nd], dtype=np.float64).reshape(n, nd)
+    x = np.ascontiguousarray(xk[..., :nd], dtype=np.float64)[keep]
     if a.verbose:
         print('embedding %d of %d samples of %s from %d to %d components, perplexity %g, %d neighbours, %d steps (%d at exaggeration %g)' % (
             n, pn * tn * sn, ft, nd, nc, px, k, a.iterations, a.exaggerated, a.exaggeration))
@@ -153,8 +157,8 @@ def main(argv=None):
         y, beta, trace = embed(x, nc, px, a.exaggeration, a.learning_rate, a.iterations, a.exaggerated, a.device)
     except (RuntimeError, ValueError) as err:
         raise SystemExit('manifold: %s: %s' % (path, err))
-    np.save(prefix + '.%s.mfy.npy' % ft, spread(y.reshape(pn, tn, kept, nc), pe.shape + (nc,), a.skip, a.stride))
-    np.save(prefix + '.%s.mfb.npy' % ft, spread(beta.reshape(pn, tn, kept), pe.shape, a.skip, a.stride))
+    np.save(prefix + '.%s.mfy.npy' % ft, S.spread_kept(y, keep, pe.shape + (nc,), a.skip, a.stride, np.nan))
+    np.save(prefix + '.%s.mfb.npy' % ft, S.spread_kept(beta, keep, pe.shape, a.skip, a.stride, np.nan))
     np.save(prefix + '.%s.mft.npy' % ft, trace)
     if a.verbose:
         print('kl %.6g at the start, %.6g before step %d; beta %.4g .. %.4g; the embedding spans %s' % (
