@@ -246,6 +246,63 @@ int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const flo
                      double r_avg, double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean,
                      int32_t *nlow);
 
+/* nm_cluster_kmeans — k-means for the cluster stage: Lloyd's iteration of a set of points from given
+ * initial centres, nrestarts independent runs in one call, the reference's other practical clustering (lammps_vae.py -cl kmeans,
+ * -nc the number of clusters).  It is declared and built here, beside nm_distr_lof and with this header's error channel, because
+ * the tests pin include/nm_cluster.h at its three DBSCAN symbols; the kernels share DBSCAN's distance (csrc/nm_cluster.h, cl_d2).
+ * The definitions are the build's own; off ties, and while no cluster runs empty, restart r gives the labels of
+ * sklearn.cluster.KMeans(n_clusters=k, init=init[r], n_init=1, algorithm='lloyd', max_iter=max_iter), and `tol` is sklearn's tol
+ * already multiplied by the mean variance of the coordinates.  No random number is drawn in the library.  u = 2^-53.
+ *
+ * Points.  x[n][c], n = 0..npoints-1 points of c = 0..ndim-1 coordinates, float64, row-major, in host memory.
+ * Distance.  d2(i, j) of point i and centre j is include/nm_cluster.h's, the point first and the centre second:
+ *   d = x[i][c] - C[j][c], c ascending, the first square a plain product, every further one a fused multiply-add.  One device
+ *   function for every pass: the same point and centre give the same bits everywhere.  Error at most (ndim + 2) u d2.
+ * Assignment.  The label of i is the j with the smallest d2(i, j); on equal bits the smallest j.
+ * Update.  Centre j becomes, coordinate by coordinate, the sum of its members divided by their number, one IEEE division rounded
+ *   once.  The order of the sum is a function of the indices alone: the points are cut into chunks of 4096 and a chunk into 64
+ *   pieces of 64 consecutive points; a piece's members are added in ascending index, starting from +0; the 64 pieces of a chunk are
+ *   added as a binary tree (piece 2 p with piece 2 p + 1, level by level; a piece without members is +0); the chunks are added in
+ *   ascending order.  A cluster without members keeps its centre and has count 0: sklearn relocates such a centre to the point
+ *   farthest from its own, this library does not, and a restart in which that happens is no longer sklearn's.
+ * Step t = 1, 2, ... of one restart, C_1 = init[r]:
+ *   1. L_t is the assignment against C_t.
+ *   2. If t > 1 and L_t == L_{t-1}: the fixed point.  status 0, iters = t - 1, the centres are C_t and the labels L_t.
+ *   3. Else C_{t+1} is the update of L_t, and shift = sum_j sum_c (C_{t+1}[j][c] - C_t[j][c])^2, every square rounded once and then
+ *      added, j then c ascending.
+ *   4. If shift <= tol: status 1, iters = t.
+ *   5. Else if t == max_iter: status 2, iters = t.
+ *   6. With status 1 or 2 one more assignment, against C_{t+1}, is the result: the returned labels are always the assignment
+ *      against the returned centres.
+ * Inertia.  inertia[r] = the sum over i of d2(i, centre of label[i]) for the returned labels and centres of restart r, in the order
+ *   of the update's sum (pieces ascending, tree, chunks ascending), every term rounded as d2 leaves it and then added.
+ * Best restart.  best = the restart with the smallest inertia, the lowest index on equal bits; label, centre and count (the members
+ *   of the returned labels) are that restart's, and cluster j is the one that began at init[best][j].
+ * Independence.  What restart r returns is a function of x, init[r], max_iter and tol alone, not of the other restarts or of when
+ *   they finish: a finished restart is frozen.
+ * Determinism.  The same bytes on every call and on every device, whatever the schedule: fixed orders and one integer atomic (an
+ *   OR), no floating-point atomic.
+ * Memory.  O(npoints (ndim + nrestarts)) on the device: x, one byte per point and restart, and per chunk the sums of all
+ *   k * nrestarts <= 4096 clusters.  No npoints x k array of distances exists.
+ *
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_cluster_kmeans:".  NM_ERR_ARG, checked
+ * before the device is looked for and with every output left untouched, for, in this order: npoints outside 1..2^21, ndim outside
+ * 1..16, k outside 1..256 or k > npoints, nrestarts outside 1..64 or k * nrestarts > 4096, max_iter outside 1..10000, a tol that is
+ * not finite or is negative, a pointer that is null, a value of init that is not finite (the message names the restart and the
+ * centre), a negative device ordinal.  A value of x that is not finite is found on the device by a first screen: NM_ERR_ARG, the
+ * message names the first such point, the outputs are left untouched.  NM_ERR_HIP without a device or when a HIP call fails.
+ *
+ * x [npoints][ndim]; init [nrestarts][k][ndim]; label [npoints]; centre [k][ndim]; count [k];
+ * inertia, iters, status [nrestarts]; best [1]. */
+int nm_cluster_kmeans(int device, int64_t npoints, int ndim, const double *x, int k, int nrestarts, const double *init,
+                      int max_iter, double tol, int32_t *label, double *centre, int32_t *count,
+                      double *inertia, int32_t *iters, int32_t *status, int32_t *best);
+
+/* Where the device time of the calling thread's last successful nm_cluster_kmeans went, in milliseconds between device events:
+ * ms[0] the upload and the screen, ms[1] the assignment passes and the inertia pass, ms[2] the update passes and the host's looks at
+ * the restarts' states.  Slots of its own: nm_distr_last_timing and nm_cluster_last_timing are left alone by a k-means call. */
+int nm_cluster_kmeans_last_timing(double *ms);
+
 /* nm_distr_lof — the local outlier factor of many small sets of points at once: not a histogram of frames
  * but the distribution of a grid point's samples among themselves.  The reference's inlier selection (lammps_vae.py -ad) fits
  * sklearn.neighbors.LocalOutlierFactor(contamination='auto'), 20 neighbours, to the samples of every (P, T) grid point alone.  The

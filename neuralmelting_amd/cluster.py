@@ -14,6 +14,12 @@ The unit of -nc: the used components are divided by one factor, max - min of com
 fraction of pc0's range and the geometry is unchanged.  There is no default: `.F.cld.npy`, the number of samples within EPS of each
 sample, is the data to choose it from.  Of the NK largest clusters the one with the lowest mean target temperature is cl0 (on a
 melting grid the solid), the next cl1 (the liquid).
+
+-cl kmeans is the reference's other clustering, for a grid whose number of phases is known: -nc is then the number of clusters and
+nothing is tuned.  The restarts (-ri, seeded on the host by k-means++ from -rs) run as one batch in the library (nm_cluster_kmeans),
+the restart with the smallest inertia gives the labels, and `.F.clr.npy` says how every restart ended:
+
+    python -m neuralmelting_amd.cluster -v -n remcmc_run_5 -e LJ -sk 128 -cl kmeans -nc 2
 """
 import argparse
 import sys
@@ -25,6 +31,7 @@ from . import _stage as S
 from ._stage import spread
 
 MAX_POINTS, MAX_DIM, MAX_KEPT = 2 ** 21, 16, 8     # include/nm_cluster.h: npoints and ndim; the indicators of -nk
+MAX_K, MAX_RESTARTS, MAX_CENTRES, MAX_ITER = 256, 64, 4096, 10000      # include/nm_distr.h, nm_cluster_kmeans: k, nrestarts, their product, max_iter
 
 
 def parse_args(argv=None):
@@ -32,7 +39,10 @@ def parse_args(argv=None):
         description='DBSCAN of the projections .F.pcz of pca over the (P, T) grid: .F.cll (PN, TN, SN) int32 the labels, -1 for noise and for '
         'samples left out; .F.cld (PN, TN, SN) int32 the samples within EPS, the sample among them; .F.cls (K, 3 + ND) float64 per '
         'cluster: members, core members, mean target temperature, centroid in the projections; .F.cl0 ... (PN, TN, SN) float64 the '
-        'membership indicators of the NK largest clusters from the coldest to the hottest, for reweight -ob F.cl1 -hq F.cl1 -hx 0.5.')
+        'membership indicators of the NK largest clusters from the coldest to the hottest, for reweight -ob F.cl1 -hq F.cl1 -hx 0.5.  '
+        'With -cl kmeans: .F.cll the labels of the best restart, .F.cls with core members = members, .F.cl0 ... as above, .F.clr (R, 3) '
+        'float64 the inertia, the iterations and the status (0 a fixed point, 1 within -tl, 2 stopped at -mi) of every restart; '
+        '.F.cld is not written.')
     p.add_argument('-v', '--verbose', action='store_true')
     p.add_argument('-n', '--name', type=str, default='remcmc_init')
     p.add_argument('-e', '--element', type=str, default='LJ')
@@ -40,9 +50,16 @@ def parse_args(argv=None):
     p.add_argument('-em', '--embedding', type=str, default='pcz', choices=('pcz', 'mfy'),
                    help="what is clustered: pca's projections <PREFIX>.F.pcz.npy, or manifold's embedding <PREFIX>.F.mfy.npy of the same -sk and -sd")
     p.add_argument('-nd', '--dimensions', type=int, default=2, help='leading components used, 1..16 and at most LD')
+    p.add_argument('-cl', '--clustering', type=str, default='dbscan', choices=('dbscan', 'kmeans'))
     p.add_argument('-nc', '--neighbourhood', type=float, required=True, metavar='EPS',
-                   help='the radius of a neighbourhood as a fraction of the range of component 0')
-    p.add_argument('-ms', '--min_samples', type=int, default=5, help='samples within EPS, itself among them, that make a sample a core')
+                   help='the radius of a neighbourhood as a fraction of the range of component 0; with -cl kmeans the number of clusters, 1..256')
+    p.add_argument('-ms', '--min_samples', type=int, default=5,
+                   help='samples within EPS, itself among them, that make a sample a core; ignored with -cl kmeans')
+    p.add_argument('-ri', '--restarts', type=int, default=10, help='-cl kmeans: restarts from k-means++ seeds, 1..64; the best is kept')
+    p.add_argument('-mi', '--max_iter', type=int, default=300, help='-cl kmeans: steps of a restart at most, 1..10000')
+    p.add_argument('-tl', '--tolerance', type=float, default=1e-4,
+                   help="-cl kmeans: a restart stops where its centres' squared shift is at most TL times the mean variance of the used components")
+    p.add_argument('-rs', '--seed', type=int, default=256, help='-cl kmeans: the seed of the k-means++ draws')
     p.add_argument('-nk', '--clusters_kept', type=int, default=2, help='phase indicators written, 1..8')
     p.add_argument('-sk', '--skip', type=int, default=0, help='samples of every grid point left out at its start')
     p.add_argument('-sd', '--stride', type=int, default=1, help='every STRIDE-th sample is clustered')
@@ -53,6 +70,12 @@ def parse_args(argv=None):
     if (a.skip < 0 or a.stride < 1 or not 1 <= a.dimensions <= MAX_DIM or not 1 <= a.clusters_kept <= MAX_KEPT or a.min_samples < 1
             or not (np.isfinite(a.neighbourhood) and a.neighbourhood > 0.0)):
         p.error('need -sk >= 0, -sd >= 1, -nd in 1..16, -nk in 1..8, -ms >= 1 and a finite -nc > 0')
+    if a.clustering == 'kmeans':
+        if a.neighbourhood != int(a.neighbourhood) or not 1 <= a.neighbourhood <= MAX_K:
+            p.error('with -cl kmeans -nc is the number of clusters: an integer in 1..256')
+        if (not 1 <= a.restarts <= MAX_RESTARTS or int(a.neighbourhood) * a.restarts > MAX_CENTRES or not 1 <= a.max_iter <= MAX_ITER
+                or not (np.isfinite(a.tolerance) and a.tolerance >= 0.0) or a.seed < 0):
+            p.error('need -ri in 1..64 with -nc * -ri <= 4096, -mi in 1..10000, a finite -tl >= 0 and -rs >= 0')
     return a
 
 
@@ -65,6 +88,53 @@ def dbscan(x, eps, min_pts, device=0):
     label, degree, ncl = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.zeros(1, dtype=np.int32)
     B.call('nm_cluster_dbscan', device, n, nd, x, float(eps), int(min_pts), label, degree, ncl)
     return label, degree, int(ncl[0])
+
+
+def kmeans(x, init, max_iter=300, tol=0.0, device=0):
+    """nm_cluster_kmeans of x (N, ND) from the initial centres init (R, K, ND): (label (N,) int32, centre (K, ND), count (K,) int32 of
+    the best restart; inertia (R,), iters (R,) int32, status (R,) int32 of every restart; best)"""
+    x, init = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(init, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError('x wants the shape (N, ND)')
+    if init.ndim != 3 or init.shape[2] != x.shape[1]:
+        raise ValueError('init wants the shape (R, K, ND)')
+    (n, nd), (r, k) = x.shape, init.shape[:2]
+    label, centre, count = np.empty(n, dtype=np.int32), np.empty((k, nd)), np.empty(k, dtype=np.int32)
+    inertia, iters, status, best = np.empty(r), np.empty(r, dtype=np.int32), np.empty(r, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    B.call('nm_cluster_kmeans', device, n, nd, x, k, r, init, int(max_iter), float(tol), label, centre, count, inertia, iters, status, best)
+    return label, centre, count, inertia, iters, status, int(best[0])
+
+
+def seeds(x, k, nrestarts, seed):
+    """k-means++ on the host, (R, K, ND): the first centre of a restart is a point drawn uniformly, every further one a point drawn
+    with a probability proportional to its squared distance from the nearest centre so far (a point that is a centre already has
+    none), so a restart's centres are k distinct points of x; numpy.random.default_rng(seed), restart after restart.  ValueError
+    where x has fewer than k distinct points."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError('x wants the shape (N, ND)')
+    rng = np.random.default_rng(seed)
+    out = np.empty((nrestarts, k, x.shape[1]))
+    for r in range(nrestarts):
+        i = int(rng.integers(x.shape[0]))
+        near = np.full(x.shape[0], np.inf)
+        for j in range(k):
+            if j:
+                if not near.max() > 0.0:
+                    raise ValueError('x has only %d distinct points, fewer than the %d clusters' % (j, k))
+                i = int(rng.choice(x.shape[0], p=near / near.sum()))
+            out[r, j] = x[i]
+            near = np.minimum(near, ((x - x[i]) ** 2).sum(axis=1))
+    return out
+
+
+def kmeans_table(label, count, temp, z):
+    """the cluster table (K, 3 + ND) of k-means labels: `table` with every member a core member; a cluster without members is a row
+    of zeros"""
+    out = np.zeros((len(count), 3 + z.shape[1]))
+    for c in np.nonzero(count)[0]:
+        out[c] = table(np.where(label == c, 0, -1), np.ones(len(label), dtype=np.int32), 1, temp, z)[0]
+    return out
 
 
 def scaled(z):
@@ -119,6 +189,8 @@ def main(argv=None):
         if np.isnan(z).any() or not np.isnan(pcz[:, :, out]).all() or not np.isnan(zk[~keep]).all():
             raise SystemExit('cluster: -sk %d -sd %d%s are not those that %s was written with' % (a.skip, a.stride, ' -il' if a.inliers else '', path))
     temp = np.broadcast_to(np.asarray(T, dtype=np.float64)[None, :, None], (pn, tn, kept))[keep]
+    if a.clustering == 'kmeans':
+        return main_kmeans(a, prefix, path, pe.shape, keep, z, temp)
     if a.verbose:
         print('clustering %d of %d samples of %s in %d components, eps %g of the range of pc0, min_pts %d' % (
             n, pn * tn * sn, ft, nd, a.neighbourhood, a.min_samples))
@@ -139,6 +211,42 @@ def main(argv=None):
                                                                               int(np.median(degree))))
         for k, c in enumerate(order):
             print('cl%d: cluster %d, %d members (%d core), mean target temperature %.6g' % (k, c, tab[c, 0], tab[c, 1], tab[c, 2]))
+        if len(order) < a.clusters_kept:
+            print('only %d clusters: cl%d .. cl%d are all zero' % (len(order), len(order), a.clusters_kept - 1))
+    return 0
+
+
+def main_kmeans(a, prefix, path, shape, keep, z, temp):
+    """-cl kmeans of the clustered points z (N, ND) with their target temperatures: the files of the best of -ri restarts"""
+    ft, k, n = a.feature, int(a.neighbourhood), z.shape[0]
+    if k > n:
+        raise SystemExit('cluster: -nc %d clusters are more than the %d samples of %s' % (k, n, path))
+    try:
+        zs = scaled(z)
+        tol = a.tolerance * float(zs.var(axis=0).mean())
+        if a.verbose:
+            print('clustering %d samples of %s in %d components into %d clusters: %d restarts, max_iter %d, tol %g' % (
+                n, ft, z.shape[1], k, a.restarts, a.max_iter, tol))
+        label, centre, count, inertia, iters, status, best = kmeans(zs, seeds(zs, k, a.restarts, a.seed), a.max_iter, tol, a.device)
+    except (RuntimeError, ValueError) as err:
+        raise SystemExit('cluster: %s: %s' % (path, err))
+    tab = kmeans_table(label, count, temp, z)
+    order = [c for c in phases(tab, a.clusters_kept) if count[c]]
+    full = S.spread_kept(label, keep, shape, a.skip, a.stride, -1)
+    np.save(prefix + '.%s.cll.npy' % ft, full)
+    np.save(prefix + '.%s.cls.npy' % ft, tab)
+    np.save(prefix + '.%s.clr.npy' % ft, np.stack([inertia, iters.astype(np.float64), status.astype(np.float64)], axis=1))
+    for c in range(a.clusters_kept):
+        np.save(prefix + '.%s.cl%d.npy' % (ft, c), (full == order[c]).astype(np.float64) if c < len(order) else np.zeros(shape))
+    if a.verbose:
+        print('best restart %d of %d: inertia %.9g after %d steps, status %d; the inertias lie in %.9g .. %.9g' % (
+            best, a.restarts, inertia[best], iters[best], status[best], inertia.min(), inertia.max()))
+        if status[best] == 2:
+            print('warning: the best restart stopped at -mi %d before its centres came to rest' % a.max_iter)
+        if count.min() == 0:
+            print('warning: %d clusters of the best restart have no member' % int((count == 0).sum()))
+        for c, j in enumerate(order):
+            print('cl%d: cluster %d, %d members, mean target temperature %.6g' % (c, j, tab[j, 0], tab[j, 2]))
         if len(order) < a.clusters_kept:
             print('only %d clusters: cl%d .. cl%d are all zero' % (len(order), len(order), a.clusters_kept - 1))
     return 0

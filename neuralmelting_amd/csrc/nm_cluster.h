@@ -49,6 +49,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nm_d2.h"
 #include "nm_scan.h"
 
 namespace nm {
@@ -66,18 +67,7 @@ constexpr int CL_SPAN = 128;                        // tiles a workgroup walks a
 using ClScan = ScanShape<CL_BLOCK, CL_RPT, CL_TILE, CL_GRID, CL_SPAN>;
 static_assert(CL_TILE <= CL_BLOCK, "a tile's ints are staged by one thread each");
 
-// the squared distance of the header, in the one order that every pass uses
-template <int ND> __device__ __forceinline__ double cl_d2(const double *a, const double *b)
-{
-    double d = a[0] - b[0];
-    double acc = d * d;
-#pragma unroll
-    for (int c = 1; c < ND; ++c) {
-        d = a[c] - b[c];
-        acc = __builtin_fma(d, d, acc);
-    }
-    return acc;
-}
+// (cl_d2, the squared distance of the header in the one order that every pass uses, stands in nm_d2.h: k-means shares it)
 
 __device__ __forceinline__ int cl_peek(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

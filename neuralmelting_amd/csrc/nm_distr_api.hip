@@ -1,11 +1,14 @@
 // nm_distr_api.hip — the structural histograms and order parameters of include/nm_distr.h over the kernels of nm_distr.h
 // (lammps_distr.py:123-171).  Every entry point takes a device ordinal, owns what it allocates for the length of the call and
 // walks the samples in chunks.  The last one, nm_distr_lof, is the outlier stage's (kernels: nm_lof.h): float64 points in sets, one
-// upload, the screen of nm_scan.h, the neighbour pass and two gathers.
+// upload, the screen of nm_scan.h, the neighbour pass and two gathers.  nm_cluster_kmeans, the cluster stage's k-means (kernels:
+// nm_kmeans.h), stands here too, with this file's error channel: the screen, the chain of steps of all restarts with a look at their
+// states every KM_LOOK steps, and the choice of the best restart.
 #include "../../include/nm_distr.h"
 #include "nm_distr.h"
 #include "nm_distr_w.h"
 #include "nm_lof.h"
+#include "nm_kmeans.h"
 #include "nm_host.h"
 
 #include <cmath>
@@ -201,6 +204,21 @@ enum { LOF_T_UPLOAD, LOF_T_NEIGHBOURS, LOF_T_LRD, LOF_T_LOF, LOF_T_COUNT };
 thread_local double g_distr_ms[LOF_T_COUNT];
 using LofNeighbours = void (*)(int, int, int, const double *, int *, double *, double *);
 const auto LOF_NEIGHBOURS = scan_table<LOF_MAXDIM>([](auto nd) -> LofNeighbours { return nm_lof_neighbours_kernel<decltype(nd)::value>; });
+
+// the slots of nm_cluster_kmeans_last_timing
+enum { KM_T_UPLOAD, KM_T_ASSIGN, KM_T_UPDATE, KM_T_COUNT };
+thread_local double g_kmeans_ms[KM_T_COUNT];
+
+// the kernels of k-means for one ndim
+struct Lloyd {
+    void (*assign)(int, const double *, int, int, const double *, const int *, size_t, uint8_t *, int *);
+    void (*sums)(int, const double *, int, int, int, const int *, const int *, size_t, const uint8_t *, double *, int *);
+    void (*inertia)(int, const double *, int, int, const double *, size_t, const uint8_t *, double *);
+};
+const auto LLOYD = scan_table<KM_MAXDIM>([](auto nd) {
+    constexpr int ND = decltype(nd)::value;
+    return Lloyd{nm_kmeans_assign_kernel<ND>, nm_kmeans_sums_kernel<ND>, nm_kmeans_inertia_kernel<ND>};
+});
 } // namespace
 
 extern "C" {
@@ -658,6 +676,86 @@ int nm_distr_lof(int device, int64_t nsets, int npts, int ndim, const double *x,
     STAGE_CHK(fn, d_lrd.download(lrd, n));
     STAGE_CHK(fn, d_kdist.download(kdist, n));
     if (nbr) STAGE_CHK(fn, d_nbr.download(nbr, (size_t)n * k));
+    return NM_OK;
+}
+
+int nm_cluster_kmeans_last_timing(double *ms) { return last_timing("nm_cluster_kmeans_last_timing", g_kmeans_ms, ms); }
+
+int nm_cluster_kmeans(int device, int64_t npoints, int ndim, const double *x, int k, int nrestarts, const double *init, int max_iter,
+                      double tol, int32_t *label, double *centre, int32_t *count, double *inertia, int32_t *iters, int32_t *status,
+                      int32_t *best)
+{
+    static const char *const fn = "nm_cluster_kmeans";
+    if (npoints < 1 || npoints > KM_MAXN) return refuse(fn, "npoints must lie in 1..2^21");
+    if (ndim < 1 || ndim > KM_MAXDIM) return refuse(fn, "ndim must lie in 1..16");
+    if (k < 1 || k > KM_MAXK || k > npoints) return refuse(fn, "k must lie in 1..256 and be at most npoints");
+    if (nrestarts < 1 || nrestarts > KM_MAXR || k * nrestarts > KM_MAXCOLS)
+        return refuse(fn, "nrestarts must lie in 1..64 and k * nrestarts be at most 4096");
+    if (max_iter < 1 || max_iter > 10000) return refuse(fn, "max_iter must lie in 1..10000");
+    if (!std::isfinite(tol) || tol < 0.0) return refuse(fn, "tol must be finite and not negative");
+    if (!x || !init || !label || !centre || !count || !inertia || !iters || !status || !best) return refuse(fn, "a needed pointer is null");
+    const int64_t bad = first_not_finite(init, (int64_t)nrestarts * k * ndim);
+    if (bad >= 0)
+        return fail(NM_ERR_ARG, std::string(fn) + ": init is not finite in restart " + std::to_string(bad / ((int64_t)k * ndim)) + ", centre " +
+                                    std::to_string(bad / ndim % k));
+    if (const int rc = stage_device(fn, device)) return rc;
+    const int n = (int)npoints, nr = nrestarts, nchunks = (n + KM_CHUNK - 1) / KM_CHUNK;
+    const size_t stride = (size_t)nchunks * KM_CHUNK;           // of a restart's labels
+    const Lloyd &kn = LLOYD[ndim - 1];
+    const dim3 rows((unsigned)((n + KM_ROWS - 1) / KM_ROWS)), chunks((unsigned)nchunks, (unsigned)nr);
+    Laps<KM_T_COUNT> laps;
+    DevBuf<double> d_x, d_centre, d_part, d_ipart;
+    DevBuf<uint8_t> d_lab;
+    DevBuf<int> d_cntp, d_ctl;                                  // d_ctl: state, status, iters, changed, nr ints each
+    laps.lap(KM_T_UPLOAD);
+    STAGE_CHK(fn, d_x.upload(x, (size_t)n * ndim));
+    STAGE_CHK(fn, d_centre.upload(init, (size_t)nr * k * ndim));
+    STAGE_CHK(fn, d_part.alloc((size_t)nchunks * nr * k * ndim));
+    STAGE_CHK(fn, d_cntp.alloc((size_t)nchunks * nr * k));
+    STAGE_CHK(fn, d_ipart.alloc((size_t)nchunks * nr));
+    STAGE_CHK(fn, d_lab.alloc(stride * nr));
+    STAGE_CHK(fn, d_ctl.alloc_zeroed((size_t)4 * nr));          // KM_RUN
+    int *const d_state = d_ctl, *const d_status = d_state + nr, *const d_iters = d_status + nr, *const d_changed = d_iters + nr;
+    int first = -1;
+    STAGE_CHK(fn, scan_screen<KmScan>(n, ndim, d_x, first));
+    if (first >= 0) return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in point " + std::to_string(first));
+    laps.lap(KM_T_UPLOAD);
+    // step max_iter + 1 holds nothing but the last assignment of a restart that stopped at max_iter
+    std::vector<int> ctl((size_t)4 * nr);
+    for (int step = 1, live = nr; live && step <= max_iter + 1; ++step) {
+        hipLaunchKernelGGL(kn.assign, rows, dim3(KM_BLOCK), 0, 0, n, d_x, k, nr, d_centre, d_state, stride, d_lab, d_changed);
+        laps.lap(KM_T_ASSIGN);
+        hipLaunchKernelGGL(kn.sums, chunks, dim3(KM_BLOCK), 0, 0, n, d_x, k, nr, step, d_state, d_changed, stride, d_lab, d_part, d_cntp);
+        hipLaunchKernelGGL(nm_kmeans_finish_kernel, dim3((unsigned)nr), dim3(KM_BLOCK), 0, 0, ndim, k, nr, nchunks, step, max_iter, tol, d_part,
+                           d_cntp, d_centre, d_state, d_status, d_iters, d_changed);
+        STAGE_CHK(fn, hipGetLastError());
+        laps.lap(KM_T_UPDATE);
+        if (step % KM_LOOK && step != max_iter + 1) continue;
+        STAGE_CHK(fn, d_ctl.download(ctl.data(), (size_t)4 * nr));
+        live = 0;
+        for (int r = 0; r < nr; ++r) live += ctl[r] != KM_DONE;
+        laps.lap(KM_T_UPDATE);
+    }
+    hipLaunchKernelGGL(kn.inertia, chunks, dim3(64), 0, 0, n, d_x, k, nr, d_centre, stride, d_lab, d_ipart);
+    STAGE_CHK(fn, hipGetLastError());
+    laps.lap(KM_T_ASSIGN);
+    STAGE_CHK(fn, hipDeviceSynchronize());
+    laps.book(g_kmeans_ms);
+    std::vector<double> ipart((size_t)nchunks * nr), sum((size_t)nr, 0.0), cen((size_t)k * ndim);
+    std::vector<uint8_t> lab((size_t)n);
+    STAGE_CHK(fn, d_ipart.download(ipart.data(), ipart.size()));
+    int b = 0;
+    for (int r = 0; r < nr; ++r) {
+        for (int c = 0; c < nchunks; ++c) sum[r] += ipart[(size_t)c * nr + r];      // the chunks ascending
+        if (sum[r] < sum[b]) b = r;                             // the lowest index on equal bits
+    }
+    STAGE_CHK(fn, hipMemcpy(lab.data(), d_lab.p + stride * b, (size_t)n, hipMemcpyDeviceToHost));
+    STAGE_CHK(fn, hipMemcpy(cen.data(), d_centre.p + (size_t)b * k * ndim, cen.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int j = 0; j < k; ++j) count[j] = 0;
+    for (int i = 0; i < n; ++i) { label[i] = lab[i]; ++count[lab[i]]; }
+    for (size_t e = 0; e < cen.size(); ++e) centre[e] = cen[e];
+    for (int r = 0; r < nr; ++r) { inertia[r] = sum[r]; status[r] = ctl[nr + r]; iters[r] = ctl[2 * nr + r]; }
+    *best = b;
     return NM_OK;
 }
 
