@@ -230,6 +230,57 @@ def test_layer_gradients_of_the_restatement_are_autograd_s():
     np.testing.assert_allclose(gb, ab.numpy(), atol=1e-13)
 
 
+# ---- a guard on the case lists of tests/test_vae_forms_gpu.py, not an oracle: vae_split, wgrad_split and bgrad_split of nm_vae_api.hip
+# restated, and every edge of a split that those cases are there to reach.  It fails when the constants change and the cases
+# silently stop covering an edge.
+def vae_split(count, most, even):
+    """(L, chunks): count positions in chunks of L consecutive ones, at most `most` of them; even: L is even"""
+    L = -(-count // most)
+    if even:
+        L = max(2, L + (L & 1))
+    L = max(L, 1)
+    return L, -(-count // L)
+
+
+def splits_of(case):
+    """(count, L, chunks, on the matrix unit) of the weight gradient's split, (rows, L, chunks) of the bias gradient's"""
+    cin, cout, stride, tr, side, n = case
+    so = side * stride if tr else side // stride
+    mfma = cin % 32 == 0 and cout % 32 == 0
+    count, rows = n * min(side, so) ** 3, n * so ** 3
+    return (count,) + vae_split(count, 32 if mfma else 256, mfma) + (mfma,), (rows,) + vae_split(rows, 256, False)
+
+
+def test_the_forms_cases_reach_every_edge_of_the_splits():
+    from test_vae_forms_gpu import CUBE_CASES, PLAIN_CASES
+    txt = open(os.path.join(ROOT, 'neuralmelting_amd', 'csrc', 'nm_vae.h')).read()
+    assert re.search(r'VAE_WG_CHUNKS_MFMA = 32, VAE_WG_CHUNKS_PLAIN = 256, VAE_BG_CHUNKS = 256;', txt)
+    wg, bg = zip(*[splits_of(c) for c in CUBE_CASES + PLAIN_CASES])
+    both = [(count, L, chunks) for count, L, chunks, _ in wg] + list(bg)
+    for count, L, chunks in both:
+        assert (chunks - 1) * L < count <= chunks * L and chunks <= 256
+    assert all(L % 2 == 0 and chunks <= 32 for _, L, chunks, mfma in wg if mfma)
+    reached = {
+        'a single chunk, matrix unit': any(mfma and chunks == 1 for _, _, chunks, mfma in wg),
+        'a single chunk, plain': any(not mfma and chunks == 1 for _, _, chunks, mfma in wg),
+        'a single chunk, bias': any(chunks == 1 for _, _, chunks in bg),
+        'a ragged last sixteen in the sum of the chunks, matrix unit': any(mfma and chunks > 16 and chunks % 16 for _, _, chunks, mfma in wg),
+        'a ragged last sixteen in the sum of the chunks, plain': any(not mfma and chunks > 16 and chunks % 16 for _, _, chunks, mfma in wg),
+        'a ragged last sixteen in the sum of the chunks, bias': any(chunks > 16 and chunks % 16 for _, _, chunks in bg),
+        'fewer than sixteen chunks but more than one': any(1 < chunks < 16 for _, _, chunks in both),
+        'all 32 chunks of the matrix unit': any(mfma and chunks == 32 for _, _, chunks, mfma in wg),
+        'a last chunk shorter than L, matrix unit': any(mfma and count % L for count, L, _, mfma in wg),
+        'a last chunk shorter than L, plain': any(not mfma and count % L for count, L, _, mfma in wg),
+        'a last chunk shorter than L, bias': any(rows % L for rows, L, _ in bg),
+        # L is even and the two half-waves take alternate positions: an odd count ends on the low half-wave, the high one's is masked
+        'an odd position count under the even-L rule, one chunk': any(mfma and count % 2 and chunks == 1 for count, _, chunks, mfma in wg),
+        'an odd position count under the even-L rule, 32 chunks': any(mfma and count % 2 and chunks == 32 for count, _, chunks, mfma in wg),
+        'a plain split with L >= 2': any(not mfma and L >= 2 for _, L, _, mfma in wg),
+        'a bias split with L >= 2': any(L >= 2 for _, L, _ in bg),
+    }
+    assert all(reached.values()), [k for k, v in reached.items() if not v]
+
+
 def test_command_line_refusals(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
     for argv in (['-ld', '0'], ['-ld', '65'], ['-bs', '0'], ['-vf', '1.0'], ['-lr', '0'], ['-sc', 'tanh'], ['-ep', '0']):

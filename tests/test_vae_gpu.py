@@ -1,7 +1,9 @@
 """The VAE stage on the GPU (include/nm_vae.h) against tests/vae_ref.py: every layer of the network at sides 4 (a 1^3 bottleneck:
 every tap but the centre is padding), 8 and 12 (odd inner sides 6 -> 3) and n = 1, 3, 65 (ragged against every 32- and 64-row tile),
 exact on integers and within the any-order summation bound on floats; the model's forward, gradient, Nadam steps and training
-against float64 within 8 times what float32 on the CPU differs from it; and neuralmelting_amd.vae end to end."""
+against float64 within 8 times what float32 on the CPU differs from it, also at sides 16 and 32, latent sizes 1 and 64, without noise,
+at a batch of one, a batch longer than the epoch and a repeated sample; a sample's forward bits whatever its batch; one context through
+many calls; and neuralmelting_amd.vae end to end.  (tests/test_vae_forms_gpu.py: the kernel forms that these layers do not reach.)"""
 import ctypes as C
 import functools
 
@@ -107,11 +109,11 @@ def gpu_dense(x, w, b, act):
     return y
 
 
-def gpu_dense_grad(x, w, y, gy, act):
+def gpu_dense_grad(x, w, y, gy, act, want_gx=True):
     n, (din, dout) = x.shape[0], w.shape
     gx, gw, gb = np.full(x.shape, SENT), np.full(w.shape, SENT), np.full(dout, SENT)
-    _check(B.load().nm_vae_dense_grad(0, n, din, dout, act, _p(x), _p(w), _p(y), _p(gy), _p(gx), _p(gw), _p(gb)))
-    assert (gx != SENT).all() and (gw != SENT).all() and (gb != SENT).all()
+    _check(B.load().nm_vae_dense_grad(0, n, din, dout, act, _p(x), _p(w), _p(y), _p(gy), _p(gx) if want_gx else None, _p(gw), _p(gb)))
+    assert (gw != SENT).all() and (gb != SENT).all() and (gx != SENT).all() == want_gx
     return gx, gw, gb
 
 
@@ -204,15 +206,20 @@ def tensors(S, LD):
     return [(names[i], slice(int(off[i]), int(off[i + 1]))) for i in range(26)]
 
 
-@functools.lru_cache(maxsize=None)
-def model_case(S, LD, n):
-    """random parameters (the command line's initial ones, with biases that count), n samples in [0, 1), noise; the restatement's
-    forward and gradient in both precisions, computed once"""
-    rng = np.random.default_rng(S * 1000 + LD * 10 + n)
+def random_params(S, LD, rng):
+    """the command line's initial parameters, with biases that count"""
     theta = vae.initial_params(S, LD, rng)
     off = R.offsets(S, LD)
     for l in range(13):
         theta[off[2 * l + 1]:off[2 * l + 2]] = 0.1 * rng.standard_normal(int(off[2 * l + 2] - off[2 * l + 1]))
+    return theta
+
+
+@functools.lru_cache(maxsize=None)
+def model_case(S, LD, n):
+    """random parameters, n samples in [0, 1), noise; the restatement's forward and gradient in both precisions, computed once"""
+    rng = np.random.default_rng(S * 1000 + LD * 10 + n)
+    theta = random_params(S, LD, rng)
     x = rng.random((n + 2, S, S, S), dtype=np.float32)
     idx = np.arange(n + 2, dtype=np.int64)[::-1][:n].copy()                 # the resident samples in another order, two left out
     eps = rng.standard_normal((n, LD), dtype=np.float32)
@@ -237,7 +244,8 @@ def raw_grad(m, idx, eps):
     return g, loss
 
 
-MODEL_CASES = [(4, 2, 3), (8, 8, 65), (12, 3, 1)]
+# (the last two: long sides, and both ends of the latent size's range)
+MODEL_CASES = [(4, 2, 3), (8, 8, 65), (12, 3, 1), (16, 64, 2), (32, 1, 1)]
 
 
 @pytest.mark.parametrize('S,LD,n', MODEL_CASES)
@@ -315,6 +323,122 @@ def test_optimiser_three_steps():
         m.set_params(theta)                                              # resets the optimiser: the same bits again
         loss2 = m.epoch(idx, eps, 3, 1e-3)
         assert np.array_equal(loss, loss2) and np.array_equal(m.get_params(), got)
+
+
+# ---- the training paths at the edges of their arguments: no noise (the `eps ?` branches), a batch of one (the scale 2 / nb), a batch
+# longer than the epoch, a sample twice in a batch
+def both_precisions(f):
+    """f(torch dtype, numpy type) for float32 and float64"""
+    return f(torch.float32, np.float32), f(torch.float64, np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def seven_samples():
+    S, LD = 4, 2
+    rng = np.random.default_rng(78)
+    return (S, LD, random_params(S, LD, rng), rng.random((7, S, S, S), dtype=np.float32), rng.permutation(7).astype(np.int64),
+            rng.standard_normal((7, LD), dtype=np.float32))
+
+
+def test_model_grad_without_noise():
+    S, LD, n = 4, 2, 3
+    theta, x, idx, _, _ = model_case(S, LD, n)
+    r32, r64 = both_precisions(lambda dt, ty: R.gradient(theta, S, LD, x[idx], None, dt))
+    with vae.Model(S, LD) as m:
+        m.set_params(theta)
+        m.data(x)
+        g, loss = raw_grad(m, idx, None)
+        allowance('grad without noise', g, r32[0], r64[0], tensors(S, LD))
+        allowance('grad loss without noise', loss, np.array(r32[1]), np.array(r64[1]))
+
+
+def test_model_grad_of_a_repeated_sample():
+    S, LD, theta, x, _, eps = seven_samples()
+    idx, e = np.array([5, 2, 5, 0, 5], dtype=np.int64), eps[:5]
+    r32, r64 = both_precisions(lambda dt, ty: R.gradient(theta, S, LD, x[idx], e, dt))
+    with vae.Model(S, LD) as m:
+        m.set_params(theta)
+        m.data(x)
+        g, loss = raw_grad(m, idx, e)
+        allowance('grad of a batch that repeats a sample', g, r32[0], r64[0], tensors(S, LD))
+        allowance('its loss', loss, np.array(r32[1]), np.array(r64[1]))
+
+
+@pytest.mark.parametrize('batch,noise', [(3, False), (1, True), (16, True)], ids=['batch3-no-noise', 'batch1', 'batch16'])
+def test_optimiser_batch_shapes(batch, noise):
+    """7 samples: three steps without noise, seven steps of one sample, one step of all seven (batch > nidx), against the
+    restatement's steps as in test_optimiser_three_steps"""
+    S, LD, theta, x, idx, eps = seven_samples()
+    e = eps if noise else None
+
+    def steps(dt, ty):
+        opt = R.Nadam(theta.astype(ty))
+        loss = R.epoch(opt, S, LD, x, idx, e, batch, 1e-3, dt)
+        return opt.theta, loss
+    r32, r64 = both_precisions(steps)
+    with vae.Model(S, LD) as m:
+        m.set_params(theta)
+        m.data(x)
+        loss = m.epoch(idx, e, batch, 1e-3)
+        got = m.get_params()
+        allowance('Nadam steps at batch %d%s' % (batch, '' if noise else ', no noise'), got.astype(np.float64) - theta, r32[0].astype(np.float64) - theta,
+                  r64[0] - theta, tensors(S, LD))
+        np.testing.assert_allclose(loss, r64[1], rtol=1e-5, atol=1e-6)      # (as in test_optimiser_three_steps)
+
+
+def test_forward_does_not_depend_on_the_batch():
+    """131 samples in eval's batches of 64, 64 and 3: every forward sum is one output's own, in tap and channel order, so a sample's
+    results are the same bits alone, in another batch or at another row of a tile"""
+    S, LD, n = 8, 3, 131
+    rng = np.random.default_rng(80)
+    theta, x = random_params(S, LD, rng), rng.random((n, S, S, S), dtype=np.float32)
+    idx, eps = rng.permutation(n).astype(np.int64), rng.standard_normal((n, LD), dtype=np.float32)
+    with vae.Model(S, LD) as m:
+        m.set_params(theta)
+        m.data(x)
+        whole = raw_eval(m, idx, eps)
+        for sl in [slice(i, i + 1) for i in (0, 63, 64, 127, 128, 130)] + [slice(64, 128)]:
+            part = raw_eval(m, idx[sl].copy(), eps[sl].copy())
+            for what, a, b in zip(('z_mean', 'z_log_var', 'recon', 'rec', 'kl'), part, whole):
+                assert np.array_equal(a, b[sl]), (what, sl)
+
+
+def test_one_context_through_many_calls():
+    """the activations' buffers grow and keep their gradient halves (grad of 3, eval of 70, grad of 3; eval first, then grad), and no
+    call leaves anything behind that the next one reads"""
+    S, LD, n = 4, 2, 70
+    rng = np.random.default_rng(79)
+    theta, x = random_params(S, LD, rng), rng.random((n, S, S, S), dtype=np.float32)
+    few, many = np.array([69, 0, 33], dtype=np.int64), rng.permutation(n).astype(np.int64)
+    eps3, eps70 = rng.standard_normal((3, LD), dtype=np.float32), rng.standard_normal((n, LD), dtype=np.float32)
+    with vae.Model(S, LD) as fresh:
+        fresh.set_params(theta)
+        fresh.data(x)
+        want = raw_eval(fresh, many, eps70)
+        g0 = raw_grad(fresh, few, eps3)                                     # buffers without gradients, then with
+    with vae.Model(S, LD) as m:
+        m.set_params(theta)
+        m.data(x)
+        g1 = raw_grad(m, few, eps3)
+        got = raw_eval(m, many, eps70)
+        assert all(np.array_equal(a, b) for a, b in zip(got, want))
+        g2 = raw_grad(m, few, eps3)
+        m.epoch(many[:6].copy(), eps70[:6].copy(), 2, 1e-3)
+        assert not np.array_equal(m.get_params(), theta)
+        m.set_params(theta)
+        g3 = raw_grad(m, few, eps3)
+        for g in (g0, g2, g3):
+            assert np.array_equal(g[0], g1[0]) and np.array_equal(g[1], g1[1])
+        m.data(x[:5])                                                       # fewer samples: 69 was resident, and is not any more
+        ip, buf, two = few.ctypes.data_as(B.c_int64_p), np.full(m.nparams, SENT), np.full(2, -7.25)
+        assert m.L.nm_vae_grad(m.ctx, 1, ip, None, _p(buf), two.ctypes.data_as(B.c_double_p)) == B.NM_ERR_ARG
+        assert 'idx[0]' in m.L.nm_vae_last_error().decode()
+        out = [np.full((1, LD), SENT), np.full((1, LD), SENT), np.full((1, S ** 3), SENT), np.full(1, SENT), np.full(1, SENT)]
+        assert m.L.nm_vae_eval(m.ctx, 1, ip, None, *[_p(o) for o in out]) == B.NM_ERR_ARG
+        assert m.L.nm_vae_epoch(m.ctx, 1, ip, None, 1, 1e-3, two.ctypes.data_as(B.c_double_p)) == B.NM_ERR_ARG
+        assert (buf == SENT).all() and (two == -7.25).all() and all((o == SENT).all() for o in out)
+        np.testing.assert_array_equal(m.get_params(), theta)
+        raw_grad(m, np.array([4], dtype=np.int64), None)                   # the last of the new samples is taken
 
 
 def test_learning_two_kinds_of_cubes():
