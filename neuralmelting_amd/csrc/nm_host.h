@@ -45,7 +45,7 @@ int stage_device(const char *fn, int device)
 int batch_rest(int n, int t0, int64_t batch) { return (n - t0) < batch ? (n - t0) : (int)batch; }
 
 // the index of the first of x[0 .. n - 1] that is not finite, or -1
-int64_t first_not_finite(const double *x, int64_t n)
+template <class T> int64_t first_not_finite(const T *x, int64_t n)
 {
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(x[i])) return i;

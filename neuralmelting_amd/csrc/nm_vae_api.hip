@@ -150,12 +150,28 @@ int dense_check(const char *fn, int n, int din, int dout, int act)
     return NM_OK;
 }
 
-// ---- the network
+// ---- the network: its activations by name, and one row per layer that net_make fills; the parameters' offsets, the activations'
+// sizes, forward and backward are all walks of these rows
+enum { X, A0, A1, A2, A3, E0, MU, LV, Z, F1, T0, T1, T2, T3, Y, VAE_ACTS, NO_GRAD = -1 };
+
+struct Layer {
+    bool dense;
+    Conv c;                 // a convolution's shape, or
+    int din, dout, act;     // a dense layer's
+    int in, out;            // the activation it reads and the one it writes
+    int gin, add;           // whose gradient buffer takes its data gradient (NO_GRAD: none is taken), and whether it is added there
+};
+Layer conv_layer(const Conv &c, int in, int out, int gin) { return Layer{false, c, 0, 0, 0, in, out, gin, 0}; }
+Layer dense_layer(int din, int dout, int act, int in, int out, int gin, int add = 0) { return Layer{true, Conv{}, din, dout, act, in, out, gin, add}; }
+// backward walks the rows from the last to the first, but the two heads as they came: dm writes E0's gradient, dv adds to it
+constexpr int VAE_BACKWARD[VAE_LAYERS] = {12, 11, 10, 9, 8, 7, 5, 6, 4, 3, 2, 1, 0};
+
 struct Net {
-    int S = 0, LD = 0, h = 0, q = 0, F = 0;
-    Conv c[4], t[5];
-    int64_t off[NM_VAE_NTENSORS + 1];
-    int64_t per() const { return (int64_t)S * S * S; }
+    int LD = 0;
+    Layer layer[VAE_LAYERS];
+    int64_t off[NM_VAE_NTENSORS + 1];   // of layer l the kernel at off[2 l], the bias at off[2 l + 1]
+    int64_t size[VAE_ACTS];             // of an activation, per sample
+    int64_t per() const { return size[X]; }
     int64_t nparams() const { return off[NM_VAE_NTENSORS]; }
 };
 int net_make(const char *fn, int side, int latent, Net &net)
@@ -164,36 +180,42 @@ int net_make(const char *fn, int side, int latent, Net &net)
         return refuse(fn, "side must be a multiple of 4 in 4..32: the decoder doubles a quarter of the side twice and cannot rebuild another one "
                           "(-cb 11 gives 11 -> 6 -> 3 -> 6 -> 12)");
     if (latent < 1 || latent > 64) return refuse(fn, "latent must lie in 1..64");
-    const int S = side, h = S / 2, q = S / 4, LD = latent, F = 64 * q * q * q, R = VAE_ACT_RELU;
-    net.S = S; net.LD = LD; net.h = h; net.q = q; net.F = F;
-    net.c[0] = Conv{S, 1, 32, 1, 0, R};
-    net.c[1] = Conv{S, 32, 64, 2, 0, R};
-    net.c[2] = Conv{h, 64, 32, 1, 0, R};
-    net.c[3] = Conv{h, 32, 64, 2, 0, R};
-    net.t[0] = Conv{q, 64, 64, 1, 1, R};
-    net.t[1] = Conv{q, 64, 32, 2, 1, R};
-    net.t[2] = Conv{h, 32, 64, 1, 1, R};
-    net.t[3] = Conv{h, 64, 32, 2, 1, R};
-    net.t[4] = Conv{S, 32, 1, 1, 1, VAE_ACT_TANH};
-    const int64_t kernel[VAE_LAYERS] = {net.c[0].wcount(), net.c[1].wcount(), net.c[2].wcount(), net.c[3].wcount(), (int64_t)F * 8 * LD, 8 * LD * LD,
-                                        8 * LD * LD, (int64_t)LD * F, net.t[0].wcount(), net.t[1].wcount(), net.t[2].wcount(), net.t[3].wcount(),
-                                        net.t[4].wcount()};
-    const int64_t bias[VAE_LAYERS] = {32, 64, 32, 64, 8 * LD, LD, LD, F, 64, 32, 64, 32, 1};
+    const int S = side, h = S / 2, q = S / 4, LD = latent, F = 64 * q * q * q, R = VAE_ACT_RELU, TANH = VAE_ACT_TANH, NONE = VAE_ACT_NONE;
+    const Layer rows[VAE_LAYERS] = {
+        //          the shape                   reads writes  its data gradient goes to
+        conv_layer({S, 1, 32, 1, 0, R},         X,    A0,     NO_GRAD),     // c0: the samples take no gradient
+        conv_layer({S, 32, 64, 2, 0, R},        A0,   A1,     A0),          // c1
+        conv_layer({h, 64, 32, 1, 0, R},        A1,   A2,     A1),          // c2
+        conv_layer({h, 32, 64, 2, 0, R},        A2,   A3,     A2),          // c3
+        dense_layer(F, 8 * LD, R,               A3,   E0,     A3),          // d0
+        dense_layer(8 * LD, LD, NONE,           E0,   MU,     E0),          // dm
+        dense_layer(8 * LD, LD, NONE,           E0,   LV,     E0, 1),       // dv: added to what dm wrote
+        // d1's data gradient gz goes to MU's gradient buffer (Z has none): nm_vae_latent_grad_kernel turns it into mu's and lv's in place
+        dense_layer(LD, F, R,                   Z,    F1,     MU),          // d1
+        conv_layer({q, 64, 64, 1, 1, R},        F1,   T0,     F1),          // t0
+        conv_layer({q, 64, 32, 2, 1, R},        T0,   T1,     T0),          // t1
+        conv_layer({h, 32, 64, 1, 1, R},        T1,   T2,     T1),          // t2
+        conv_layer({h, 64, 32, 2, 1, R},        T2,   T3,     T2),          // t3
+        conv_layer({S, 32, 1, 1, 1, TANH},      T3,   Y,      T3)};         // t4
+    net.LD = LD;
+    net.size[X] = (int64_t)S * S * S;
+    net.size[Z] = LD;                   // (nm_vae_latent_kernel writes it, no layer does)
     int64_t at = 0;
     for (int l = 0; l < VAE_LAYERS; ++l) {
-        net.off[2 * l] = at; at += kernel[l];
-        net.off[2 * l + 1] = at; at += bias[l];
+        const Layer &L = net.layer[l] = rows[l];
+        net.size[L.out] = L.dense ? L.dout : L.c.out_per();
+        net.off[2 * l] = at; at += L.dense ? (int64_t)L.din * L.dout : L.c.wcount();
+        net.off[2 * l + 1] = at; at += L.dense ? L.dout : L.c.cout;
     }
     net.off[NM_VAE_NTENSORS] = at;
     return NM_OK;
 }
 
-// the activations of a batch (and, for training, their gradients), sized for `cap` samples
+// the activations of a batch (and, for training, the gradients of every layer's output), sized for `cap` samples
 struct Acts {
     int cap = 0;
     bool grads = false;
-    DevBuf<float> x, a[4], e0, mu, lv, z, f1, t[4], y, eps, rec, kl;
-    DevBuf<float> ga[4], ge0, gmu, glv, gf1, gt[4], gy, part;
+    DevBuf<float> v[VAE_ACTS], g[VAE_ACTS], eps, rec, kl, part;
     DevBuf<long long> idx;
 };
 } // namespace
@@ -217,19 +239,17 @@ int acts_reserve(const char *fn, nm_vae_ctx *ctx, int nb, bool grads)
     Acts &A = ctx->acts;
     if (nb <= A.cap && (!grads || A.grads)) return NM_OK;
     const Net &N = ctx->net;
-    const int64_t cap = std::max(nb, A.cap), S3 = N.per(), h3 = (int64_t)N.h * N.h * N.h, F = N.F, LD = N.LD;
+    const int64_t cap = std::max(nb, A.cap);
     Acts B;
-    ACT_ALLOC(B.x, cap * S3); ACT_ALLOC(B.a[0], cap * S3 * 32); ACT_ALLOC(B.a[1], cap * h3 * 64); ACT_ALLOC(B.a[2], cap * h3 * 32); ACT_ALLOC(B.a[3], cap * F);
-    ACT_ALLOC(B.e0, cap * 8 * LD); ACT_ALLOC(B.mu, cap * LD); ACT_ALLOC(B.lv, cap * LD); ACT_ALLOC(B.z, cap * LD); ACT_ALLOC(B.f1, cap * F);
-    ACT_ALLOC(B.t[0], cap * F); ACT_ALLOC(B.t[1], cap * h3 * 32); ACT_ALLOC(B.t[2], cap * h3 * 64); ACT_ALLOC(B.t[3], cap * S3 * 32); ACT_ALLOC(B.y, cap * S3);
-    ACT_ALLOC(B.eps, cap * LD); ACT_ALLOC(B.rec, cap); ACT_ALLOC(B.kl, cap); ACT_ALLOC(B.idx, cap);
+    for (int a = 0; a < VAE_ACTS; ++a) ACT_ALLOC(B.v[a], cap * N.size[a]);
+    ACT_ALLOC(B.eps, cap * N.LD); ACT_ALLOC(B.rec, cap); ACT_ALLOC(B.kl, cap); ACT_ALLOC(B.idx, cap);
     if (grads || A.grads) {
-        ACT_ALLOC(B.ga[0], cap * S3 * 32); ACT_ALLOC(B.ga[1], cap * h3 * 64); ACT_ALLOC(B.ga[2], cap * h3 * 32); ACT_ALLOC(B.ga[3], cap * F);
-        ACT_ALLOC(B.ge0, cap * 8 * LD); ACT_ALLOC(B.gmu, cap * LD); ACT_ALLOC(B.glv, cap * LD); ACT_ALLOC(B.gf1, cap * F);
-        ACT_ALLOC(B.gt[0], cap * F); ACT_ALLOC(B.gt[1], cap * h3 * 32); ACT_ALLOC(B.gt[2], cap * h3 * 64); ACT_ALLOC(B.gt[3], cap * S3 * 32); ACT_ALLOC(B.gy, cap * S3);
+        // backward reads the gradient of every layer's output; X and Z are no layer's output and have none
         size_t part = 1;
-        for (int l = 0; l < 4; ++l) part = std::max(part, part_count(N.c[l]));
-        for (int l = 0; l < 5; ++l) part = std::max(part, part_count(N.t[l]));
+        for (const Layer &L : N.layer) {
+            ACT_ALLOC(B.g[L.out], cap * N.size[L.out]);
+            if (!L.dense) part = std::max(part, part_count(L.c));
+        }
         ACT_ALLOC(B.part, part);
         B.grads = true;
     }
@@ -243,25 +263,17 @@ void forward(nm_vae_ctx *ctx, int nb, const long long *idx, const float *eps, bo
 {
     Acts &A = ctx->acts;
     const Net &N = ctx->net;
-    const float *th = ctx->theta;
-    const int64_t *o = N.off;
-    hipLaunchKernelGGL(nm_vae_take_kernel, dim3(blocks(nb * N.per())), dim3(VAE_BLOCK), 0, 0, ctx->data.p, idx, nb, (long long)N.per(), A.x.p);
+    hipLaunchKernelGGL(nm_vae_take_kernel, dim3(blocks(nb * N.per())), dim3(VAE_BLOCK), 0, 0, ctx->data.p, idx, nb, (long long)N.per(), A.v[X].p);
     ctx->laps.lap(VAE_T_UPLOAD);
-    conv_forward(N.c[0], nb, A.x, th + o[0], th + o[1], A.a[0]);
-    conv_forward(N.c[1], nb, A.a[0], th + o[2], th + o[3], A.a[1]);
-    conv_forward(N.c[2], nb, A.a[1], th + o[4], th + o[5], A.a[2]);
-    conv_forward(N.c[3], nb, A.a[2], th + o[6], th + o[7], A.a[3]);
-    dense_forward(nb, N.F, 8 * N.LD, VAE_ACT_RELU, A.a[3], th + o[8], th + o[9], A.e0);
-    dense_forward(nb, 8 * N.LD, N.LD, VAE_ACT_NONE, A.e0, th + o[10], th + o[11], A.mu);
-    dense_forward(nb, 8 * N.LD, N.LD, VAE_ACT_NONE, A.e0, th + o[12], th + o[13], A.lv);
-    hipLaunchKernelGGL(nm_vae_latent_kernel, dim3(blocks(nb)), dim3(VAE_BLOCK), 0, 0, nb, N.LD, A.mu.p, A.lv.p, eps, A.z.p, A.kl.p);
-    dense_forward(nb, N.LD, N.F, VAE_ACT_RELU, A.z, th + o[14], th + o[15], A.f1);
-    conv_forward(N.t[0], nb, A.f1, th + o[16], th + o[17], A.t[0]);
-    conv_forward(N.t[1], nb, A.t[0], th + o[18], th + o[19], A.t[1]);
-    conv_forward(N.t[2], nb, A.t[1], th + o[20], th + o[21], A.t[2]);
-    conv_forward(N.t[3], nb, A.t[2], th + o[22], th + o[23], A.t[3]);
-    conv_forward(N.t[4], nb, A.t[3], th + o[24], th + o[25], A.y);
-    hipLaunchKernelGGL(nm_vae_rec_kernel, dim3((unsigned)nb), dim3(VAE_BLOCK), 0, 0, nb, (long long)N.per(), A.x.p, A.y.p, A.rec.p, want_gy ? A.gy.p : nullptr);
+    for (int l = 0; l < VAE_LAYERS; ++l) {
+        const Layer &L = N.layer[l];
+        const float *w = ctx->theta.p + N.off[2 * l], *b = ctx->theta.p + N.off[2 * l + 1];
+        if (L.in == Z) hipLaunchKernelGGL(nm_vae_latent_kernel, dim3(blocks(nb)), dim3(VAE_BLOCK), 0, 0, nb, N.LD, A.v[MU].p, A.v[LV].p, eps, A.v[Z].p, A.kl.p);
+        if (L.dense) dense_forward(nb, L.din, L.dout, L.act, A.v[L.in], w, b, A.v[L.out]);
+        else conv_forward(L.c, nb, A.v[L.in], w, b, A.v[L.out]);
+    }
+    hipLaunchKernelGGL(nm_vae_rec_kernel, dim3((unsigned)nb), dim3(VAE_BLOCK), 0, 0, nb, (long long)N.per(), A.v[X].p, A.v[Y].p, A.rec.p,
+                       want_gy ? A.g[Y].p : nullptr);
     ctx->laps.lap(VAE_T_FORWARD);
 }
 
@@ -270,24 +282,25 @@ void backward(nm_vae_ctx *ctx, int nb, const float *eps)
 {
     Acts &A = ctx->acts;
     const Net &N = ctx->net;
-    const float *th = ctx->theta;
-    float *g = ctx->grad;
-    const int64_t *o = N.off;
-    conv_backward(N.t[4], nb, A.t[3], th + o[24], A.y, A.gy, A.gt[3], g + o[24], g + o[25], A.part);
-    conv_backward(N.t[3], nb, A.t[2], th + o[22], A.t[3], A.gt[3], A.gt[2], g + o[22], g + o[23], A.part);
-    conv_backward(N.t[2], nb, A.t[1], th + o[20], A.t[2], A.gt[2], A.gt[1], g + o[20], g + o[21], A.part);
-    conv_backward(N.t[1], nb, A.t[0], th + o[18], A.t[1], A.gt[1], A.gt[0], g + o[18], g + o[19], A.part);
-    conv_backward(N.t[0], nb, A.f1, th + o[16], A.t[0], A.gt[0], A.gf1, g + o[16], g + o[17], A.part);
-    dense_backward(nb, N.LD, N.F, VAE_ACT_RELU, A.z, th + o[14], A.f1, A.gf1, A.gmu, 0, g + o[14], g + o[15]);   // (gmu holds gz here)
-    hipLaunchKernelGGL(nm_vae_latent_grad_kernel, dim3(blocks((int64_t)nb * N.LD)), dim3(VAE_BLOCK), 0, 0, nb, N.LD, A.mu.p, A.lv.p, eps, A.gmu.p, A.glv.p);
-    dense_backward(nb, 8 * N.LD, N.LD, VAE_ACT_NONE, A.e0, th + o[10], A.mu, A.gmu, A.ge0, 0, g + o[10], g + o[11]);
-    dense_backward(nb, 8 * N.LD, N.LD, VAE_ACT_NONE, A.e0, th + o[12], A.lv, A.glv, A.ge0, 1, g + o[12], g + o[13]);
-    dense_backward(nb, N.F, 8 * N.LD, VAE_ACT_RELU, A.a[3], th + o[8], A.e0, A.ge0, A.ga[3], 0, g + o[8], g + o[9]);
-    conv_backward(N.c[3], nb, A.a[2], th + o[6], A.a[3], A.ga[3], A.ga[2], g + o[6], g + o[7], A.part);
-    conv_backward(N.c[2], nb, A.a[1], th + o[4], A.a[2], A.ga[2], A.ga[1], g + o[4], g + o[5], A.part);
-    conv_backward(N.c[1], nb, A.a[0], th + o[2], A.a[1], A.ga[1], A.ga[0], g + o[2], g + o[3], A.part);
-    conv_backward(N.c[0], nb, A.x, th + o[0], A.a[0], A.ga[0], nullptr, g + o[0], g + o[1], A.part);
+    for (const int l : VAE_BACKWARD) {
+        const Layer &L = N.layer[l];
+        const float *w = ctx->theta.p + N.off[2 * l];
+        float *gw = ctx->grad.p + N.off[2 * l], *gb = ctx->grad.p + N.off[2 * l + 1], *gx = L.gin == NO_GRAD ? nullptr : A.g[L.gin].p;
+        if (L.dense) dense_backward(nb, L.din, L.dout, L.act, A.v[L.in], w, A.v[L.out], A.g[L.out], gx, L.add, gw, gb);
+        else conv_backward(L.c, nb, A.v[L.in], w, A.v[L.out], A.g[L.out], gx, gw, gb, A.part);
+        if (L.in == Z)
+            hipLaunchKernelGGL(nm_vae_latent_grad_kernel, dim3(blocks((int64_t)nb * N.LD)), dim3(VAE_BLOCK), 0, 0, nb, N.LD, A.v[MU].p, A.v[LV].p, eps,
+                               A.g[MU].p, A.g[LV].p);
+    }
     ctx->laps.lap(VAE_T_BACKWARD);
+}
+
+// forward, the batch's mean rec and kl into the two floats at `loss` (device), backward: what nm_vae_grad and a step of nm_vae_epoch share
+void batch_gradient(nm_vae_ctx *ctx, int nb, const long long *idx, const float *eps, float *loss)
+{
+    forward(ctx, nb, idx, eps, true);
+    hipLaunchKernelGGL(nm_vae_mean_kernel, dim3(1), dim3(64), 0, 0, nb, ctx->acts.rec.p, ctx->acts.kl.p, loss);
+    backward(ctx, nb, eps);
 }
 
 // what every model call asks first
@@ -304,11 +317,14 @@ int idx_check(const char *fn, const nm_vae_ctx *ctx, int64_t nidx, const int64_t
         if (idx[i] < 0 || idx[i] >= ctx->ndata) return fail(NM_ERR_ARG, std::string(fn) + ": idx[" + std::to_string(i) + "] is outside the resident samples");
     return NM_OK;
 }
-int64_t first_not_finite_f(const float *x, int64_t n)
+// behind a layer primitive's launches: their error, their lap into `slot`, the device's end and the booking of the laps
+int primitive_done(const char *fn, Laps<VAE_T_COUNT> &laps, int slot)
 {
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(x[i])) return i;
-    return -1;
+    STAGE_CHK(fn, hipGetLastError());
+    laps.lap(slot);
+    STAGE_CHK(fn, hipDeviceSynchronize());
+    laps.book(g_vae_ms);
+    return NM_OK;
 }
 } // namespace
 
@@ -351,10 +367,7 @@ int nm_vae_conv(int device, int n, int side_in, int cin, int cout, int stride, i
     STAGE_CHK(fn, dy.alloc((size_t)(n * c.out_per())));
     laps.lap(VAE_T_UPLOAD);
     conv_forward(c, n, dx, dw, db, dy);
-    STAGE_CHK(fn, hipGetLastError());
-    laps.lap(VAE_T_FORWARD);
-    STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book(g_vae_ms);
+    if (const int rc = primitive_done(fn, laps, VAE_T_FORWARD)) return rc;
     STAGE_CHK(fn, dy.download(y, (size_t)(n * c.out_per())));
     return NM_OK;
 }
@@ -380,10 +393,7 @@ int nm_vae_conv_grad(int device, int n, int side_in, int cin, int cout, int stri
     STAGE_CHK(fn, part.alloc(part_count(c)));
     laps.lap(VAE_T_UPLOAD);
     conv_backward(c, n, dx, dw, dy, dgy, gx ? dgx.p : nullptr, dgw, dgb, part);
-    STAGE_CHK(fn, hipGetLastError());
-    laps.lap(VAE_T_BACKWARD);
-    STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book(g_vae_ms);
+    if (const int rc = primitive_done(fn, laps, VAE_T_BACKWARD)) return rc;
     if (gx) STAGE_CHK(fn, dgx.download(gx, (size_t)(n * c.in_per())));
     STAGE_CHK(fn, dgw.download(gw, (size_t)c.wcount()));
     STAGE_CHK(fn, dgb.download(gb, (size_t)cout));
@@ -405,10 +415,7 @@ int nm_vae_dense(int device, int n, int din, int dout, int act, const float *x, 
     STAGE_CHK(fn, dy.alloc((size_t)n * dout));
     laps.lap(VAE_T_UPLOAD);
     dense_forward(n, din, dout, act, dx, dw, db, dy);
-    STAGE_CHK(fn, hipGetLastError());
-    laps.lap(VAE_T_FORWARD);
-    STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book(g_vae_ms);
+    if (const int rc = primitive_done(fn, laps, VAE_T_FORWARD)) return rc;
     STAGE_CHK(fn, dy.download(y, (size_t)n * dout));
     return NM_OK;
 }
@@ -432,10 +439,7 @@ int nm_vae_dense_grad(int device, int n, int din, int dout, int act, const float
     STAGE_CHK(fn, dgb.alloc((size_t)dout));
     laps.lap(VAE_T_UPLOAD);
     dense_backward(n, din, dout, act, dx, dw, dy, dgy, gx ? dgx.p : nullptr, 0, dgw, dgb);
-    STAGE_CHK(fn, hipGetLastError());
-    laps.lap(VAE_T_BACKWARD);
-    STAGE_CHK(fn, hipDeviceSynchronize());
-    laps.book(g_vae_ms);
+    if (const int rc = primitive_done(fn, laps, VAE_T_BACKWARD)) return rc;
     if (gx) STAGE_CHK(fn, dgx.download(gx, (size_t)n * din));
     STAGE_CHK(fn, dgw.download(gw, (size_t)din * dout));
     STAGE_CHK(fn, dgb.download(gb, (size_t)dout));
@@ -480,7 +484,7 @@ int nm_vae_set_params(nm_vae_ctx *ctx, const float *theta)
     if (const int rc = ctx_enter(fn, ctx, false, false)) return rc;
     if (!theta) return refuse(fn, "a needed pointer is null");
     const size_t np = (size_t)ctx->net.nparams();
-    if (first_not_finite_f(theta, (int64_t)np) >= 0) return refuse(fn, "a parameter is not finite");
+    if (first_not_finite(theta, (int64_t)np) >= 0) return refuse(fn, "a parameter is not finite");
     STAGE_CHK(fn, hipSetDevice(ctx->device));
     STAGE_CHK(fn, hipMemcpy(ctx->theta.p, theta, np * sizeof(float), hipMemcpyHostToDevice));
     STAGE_CHK(fn, ctx->m.zero(np));
@@ -554,11 +558,11 @@ int nm_vae_eval(nm_vae_ctx *ctx, int64_t nidx, const int64_t *idx, const float *
         if (eps) STAGE_CHK(fn, hipMemcpy(A.eps.p, eps + b0 * LD, (size_t)nb * LD * sizeof(float), hipMemcpyHostToDevice));
         forward(ctx, nb, A.idx, eps ? A.eps.p : nullptr, false);
         STAGE_CHK(fn, hipGetLastError());
-        STAGE_CHK(fn, A.mu.download(hmu.data() + b0 * LD, (size_t)nb * LD));
-        STAGE_CHK(fn, A.lv.download(hlv.data() + b0 * LD, (size_t)nb * LD));
+        STAGE_CHK(fn, A.v[MU].download(hmu.data() + b0 * LD, (size_t)nb * LD));
+        STAGE_CHK(fn, A.v[LV].download(hlv.data() + b0 * LD, (size_t)nb * LD));
         STAGE_CHK(fn, A.rec.download(hrec.data() + b0, (size_t)nb));
         STAGE_CHK(fn, A.kl.download(hkl.data() + b0, (size_t)nb));
-        if (recon) STAGE_CHK(fn, A.y.download(hy.data() + b0 * per, (size_t)(nb * per)));
+        if (recon) STAGE_CHK(fn, A.v[Y].download(hy.data() + b0 * per, (size_t)(nb * per)));
         ctx->laps.lap(VAE_T_UPLOAD);
     }
     ctx->laps.book(g_vae_ms);
@@ -587,9 +591,7 @@ int nm_vae_grad(nm_vae_ctx *ctx, int64_t nidx, const int64_t *idx, const float *
     ctx->laps.lap(VAE_T_UPLOAD);
     STAGE_CHK(fn, hipMemcpy(A.idx.p, idx, (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice));
     if (eps) STAGE_CHK(fn, hipMemcpy(A.eps.p, eps, (size_t)nb * N.LD * sizeof(float), hipMemcpyHostToDevice));
-    forward(ctx, nb, A.idx, eps ? A.eps.p : nullptr, true);
-    hipLaunchKernelGGL(nm_vae_mean_kernel, dim3(1), dim3(64), 0, 0, nb, A.rec.p, A.kl.p, ctx->lossb.p);
-    backward(ctx, nb, eps ? A.eps.p : nullptr);
+    batch_gradient(ctx, nb, A.idx, eps ? A.eps.p : nullptr, ctx->lossb.p);
     STAGE_CHK(fn, hipGetLastError());
     STAGE_CHK(fn, hipDeviceSynchronize());
     ctx->laps.book(g_vae_ms);
@@ -614,7 +616,6 @@ int nm_vae_epoch(nm_vae_ctx *ctx, int64_t nidx, const int64_t *idx, const float 
     const Net &N = ctx->net;
     const int64_t steps = (nidx + batch - 1) / batch, np = N.nparams();
     if (const int rc = acts_reserve(fn, ctx, (int)std::min<int64_t>(batch, nidx), true)) return rc;
-    Acts &A = ctx->acts;
     STAGE_CHK(fn, ctx->lossb.reserve((size_t)(2 * steps)));
     ctx->laps = Laps<VAE_T_COUNT>();
     ctx->laps.lap(VAE_T_UPLOAD);
@@ -627,10 +628,7 @@ int nm_vae_epoch(nm_vae_ctx *ctx, int64_t nidx, const int64_t *idx, const float 
     for (int64_t s = 0; s < steps; ++s) {
         const int64_t b0 = s * batch;
         const int nb = (int)std::min<int64_t>(batch, nidx - b0);
-        const float *e = eps ? deps.p + b0 * N.LD : nullptr;
-        forward(ctx, nb, didx.p + b0, e, true);
-        hipLaunchKernelGGL(nm_vae_mean_kernel, dim3(1), dim3(64), 0, 0, nb, A.rec.p, A.kl.p, ctx->lossb.p + 2 * s);
-        backward(ctx, nb, e);
+        batch_gradient(ctx, nb, didx.p + b0, eps ? deps.p + b0 * N.LD : nullptr, ctx->lossb.p + 2 * s);
         // Keras 2's Nadam: the schedule in float64 on the host
         const double t = (double)(ctx->step + 1);
         const double mc_t = 0.9 * (1.0 - 0.5 * std::pow(0.96, 0.004 * t)), mc_t1 = 0.9 * (1.0 - 0.5 * std::pow(0.96, 0.004 * (t + 1.0)));

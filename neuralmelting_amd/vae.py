@@ -32,6 +32,7 @@ SCALERS = ('none', 'global', 'standard', 'minmax')
 SUFFIXES = ('vaw', 'vat', 'vam', 'vas', 'vak', 'var')
 FACTOR, PATIENCE, MIN_DELTA = 0.1, 4, 1e-4      # ReduceLROnPlateau, Keras's defaults
 CONV_LAYERS = (0, 1, 2, 3, 8, 9, 10, 11, 12)    # of the 13 layers c0 c1 c2 c3 d0 dm dv d1 t0 t1 t2 t3 t4
+TRANSPOSED_FROM = 8                             # t0 .. t4 are transposed convolutions
 
 
 def parse_args(argv=None):
@@ -81,12 +82,9 @@ def layout(side, latent):
 def initial_params(side, latent, rng):
     """the flat float32 parameter vector as Keras would draw its kind: see the module's text"""
     off = layout(side, latent)
-    f = 64 * (side // 4) ** 3
-    dense = {4: (f, 8 * latent), 5: (8 * latent, latent), 6: (8 * latent, latent), 7: (latent, f)}
-    fan = {0: 1, 1: 32, 2: 64, 3: 32, 8: 64, 9: 32, 10: 64, 11: 32, 12: 1}        # the kernel's axis -2
     theta = np.zeros(off[-1], dtype=np.float32)
     for l in range(13):
-        count = int(off[2 * l + 1] - off[2 * l])
+        count, out = int(off[2 * l + 1] - off[2 * l]), int(off[2 * l + 2] - off[2 * l + 1])      # of the kernel; of the bias: cout or dout
         if l in CONV_LAYERS:
             w = rng.standard_normal(count)
             while True:
@@ -94,9 +92,10 @@ def initial_params(side, latent, rng):
                 if far.size == 0:
                     break
                 w[far] = rng.standard_normal(far.size)
-            w *= np.sqrt(2.0 / (27 * fan[l]))
+            # the kernel's axis -2: cin of a convolution (k, cin, cout), cout of a transposed one (k, cout, cin)
+            w *= np.sqrt(2.0 / (27 * (count // (27 * out) if l < TRANSPOSED_FROM else out)))
         else:
-            limit = np.sqrt(6.0 / sum(dense[l]))
+            limit = np.sqrt(6.0 / (count // out + out))
             w = rng.uniform(-limit, limit, count)
         theta[off[2 * l]:off[2 * l + 1]] = w
     return theta

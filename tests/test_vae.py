@@ -40,6 +40,31 @@ def test_nparams_and_layout_match_the_restatement(side, latent):
     np.testing.assert_array_equal(vae.layout(side, latent), R.offsets(side, latent))
 
 
+@pytest.mark.parametrize('side,latent', [(4, 1), (8, 8), (16, 64), (32, 1)])
+def test_initial_params_are_the_restatement_s_draws(side, latent):
+    """bit for bit, and the generator left where the restatement leaves it: convolution kernels He-normal with Keras's fan 27 *
+    shape[-2], redrawn beyond two standard deviations; dense kernels Glorot-uniform; biases zero; the shapes from vae_ref"""
+    seed = 1000 * side + latent
+    rng, shapes, off = np.random.default_rng(seed), R.shapes(side, latent), R.offsets(side, latent)
+    want = np.zeros(off[-1], dtype=np.float32)
+    for l in range(len(R.NAMES)):
+        k = shapes[2 * l]
+        if len(k) == 5:
+            w = rng.standard_normal(int(np.prod(k)))
+            while (np.abs(w) > 2.0).any():
+                far = np.nonzero(np.abs(w) > 2.0)[0]
+                w[far] = rng.standard_normal(far.size)
+            w *= np.sqrt(2.0 / (27 * k[-2]))
+        else:
+            limit = np.sqrt(6.0 / (k[0] + k[1]))
+            w = rng.uniform(-limit, limit, int(np.prod(k)))
+        want[off[2 * l]:off[2 * l + 1]] = w
+    mine = np.random.default_rng(seed)
+    got = vae.initial_params(side, latent, mine)
+    assert got.dtype == np.float32 and got.shape == want.shape and got.tobytes() == want.tobytes()
+    assert mine.random() == rng.random()
+
+
 # ---- refusals: NM_ERR_ARG without a device, the message in the function's name, the outputs untouched
 def _p(a):
     return None if a is None else a.ctypes.data_as(B.c_float_p)
