@@ -77,7 +77,7 @@ MAP_CASES = {
     'K1': dict(k=1, n=1009), 'K2': dict(k=2, n=1009), 'K63': dict(k=63, n=1009), 'K64': dict(k=64, n=1009), 'K65': dict(k=65, n=1009),
     'K513-above-the-tile': dict(k=KT + 1, n=1009), 'N1': dict(k=5, n=1), 'N63': dict(k=5, n=63), 'N64': dict(k=5, n=64),
     'N65': dict(k=5, n=65), 'N4095': dict(k=5, n=CH - 1), 'N4096': dict(k=5, n=CH), 'N4097': dict(k=5, n=CH + 1),
-    'N100003': dict(k=5, n=100003), 'a-state-without-samples': dict(k=6, n=1009, empty=(0, 3)),
+    'N100003': dict(k=5, n=100003), 'N262145-above-the-lanes': dict(k=5, n=64 * CH + 1), 'a-state-without-samples': dict(k=6, n=1009, empty=(0, 3)),
     'two-identical-states': dict(k=7, n=1009, same=(1, 5)),
 }
 
@@ -175,9 +175,12 @@ def check_expectations(got, want, n, k, b, c, tb, tc, e, v, obs, extra_tf=0.0):
         assert np.abs(got['omean'][:, 0] - 3.25).max() <= 2 * tol * 3.25
 
 
-@pytest.mark.parametrize('nt,nobs', ((1, 0), (1, 8), (TGB - 1, 1), (TGB, 8), (TGB + 1, 1), (TGB + 1, 0)))
-def test_expectations(nt, nobs):
-    b, c, count, e, v, f = data(5, CH + 37, seed=3)
+# the last: 65 chunks, so a lane of the wave that joins a target's chunks takes a second one
+@pytest.mark.parametrize('nt,nobs,n', [pytest.param(nt, nobs, CH + 37, id='%d-%d' % (nt, nobs))
+                                       for nt, nobs in ((1, 0), (1, 8), (TGB - 1, 1), (TGB, 8), (TGB + 1, 1), (TGB + 1, 0))]
+                         + [pytest.param(TGB + 1, 1, 64 * CH + 1, id='%d-1-N262145-above-the-lanes' % (TGB + 1))])
+def test_expectations(nt, nobs, n):
+    b, c, count, e, v, f = data(5, n, seed=3)
     rng = np.random.default_rng(nt * 10 + nobs)
     tb, tc = targets(b, c, nt, rng)
     obs = observables(nobs, e, rng) if nobs else None
