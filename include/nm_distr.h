@@ -246,7 +246,83 @@ int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const flo
                      double r_avg, double s_cut, double *s, double *sbar, int32_t *nnb, double *smean, double *sbarmean,
                      int32_t *nlow);
 
-/* nm_cluster_kmeans — k-means for the cluster stage: Lloyd's iteration of a set of points from given
+/* nm_cluster_spectral — the spectral embedding of a set of points for the cluster stage: the leading
+ * eigenvectors of the normalised affinity of a Gaussian kernel, which nm_cluster_kmeans then clusters (lammps_vae.py -cl spectral).
+ * It is declared and built here for the reason nm_cluster_kmeans is.  The definitions are the build's own; off ties they are
+ * sklearn.cluster.SpectralClustering(n_clusters=K, affinity='rbf', gamma=gamma, assign_labels='kmeans'), that is
+ * sklearn.manifold.spectral_embedding(norm_laplacian=True, drop_first=False) followed by k-means.  No random number is drawn in the
+ * library: the start block is the caller's.  u = 2^-53, N = npoints.
+ *
+ * Points.  x[n][c], float64, row-major, in host memory.  d2(i, j) is include/nm_cluster.h's: d = x[i][c] - x[j][c], c ascending, the
+ *   first square a plain product, every further one a fused multiply-add; d2(i, j) == d2(j, i) bit for bit, error at most
+ *   (ndim + 2) u d2.
+ * Affinity.  A(i, j) = exp(-(gamma d2(i, j))) for j != i and A(i, i) = 0: float64, the product rounded once, exp the device
+ *   library's double exp (1 ulp).  A is symmetric bit for bit.  It is never stored: every use of it is one pass over all pairs.
+ * Degree.  deg[i] = sum_j A(i, j), in the order given under Determinism.
+ * Operator.  M = D^-1/2 A D^-1/2, D = diag(deg), D^-1/2 computed as 1 / sqrt(deg[i]), two roundings.  M is symmetric, its spectrum
+ *   lies in [-1, 1] and its largest eigenvalue is 1 (eigenvector D^1/2 1).
+ * Wanted.  The ncomp largest eigenvalues of M, descending, with orthonormal eigenvectors v_c.
+ * Embedding.  embed[i][c] = v_c[i] / sqrt(deg[i]).  The sign of column c is fixed so that its entry of largest magnitude, the first
+ *   index on equal magnitudes, is positive: sklearn's deterministic sign flip.
+ * Degenerate eigenvalues.  Inside the eigenspace of a multiple eigenvalue (or of eigenvalues closer than the residuals) the basis
+ *   is whatever the iteration gives; only the space is defined.  Compare spaces, not vectors.
+ *
+ * Method: Chebyshev-filtered subspace iteration on a block V of nblock >= ncomp orthonormal columns, V_0 = the orthonormalised init.
+ *   1. The Rayleigh-Ritz pass.  W = M V (one pass over all pairs), H = V^T W; the host solves the nblock x nblock symmetric
+ *      eigenproblem of (H + H^T) / 2 by cyclic Jacobi, theta descending; V and W are rotated onto the Ritz vectors, and
+ *      resid[c] = ||W_c - theta_c V_c||_2, formed element by element on the device and then summed: a residual, not a difference
+ *      of norms.  eigval = theta.  passes += 1.
+ *   2. Stop with status 0 where max_{c < ncomp} resid[c] <= tol; else with status 2 where passes + degree > max_pass (the next
+ *      round would pass it).  Either way the outputs are the Ritz pairs of step 1 and their residuals.
+ *   3. The filter of degree `degree`: Zhou and Saad's scaled Chebyshev recurrence for the polynomial that is 1 at 1 and
+ *      equi-oscillates on the damped interval [-1, low], e = (low + 1) / 2, c = (low - 1) / 2, sigma_1 = e / (1 - c):
+ *        Y_1 = (sigma_1 / e) (W - c V);   Y_k = 2 (sigma_k / e) (M Y_{k-1} - c Y_{k-1}) - sigma_{k-1} sigma_k Y_{k-2},
+ *        sigma_k = 1 / (2 / sigma_1 - sigma_{k-1}),  Y_0 = V.
+ *      Y_1 needs no pass (W is at hand), so a round costs degree passes: degree - 1 here and one in step 1.  low is the smallest
+ *      Ritz value of step 1, not below -1 + 2^-10.  Where nblock == ncomp the block's last column is itself wanted and must stay
+ *      outside the damped interval, so low stays what the first round made it; such a block converges at the rate of its gap alone,
+ *      and nblock > ncomp is the intended use.
+ *   4. V = the columns of Y_degree made orthonormal through their Gram matrix (Cholesky QR, applied twice); back to 1.
+ *   The small matrices are solved on the host in float64; everything of length N runs on the device.
+ * Determinism.  The same bytes on every call and on every device.  Every sum runs in an order fixed by the indices alone: a row's
+ *   sum over j is cut into S = S(N) slices, slice s holding the columns of the tiles s, s + S, ... of 128 consecutive points, added
+ *   in ascending j from +0 by one fused multiply-add each, and the slices are added in ascending s; a sum over the points (H, the
+ *   Gram matrices, the residuals) is cut into chunks of 4096 points, in a chunk lane p of 64 adds the points p, p + 64, ... in
+ *   ascending order, the lanes are added as a binary tree and the chunks in ascending order.  No floating-point atomic.
+ * Memory.  O(N (ndim + 3 W)) on the device, W = nblock padded to 1, 8 or 16, plus the slices' partial sums, S N W doubles with
+ *   S N <= about 2^20 below 2^19 points and S <= 8 above: at most 1 GiB.  No N x N array exists.  The work is N^2 affinities per pass.
+ * Bounds.  Write t_ij = gamma d2(i, j).  The computed argument of exp is within (ndim + 3) u t_ij of t_ij, so the computed
+ *   A(i, j) is within ((ndim + 3) t_ij + 2) u of itself; a row adds at most N + S positive terms one after the other.  So
+ *     |deg[i] - exact| <= u ((ndim + 3) sum_j t_ij A(i, j) + (2 N + 2) deg[i])  <=  u ((ndim + 3) T + 2 N + 2) deg[i],
+ *   T = gamma times the largest d2 of any pair.  One application of M to a vector v of unit 2-norm: a term
+ *   deg[i]^-1/2 A(i, j) deg[j]^-1/2 v[j] carries the two degrees' errors halved and two roundings each for the root and the
+ *   quotient, one for each of the three products, the affinity's and the row's adding; M has no negative entry and 2-norm 1, so
+ *     ||computed M v - M v||_2 <= eps_M = (2 (ndim + 3) T + 4 N + 16) u.
+ *   The rotation onto the Ritz vectors mixes nblock such columns, so with v_c = embed[.][c] sqrt(deg[.])
+ *     |resid[c] - ||M v_c - eigval[c] v_c||_2| <= eps_R = sqrt(nblock) eps_M + 160 u,
+ *   and M has an eigenvalue within resid[c] + 2 eps_R of eigval[c].  The v_c are orthonormal to 64 nblock u.
+ *
+ * x [npoints][ndim]; init [npoints][nblock]; embed [npoints][ncomp]; eigval, resid [nblock], every Ritz pair of the block, descending;
+ * deg [npoints]; info [2]: the passes done, and the status, 0 within tol, 2 stopped at max_pass.
+ * Returns 0 or a negative NM_ERR_* code; message via nm_distr_last_error(), starting with "nm_cluster_spectral:".  NM_ERR_ARG, checked
+ * before the device is looked for and with every output left untouched, for, in this order: npoints outside 2..2^20, ndim outside
+ * 1..16, a gamma that is not finite or not positive, ncomp outside 1..8 or above npoints, nblock outside ncomp..16 or above npoints,
+ * degree outside 1..64, max_pass outside 1..100000, a tol that is not finite or is negative, a pointer that is null, a value of init
+ * that is not finite (the message names the row and the column), a negative device ordinal.  Found on the device, NM_ERR_ARG as
+ * well and the outputs untouched: a value of x that is not finite (a first screen; the message names the first such point); a point
+ * of degree 0, which no other point reaches (the message names the first and says that gamma is too large for it); a start block
+ * whose columns are dependent to working precision (a pivot of the first Cholesky factor not above 256 u of its diagonal element).
+ * NM_ERR_STATE, outputs untouched, if a later Cholesky factor fails that way.  NM_ERR_HIP without a device or when a HIP call fails. */
+int nm_cluster_spectral(int device, int64_t npoints, int ndim, const double *x, double gamma, int ncomp, int nblock,
+                        const double *init, int degree, int max_pass, double tol, double *embed, double *eigval,
+                        double *resid, double *deg, int32_t *info);
+
+/* Where the device time of the calling thread's last successful nm_cluster_spectral went, in milliseconds between device events:
+ * ms[0] the upload and the screen, ms[1] the degree pass, ms[2] the operator passes with the joining of their slices, ms[3] the
+ * block reductions and applies, ms[4] the host's small matrices including their transfers.  Slots of its own. */
+int nm_cluster_spectral_last_timing(double *ms);
+
+/* nm_cluster_kmeans —k-means for the cluster stage: Lloyd's iteration of a set of points from given
  * initial centres, nrestarts independent runs in one call, the reference's other practical clustering (lammps_vae.py -cl kmeans,
  * -nc the number of clusters).  It is declared and built here, beside nm_distr_lof and with this header's error channel, because
  * the tests pin include/nm_cluster.h at its three DBSCAN symbols; the kernels share DBSCAN's distance (csrc/nm_cluster.h, cl_d2).

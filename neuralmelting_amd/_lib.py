@@ -119,6 +119,8 @@ def _prototypes():
             'nm_distr_solid': (i, frames + [d, d, i, d, i, I32, I32, I32, I32, I32]),
             'nm_distr_cna': (i, frames + [d, d, i, I32, I32, I32, I32]),
             'nm_distr_entropy': (i, frames + [d, d, i, d, d, D, D, I32, D, D, I32]),
+            'nm_cluster_spectral': (i, [i, i64, i, D, d, i, i, D, i, i, d, D, D, D, D, I32]),
+            'nm_cluster_spectral_last_timing': (i, [D]),
             'nm_cluster_kmeans': (i, [i, i64, i, D, i, i, D, i, d, I32, D, I32, D, I32, I32, I32]),
             'nm_cluster_kmeans_last_timing': (i, [D]),
             'nm_distr_lof': (i, [i, i64, i, i, D, i, D, D, D, I32]),

@@ -20,6 +20,14 @@ nothing is tuned.  The restarts (-ri, seeded on the host by k-means++ from -rs) 
 the restart with the smallest inertia gives the labels, and `.F.clr.npy` says how every restart ended:
 
     python -m neuralmelting_amd.cluster -v -n remcmc_run_5 -e LJ -sk 128 -cl kmeans -nc 2
+
+-cl spectral is for what centroids cannot cut: two curved, elongated branches joined by a thin bridge of coexistence samples.  -nc is
+again the number of clusters.  The library (nm_cluster_spectral) finds the -nc leading eigenvectors of the normalised Gaussian affinity
+of the scaled points by a Chebyshev-filtered subspace iteration, every application of the affinity one pass over all pairs with no
+N x N array; the embedding then goes through the same seeds and the same k-means.  `.F.clg.npy`, the degree of every sample, is the
+data to judge the width -gm from, `.F.cle.npy` says how the eigensolver ended:
+
+    python -m neuralmelting_amd.cluster -v -n remcmc_run_5 -e LJ -sk 128 -cl spectral -nc 2
 """
 import argparse
 import sys
@@ -32,6 +40,7 @@ from ._stage import spread
 
 MAX_POINTS, MAX_DIM, MAX_KEPT = 2 ** 21, 16, 8     # include/nm_cluster.h: npoints and ndim; the indicators of -nk
 MAX_K, MAX_RESTARTS, MAX_CENTRES, MAX_ITER = 256, 64, 4096, 10000      # include/nm_distr.h, nm_cluster_kmeans: k, nrestarts, their product, max_iter
+SP_MAX_POINTS, SP_MAX_K, SP_MAX_BLOCK, SP_MAX_DEGREE, SP_MAX_PASS = 2 ** 20, 8, 16, 64, 100000     # nm_cluster_spectral: npoints, ncomp, nblock, degree, max_pass
 
 
 def parse_args(argv=None):
@@ -42,7 +51,9 @@ def parse_args(argv=None):
         'membership indicators of the NK largest clusters from the coldest to the hottest, for reweight -ob F.cl1 -hq F.cl1 -hx 0.5.  '
         'With -cl kmeans: .F.cll the labels of the best restart, .F.cls with core members = members, .F.cl0 ... as above, .F.clr (R, 3) '
         'float64 the inertia, the iterations and the status (0 a fixed point, 1 within -tl, 2 stopped at -mi) of every restart; '
-        '.F.cld is not written.')
+        '.F.cld is not written.  With -cl spectral: the files of -cl kmeans from k-means of the spectral embedding, and .F.cle (NB, 2) '
+        'float64 the Ritz values of the block and their residuals, .F.clv (PN, TN, SN, K) float64 the embedding and .F.clg (PN, TN, SN) '
+        'float64 the degree, both NaN for samples left out.')
     p.add_argument('-v', '--verbose', action='store_true')
     p.add_argument('-n', '--name', type=str, default='remcmc_init')
     p.add_argument('-e', '--element', type=str, default='LJ')
@@ -50,9 +61,9 @@ def parse_args(argv=None):
     p.add_argument('-em', '--embedding', type=str, default='pcz', choices=('pcz', 'mfy'),
                    help="what is clustered: pca's projections <PREFIX>.F.pcz.npy, or manifold's embedding <PREFIX>.F.mfy.npy of the same -sk and -sd")
     p.add_argument('-nd', '--dimensions', type=int, default=2, help='leading components used, 1..16 and at most LD')
-    p.add_argument('-cl', '--clustering', type=str, default='dbscan', choices=('dbscan', 'kmeans'))
+    p.add_argument('-cl', '--clustering', type=str, default='dbscan', choices=('dbscan', 'kmeans', 'spectral'))
     p.add_argument('-nc', '--neighbourhood', type=float, required=True, metavar='EPS',
-                   help='the radius of a neighbourhood as a fraction of the range of component 0; with -cl kmeans the number of clusters, 1..256')
+                   help='the radius of a neighbourhood as a fraction of the range of component 0; with -cl kmeans the number of clusters, 1..256, with -cl spectral 2..8')
     p.add_argument('-ms', '--min_samples', type=int, default=5,
                    help='samples within EPS, itself among them, that make a sample a core; ignored with -cl kmeans')
     p.add_argument('-ri', '--restarts', type=int, default=10, help='-cl kmeans: restarts from k-means++ seeds, 1..64; the best is kept')
@@ -60,6 +71,15 @@ def parse_args(argv=None):
     p.add_argument('-tl', '--tolerance', type=float, default=1e-4,
                    help="-cl kmeans: a restart stops where its centres' squared shift is at most TL times the mean variance of the used components")
     p.add_argument('-rs', '--seed', type=int, default=256, help='-cl kmeans: the seed of the k-means++ draws')
+    p.add_argument('-gm', '--gamma', type=float, default=1.0,
+                   help="-cl spectral: the width of the affinity exp(-gamma d^2), in the unit 1 / (the sum of the used scaled components' variances "
+                   "over the clustered points): the library's gamma is GM divided by that sum")
+    p.add_argument('-eb', '--eigen_block', type=int, default=16,
+                   help='-cl spectral: columns of the iterated block, -nc..16; fewer where fewer samples are clustered')
+    p.add_argument('-ed', '--eigen_degree', type=int, default=8, help='-cl spectral: the degree of the Chebyshev filter, 1..64')
+    p.add_argument('-et', '--eigen_tolerance', type=float, default=1e-6,
+                   help='-cl spectral: the largest residual of the -nc leading Ritz pairs at which the eigensolver stops')
+    p.add_argument('-ei', '--eigen_passes', type=int, default=2000, help='-cl spectral: passes over all pairs at most, 1..100000')
     p.add_argument('-nk', '--clusters_kept', type=int, default=2, help='phase indicators written, 1..8')
     p.add_argument('-sk', '--skip', type=int, default=0, help='samples of every grid point left out at its start')
     p.add_argument('-sd', '--stride', type=int, default=1, help='every STRIDE-th sample is clustered')
@@ -70,7 +90,14 @@ def parse_args(argv=None):
     if (a.skip < 0 or a.stride < 1 or not 1 <= a.dimensions <= MAX_DIM or not 1 <= a.clusters_kept <= MAX_KEPT or a.min_samples < 1
             or not (np.isfinite(a.neighbourhood) and a.neighbourhood > 0.0)):
         p.error('need -sk >= 0, -sd >= 1, -nd in 1..16, -nk in 1..8, -ms >= 1 and a finite -nc > 0')
-    if a.clustering == 'kmeans':
+    if a.clustering == 'spectral':
+        if a.neighbourhood != int(a.neighbourhood) or not 2 <= a.neighbourhood <= SP_MAX_K:
+            p.error('with -cl spectral -nc is the number of clusters: an integer in 2..8')
+        if (not (np.isfinite(a.gamma) and a.gamma > 0.0) or not a.neighbourhood <= a.eigen_block <= SP_MAX_BLOCK
+                or not 1 <= a.eigen_degree <= SP_MAX_DEGREE or not (np.isfinite(a.eigen_tolerance) and a.eigen_tolerance >= 0.0)
+                or not 1 <= a.eigen_passes <= SP_MAX_PASS):
+            p.error('need a finite -gm > 0, -eb in -nc..16, -ed in 1..64, a finite -et >= 0 and -ei in 1..100000')
+    if a.clustering in ('kmeans', 'spectral'):
         if a.neighbourhood != int(a.neighbourhood) or not 1 <= a.neighbourhood <= MAX_K:
             p.error('with -cl kmeans -nc is the number of clusters: an integer in 1..256')
         if (not 1 <= a.restarts <= MAX_RESTARTS or int(a.neighbourhood) * a.restarts > MAX_CENTRES or not 1 <= a.max_iter <= MAX_ITER
@@ -103,6 +130,21 @@ def kmeans(x, init, max_iter=300, tol=0.0, device=0):
     inertia, iters, status, best = np.empty(r), np.empty(r, dtype=np.int32), np.empty(r, dtype=np.int32), np.zeros(1, dtype=np.int32)
     B.call('nm_cluster_kmeans', device, n, nd, x, k, r, init, int(max_iter), float(tol), label, centre, count, inertia, iters, status, best)
     return label, centre, count, inertia, iters, status, int(best[0])
+
+
+def spectral(x, gamma, ncomp, init, degree=8, max_pass=2000, tol=1e-6, device=0):
+    """nm_cluster_spectral of x (N, ND) from the start block init (N, NB): (embed (N, ncomp), eigval (NB,), resid (NB,), deg (N,), the
+    passes done, the status: 0 within tol, 2 stopped at max_pass)"""
+    x, init = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(init, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError('x wants the shape (N, ND)')
+    if init.ndim != 2 or init.shape[0] != x.shape[0]:
+        raise ValueError('init wants the shape (N, NB)')
+    (n, nd), nb = x.shape, init.shape[1]
+    embed, eigval, resid, deg, info = np.empty((n, max(int(ncomp), 0))), np.empty(nb), np.empty(nb), np.empty(n), np.zeros(2, dtype=np.int32)
+    B.call('nm_cluster_spectral', device, n, nd, x, float(gamma), int(ncomp), nb, init, int(degree), int(max_pass), float(tol), embed, eigval,
+           resid, deg, info)
+    return embed, eigval, resid, deg, int(info[0]), int(info[1])
 
 
 def seeds(x, k, nrestarts, seed):
@@ -191,6 +233,8 @@ def main(argv=None):
     temp = np.broadcast_to(np.asarray(T, dtype=np.float64)[None, :, None], (pn, tn, kept))[keep]
     if a.clustering == 'kmeans':
         return main_kmeans(a, prefix, path, pe.shape, keep, z, temp)
+    if a.clustering == 'spectral':
+        return main_spectral(a, prefix, path, pe.shape, keep, z, temp)
     if a.verbose:
         print('clustering %d of %d samples of %s in %d components, eps %g of the range of pc0, min_pts %d' % (
             n, pn * tn * sn, ft, nd, a.neighbourhood, a.min_samples))
@@ -216,18 +260,21 @@ def main(argv=None):
     return 0
 
 
-def main_kmeans(a, prefix, path, shape, keep, z, temp):
-    """-cl kmeans of the clustered points z (N, ND) with their target temperatures: the files of the best of -ri restarts"""
+def main_kmeans(a, prefix, path, shape, keep, z, temp, embedded=None):
+    """-cl kmeans of the clustered points z (N, ND) with their target temperatures: the files of the best of -ri restarts.
+    embedded: a function of the scaled points that gives what k-means clusters in their place, and the generator of its seeds"""
     ft, k, n = a.feature, int(a.neighbourhood), z.shape[0]
     if k > n:
         raise SystemExit('cluster: -nc %d clusters are more than the %d samples of %s' % (k, n, path))
     try:
-        zs = scaled(z)
+        zs, rng = scaled(z), a.seed
+        if embedded:
+            zs, rng = embedded(zs)
         tol = a.tolerance * float(zs.var(axis=0).mean())
         if a.verbose:
             print('clustering %d samples of %s in %d components into %d clusters: %d restarts, max_iter %d, tol %g' % (
-                n, ft, z.shape[1], k, a.restarts, a.max_iter, tol))
-        label, centre, count, inertia, iters, status, best = kmeans(zs, seeds(zs, k, a.restarts, a.seed), a.max_iter, tol, a.device)
+                n, ft, zs.shape[1], k, a.restarts, a.max_iter, tol))
+        label, centre, count, inertia, iters, status, best = kmeans(zs, seeds(zs, k, a.restarts, rng), a.max_iter, tol, a.device)
     except (RuntimeError, ValueError) as err:
         raise SystemExit('cluster: %s: %s' % (path, err))
     tab = kmeans_table(label, count, temp, z)
@@ -250,6 +297,38 @@ def main_kmeans(a, prefix, path, shape, keep, z, temp):
         if len(order) < a.clusters_kept:
             print('only %d clusters: cl%d .. cl%d are all zero' % (len(order), len(order), a.clusters_kept - 1))
     return 0
+
+
+def main_spectral(a, prefix, path, shape, keep, z, temp):
+    """-cl spectral: the spectral embedding of the scaled points, its files, then main_kmeans on the embedding.  The start block is
+    drawn first and the k-means++ seeds behind it, from one generator numpy.random.default_rng(-rs)."""
+    ft, k, n = a.feature, int(a.neighbourhood), z.shape[0]
+    if not k <= n <= SP_MAX_POINTS:
+        raise SystemExit('cluster: -cl spectral wants %d..%d samples, %s leaves %d' % (k, SP_MAX_POINTS, path, n))
+
+    def embedded(zs):
+        rng = np.random.default_rng(a.seed)
+        nb = min(a.eigen_block, n)
+        gamma = a.gamma / float(zs.var(axis=0).sum())
+        if not np.isfinite(gamma):
+            raise ValueError('the used components do not vary, -gm has no unit')
+        if a.verbose:
+            print('spectral embedding of %d samples of %s in %d components: gamma %g, block %d, filter degree %d, tol %g' % (
+                n, ft, zs.shape[1], gamma, nb, a.eigen_degree, a.eigen_tolerance))
+        embed, eigval, resid, deg, passes, status = spectral(zs, gamma, k, rng.standard_normal((n, nb)), a.eigen_degree, a.eigen_passes,
+                                                             a.eigen_tolerance, a.device)
+        np.save(prefix + '.%s.cle.npy' % ft, np.stack([eigval, resid], axis=1))
+        np.save(prefix + '.%s.clv.npy' % ft, S.spread_kept(embed, keep, shape + (k,), a.skip, a.stride, np.nan))
+        np.save(prefix + '.%s.clg.npy' % ft, S.spread_kept(deg, keep, shape, a.skip, a.stride, np.nan))
+        if a.verbose:
+            print('eigenvalues %s after %d passes, residuals at most %.3g; the gap behind the %d-th is %s; degree %.4g .. %.4g, median %.4g' % (
+                ' '.join('%.6f' % v for v in eigval[:k]), passes, resid[:k].max(), k, '%.3g' % (eigval[k - 1] - eigval[k]) if nb > k else 'not known (-eb = -nc)',
+                deg.min(), deg.max(), float(np.median(deg))))
+            if status == 2:
+                print('warning: the eigensolver stopped at -ei %d passes before its residuals came to -et %g' % (a.eigen_passes, a.eigen_tolerance))
+        return embed, rng
+
+    return main_kmeans(a, prefix, path, shape, keep, z, temp, embedded)
 
 
 if __name__ == '__main__':

@@ -3,12 +3,14 @@
 // walks the samples in chunks.  The last one, nm_distr_lof, is the outlier stage's (kernels: nm_lof.h): float64 points in sets, one
 // upload, the screen of nm_scan.h, the neighbour pass and two gathers.  nm_cluster_kmeans, the cluster stage's k-means (kernels:
 // nm_kmeans.h), stands here too, with this file's error channel: the screen, the chain of steps of all restarts with a look at their
-// states every KM_LOOK steps, and the choice of the best restart.
+// states every KM_LOOK steps, and the choice of the best restart.  nm_cluster_spectral, the cluster stage's spectral embedding (kernels:
+// nm_spectral.h), likewise: the degree pass, then rounds of a Rayleigh-Ritz pass and a Chebyshev filter, the small matrices on the host.
 #include "../../include/nm_distr.h"
 #include "nm_distr.h"
 #include "nm_distr_w.h"
 #include "nm_lof.h"
 #include "nm_kmeans.h"
+#include "nm_spectral.h"
 #include "nm_host.h"
 
 #include <cmath>
@@ -219,6 +221,163 @@ const auto LLOYD = scan_table<KM_MAXDIM>([](auto nd) {
     constexpr int ND = decltype(nd)::value;
     return Lloyd{nm_kmeans_assign_kernel<ND>, nm_kmeans_sums_kernel<ND>, nm_kmeans_inertia_kernel<ND>};
 });
+
+// the slots of nm_cluster_spectral_last_timing
+enum { SP_T_UPLOAD, SP_T_DEGREE, SP_T_PASS, SP_T_BLOCK, SP_T_HOST, SP_T_COUNT };
+thread_local double g_spectral_ms[SP_T_COUNT];
+
+// the kernels of the spectral embedding that depend on ndim or on the padded width: [ndim - 1], then [0, 1, 2] for the widths 1, 8, 16
+using SpPass = void (*)(int, const double *, double, const double *, double *);
+using SpGram = void (*)(int, const double *, const double *, double *);
+using SpApply = void (*)(int, const double *, const double *, const double *, double *, double *);
+const auto SP_PASS = scan_table<SP_MAXDIM>([](auto nd) {
+    constexpr int ND = decltype(nd)::value;
+    return std::array<SpPass, 3>{nm_spectral_pass_kernel<ND, 1>, nm_spectral_pass_kernel<ND, 8>, nm_spectral_pass_kernel<ND, 16>};
+});
+const SpGram SP_GRAM[3] = {nm_spectral_gram_kernel<1>, nm_spectral_gram_kernel<8>, nm_spectral_gram_kernel<16>};
+const SpApply SP_APPLY[3] = {nm_spectral_apply_kernel<1>, nm_spectral_apply_kernel<8>, nm_spectral_apply_kernel<16>};
+
+// The host's small matrices are m x m in the corner of w x w (w the padded width), row-major, the rest zero.
+
+// c = L^-T for g = L L^T, so that the columns of Y c are orthonormal where g = Y^T Y; false where a pivot is not above 256 u of its
+// diagonal element: the columns are dependent to working precision
+bool sp_cholesky(int m, int w, const double *g, double *c)
+{
+    double l[SP_MAXBLOCK][SP_MAXBLOCK] = {}, li[SP_MAXBLOCK][SP_MAXBLOCK] = {};
+    for (int j = 0; j < m; ++j) {
+        double d = g[j * w + j];
+        for (int k = 0; k < j; ++k) d -= l[j][k] * l[j][k];
+        if (!(d > 256.0 * 0x1p-53 * g[j * w + j])) return false;
+        l[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < m; ++i) {
+            double v = 0.5 * (g[i * w + j] + g[j * w + i]);
+            for (int k = 0; k < j; ++k) v -= l[i][k] * l[j][k];
+            l[i][j] = v / l[j][j];
+        }
+    }
+    for (int j = 0; j < m; ++j) {                               // column j of L^-1 by forward substitution
+        li[j][j] = 1.0 / l[j][j];
+        for (int i = j + 1; i < m; ++i) {
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v -= l[i][k] * li[k][j];
+            li[i][j] = v / l[i][i];
+        }
+    }
+    for (int e = 0; e < w * w; ++e) c[e] = 0.0;
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j <= i; ++j) c[j * w + i] = li[i][j];
+    return true;
+}
+
+// cyclic Jacobi of the symmetric part of h: theta[0 .. m-1] descending (the lower index first on equal values) and q, whose column
+// c is the eigenvector of theta[c].  A rotation is skipped where the element cannot change the diagonal's bits; the sweeps end
+// where one skipped them all (64 at most: a 16 x 16 matrix takes about 8).
+void sp_jacobi(int m, int w, const double *h, double *q, double *theta)
+{
+    double a[SP_MAXBLOCK][SP_MAXBLOCK], v[SP_MAXBLOCK][SP_MAXBLOCK];
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) {
+            a[i][j] = 0.5 * (h[i * w + j] + h[j * w + i]);
+            v[i][j] = i == j ? 1.0 : 0.0;
+        }
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < m - 1; ++p)
+            for (int r = p + 1; r < m; ++r) {
+                const double apr = a[p][r];
+                if (std::fabs(apr) <= 0x1p-60 * (std::fabs(a[p][p]) + std::fabs(a[r][r])) || apr == 0.0) continue;
+                rotated = true;
+                const double tau = (a[r][r] - a[p][p]) / (2.0 * apr);
+                const double t = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = t * cs;
+                for (int k = 0; k < m; ++k) {                   // columns p and r
+                    const double akp = a[k][p], akr = a[k][r];
+                    a[k][p] = cs * akp - sn * akr;
+                    a[k][r] = sn * akp + cs * akr;
+                }
+                for (int k = 0; k < m; ++k) {                   // rows p and r
+                    const double apk = a[p][k], ark = a[r][k];
+                    a[p][k] = cs * apk - sn * ark;
+                    a[r][k] = sn * apk + cs * ark;
+                }
+                a[p][r] = a[r][p] = 0.0;
+                for (int k = 0; k < m; ++k) {
+                    const double vkp = v[k][p], vkr = v[k][r];
+                    v[k][p] = cs * vkp - sn * vkr;
+                    v[k][r] = sn * vkp + cs * vkr;
+                }
+            }
+        if (!rotated) break;
+    }
+    int order[SP_MAXBLOCK];
+    for (int c = 0; c < m; ++c) order[c] = c;
+    for (int c = 1; c < m; ++c)                                 // a stable insertion sort, descending
+        for (int k = c; k > 0 && a[order[k]][order[k]] > a[order[k - 1]][order[k - 1]]; --k) std::swap(order[k], order[k - 1]);
+    for (int e = 0; e < w * w; ++e) q[e] = 0.0;
+    for (int c = 0; c < m; ++c) {
+        theta[c] = a[order[c]][order[c]];
+        for (int k = 0; k < m; ++k) q[k * w + c] = v[k][order[c]];
+    }
+}
+
+// What one call of nm_cluster_spectral holds on the device and the launches it is made of.  a, b and u are npoints x w.
+struct Spectral {
+    int n, ndim, m, w, wi, ne, nchunks;
+    double gamma;
+    dim3 grid, flat, rows;
+    DevBuf<double> x, deg, rs, a, b, u, part, gpart, small, theta;
+    DevBuf<int> bad;
+    Laps<SP_T_COUNT> laps;
+
+    void pass(const double *in, int width_index, int slot)
+    {
+        hipLaunchKernelGGL(SP_PASS[ndim - 1][width_index], grid, dim3(SP_BLOCK), 0, 0, n, x, gamma, in, part);
+        laps.lap(slot);
+    }
+    // dst = alpha M cur + beta cur + gam dst behind a pass over u; the next pass's u where `next`
+    void join(double alpha, double beta, double gam, const double *cur, double *dst, bool next)
+    {
+        hipLaunchKernelGGL(nm_spectral_rows_kernel, flat, dim3(SP_BLOCK), 0, 0, ne, w, (int)grid.y, part, rs, alpha, beta, gam, cur, dst,
+                           next ? u.p : nullptr);
+        laps.lap(SP_T_PASS);
+    }
+    // g (w x w, on the host) = p^T q
+    hipError_t gram(const double *p, const double *q, double *g)
+    {
+        hipLaunchKernelGGL(SP_GRAM[wi], dim3((unsigned)nchunks), dim3(SP_BLOCK), 0, 0, n, p, q, gpart);
+        hipLaunchKernelGGL(nm_spectral_gram_join_kernel, dim3(1), dim3(SP_BLOCK), 0, 0, nchunks, w * w, gpart, small);
+        hipError_t e = hipGetLastError();
+        laps.lap(SP_T_BLOCK);
+        if (e == hipSuccess) e = small.download(g, (size_t)w * w);
+        laps.lap(SP_T_HOST);
+        return e;
+    }
+    // dst = src c, c (w x w) from the host; u = rs dst where `next`
+    hipError_t apply(const double *src, const double *c, double *dst, bool next)
+    {
+        hipError_t e = hipMemcpy(small, c, (size_t)w * w * sizeof(double), hipMemcpyHostToDevice);
+        laps.lap(SP_T_HOST);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(SP_APPLY[wi], rows, dim3(SP_BLOCK), 0, 0, n, src, small, rs, dst, next ? u.p : nullptr);
+        e = hipGetLastError();
+        laps.lap(SP_T_BLOCK);
+        return e;
+    }
+    // the columns of src made orthonormal into a (Cholesky QR, twice), u = rs a; *rank = false where the first factor fails
+    hipError_t orthonormalise(const double *src, bool *rank)
+    {
+        double g[SP_MAXBLOCK * SP_MAXBLOCK], c[SP_MAXBLOCK * SP_MAXBLOCK];
+        *rank = true;
+        for (int round = 0; round < 2; ++round) {
+            hipError_t e = gram(src, src, g);
+            if (e != hipSuccess) return e;
+            if (!sp_cholesky(m, w, g, c)) { *rank = false; return hipSuccess; }
+            if ((e = apply(src, c, a, round == 1)) != hipSuccess) return e;
+            src = a;
+        }
+        return hipSuccess;
+    }
+};
 } // namespace
 
 extern "C" {
@@ -630,6 +789,141 @@ int nm_distr_entropy(int device, int ns, int natoms, const float *pos, const flo
         STAGE_CHK(fn, d_low.fetch(s0, n));
         return NM_OK;
     });
+}
+
+int nm_cluster_spectral_last_timing(double *ms) { return last_timing("nm_cluster_spectral_last_timing", g_spectral_ms, ms); }
+
+int nm_cluster_spectral(int device, int64_t npoints, int ndim, const double *x, double gamma, int ncomp, int nblock, const double *init,
+                        int degree, int max_pass, double tol, double *embed, double *eigval, double *resid, double *deg, int32_t *info)
+{
+    static const char *const fn = "nm_cluster_spectral";
+    if (npoints < 2 || npoints > SP_MAXN) return refuse(fn, "npoints must lie in 2..2^20");
+    if (ndim < 1 || ndim > SP_MAXDIM) return refuse(fn, "ndim must lie in 1..16");
+    if (!std::isfinite(gamma) || !(gamma > 0.0)) return refuse(fn, "gamma must be finite and positive");
+    if (ncomp < 1 || ncomp > SP_MAXCOMP || ncomp > npoints) return refuse(fn, "ncomp must lie in 1..8 and be at most npoints");
+    if (nblock < ncomp || nblock > SP_MAXBLOCK || nblock > npoints) return refuse(fn, "nblock must lie in ncomp..16 and be at most npoints");
+    if (degree < 1 || degree > 64) return refuse(fn, "degree must lie in 1..64");
+    if (max_pass < 1 || max_pass > 100000) return refuse(fn, "max_pass must lie in 1..100000");
+    if (!std::isfinite(tol) || tol < 0.0) return refuse(fn, "tol must be finite and not negative");
+    if (!x || !init || !embed || !eigval || !resid || !deg || !info) return refuse(fn, "a needed pointer is null");
+    const int64_t bad = first_not_finite(init, npoints * nblock);
+    if (bad >= 0)
+        return fail(NM_ERR_ARG, std::string(fn) + ": init is not finite in row " + std::to_string(bad / nblock) + ", column " + std::to_string(bad % nblock));
+    if (const int rc = stage_device(fn, device)) return rc;
+
+    Spectral sp;
+    const int n = sp.n = (int)npoints, m = sp.m = nblock, w = sp.w = sp_width(nblock);
+    sp.ndim = ndim;
+    sp.gamma = gamma;
+    sp.wi = w == 1 ? 0 : w == 8 ? 1 : 2;
+    sp.ne = n * w;
+    sp.nchunks = (n + SP_CHUNK - 1) / SP_CHUNK;
+    sp.grid = scan_grid<SpScan>(n, n);
+    sp.flat = dim3((unsigned)((sp.ne + SP_BLOCK - 1) / SP_BLOCK));
+    sp.rows = dim3((unsigned)((n + SP_BLOCK - 1) / SP_BLOCK));
+    std::vector<double> block((size_t)n * w, 0.0);             // the start block at the padded width
+    for (int i = 0; i < n; ++i)
+        for (int c = 0; c < m; ++c) block[(size_t)i * w + c] = init[(size_t)i * m + c];
+
+    sp.laps.lap(SP_T_UPLOAD);
+    STAGE_CHK(fn, sp.x.upload(x, (size_t)n * ndim));
+    STAGE_CHK(fn, sp.a.upload(block.data(), block.size()));
+    STAGE_CHK(fn, sp.b.alloc((size_t)sp.ne));
+    STAGE_CHK(fn, sp.u.alloc((size_t)sp.ne));
+    STAGE_CHK(fn, sp.deg.alloc(n));
+    STAGE_CHK(fn, sp.rs.alloc(n));
+    STAGE_CHK(fn, sp.part.alloc((size_t)sp.grid.y * sp.ne));
+    STAGE_CHK(fn, sp.gpart.alloc((size_t)sp.nchunks * w * w));
+    STAGE_CHK(fn, sp.small.alloc((size_t)w * w));
+    STAGE_CHK(fn, sp.theta.alloc(w));
+    int first = -1;
+    STAGE_CHK(fn, scan_screen<SpScan>(n, ndim, sp.x, first));
+    if (first >= 0) return fail(NM_ERR_ARG, std::string(fn) + ": x is not finite in point " + std::to_string(first));
+    sp.laps.lap(SP_T_UPLOAD);
+
+    // the degree: the pass at width 1 over u = 1, and the screen for a point that no other point reaches
+    const int none = 0x7fffffff;
+    STAGE_CHK(fn, sp.bad.upload(&none, 1));
+    sp.pass(nullptr, 0, SP_T_DEGREE);
+    hipLaunchKernelGGL(nm_spectral_degree_kernel, sp.rows, dim3(SP_BLOCK), 0, 0, n, (int)sp.grid.y, sp.part, sp.deg, sp.rs, sp.bad);
+    STAGE_CHK(fn, hipGetLastError());
+    STAGE_CHK(fn, sp.bad.download(&first, 1));
+    sp.laps.lap(SP_T_DEGREE);
+    if (first != none)
+        return fail(NM_ERR_ARG, std::string(fn) + ": the degree of point " + std::to_string(first) +
+                                    " is 0: gamma is too large for it, no other point lies within its reach");
+
+    bool rank = true;
+    STAGE_CHK(fn, sp.orthonormalise(sp.a, &rank));
+    if (!rank) return refuse(fn, "the columns of init are linearly dependent to working precision");
+
+    double h[SP_MAXBLOCK * SP_MAXBLOCK], q[SP_MAXBLOCK * SP_MAXBLOCK], theta[SP_MAXBLOCK] = {}, res[SP_MAXBLOCK] = {};
+    double low = 0.0;                                           // the upper end of the damped interval
+    int passes = 0, status = 0;
+    for (int round = 0;; ++round) {
+        // the Rayleigh-Ritz pass: b = M a, the Ritz pairs of a^T b, both rotated onto them, and the residuals b - a theta
+        sp.pass(sp.u, sp.wi, SP_T_PASS);
+        sp.join(1.0, 0.0, 0.0, nullptr, sp.b, false);
+        ++passes;
+        STAGE_CHK(fn, sp.gram(sp.a, sp.b, h));
+        sp_jacobi(m, w, h, q, theta);
+        STAGE_CHK(fn, sp.apply(sp.a, q, sp.a, false));
+        STAGE_CHK(fn, sp.apply(sp.b, q, sp.b, false));
+        STAGE_CHK(fn, hipMemcpy(sp.theta, theta, (size_t)w * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nm_spectral_resid_kernel, sp.flat, dim3(SP_BLOCK), 0, 0, sp.ne, w, sp.theta, sp.a, sp.b, sp.u);
+        STAGE_CHK(fn, sp.gram(sp.u, sp.u, h));
+        double worst = 0.0;
+        for (int c = 0; c < m; ++c) {
+            res[c] = std::sqrt(h[c * w + c]);
+            if (c < ncomp && !(res[c] <= worst)) worst = res[c];
+        }
+        if (worst <= tol) { status = 0; break; }
+        if (passes + degree > max_pass) { status = 2; break; } // the next round is degree - 1 filter passes and its Rayleigh-Ritz pass
+        // The filter: Zhou and Saad's scaled Chebyshev recurrence that damps [-1, low] and is 1 at 1.  low is the smallest Ritz
+        // value of the block; a block no wider than ncomp keeps that of its first round, since its last column is wanted and
+        // must stay outside.  Its first term needs M a, which is b.
+        if (round == 0 || m > ncomp) low = theta[m - 1] > -1.0 + 0x1p-10 ? theta[m - 1] : -1.0 + 0x1p-10;
+        const double e = 0.5 * (low + 1.0), c0 = 0.5 * (low - 1.0);
+        double sigma = e / (1.0 - c0);
+        const double sigma1 = sigma;
+        hipLaunchKernelGGL(nm_spectral_axpby_kernel, sp.flat, dim3(SP_BLOCK), 0, 0, sp.ne, w, sp.rs, sigma1 / e, -c0 * (sigma1 / e), sp.a, sp.b,
+                           sp.u);
+        sp.laps.lap(SP_T_BLOCK);
+        double *cur = sp.b, *prev = sp.a;
+        for (int k = 2; k <= degree; ++k) {
+            const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
+            sp.pass(sp.u, sp.wi, SP_T_PASS);
+            sp.join(2.0 * (sigma2 / e), -2.0 * c0 * (sigma2 / e), -(sigma * sigma2), cur, prev, true);
+            ++passes;
+            std::swap(cur, prev);
+            sigma = sigma2;
+        }
+        STAGE_CHK(fn, hipGetLastError());
+        STAGE_CHK(fn, sp.orthonormalise(cur, &rank));
+        if (!rank) return fail(NM_ERR_STATE, std::string(fn) + ": the filtered block lost its rank in pass " + std::to_string(passes));
+    }
+    STAGE_CHK(fn, hipDeviceSynchronize());
+    sp.laps.lap(SP_T_HOST);
+    sp.laps.book(g_spectral_ms);
+
+    std::vector<double> d((size_t)n);
+    STAGE_CHK(fn, sp.a.download(block.data(), block.size()));
+    STAGE_CHK(fn, sp.deg.download(d.data(), d.size()));
+    for (int c = 0; c < ncomp; ++c) {                           // embed = v / sqrt(deg), the entry of largest magnitude positive
+        double top = -1.0, sign = 1.0;
+        for (int i = 0; i < n; ++i) {
+            const double v = block[(size_t)i * w + c] / std::sqrt(d[i]);
+            embed[(size_t)i * ncomp + c] = v;
+            if (std::fabs(v) > top) { top = std::fabs(v); sign = v < 0.0 ? -1.0 : 1.0; }
+        }
+        if (sign < 0.0)
+            for (int i = 0; i < n; ++i) embed[(size_t)i * ncomp + c] = -embed[(size_t)i * ncomp + c];
+    }
+    for (int i = 0; i < n; ++i) deg[i] = d[i];
+    for (int c = 0; c < m; ++c) { eigval[c] = theta[c]; resid[c] = res[c]; }
+    info[0] = passes;
+    info[1] = status;
+    return NM_OK;
 }
 
 int nm_distr_lof(int device, int64_t nsets, int npts, int ndim, const double *x, int k, double *lof, double *lrd, double *kdist,
