@@ -1107,11 +1107,22 @@ struct Replica {
                     // (rows < groups) write what the row's own group writes
                     constexpr unsigned int LT = TPA == 1 ? 0 : TPA == 2 ? 1 : TPA == 4 ? 2 : TPA == 8 ? 3 : 4; // log2 TPA
                     const unsigned int rowc = ((unsigned int)lrow(i) * TPA) << C::LOG2PW;
+                    constexpr unsigned int CHUNK = (unsigned int)C::NLIST * TPA * C::PW; // elements from one chunk of a row to its next
+                    if (r + (unsigned int)mine_n <= (unsigned int)MAXNB) {
+                        // (nearly always: every hit has a slot of its own, no clamp; the rank is carried as r << LOG2PW, where the slot
+                        //  wants the thread's field of it — nm_math.h list_slot_shifted: twelve VALU instructions a hit against fourteen)
+                        unsigned int rp = r << C::LOG2PW;
+                        while (m) {
+                            const unsigned int j = (unsigned int)jb + (unsigned int)__builtin_ctz(m);
+                            m &= m - 1u;
+                            nbr_list[rowc + list_slot_shifted(rp, LT, C::LOG2PW, CHUNK)] = (IdxT)j;
+                            rp += C::PW;
+                        }
+                    } else
                     while (m) {
                         const unsigned int j = (unsigned int)jb + (unsigned int)__builtin_ctz(m);
                         m &= m - 1u;
-                        const unsigned int rr = min(r, (unsigned int)MAXNB - 1u), k = rr >> LT;
-                        nbr_list[(k >> C::LOG2PW) * ((unsigned int)C::NLIST * TPA * C::PW) + rowc + (((rr & (TPA - 1)) << C::LOG2PW) | (k & (C::PW - 1)))] = (IdxT)j;
+                        nbr_list[rowc + list_slot(min(r, (unsigned int)MAXNB - 1u), LT, C::LOG2PW, CHUNK)] = (IdxT)j;
                         ++r;
                     }
                 }

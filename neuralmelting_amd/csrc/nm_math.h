@@ -80,4 +80,19 @@ NM_HD GranuleState granule_state(unsigned long long x)
     return { bool((x == 0ull) | pz), pz };
 }
 
+// Element of the entry of rank rr in a row of an LDS Verlet list, counted from the row's first word of chunk 0 (nm_kernels.h: nbr_at,
+// Replica::rebuild).  The row's 2^lt threads own one word of 2^lpw entries per chunk; consecutive ranks go round the threads, then along
+// the word, then to the next chunk, chunk_elems elements on: sub = rr mod 2^lt, k = rr / 2^lt, chunk k / 2^lpw, place k mod 2^lpw.
+NM_HD unsigned int list_slot(unsigned int rr, unsigned int lt, unsigned int lpw, unsigned int chunk_elems)
+{
+    const unsigned int k = rr >> lt;
+    return (k >> lpw) * chunk_elems + (((rr & ((1u << lt) - 1u)) << lpw) | (k & ((1u << lpw) - 1u)));
+}
+// The same element from rp = rr << lpw, which is what the rebuild's append loop counts up (by 2^lpw per entry): the thread's field of rp
+// then lies where the slot wants it and needs one mask, no shift, and the chunk is one shift away.
+NM_HD unsigned int list_slot_shifted(unsigned int rp, unsigned int lt, unsigned int lpw, unsigned int chunk_elems)
+{
+    return (rp >> (lt + 2u * lpw)) * chunk_elems + ((rp & (((1u << lt) - 1u) << lpw)) | ((rp >> (lt + lpw)) & ((1u << lpw) - 1u)));
+}
+
 } // namespace nm

@@ -1,16 +1,20 @@
 """dev probe (experiment build with -DNM_TL_REBUILD: `make -C neuralmelting_amd/csrc exprb`): where does a list rebuild of the 4^3 cluster kernel spend its time?  Stamps of slot 0's
 evaluations: 0 entry, 3 conversion issued, 4 past the barrier, 5 tests done, 6 scan + appends done, 7 past the closing reduction.
-    NM_TL_TREV=1 python scripts/probe_rebuild.py      (slot 0 = the hottest replica of the first pressure row)"""
+    NM_TL_TREV=1 python scripts/probe_rebuild.py      (slot 0 = the hottest replica of the first pressure row)
+    NM_TL_PREV=1 ...                                  (the first pressure row is the densest one, P = 8)
+    NM_TL_LIB=build/variants/other_exprb.so ...       (another build with the same stamps: a before/after pair on one box)"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ['NM_HIP_LIB'] = os.path.join(ROOT, 'build', 'variants', 'libnm_hip_exprb.so')
+os.environ['NM_HIP_LIB'] = os.path.join(ROOT, os.environ.get('NM_TL_LIB', os.path.join('build', 'variants', 'libnm_hip_exprb.so')))
 import numpy as np
 import neuralmelting_amd as nm
 from neuralmelting_amd import lattice, _lib
 P = np.linspace(1, 8, 8, dtype=np.float32); T = np.linspace(.25, 2.5, 8, dtype=np.float32)
 if os.environ.get('NM_TL_TREV'):
     T = T[::-1].copy()
+if os.environ.get('NM_TL_PREV'):
+    P = P[::-1].copy()
 x, v, box, d = lattice.init_states(4, P, T, 0.03125, 0.03125)
 e = nm.Engine(256, P, T)
 e.set_state(x, v, box, d)
